@@ -7,9 +7,16 @@
 One step = one MyModel.forward (the whole hot path, through the C-ABI) over one batch of synthetic
 IR/visible pairs already resident in HBM, plus — for N > 1 — the RCCL all-gather of the fused output
 (SURVEY.md §8e).  Weak scaling: every GPU processes `--batch` pairs (BASELINE.json config 4 = 16 x 8).
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events on the launch stream around
-the dominant unit (the level-0 window-attention BasicBlock launch); `cpu_baseline` times the CPU oracle
-(a port of the reference's PyTorch-CPU path) on a bounded sample on rank 0 at N=1.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes the last step's
+output if `--dump-outputs DIR` is given, and prints the line.  `--full` adds what needs runs of its own:
+the same steps one at a time (`config.one_step_at_a_time`), the check that the hipGraph replay equals an
+eager forward (`config.graph_equals_eager`), `roofline` — measured live with HIP events on the launch
+stream around the dominant unit (the level-0 window-attention BasicBlock launch) and per level — and
+`cpu_baseline`, which times the CPU oracle (a port of the reference's PyTorch-CPU path) on a bounded
+sample on rank 0 at N=1.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # DIR/fused.npy: fp32 (B*N, 1, H, W)
 """
 from __future__ import annotations
 
@@ -31,6 +38,7 @@ HBM_PEAK_GBS = 8000.0       # MI355X_MICROARCH.md: 8 TB/s HBM3E (spec)
 BYTES_PER_ELEM = 4          # the residual stream is stored fp32 (DESIGN.md "Data layout")
 TRAFFIC_FILE = "r03_traffic.json"    # committed PMC summary of the level-0 block kernel (tools/pmc_levels.sh, tools/traffic_summary.py)
 PMC_LEVELS_FILE = "r03_pmc_levels.json"   # committed per-level counter summary (tools/pmc_levels.sh, tools/pmc_levels_summary.py)
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: at most this much per run
 
 
 def parse():
@@ -57,7 +65,27 @@ def parse():
                     help="rehearse the control flow (process group, barriers, pipelined step_async, MAX all-reduce of the elapsed time, rank-0 "
                          "JSON) on CPU tensors over gloo with a stub forward: no GPU, no library, no number worth reading (tests/test_bench_dryrun.py)")
     ap.add_argument("--no-levels", action="store_true", help="skip the per-level roofline pass (swf_model_forward_profiled)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what a plain run leaves out: one step at a time, hipGraph replay == eager, the level-0 "
+                         "and per-level rooflines, the CPU baseline (--no-levels / --no-cpu-baseline drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the fused output of the last timed step to DIR/fused.npy (fp32; a fixed seeded sample of it beyond "
+                         f"{DUMP_MAX_BYTES >> 20} MiB)")
     return ap.parse_args()
+
+
+def dump_outputs(out_dir, fused):
+    """The fused images of the last timed step, as a caller of the step receives them (rank-major, (B*N, 1, H, W) fp32).  Larger than
+    DUMP_MAX_BYTES: a sorted sample of elements drawn with a fixed seed from the flattened output instead (the same elements every run
+    of the same arguments), as a 1-D array."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    out = fused.detach().float()
+    cap = DUMP_MAX_BYTES // 4
+    if out.numel() > cap:
+        idx = np.sort(np.random.default_rng(np.random.PCG64(0)).integers(0, out.numel(), size=cap))
+        out = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+    np.save(os.path.join(out_dir, "fused.npy"), out.cpu().numpy())
 
 
 def level0_block_roofline(model, batch, size, precision, iters=20, height=0, width=0):
@@ -401,10 +429,12 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert fused.shape[0] == args.batch * world and bool(torch.isfinite(fused).all())
-    # the same steps one at a time (each waited for before the next is enqueued): the latency of one step, for the record
+    if args.dump_outputs and rank == 0:   # before anything else runs: `fused` is a lane's static buffer
+        dump_outputs(args.dump_outputs, fused)
+    # --full: the same steps one at a time (each waited for before the next is enqueued): the latency of one step, for the record
     # (its own one-lane runner in the latency schedule: what a caller gets who waits for every step before enqueueing the next)
     serial_ms = None
-    if not dry and world == 1 and runner.in_flight > 1 and runner.graph_active:   # (one GPU only: how many lanes a rank found is its own business, and extra collectives on some ranks would hang the job)
+    if args.full and not dry and world == 1 and runner.in_flight > 1 and runner.graph_active:   # (one GPU only: how many lanes a rank found is its own business, and extra collectives on some ranks would hang the job)
         lanes_schedule = model.schedule
         model.schedule = "latency"
         single = ShardedFusion(model, world_size=world, rank=rank, use_graph=True, in_flight=1, force_collective=runner.force_collective)
@@ -419,9 +449,9 @@ def main():
         serial_ms = (time.perf_counter() - t1) / n_serial * 1e3
         del single
         model.schedule = lanes_schedule
-    # the timed path is the hipGraph replay: check it against one eager forward of the same inputs before reporting it
+    # --full: the timed path is the hipGraph replay: check it against one eager forward of the same inputs before reporting it
     graph_equals_eager = None
-    if runner.graph_active:
+    if args.full and runner.graph_active:
         graph_equals_eager = bool(torch.equal(runner.local_forward(ir, vis), model(ir, vis)))
         assert graph_equals_eager, "hipGraph replay differs from the eager forward"
 
@@ -451,7 +481,7 @@ def main():
             line["dry_run"] = True
             line["data"] = "synthetic; DRY RUN on CPU over gloo with a stub forward: the value measures nothing"
             line["config"]["collective"] = "gloo all_gather (stub forward)" if world > 1 else "none"
-        else:
+        elif args.full:
             line["roofline"] = level0_block_roofline(model, args.batch, args.size, args.precision, height=args.height, width=args.width)
             if not args.no_levels and args.precision == "fast":
                 per_level = level_rooflines(model, ir, vis, elapsed / args.steps * 1e3)

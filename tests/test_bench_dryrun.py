@@ -42,3 +42,22 @@ def test_single_process_dry_run():
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = _line(r.stdout)
     assert d["dry_run"] is True and d["n_gpus"] == 1 and d["config"]["global_batch"] == 2
+
+
+def test_dry_run_dumps_the_last_step(tmp_path):
+    """--dump-outputs writes what the timed path returned in its last step, and the same arguments give the same arrays."""
+    import numpy as np
+    outs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1", "--batch", "2", "--size", "16",
+                            "--dry-run", "--dump-outputs", str(d)],
+                           cwd=REPO, env=dict(os.environ, OMP_NUM_THREADS="1"), capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        assert _line(r.stdout)["steps"] == 3
+        outs.append(np.load(d / "fused.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (2, 1, 16, 16)
+    assert np.array_equal(outs[0], outs[1])
+    from swin_unet_image_fusion_amd import synthetic_pair
+    ir, vis = synthetic_pair(2, 16, 16, seed_ir=1, seed_vis=2)
+    assert np.allclose(outs[0], 0.5 * (ir + vis))        # the stub forward of the dry run, on rank 0's inputs

@@ -20,7 +20,7 @@ def test_bench_two_ranks_share_the_gpu():
     port = str(29600 + os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", port,
            os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "8", "--warmup", "3", "--batch", "4", "--size", "128", "--config", "win8_4stage",
-           "--no-levels", "--no-cpu-baseline"]
+           "--full", "--no-levels", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-2500:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -1,4 +1,4 @@
-"""Summarise a tools/pmc_levels.sh run -> JSON on stdout (profiles/r03_pmc_levels.json; bench.py reads it for roofline.levels[*].pmc).
+"""Summarise a tools/pmc_levels.sh run -> JSON on stdout (profiles/r03_pmc_levels.json; bench.py --full reads it for roofline.levels[*].pmc).
     python tools/pmc_levels_summary.py gpurun_out/pmc_levels <git commit>
 Per level and kernel of the block loop: launches averaged, duration (us, from the dispatch timestamps of the counter passes — kernels
 run serialised and a little slower under counter collection), counters per launch, and derived fractions:
