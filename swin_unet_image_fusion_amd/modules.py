@@ -15,6 +15,7 @@ from __future__ import annotations
 import ctypes as C
 import math
 from collections import deque
+from operator import attrgetter
 from typing import List, Optional, Tuple
 
 import torch
@@ -977,7 +978,10 @@ class _HeadFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, model, x, y, c1w, c1b, g, bt, c2w, c2b):
-        ctx.model, ctx.train = model, bool(model.training)
+        bn = model.final_layer[1]
+        # batch statistics exactly when torch's BatchNorm2d would use them: from the BatchNorm's own mode (a frozen BatchNorm inside a
+        # model in train() normalises with, and keeps, its running statistics), or always when it tracks none
+        ctx.model, ctx.train = model, bool(bn.training or (bn.running_mean is None and bn.running_var is None))
         b, _, h, w = x.shape
         x, y = x.detach().contiguous(), y.detach().contiguous()
         out = torch.empty((b, 1, h, w), dtype=torch.float32, device=x.device)
@@ -986,14 +990,17 @@ class _HeadFunction(torch.autograd.Function):
         stats = torch.empty(4, dtype=torch.float32, device=x.device)   # batch mean[2], biased variance[2]
         if ctx.train:
             # nn.BatchNorm2d in training mode (the reference trains under model.train(), a016:137): normalise with the batch statistics
-            # of this forward and move the running statistics towards them (momentum 0.1, unbiased variance)
-            bn = model.final_layer[1]
-            mom = 0.1 if bn.momentum is None else float(bn.momentum)
-            L.check(lib.swf_final_head_batch_stats(C.byref(hp), _ptr(x), _ptr(y), stats.data_ptr(), stats.data_ptr() + 8,
-                                                   _ptr(bn.running_mean) if bn.track_running_stats else None,
-                                                   _ptr(bn.running_var) if bn.track_running_stats else None, mom, b, h, w, ks, ws, wsn, _stream(x.device)))
-            if bn.track_running_stats and bn.num_batches_tracked is not None:
+            # of this forward and move the running statistics towards them (momentum 0.1, unbiased variance); momentum None is torch's
+            # cumulative average, 1 / num_batches_tracked counted after this forward's increment
+            track = bn.training and bn.track_running_stats
+            mom = 0.0 if bn.momentum is None else float(bn.momentum)
+            if track and bn.num_batches_tracked is not None:
                 bn.num_batches_tracked += 1
+                if bn.momentum is None:
+                    mom = 1.0 / float(bn.num_batches_tracked)
+            L.check(lib.swf_final_head_batch_stats(C.byref(hp), _ptr(x), _ptr(y), stats.data_ptr(), stats.data_ptr() + 8,
+                                                   _ptr(bn.running_mean) if track else None,
+                                                   _ptr(bn.running_var) if track else None, mom, b, h, w, ks, ws, wsn, _stream(x.device)))
             hp.bn_mean, hp.bn_var = stats.data_ptr(), stats.data_ptr() + 8
         ctx.save_for_backward(x, y, stats)
         L.check(lib.swf_final_head_fwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(out), b, h, w, ks, ws, wsn, _stream(x.device)))
@@ -1076,6 +1083,7 @@ class MyModel(_FwdAlias, nn.Module):
         self._arena: Optional[Tensor] = None
         self._arena_key = None
         self._packed: Optional[Tensor] = None
+        self._fp_params: Optional[Tuple[Tensor, ...]] = None   # the parameters whose in-place versions _weights_fingerprint() sums
         # bumped whenever the arena / packed images are dropped: anything that baked their addresses into a captured
         # hipGraph (shard.ShardedFusion) compares it before replaying
         self.weights_epoch = 0
@@ -1128,21 +1136,35 @@ class MyModel(_FwdAlias, nn.Module):
 
     def refresh_weights(self) -> None:
         """Drop the packed arena; it is rebuilt from the current parameters at the next forward.
-        Called automatically after load_state_dict() and .to(); call it by hand after editing
-        parameters in place."""
-        self._arena, self._arena_key, self._packed = None, None, None
+        Called automatically after load_state_dict() and .to().  In-place updates of the parameters themselves (an optimizer
+        step, `p.mul_(...)` under no_grad, an EMA update) bump their version counters and are picked up without it.  Call it by
+        hand after an edit that bypasses those counters: through `p.data` (`p.data.copy_(...)`), through a raw pointer, of a
+        buffer (BatchNorm running statistics), or after replacing a Parameter object."""
+        self._arena, self._arena_key, self._packed, self._fp_params = None, None, None, None
         self.weights_epoch += 1
 
     def _apply(self, fn, *a, **kw):
-        self._arena, self._arena_key, self._packed = None, None, None
+        self._arena, self._arena_key, self._packed, self._fp_params = None, None, None, None
         self.weights_epoch = getattr(self, "weights_epoch", 0) + 1
         return super()._apply(fn, *a, **kw)
 
+    _version_of = staticmethod(attrgetter("_version"))
+
+    def _weights_fingerprint(self) -> int:
+        """Sum of the parameters' in-place version counters: every in-place update of a parameter (optimizer step, EMA update under
+        no_grad) raises it, so the arena and the captured graphs follow the weights whatever the order of grad / no-grad forwards and
+        steps.  Parameters only: buffers change through paths that refresh anyway (load_state_dict, .to(), the training forward, which
+        writes the running statistics through a raw pointer).  The tuple is cached: walking self.parameters() costs ~15x the sum."""
+        ps = self._fp_params
+        if ps is None:
+            ps = self._fp_params = tuple(self.parameters())
+        return sum(map(self._version_of, ps))
+
     def graph_key(self):
-        """Everything a captured forward depends on besides the input shape: the weights epoch, the arithmetic mode and
-        the addresses of the arena / packed images (None before the first forward)."""
-        return (self.weights_epoch, self.precision, self.schedule, None if self._arena is None else self._arena.data_ptr(),
-                None if self._packed is None else self._packed.data_ptr())
+        """Everything a captured forward depends on besides the input shape: the weights epoch and fingerprint, the arithmetic mode
+        and the addresses of the arena / packed images (None before the first forward)."""
+        return (self.weights_epoch, self._weights_fingerprint(), self.precision, self.schedule,
+                None if self._arena is None else self._arena.data_ptr(), None if self._packed is None else self._packed.data_ptr())
 
     def param_layout(self):
         """[(state_dict key, element offset, numel)] of the arena, as defined by the library."""
@@ -1159,7 +1181,7 @@ class MyModel(_FwdAlias, nn.Module):
         return out
 
     def _get_arena(self, device) -> Tensor:
-        key = (torch.device(device).index,)
+        key = (torch.device(device).index, self._weights_fingerprint())
         if self._arena is None or self._arena_key != key:
             _require_elu(self.mlp_activation_func)
             lib, desc = L.lib(), self._model_desc()
@@ -1222,12 +1244,25 @@ class MyModel(_FwdAlias, nn.Module):
             raise ValueError(f"expected two (B,{self.in_dims_list[0]},H,W) tensors, got {tuple(in_x.shape)} and {tuple(in_y.shape)}")
         self.u_net_intermediate_result_recorder.delete_all()
         if self._arena is not None:
-            # a differentiable forward is a training step: an optimizer is about to change the parameters in place, which nothing
-            # here could notice — drop the fused forward's weight arena now, the next no-grad forward (a016:202) rebuilds it
+            # in train() the head writes the BatchNorm running statistics through a raw pointer, which bumps no version counter: drop
+            # the fused forward's weight arena now, the next no-grad forward (a016:202) rebuilds it (parameter updates are tracked by
+            # _weights_fingerprint)
             self.refresh_weights()
-        x, y = in_x, in_y
-        if not x.requires_grad:      # the module-level autograd Functions key on their inputs
-            x, y = x.detach().requires_grad_(True), y.detach().requires_grad_(True)
+        # the module-level autograd Functions key on their inputs; an input that requires grad is kept as it is, so it gets its gradient
+        x = in_x if in_x.requires_grad else in_x.detach().requires_grad_(True)
+        y = in_y if in_y.requires_grad else in_y.detach().requires_grad_(True)
+        # the blocks run in the MODEL's tier here (their own .precision is what they run at when called on their own)
+        blocks = [m for m in self.modules() if isinstance(m, BasicBlock)]
+        own = [blk.precision for blk in blocks]
+        for blk in blocks:
+            blk.precision = self.precision
+        try:
+            return self._forward_autograd_stages(x, y)
+        finally:
+            for blk, p in zip(blocks, own):
+                blk.precision = p
+
+    def _forward_autograd_stages(self, x: Tensor, y: Tensor) -> Tensor:
         n = len(self.in_dims_list)
         for j, stage in enumerate(self.encoder_list):          # a013:215-220
             for mod in stage:

@@ -111,11 +111,12 @@ class _DeferredGather(GatherHandle):
 
 class _Lane:
     """One captured forward: the hipGraph, the runner-owned static input / output buffers it was captured on, the key it was captured
-    for, its capture stream (also the stream it replays on when steps overlap) and the library workspace it points into."""
-    __slots__ = ("graph", "static", "key", "stream", "ws_ref")
+    for, its capture stream (also the stream it replays on when steps overlap), the library workspace and the model's weight arena /
+    packed images it points into."""
+    __slots__ = ("graph", "static", "key", "stream", "ws_ref", "weights_ref")
 
     def __init__(self):
-        self.graph = self.static = self.key = self.stream = self.ws_ref = None
+        self.graph = self.static = self.key = self.stream = self.ws_ref = self.weights_ref = None
 
 
 class ShardedFusion:
@@ -140,10 +141,14 @@ class ShardedFusion:
     A captured graph bakes in raw addresses: the model's weight arena and packed images, the library
     workspace, the arithmetic mode and the static input / output buffers.  It is therefore keyed on
     (input shape, model.graph_key()) and re-captured whenever either changes — after load_state_dict(),
-    refresh_weights(), .to() or `model.precision = ...` the next step runs the new weights (a017:50-54: load,
-    then infer).  The static input buffers belong to the runner (callers' tensors are copied in, never
+    refresh_weights(), .to(), an in-place update of the parameters (optimizer step, EMA) or `model.precision = ...`
+    the next step runs the new weights (a017:50-54: load, then infer).  Each lane holds the arena and packed images
+    its graph reads until it is re-captured, so steps still in flight when the weights change finish on the old ones.  The static input buffers belong to the runner (callers' tensors are copied in, never
     adopted), and the tensor returned by local_forward()/step() at world_size 1 is the runner's static
-    output buffer: it is overwritten by a later step — clone it to keep it."""
+    output buffer: it is overwritten by a later step — clone it to keep it.
+
+    It is an inference runner: every forward it runs or captures runs under torch.no_grad(), so a model whose parameters require grad
+    takes its fused forward here, not the differentiable module-by-module path."""
 
     def __init__(self, model=None, world_size: int = 1, rank: int = 0, use_graph: bool = False,
                  forward_fn: Optional[Callable] = None, group=None, force_collective: bool = False, in_flight: int = 1):
@@ -183,8 +188,12 @@ class ShardedFusion:
         return self.model.graph_key() if hasattr(self.model, "graph_key") else None
 
     def _capture(self, lane: _Lane, ir, vis):
+        # Steps of every lane may still be running: this lane's old graph and buffers, and the weight arena / packed images the model
+        # dropped (load_state_dict, refresh_weights) or is about to rebuild, must outlive them.  The caching allocator would hand
+        # those blocks to the warm-up's torch.cat at once (it orders reuse on the caller's stream only).
+        torch.cuda.synchronize(ir.device)
         ir, vis = ir.clone(), vis.clone()             # runner-owned static buffers
-        lane.graph = lane.static = lane.ws_ref = None      # drop the old graph before its buffers
+        lane.graph = lane.static = lane.ws_ref = lane.weights_ref = None      # drop the old graph before its buffers
         self.forward_fn(ir, vis)                      # warm-up: sizes the workspace, builds the arena, first-forward check
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -208,6 +217,9 @@ class ShardedFusion:
             lane.ws_ref = _workspace_tensor(ir.device, s.cuda_stream)
         except ImportError:       # forward_fn-only runners (tests on CPU) never get here: capture needs CUDA tensors
             lane.ws_ref = None
+        # the graph also holds the raw addresses of the model's weight arena and packed images: kept alive the same way, until this lane
+        # is re-captured (after the synchronize above)
+        lane.weights_ref = (getattr(self.model, "_arena", None), getattr(self.model, "_packed", None))
         lane.graph, lane.static, self.graph_active = g, (ir, vis, out), True
         lane.key = (tuple(ir.shape), self._model_key())   # after the capture: the arena / packed images exist now
         self.captures += 1
@@ -262,6 +274,7 @@ class ShardedFusion:
     def _overlapped(self, ir) -> bool:
         return self.in_flight > 1 and self.use_graph and ir.is_cuda
 
+    @torch.no_grad()
     def local_forward(self, ir, vis):
         if not (self.use_graph and ir.is_cuda):
             return self.forward_fn(ir, vis)
@@ -312,6 +325,7 @@ class ShardedFusion:
         while self._unissued and not handle._issued:
             self._unissued.pop(0)._start()
 
+    @torch.no_grad()
     def step_async(self, ir_shard: torch.Tensor, vis_shard: torch.Tensor) -> GatherHandle:
         if not self._overlapped(ir_shard):
             return self.gather_async(self.local_forward(ir_shard, vis_shard))
@@ -335,6 +349,7 @@ class ShardedFusion:
     def step(self, ir_shard: torch.Tensor, vis_shard: torch.Tensor) -> torch.Tensor:
         return self.step_async(ir_shard, vis_shard).wait()
 
+    @torch.no_grad()
     def fuse_global(self, ir: torch.Tensor, vis: torch.Tensor) -> torch.Tensor:
         """Every rank passes the same global batch; returns the full fused batch on every rank."""
         b = ir.shape[0]

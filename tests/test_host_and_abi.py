@@ -150,3 +150,54 @@ def test_reference_format_checkpoint_roundtrip(tmp_path):
     k1 = "encoder_list.0.3.self_att_block.normal_window_block.auto_path_win_att.window_attention_x.q_for_heads.weight"
     k2 = "encoder_list.0.3.self_att_block.normal_window_block.stage_1.other_module.window_attention_x.q_for_heads.weight"
     assert sd[k1].data_ptr() == sd[k2].data_ptr()
+
+
+def test_graph_key_follows_in_place_parameter_updates():
+    """MyModel keys its weight arena, packed images and graph_key() on the parameters' in-place version counters: an optimizer step or
+    an EMA update under no_grad changes the key whatever the order of forwards around it; nothing else does.  Edits that bypass the
+    counters (p.data) need refresh_weights(), which its docstring says."""
+    m = MyModel(**CONFIGS["tiny"].model_kwargs(nn.ELU(inplace=True))).eval()
+    load_recipe_into(m, seed=1, flavor="stress")
+    k0 = m.graph_key()
+    assert m.graph_key() == k0
+    m.zero_grad(set_to_none=True)
+    with torch.no_grad():
+        _ = [p.clone() for p in m.parameters()]
+    assert m.graph_key() == k0
+    keys = {k0}
+    for opt in (torch.optim.SGD(m.parameters(), lr=1e-2, momentum=0.9), torch.optim.Adam(m.parameters(), lr=1e-3)):
+        for p in m.parameters():
+            p.grad = torch.ones_like(p)
+        opt.step()
+        keys.add(m.graph_key())
+    assert len(keys) == 3
+    other = MyModel(**CONFIGS["tiny"].model_kwargs(nn.ELU(inplace=True)))
+    with torch.no_grad():
+        for p, q in zip(m.parameters(), other.parameters()):
+            p.mul_(0.9).add_(q, alpha=0.1)
+    assert m.graph_key() not in keys
+    keys.add(m.graph_key())
+    with torch.no_grad():
+        next(m.parameters()).data.add_(1.0)
+    assert "p.data" in MyModel.refresh_weights.__doc__
+    m.refresh_weights()
+    assert m.graph_key() not in keys
+    keys.add(m.graph_key())
+    m.load_state_dict(other.state_dict(), strict=True)
+    assert m.graph_key() not in keys
+
+
+def test_weights_fingerprint_tuple_is_cached_and_rebuilt():
+    """graph_key() runs on every runner step: the parameter tuple it sums over is built once, and again after .to() / _apply,
+    load_state_dict() and refresh_weights() (which may have replaced Parameter objects)."""
+    m = MyModel(**CONFIGS["tiny"].model_kwargs(nn.ELU(inplace=True))).eval()
+    m.graph_key()
+    cached = m._fp_params
+    assert cached is not None and len(cached) == len(list(m.parameters()))
+    m.graph_key()
+    assert m._fp_params is cached
+    for reset in (lambda: m.float(), lambda: m.load_state_dict(m.state_dict()), m.refresh_weights):
+        reset()
+        assert m._fp_params is None
+        m.graph_key()
+        assert m._fp_params is not None

@@ -77,3 +77,23 @@ def test_two_rank_gloo_matches_unsharded(batch):
         assert p.exitcode == 0
     res = dict(q.get(timeout=5) for _ in range(2))
     assert res == {0: True, 1: True}
+
+
+def test_runner_runs_every_forward_without_grad():
+    """ShardedFusion is an inference runner: step, step_async, local_forward and fuse_global call forward_fn under no_grad even when the
+    caller has grad enabled, so a model whose parameters require grad takes its fused forward there."""
+    seen = []
+
+    def fwd(a, b):
+        seen.append(torch.is_grad_enabled())
+        return a * b
+
+    runner = ShardedFusion(world_size=1, rank=0, forward_fn=fwd)
+    a, b = torch.rand(2, 1, 4, 4, requires_grad=True), torch.rand(2, 1, 4, 4)
+    assert torch.is_grad_enabled()
+    outs = [runner.step(a, b), runner.step_async(a, b).wait(), runner.local_forward(a, b), runner.fuse_global(a, b)]
+    assert seen == [False] * 4
+    assert torch.is_grad_enabled()
+    for o in outs:
+        assert o.grad_fn is None and not o.requires_grad
+        assert torch.equal(o, (a * b).detach())
