@@ -18,8 +18,8 @@
  *    synchronises, and is safe to capture into a hipGraph.
  *  - Return value: 0 = SWF_OK, negative = swf_status.  Nothing throws or aborts.
  *    swf_last_error_string() gives a thread-local description of the last failure.
- *  - Only the eval()/no_grad forward is provided (dropout p=0 -> identity, BatchNorm running
- *    statistics).
+ *  - The inference forward (eval(): dropout is the identity, BatchNorm uses its running statistics) is the hot path; the
+ *    training side adds exact-fp32 backward entries (*_bwd), the head's batch statistics and dropout (*_drop, swf_dropout_mask).
  */
 #ifndef SWINFUSE_H
 #define SWINFUSE_H
@@ -176,6 +176,56 @@ int swf_mlp_bwd(const swf_linear* fc1, const swf_linear* fc2, const float* x, co
 size_t swf_layernorm_bwd_workspace_bytes(int64_t tokens, int32_t C);
 int swf_layernorm_bwd(const swf_norm* ln, const float* x, const float* gout, float* gx, const swf_norm_grad* gp,
                       int64_t tokens, int32_t C, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
+/* ---- training side: dropout (attention_drop_ratio, linear_after_att_drop_ratio, mlp_drop_ratio; a005:22-27, a013:29-33) ------------
+ * Inverted dropout, x * mask / (1 - p), at the reference's four points of one stream of a block:
+ *   site 0  the attention output values P.V before the projection (a001:351-354)       [tokens][heads*head_dim]
+ *   site 1  the projection output before the residual add (a001:412-414)              [tokens][channels]
+ *   site 2  the MLP hidden activation after ELU, before fc2 (a003:25-31, dropout_*_1)  [tokens][hidden]
+ *   site 3  the fc2 output before the residual add (a003:25-31, dropout_*_2)           [tokens][channels]
+ * The mask is a function of (seed, stream, site, element index) only: element i = token * width + channel, token = the row in the
+ * image-order NHWC layout ((b * H + h) * W + w of the unshifted map), so it does not depend on tiling, window partition or cyclic
+ * shift.  r = word (i % 4) of Philox4x32-10 with key {seed & 0xffffffff, seed >> 32} and counter {(i / 4) & 0xffffffff, (i / 4) >> 32,
+ * site, stream}; the element is kept iff (r >> 8) * 2^-24 >= p and then multiplied by 1 / (1 - p) computed in fp32, else it becomes 0
+ * (p = 1 drops everything).  stream: 0 = the x stream, 1 = the y stream of a dual-path block.
+ * The *_drop entries run the exact fp32 tier whatever desc->precision says (the fused fast kernels have no masks), and their backward
+ * recomputes the forward with the same seed, so nothing is kept between the two calls.  A site with p = 0 applies no mask. */
+typedef struct swf_dropout {
+    uint64_t seed;
+    float attn_p;   /* site 0: attention_drop_ratio */
+    float proj_p;   /* site 1: linear_after_att_drop_ratio */
+    float mlp_p;    /* sites 2 and 3: mlp_drop_ratio */
+} swf_dropout;
+/* out[i] = the factor the kernels apply to element i (0 or 1 / (1 - p)), i < count: the documented way to reproduce a mask. */
+int swf_dropout_mask(uint64_t seed, int32_t stream_id, int32_t site, int64_t count, float p, float* out, swf_stream_t stream);
+/* BasicBlock.forward / its backward with dropout; arguments as swf_basic_block_fwd / swf_basic_block_bwd, both with the workspace of
+ * swf_basic_block_drop_workspace_bytes.  x_out / y_out may alias x_in / y_in. */
+size_t swf_basic_block_drop_workspace_bytes(const swf_block_desc* desc, int32_t B, int32_t H, int32_t W);
+int swf_basic_block_fwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W,
+                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_basic_block_bwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
+                             const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
+                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* WindowAttention on its own (sites 0 and 1 of mask stream stream_id; drop->mlp_p is ignored): forward as swf_window_attention_fwd
+ * (residual may be NULL), backward as swf_window_attention_bwd; workspace of swf_window_attention_drop_workspace_bytes. */
+size_t swf_window_attention_drop_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W);
+int swf_window_attention_fwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                  const float* residual, float* out, int32_t B, int32_t H, int32_t W, const swf_dropout* drop,
+                                  int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_window_attention_bwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                  const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                                  int32_t W, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes,
+                                  swf_stream_t stream);
+/* One stream of AutoPathMLP (sites 2 and 3 of mask stream stream_id): out = d3(fc2(d2(ELU(fc1(x))))), x / out [tokens][channels];
+ * backward as swf_mlp_bwd; workspace of swf_mlp_drop_workspace_bytes. */
+size_t swf_mlp_drop_workspace_bytes(int64_t tokens, int32_t channels, int32_t hidden);
+int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens, int32_t channels,
+                     int32_t hidden, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_mlp_bwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                     const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                     const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* SelfAndCrossBlockPair.forward (a012_SelfAndCrossBlockPair.py:70-78): four BasicBlocks in the
  * order self/normal, self/shifted, cross/normal, cross/shifted (a009:90-109).  `desc` gives the

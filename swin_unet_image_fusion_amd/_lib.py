@@ -48,6 +48,10 @@ class BlockStreamParams(C.Structure):
     _fields_ = [("ln1", Norm), ("attn", AttnParams), ("ln2", Norm), ("fc1", Linear), ("fc2", Linear)]
 
 
+class Dropout(C.Structure):
+    _fields_ = [("seed", C.c_uint64), ("attn_p", C.c_float), ("proj_p", C.c_float), ("mlp_p", C.c_float)]
+
+
 class PatchParams(C.Structure):
     _fields_ = [("conv", Linear), ("ln", Norm)]
 
@@ -94,6 +98,21 @@ SIGNATURES = {
     "swf_window_attention_bwd": (C.c_int, [P(AttnDesc), P(AttnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(AttnParams), _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_mlp_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "swf_mlp_bwd": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _vp, P(Linear), P(Linear), _i64, _i32, _i32, _vp, _sz, _vp]),
+    "swf_dropout_mask": (C.c_int, [C.c_uint64, _i32, _i32, _i64, C.c_float, _vp, _vp]),
+    "swf_basic_block_drop_workspace_bytes": (_sz, [P(BlockDesc), _i32, _i32, _i32]),
+    "swf_basic_block_fwd_drop": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                           P(Dropout), _vp, _sz, _vp]),
+    "swf_basic_block_bwd_drop": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                                           P(BlockStreamParams), P(BlockStreamParams), _i32, _i32, _i32, P(Dropout), _vp, _sz, _vp]),
+    "swf_window_attention_drop_workspace_bytes": (_sz, [P(AttnDesc), _i32, _i32, _i32]),
+    "swf_window_attention_fwd_drop": (C.c_int, [P(AttnDesc), P(AttnParams), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, P(Dropout), _i32,
+                                                _vp, _sz, _vp]),
+    "swf_window_attention_bwd_drop": (C.c_int, [P(AttnDesc), P(AttnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(AttnParams), _i32, _i32,
+                                                _i32, P(Dropout), _i32, _vp, _sz, _vp]),
+    "swf_mlp_drop_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "swf_mlp_fwd_drop": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _i64, _i32, _i32, P(Dropout), _i32, _vp, _sz, _vp]),
+    "swf_mlp_bwd_drop": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _vp, P(Linear), P(Linear), _i64, _i32, _i32, P(Dropout), _i32,
+                                   _vp, _sz, _vp]),
     "swf_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i32]),
     "swf_layernorm_bwd": (C.c_int, [P(Norm), _vp, _vp, _vp, P(Norm), _i64, _i32, _vp, _sz, _vp]),
     "swf_patch_layer_bwd_workspace_bytes": (_sz, [_i32] * 8),

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 
+#include "kernels_dropout.h"
 #include "kernels_generic.h"
 
 namespace swf {
@@ -661,9 +662,75 @@ size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, in
     return t;
 }
 
-int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
-                    const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
-                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t st) {
+// the dropout entries carve one more buffer per stream: the dropped hidden activation (h itself stays undropped for ELU')
+size_t basic_block_drop_ws(const swf_block_desc& d, int nstream, int B, int H, int W) {
+    return basic_block_bwd_ws(d, nstream, B, H, W) + (size_t)nstream * carve_bytes({(int64_t)B * H * W * d.hidden});
+}
+
+namespace {
+
+struct BlockBufs { float *xn, *q, *k, *v, *o, *x1, *xn2, *h, *hd, *dh, *dxn2, *gx1, *dO, *dq, *dk, *dv, *dxn, *dtab; };
+
+// carves the buffers of basic_block_bwd_ws (with `drop`: basic_block_drop_ws) and returns the scratch of the weight gradients
+float* carve_block(Carver& ws, BlockBufs* b, int nstream, int64_t N, int C, int HD, int hid, int64_t tab_floats, int64_t scratch_floats, bool drop) {
+    for (int s = 0; s < nstream; ++s) {
+        b[s].xn = ws.floats(N * C); b[s].q = ws.floats(N * HD); b[s].k = ws.floats(N * HD); b[s].v = ws.floats(N * HD); b[s].o = ws.floats(N * HD);
+        b[s].x1 = ws.floats(N * C); b[s].xn2 = ws.floats(N * C); b[s].h = ws.floats(N * hid);
+        b[s].dh = ws.floats(N * hid); b[s].dxn2 = ws.floats(N * C); b[s].gx1 = ws.floats(N * C); b[s].dO = ws.floats(N * HD);
+        b[s].dq = ws.floats(N * HD); b[s].dk = ws.floats(N * HD); b[s].dv = ws.floats(N * HD); b[s].dxn = ws.floats(N * C);
+        b[s].dtab = ws.floats(tab_floats);
+        b[s].hd = drop ? ws.floats(N * hid) : b[s].h;
+    }
+    return ws.floats(scratch_floats);
+}
+
+// The forward intermediates of both streams in the exact tier: xn, q, k, v, o, x1, xn2, h (and hd).  With `drop` (stream s = mask
+// stream s): o holds the DROPPED attention values (site 0), x1 = x + dropped projection (site 1), hd = the dropped hidden activation
+// (site 2) next to the undropped h; a site with p = 0 runs exactly the kernels of drop == nullptr.
+int block_forward(const swf_block_desc& d, int nstream, const swf_block_stream_params* const* pp, const float* const* xin, BlockBufs* b,
+                  const swf_dropout* drop, int B, int H, int W, hipStream_t st) {
+    const int64_t N = (int64_t)B * H * W;
+    const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
+    const bool cross = d.cross && nstream == 2;
+    const float pa = drop ? drop->attn_p : 0.f, pj = drop ? drop->proj_p : 0.f, pm = drop ? drop->mlp_p : 0.f;
+    if (pm == 0.f)
+        for (int s = 0; s < nstream; ++s) b[s].hd = b[s].h;   // no hidden mask: fc2 and dW2 read h itself
+    LnBatch l1{};
+    for (int s = 0; s < nstream; ++s) l1.p[s] = LnProb{xin[s], b[s].xn, pp[s]->ln1.gamma, pp[s]->ln1.beta};
+    SWF_TRY(launch_layernorm(l1, nstream, N, C, 0, st));
+    GemmBatch gq{};
+    for (int s = 0; s < nstream; ++s) {
+        const int kvs = cross ? 1 - s : s;
+        gq.p[3 * s] = GemmProb{b[s].xn, pp[s]->attn.q.weight, pp[s]->attn.q.bias, nullptr, b[s].q};
+        gq.p[3 * s + 1] = GemmProb{b[kvs].xn, pp[s]->attn.k.weight, pp[s]->attn.k.bias, nullptr, b[s].k};
+        gq.p[3 * s + 2] = GemmProb{b[kvs].xn, pp[s]->attn.v.weight, pp[s]->attn.v.bias, nullptr, b[s].v};
+    }
+    SWF_TRY(launch_gemm_f32(gq, 3 * nstream, (int)N, HD, C, C, HD, 0, st));
+    AttnCoreBatch ab{};
+    for (int s = 0; s < nstream; ++s) ab.p[s] = AttnCoreProb{b[s].q, b[s].k, b[s].v, b[s].o, pp[s]->attn.bias_table};
+    SWF_TRY(launch_attn_core(ab, nstream, HD, HD, HD, HD, B, H, W, d.attn.win_h, d.attn.win_w, d.attn.heads, d.attn.head_dim, d.attn.shift, st));
+    if (pa > 0.f)
+        for (int s = 0; s < nstream; ++s) SWF_TRY(launch_dropout_mul(b[s].o, b[s].o, N * HD, drop_site(drop->seed, s, kDropAttn, pa), st));
+    GemmBatch gpj{};
+    for (int s = 0; s < nstream; ++s) gpj.p[s] = GemmProb{b[s].o, pp[s]->attn.proj.weight, pp[s]->attn.proj.bias, pj > 0.f ? nullptr : xin[s], b[s].x1};
+    SWF_TRY(launch_gemm_f32(gpj, nstream, (int)N, C, HD, HD, C, 0, st));
+    if (pj > 0.f)
+        for (int s = 0; s < nstream; ++s) SWF_TRY(launch_dropout_add(b[s].x1, xin[s], b[s].x1, N * C, drop_site(drop->seed, s, kDropProj, pj), st));
+    LnBatch l2{};
+    for (int s = 0; s < nstream; ++s) l2.p[s] = LnProb{b[s].x1, b[s].xn2, pp[s]->ln2.gamma, pp[s]->ln2.beta};
+    SWF_TRY(launch_layernorm(l2, nstream, N, C, 0, st));
+    GemmBatch g1{};
+    for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{b[s].xn2, pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, b[s].h};
+    SWF_TRY(launch_gemm_f32(g1, nstream, (int)N, hid, C, C, hid, 1, st));
+    if (pm > 0.f)
+        for (int s = 0; s < nstream; ++s) SWF_TRY(launch_dropout_mul(b[s].h, b[s].hd, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
+    return SWF_OK;
+}
+
+int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
+                         const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
+                         const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout* drop, void* workspace, size_t workspace_bytes,
+                         hipStream_t st) {
     const int nstream = py ? 2 : 1;
     const int64_t N = (int64_t)B * H * W;
     const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
@@ -672,61 +739,41 @@ int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, 
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_bwd: token count");
     Carver ws(workspace, workspace_bytes);
-    struct S { float *xn, *q, *k, *v, *o, *x1, *xn2, *h, *dh, *dxn2, *gx1, *dO, *dq, *dk, *dv, *dxn, *dtab; } b[2];
-    for (int s = 0; s < nstream; ++s) {
-        b[s].xn = ws.floats(N * C); b[s].q = ws.floats(N * HD); b[s].k = ws.floats(N * HD); b[s].v = ws.floats(N * HD); b[s].o = ws.floats(N * HD);
-        b[s].x1 = ws.floats(N * C); b[s].xn2 = ws.floats(N * C); b[s].h = ws.floats(N * hid);
-        b[s].dh = ws.floats(N * hid); b[s].dxn2 = ws.floats(N * C); b[s].gx1 = ws.floats(N * C); b[s].dO = ws.floats(N * HD);
-        b[s].dq = ws.floats(N * HD); b[s].dk = ws.floats(N * HD); b[s].dv = ws.floats(N * HD); b[s].dxn = ws.floats(N * C);
-        b[s].dtab = ws.floats(tree_rows(nwin * d.attn.heads) * tsz);
-    }
+    BlockBufs b[2];
     const int64_t mx = std::max(std::max(C, HD), hid);
-    float* scratch = ws.floats(bwd_scratch_floats(N, mx, C));
+    float* scratch = carve_block(ws, b, nstream, N, C, HD, hid, tree_rows(nwin * d.attn.heads) * tsz, bwd_scratch_floats(N, mx, C), drop != nullptr);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_bwd workspace too small (need %zu B)", ws.used);
     const swf_block_stream_params* pp[2] = {px, py};
     const swf_block_stream_grads* gp[2] = {gx, gy};
     const float* xin[2] = {x_in, y_in};
     const float* gout[2] = {gx_out, gy_out};
     float* gin[2] = {gx_in, gy_in};
+    const float pa = drop ? drop->attn_p : 0.f, pj = drop ? drop->proj_p : 0.f, pm = drop ? drop->mlp_p : 0.f;
 
-    // ---- recompute the forward intermediates (exact tier) ----
-    {
-        LnBatch l1{};
-        for (int s = 0; s < nstream; ++s) l1.p[s] = LnProb{xin[s], b[s].xn, pp[s]->ln1.gamma, pp[s]->ln1.beta};
-        SWF_TRY(launch_layernorm(l1, nstream, N, C, 0, st));
-        GemmBatch gq{};
-        for (int s = 0; s < nstream; ++s) {
-            const int kvs = cross ? 1 - s : s;
-            gq.p[3 * s] = GemmProb{b[s].xn, pp[s]->attn.q.weight, pp[s]->attn.q.bias, nullptr, b[s].q};
-            gq.p[3 * s + 1] = GemmProb{b[kvs].xn, pp[s]->attn.k.weight, pp[s]->attn.k.bias, nullptr, b[s].k};
-            gq.p[3 * s + 2] = GemmProb{b[kvs].xn, pp[s]->attn.v.weight, pp[s]->attn.v.bias, nullptr, b[s].v};
-        }
-        SWF_TRY(launch_gemm_f32(gq, 3 * nstream, (int)N, HD, C, C, HD, 0, st));
-        AttnCoreBatch ab{};
-        for (int s = 0; s < nstream; ++s) ab.p[s] = AttnCoreProb{b[s].q, b[s].k, b[s].v, b[s].o, pp[s]->attn.bias_table};
-        SWF_TRY(launch_attn_core(ab, nstream, HD, HD, HD, HD, B, H, W, wh, ww, d.attn.heads, d.attn.head_dim, d.attn.shift, st));
-        GemmBatch gpj{};
-        for (int s = 0; s < nstream; ++s) gpj.p[s] = GemmProb{b[s].o, pp[s]->attn.proj.weight, pp[s]->attn.proj.bias, xin[s], b[s].x1};
-        SWF_TRY(launch_gemm_f32(gpj, nstream, (int)N, C, HD, HD, C, 0, st));
-        LnBatch l2{};
-        for (int s = 0; s < nstream; ++s) l2.p[s] = LnProb{b[s].x1, b[s].xn2, pp[s]->ln2.gamma, pp[s]->ln2.beta};
-        SWF_TRY(launch_layernorm(l2, nstream, N, C, 0, st));
-        GemmBatch g1{};
-        for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{b[s].xn2, pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, b[s].h};
-        SWF_TRY(launch_gemm_f32(g1, nstream, (int)N, hid, C, C, hid, 1, st));
-    }
+    // ---- recompute the forward intermediates (exact tier; with dropout the same masks as the forward: same seed) ----
+    SWF_TRY(block_forward(d, nstream, pp, xin, b, drop, B, H, W, st));
     auto G = [&](int s) -> const swf_block_stream_grads& { static const swf_block_stream_grads none{}; return gp[s] ? *gp[s] : none; };
-    // ---- MLP half, reverse ----
+    // ---- MLP half, reverse (dropout: g2 = dL/d(fc2 output) through site 3, dW2 from the dropped hd, the hidden gradient through site 2
+    //      and ELU' of the undropped h; the residual branch is not masked.  dxn is free until the Q/K/V reverse: it holds g2 / g1) ----
     for (int s = 0; s < nstream; ++s) {
-        SWF_TRY(dx(gout[s], pp[s]->fc2.weight, b[s].dh, N, C, hid, 0, st));                                   // dh = g2 . W2
-        SWF_TRY(dw(gout[s], b[s].h, G(s).fc2.weight, G(s).fc2.bias, N, C, hid, scratch, st));                 // dW2, db2
-        hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, b[s].dh, b[s].h, N * hid);
-        SWF_TRY(check_launch("elu_bwd"));
+        const float* g2 = gout[s];
+        if (pm > 0.f) { SWF_TRY(launch_dropout_mul(gout[s], b[s].dxn, N * C, drop_site(drop->seed, s, kDropMlpOut, pm), st)); g2 = b[s].dxn; }
+        SWF_TRY(dx(g2, pp[s]->fc2.weight, b[s].dh, N, C, hid, 0, st));                                       // dh = g2 . W2
+        SWF_TRY(dw(g2, b[s].hd, G(s).fc2.weight, G(s).fc2.bias, N, C, hid, scratch, st));                     // dW2, db2
+        if (pm > 0.f) {
+            SWF_TRY(launch_dropout_elu_bwd(b[s].dh, b[s].h, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
+        } else {
+            hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, b[s].dh, b[s].h, N * hid);
+            SWF_TRY(check_launch("elu_bwd"));
+        }
         SWF_TRY(dx(b[s].dh, pp[s]->fc1.weight, b[s].dxn2, N, hid, C, 0, st));                                 // dxn2 = du . W1
         SWF_TRY(dw(b[s].dh, b[s].xn2, G(s).fc1.weight, G(s).fc1.bias, N, hid, C, scratch, st));               // dW1, db1
         SWF_TRY(ln_bwd(b[s].x1, pp[s]->ln2.gamma, b[s].dxn2, gout[s], b[s].gx1, G(s).ln2.gamma, G(s).ln2.beta, N, C, scratch, st));
-        SWF_TRY(dx(b[s].gx1, pp[s]->attn.proj.weight, b[s].dO, N, C, HD, 0, st));                              // dO = gx1 . Wp
-        SWF_TRY(dw(b[s].gx1, b[s].o, G(s).attn.proj.weight, G(s).attn.proj.bias, N, C, HD, scratch, st));
+        const float* g1 = b[s].gx1;
+        if (pj > 0.f) { SWF_TRY(launch_dropout_mul(b[s].gx1, b[s].dxn, N * C, drop_site(drop->seed, s, kDropProj, pj), st)); g1 = b[s].dxn; }
+        SWF_TRY(dx(g1, pp[s]->attn.proj.weight, b[s].dO, N, C, HD, 0, st));                                  // dO = g1 . Wp
+        SWF_TRY(dw(g1, b[s].o, G(s).attn.proj.weight, G(s).attn.proj.bias, N, C, HD, scratch, st));           // (o: the dropped values)
+        if (pa > 0.f) SWF_TRY(launch_dropout_mul(b[s].dO, b[s].dO, N * HD, drop_site(drop->seed, s, kDropAttn, pa), st));
     }
     // ---- attention core, reverse ----
     {
@@ -755,6 +802,47 @@ int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, 
     return SWF_OK;
 }
 
+}  // namespace
+
+int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
+                    const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
+                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, nullptr, workspace, workspace_bytes, st);
+}
+
+int basic_block_bwd_drop(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
+                         const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
+                         const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout& drop, void* workspace, size_t workspace_bytes,
+                         hipStream_t st) {
+    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, &drop, workspace, workspace_bytes, st);
+}
+
+// BasicBlock.forward with dropout in the exact tier: block_forward, then out = x1 + dropout(fc2(hd)) (site 3); x_out may alias x_in
+int basic_block_fwd_drop(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
+                         const float* y_in, float* x_out, float* y_out, int B, int H, int W, const swf_dropout& drop, void* workspace,
+                         size_t workspace_bytes, hipStream_t st) {
+    const int nstream = py ? 2 : 1;
+    const int64_t N = (int64_t)B * H * W;
+    const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
+    const int64_t nwin = (int64_t)B * (H / d.attn.win_h) * (W / d.attn.win_w), tsz = (int64_t)(2 * d.attn.win_h - 1) * (2 * d.attn.win_w - 1);
+    if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_fwd_drop: token count");
+    Carver ws(workspace, workspace_bytes);
+    BlockBufs b[2];
+    carve_block(ws, b, nstream, N, C, HD, hid, tree_rows(nwin * d.attn.heads) * tsz, bwd_scratch_floats(N, std::max(std::max(C, HD), hid), C), true);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_fwd_drop workspace too small (need %zu B)", ws.used);
+    const swf_block_stream_params* pp[2] = {px, py};
+    const float* xin[2] = {x_in, y_in};
+    float* out[2] = {x_out, y_out};
+    SWF_TRY(block_forward(d, nstream, pp, xin, b, &drop, B, H, W, st));
+    const bool pm = drop.mlp_p > 0.f;
+    GemmBatch g2{};
+    for (int s = 0; s < nstream; ++s) g2.p[s] = GemmProb{b[s].hd, pp[s]->fc2.weight, pp[s]->fc2.bias, pm ? nullptr : b[s].x1, out[s]};
+    SWF_TRY(launch_gemm_f32(g2, nstream, (int)N, C, hid, hid, C, 0, st));
+    if (pm)
+        for (int s = 0; s < nstream; ++s) SWF_TRY(launch_dropout_add(out[s], b[s].x1, out[s], N * C, drop_site(drop.seed, s, kDropMlpOut, drop.mlp_p), st));
+    return SWF_OK;
+}
+
 // ---- the inner modules on their own (a001 / a003 / a004 under autograd): WindowAttention, one MLP stream, one LayerNorm ---------------
 size_t window_attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W) {
     const int64_t N = (int64_t)B * H * W, C = d.channels, HD = (int64_t)d.heads * d.head_dim;
@@ -762,13 +850,36 @@ size_t window_attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W) {
     return carve_bytes({N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, tree_rows(nwin * d.heads) * tsz}) +
            carve_bytes({bwd_scratch_floats(N, std::max(C, HD), C)});
 }
+// the dropout entries: one more [tokens][C] buffer (the output gradient through site 1)
+size_t window_attention_drop_ws(const swf_attn_desc& d, int B, int H, int W) {
+    return window_attention_bwd_ws(d, B, H, W) + carve_bytes({(int64_t)B * H * W * d.channels});
+}
+
+namespace {
+
+// Q / K / V projections and the attention core of WindowAttention in exact fp32; with dropout O holds the DROPPED values (site 0)
+int window_attention_core(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, float* Q,
+                          float* K, float* V, float* O, int B, int H, int W, const swf_dropout* drop, int stream_id, hipStream_t st) {
+    const int64_t N = (int64_t)B * H * W;
+    const int C = d.channels, HD = d.heads * d.head_dim;
+    GemmBatch gq3{};
+    gq3.p[0] = GemmProb{q_in, p.q.weight, p.q.bias, nullptr, Q};
+    gq3.p[1] = GemmProb{k_in, p.k.weight, p.k.bias, nullptr, K};
+    gq3.p[2] = GemmProb{v_in, p.v.weight, p.v.bias, nullptr, V};
+    SWF_TRY(launch_gemm_f32(gq3, 3, (int)N, HD, C, C, HD, 0, st));
+    AttnCoreBatch ac{};
+    ac.p[0] = AttnCoreProb{Q, K, V, O, p.bias_table};
+    SWF_TRY(launch_attn_core(ac, 1, HD, HD, HD, HD, B, H, W, d.win_h, d.win_w, d.heads, d.head_dim, d.shift, st));
+    if (drop && drop->attn_p > 0.f) SWF_TRY(launch_dropout_mul(O, O, N * HD, drop_site(drop->seed, stream_id, kDropAttn, drop->attn_p), st));
+    return SWF_OK;
+}
 
 // WindowAttention.forward (a001:448-474) under autograd: out = proj(attention(q_in Wq, k_in Wk, v_in Wv)).  Q / K / V and the attention
 // output are recomputed in exact fp32; gq / gk / gv are the gradients of the three inputs (separate buffers: the caller adds them where
-// one tensor was passed more than once).
-int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, const float* gout,
-                         float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W, void* workspace, size_t workspace_bytes,
-                         hipStream_t st) {
+// one tensor was passed more than once).  With dropout the output gradient goes through site 1 and dO through site 0.
+int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
+                              const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W,
+                              const swf_dropout* drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
     const int64_t N = (int64_t)B * H * W;
     const int C = d.channels, HD = d.heads * d.head_dim, wh = d.win_h, ww = d.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
@@ -778,19 +889,16 @@ int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const
     float* dO = ws.floats(N * HD); float* dQ = ws.floats(N * HD); float* dK = ws.floats(N * HD); float* dV = ws.floats(N * HD);
     float* dtab = ws.floats(tree_rows(nwin * d.heads) * tsz);
     float* scratch = ws.floats(bwd_scratch_floats(N, std::max(C, HD), C));
+    float* g1 = drop ? ws.floats(N * C) : nullptr;
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_bwd workspace too small (need %zu B)", ws.used);
     static const swf_attn_grads none{};
     const swf_attn_grads& g = gp ? *gp : none;
-    GemmBatch gq3{};
-    gq3.p[0] = GemmProb{q_in, p.q.weight, p.q.bias, nullptr, Q};
-    gq3.p[1] = GemmProb{k_in, p.k.weight, p.k.bias, nullptr, K};
-    gq3.p[2] = GemmProb{v_in, p.v.weight, p.v.bias, nullptr, V};
-    SWF_TRY(launch_gemm_f32(gq3, 3, (int)N, HD, C, C, HD, 0, st));
-    AttnCoreBatch ac{};
-    ac.p[0] = AttnCoreProb{Q, K, V, O, p.bias_table};
-    SWF_TRY(launch_attn_core(ac, 1, HD, HD, HD, HD, B, H, W, wh, ww, d.heads, d.head_dim, d.shift, st));
-    SWF_TRY(dx(gout, p.proj.weight, dO, N, C, HD, 0, st));                                  // dO = gout . Wp
-    SWF_TRY(dw(gout, O, g.proj.weight, g.proj.bias, N, C, HD, scratch, st));
+    SWF_TRY(window_attention_core(d, p, q_in, k_in, v_in, Q, K, V, O, B, H, W, drop, stream_id, st));
+    if (drop && drop->proj_p > 0.f) SWF_TRY(launch_dropout_mul(gout, g1, N * C, drop_site(drop->seed, stream_id, kDropProj, drop->proj_p), st));
+    else g1 = const_cast<float*>(gout);
+    SWF_TRY(dx(g1, p.proj.weight, dO, N, C, HD, 0, st));                                    // dO = gout . Wp
+    SWF_TRY(dw(g1, O, g.proj.weight, g.proj.bias, N, C, HD, scratch, st));
+    if (drop && drop->attn_p > 0.f) SWF_TRY(launch_dropout_mul(dO, dO, N * HD, drop_site(drop->seed, stream_id, kDropAttn, drop->attn_p), st));
     AttnBwdBatch ab{};
     ab.p[0] = AttnBwdProb{Q, K, V, dO, dQ, dK, dV, p.bias_table, dtab};
     SWF_TRY(launch_attn_bwd(ab, 1, HD, B, H, W, wh, ww, d.heads, d.head_dim, d.shift, st));
@@ -804,28 +912,107 @@ int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const
     return SWF_OK;
 }
 
-size_t mlp_bwd_ws(int64_t N, int C, int hid) {
-    return carve_bytes({N * hid, N * hid}) + carve_bytes({bwd_scratch_floats(N, std::max(C, hid), C)});
-}
-
-// one stream of AutoPathMLP.forward (a003:46-50) under autograd: out = fc2(ELU(fc1(x)))
-int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
-            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st) {
+// one stream of AutoPathMLP.forward (a003:46-50) under autograd: out = fc2(ELU(fc1(x))); with dropout out = d3(fc2(d2(ELU(fc1(x)))))
+int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
+                 const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout* drop, int stream_id, void* workspace, size_t workspace_bytes,
+                 hipStream_t st) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_bwd: token count");
     Carver ws(workspace, workspace_bytes);
     float* h = ws.floats(N * hid); float* dh = ws.floats(N * hid);
     float* scratch = ws.floats(bwd_scratch_floats(N, std::max(C, hid), C));
+    const bool pm = drop && drop->mlp_p > 0.f;
+    float* hd = pm ? ws.floats(N * hid) : h;
+    float* gf = pm ? ws.floats(N * C) : nullptr;
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_bwd workspace too small (need %zu B)", ws.used);
     static const swf_linear_grad none{};
     GemmBatch gb{};
     gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
     SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, 1, st));                          // h = ELU(fc1 x)
-    SWF_TRY(dx(gout, fc2.weight, dh, N, C, hid, 0, st));
-    SWF_TRY(dw(gout, h, (g2 ? *g2 : none).weight, (g2 ? *g2 : none).bias, N, C, hid, scratch, st));
-    hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, dh, h, N * hid);
-    SWF_TRY(check_launch("elu_bwd"));
+    const float* g = gout;
+    if (pm) {
+        SWF_TRY(launch_dropout_mul(h, hd, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
+        SWF_TRY(launch_dropout_mul(gout, gf, N * C, drop_site(drop->seed, stream_id, kDropMlpOut, drop->mlp_p), st));
+        g = gf;
+    }
+    SWF_TRY(dx(g, fc2.weight, dh, N, C, hid, 0, st));
+    SWF_TRY(dw(g, hd, (g2 ? *g2 : none).weight, (g2 ? *g2 : none).bias, N, C, hid, scratch, st));
+    if (pm) {
+        SWF_TRY(launch_dropout_elu_bwd(dh, h, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
+    } else {
+        hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, dh, h, N * hid);
+        SWF_TRY(check_launch("elu_bwd"));
+    }
     SWF_TRY(dx(dh, fc1.weight, gx, N, hid, C, 0, st));
     SWF_TRY(dw(dh, x, (g1 ? *g1 : none).weight, (g1 ? *g1 : none).bias, N, hid, C, scratch, st));
+    return SWF_OK;
+}
+
+}  // namespace
+
+int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, const float* gout,
+                         float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W, void* workspace, size_t workspace_bytes,
+                         hipStream_t st) {
+    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, nullptr, 0, workspace, workspace_bytes, st);
+}
+int window_attention_bwd_drop(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
+                              const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W,
+                              const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, &drop, stream_id, workspace, workspace_bytes, st);
+}
+
+// WindowAttention.forward with dropout (exact fp32): out = [residual +] dropout1(proj(dropout0(attention values)))
+int window_attention_fwd_drop(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
+                              const float* residual, float* out, int B, int H, int W, const swf_dropout& drop, int stream_id, void* workspace,
+                              size_t workspace_bytes, hipStream_t st) {
+    const int64_t N = (int64_t)B * H * W;
+    const int C = d.channels, HD = d.heads * d.head_dim;
+    if (N > INT32_MAX / std::max(C, HD)) return fail(SWF_ERR_UNSUPPORTED, "window_attention_fwd_drop: token count");
+    Carver ws(workspace, workspace_bytes);
+    float* Q = ws.floats(N * HD); float* K = ws.floats(N * HD); float* V = ws.floats(N * HD); float* O = ws.floats(N * HD);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_fwd_drop workspace too small (need %zu B)", ws.used);
+    SWF_TRY(window_attention_core(d, p, q_in, k_in, v_in, Q, K, V, O, B, H, W, &drop, stream_id, st));
+    const bool pj = drop.proj_p > 0.f;
+    GemmBatch pb{};
+    pb.p[0] = GemmProb{O, p.proj.weight, p.proj.bias, pj ? nullptr : residual, out};
+    SWF_TRY(launch_gemm_f32(pb, 1, (int)N, C, HD, HD, C, 0, st));
+    if (pj) {
+        const DropSite s = drop_site(drop.seed, stream_id, kDropProj, drop.proj_p);
+        SWF_TRY(residual ? launch_dropout_add(out, residual, out, N * C, s, st) : launch_dropout_mul(out, out, N * C, s, st));
+    }
+    return SWF_OK;
+}
+
+size_t mlp_bwd_ws(int64_t N, int C, int hid) {
+    return carve_bytes({N * hid, N * hid}) + carve_bytes({bwd_scratch_floats(N, std::max(C, hid), C)});
+}
+size_t mlp_drop_ws(int64_t N, int C, int hid) { return mlp_bwd_ws(N, C, hid) + carve_bytes({N * hid, N * C}); }
+
+int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
+            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, nullptr, 0, workspace, workspace_bytes, st);
+}
+int mlp_bwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
+                 const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes,
+                 hipStream_t st) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, &drop, stream_id, workspace, workspace_bytes, st);
+}
+
+// one stream of AutoPathMLP.forward with dropout (exact fp32): out = dropout3(fc2(dropout2(ELU(fc1(x)))))
+int mlp_fwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, float* out, int64_t N, int C, int hid, const swf_dropout& drop,
+                 int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_fwd_drop: token count");
+    Carver ws(workspace, workspace_bytes);
+    float* h = ws.floats(N * hid);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_fwd_drop workspace too small (need %zu B)", ws.used);
+    GemmBatch gb{};
+    gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
+    SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, 1, st));
+    const bool pm = drop.mlp_p > 0.f;
+    if (pm) SWF_TRY(launch_dropout_mul(h, h, N * hid, drop_site(drop.seed, stream_id, kDropHidden, drop.mlp_p), st));
+    GemmBatch g2{};
+    g2.p[0] = GemmProb{h, fc2.weight, fc2.bias, nullptr, out};
+    SWF_TRY(launch_gemm_f32(g2, 1, (int)N, C, hid, hid, C, 0, st));
+    if (pm) SWF_TRY(launch_dropout_mul(out, out, N * C, drop_site(drop.seed, stream_id, kDropMlpOut, drop.mlp_p), st));
     return SWF_OK;
 }
 

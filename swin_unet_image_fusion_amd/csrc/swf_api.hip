@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include "kernels_window.h"
 #include "kernels_bwd.h"
+#include "kernels_dropout.h"
 #include "kernels_win24.h"
 #include "kernels_win48.h"
 #include "kernels_win96.h"
@@ -1221,6 +1222,102 @@ int swf_mlp_bwd(const swf_linear* fc1, const swf_linear* fc2, const float* x, co
     if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "mlp_bwd: NULL argument");
     if (tokens <= 0 || channels <= 0 || hidden <= 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_bwd: bad sizes");
     return mlp_bwd(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, workspace, workspace_bytes, as_stream(stream));
+}
+
+// ---- dropout (training side) --------------------------------------------------------------------------------------------------------
+static bool drop_ratio_ok(float p) { return p >= 0.f && p <= 1.f; }   // false for NaN
+static int check_dropout(const swf_dropout* drop, const char* what) {
+    if (!drop) return fail(SWF_ERR_NULL, "%s: drop is NULL", what);
+    if (!drop_ratio_ok(drop->attn_p) || !drop_ratio_ok(drop->proj_p) || !drop_ratio_ok(drop->mlp_p))
+        return fail(SWF_ERR_BAD_SHAPE, "%s: dropout ratios must lie in [0, 1] (got %g, %g, %g)", what, drop->attn_p, drop->proj_p, drop->mlp_p);
+    return SWF_OK;
+}
+
+int swf_dropout_mask(uint64_t seed, int32_t stream_id, int32_t site, int64_t count, float p, float* out, swf_stream_t stream) {
+    if (!out) return fail(SWF_ERR_NULL, "dropout_mask: out is NULL");
+    if (count <= 0 || stream_id < 0 || site < 0 || site > 3) return fail(SWF_ERR_BAD_SHAPE, "dropout_mask: bad count, stream or site");
+    if (!drop_ratio_ok(p)) return fail(SWF_ERR_BAD_SHAPE, "dropout_mask: p = %g outside [0, 1]", p);
+    return launch_dropout_mask(out, count, drop_site(seed, stream_id, site, p), as_stream(stream));
+}
+
+size_t swf_basic_block_drop_workspace_bytes(const swf_block_desc* desc, int32_t B, int32_t H, int32_t W) {
+    if (!desc || B <= 0 || H <= 0 || W <= 0) return 0;
+    return basic_block_drop_ws(*desc, 2, B, H, W);
+}
+
+int swf_basic_block_fwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W,
+                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_block(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, true, true));
+    SWF_TRY(check_dropout(drop, "basic_block_fwd_drop"));
+    return basic_block_fwd_drop(*desc, px, py, x_in, y_in, x_out, y_out, B, H, W, *drop, workspace, workspace_bytes, as_stream(stream));
+}
+
+int swf_basic_block_bwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
+                             const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
+                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_block(desc, px, py, x_in, y_in, gx_in, gy_in, B, H, W, true, true));
+    if (!gx_out || (py && !gy_out)) return fail(SWF_ERR_NULL, "basic_block_bwd_drop: NULL output gradient");
+    SWF_TRY(check_dropout(drop, "basic_block_bwd_drop"));
+    return basic_block_bwd_drop(*desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, *drop, workspace, workspace_bytes,
+                                as_stream(stream));
+}
+
+size_t swf_window_attention_drop_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
+    if (!desc || B <= 0 || H <= 0 || W <= 0 || desc->win_h <= 0 || desc->win_w <= 0 || desc->channels <= 0 || desc->heads <= 0 || desc->head_dim <= 0) return 0;
+    return window_attention_drop_ws(*desc, B, H, W);
+}
+
+static int check_attn_drop_args(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                const swf_dropout* drop, int32_t stream_id, int32_t B, int32_t H, int32_t W, const char* what) {
+    if (!desc || !p || !q || !k || !v) return fail(SWF_ERR_NULL, "%s: NULL argument", what);
+    if (!p->q.weight || !p->k.weight || !p->v.weight || !p->proj.weight || !p->bias_table) return fail(SWF_ERR_NULL, "%s: NULL parameter", what);
+    SWF_TRY(check_attn_desc(desc, B, H, W));
+    if (stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "%s: negative stream id", what);
+    return check_dropout(drop, what);
+}
+
+int swf_window_attention_fwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                  const float* residual, float* out, int32_t B, int32_t H, int32_t W, const swf_dropout* drop,
+                                  int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_attn_drop_args(desc, p, q, k, v, drop, stream_id, B, H, W, "window_attention_fwd_drop"));
+    if (!out) return fail(SWF_ERR_NULL, "window_attention_fwd_drop: out is NULL");
+    return window_attention_fwd_drop(*desc, *p, q, k, v, residual, out, B, H, W, *drop, stream_id, workspace, workspace_bytes, as_stream(stream));
+}
+
+int swf_window_attention_bwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                  const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                                  int32_t W, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes,
+                                  swf_stream_t stream) {
+    SWF_TRY(check_attn_drop_args(desc, p, q, k, v, drop, stream_id, B, H, W, "window_attention_bwd_drop"));
+    if (!gout || !gq || !gk || !gv) return fail(SWF_ERR_NULL, "window_attention_bwd_drop: NULL gradient");
+    if (gq == gk || gq == gv || gk == gv) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd_drop: gq, gk, gv must be three buffers");
+    return window_attention_bwd_drop(*desc, *p, q, k, v, gout, gq, gk, gv, gp, B, H, W, *drop, stream_id, workspace, workspace_bytes,
+                                     as_stream(stream));
+}
+
+size_t swf_mlp_drop_workspace_bytes(int64_t tokens, int32_t channels, int32_t hidden) {
+    if (tokens <= 0 || channels <= 0 || hidden <= 0) return 0;
+    return mlp_drop_ws(tokens, channels, hidden);
+}
+
+int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens, int32_t channels,
+                     int32_t hidden, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !out) return fail(SWF_ERR_NULL, "mlp_fwd_drop: NULL argument");
+    if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_fwd_drop: bad sizes");
+    SWF_TRY(check_dropout(drop, "mlp_fwd_drop"));
+    return mlp_fwd_drop(*fc1, *fc2, x, out, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes, as_stream(stream));
+}
+
+int swf_mlp_bwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                     const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                     const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "mlp_bwd_drop: NULL argument");
+    if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_bwd_drop: bad sizes");
+    SWF_TRY(check_dropout(drop, "mlp_bwd_drop"));
+    return mlp_bwd_drop(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes,
+                        as_stream(stream));
 }
 
 size_t swf_layernorm_bwd_workspace_bytes(int64_t tokens, int32_t C) {

@@ -8,7 +8,9 @@ containers, which are used purely as named parameter holders); every `forward` m
 device pointers into the C-ABI.  No arithmetic of the hot path runs in PyTorch, and there is
 no CPU fallback: without the built library, or on a CPU tensor, forward raises.
 
-Only the eval()/no_grad forward exists (SURVEY.md §8b "Mode").
+The eval() forward is the hot path (fused kernels, one C call for MyModel).  Under torch.autograd every module is differentiable
+through exact-fp32 backward entries, and in train() the reference's three dropout ratios apply: a module with a ratio
+> 0 runs the exact-fp32 *_drop entries of the library, with or without grad.
 """
 from __future__ import annotations
 
@@ -98,6 +100,34 @@ def _wants_grad(module: nn.Module, *tensors: Optional[Tensor]) -> bool:
     """True when torch.autograd is recording and an input or a parameter of `module` takes part in it (training side)."""
     return torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in tensors) or
                                         any(p.requires_grad for p in module.parameters()))
+
+
+def _dropout(module: nn.Module, attn_p: float, proj_p: float, mlp_p: float) -> Optional[L.Dropout]:
+    """The swf_dropout of one train-mode call of `module`, or None (eval(), or every ratio 0: today's path, no RNG drawn).  Ratios
+    outside [0, 1] raise ValueError.  The seed comes from torch's CPU default generator (torch.manual_seed reproduces a run, no device
+    sync) and is kept as module.last_dropout_seed; swf_dropout_mask(seed, stream, site, ...) reproduces each mask."""
+    if not module.training:
+        return None
+    ratios = (float(attn_p), float(proj_p), float(mlp_p))
+    if not all(0.0 <= r <= 1.0 for r in ratios):
+        raise ValueError(f"dropout ratios must lie in [0, 1], got {ratios}")
+    if not any(ratios):
+        return None
+    seed = int(torch.empty((), dtype=torch.int64).random_().item())
+    module.last_dropout_seed = seed
+    return L.Dropout(seed, *ratios)
+
+
+def _drops_in_training(module: nn.Module) -> bool:
+    """True when `module` (AutoPathWinAtt, AutoPathMLP, BasicBlock, SelfAndCrossBlockPair) applies dropout in its current mode: its
+    fused single-call units have no masks, so it runs its dropping sub-modules one by one instead."""
+    if isinstance(module, AutoPathMLP):
+        ratios = (module.drop_ratio,)
+    elif isinstance(module, AutoPathWinAtt):
+        ratios = (module.attention_drop_ratio, module.linear_after_att_drop_ratio)
+    else:
+        ratios = (module.attention_drop_ratio, module.linear_after_att_drop_ratio, module.mlp_drop_ratio)
+    return module.training and any(float(r) != 0.0 for r in ratios)
 
 
 def _to_nhwc(t: Tensor) -> Tensor:
@@ -198,22 +228,18 @@ class WindowAttention(_FwdAlias, nn.Module):
         return L.AttnParams(_lin(self.q_for_heads), _lin(self.k_for_heads), _lin(self.v_for_heads),
                             _lin(self.linear_projection), _ptr(self.relative_position_bias_table))
 
-    def _check_dropout(self):
-        if self.training and (self.attention_drop_ratio or self.linear_after_att_drop_ratio):
-            raise NotImplementedError("dropout > 0 in training mode is outside the forward-only HIP path")
-
     def forward(self, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
-        """a001:448-474.  With torch.autograd recording the call is differentiable (swf_window_attention_bwd: exact fp32)."""
+        """a001:448-474.  With torch.autograd recording the call is differentiable (swf_window_attention_bwd: exact fp32).  In train()
+        with a dropout ratio > 0 it runs swf_window_attention_{fwd,bwd}_drop (exact fp32, mask stream 0) with or without grad."""
+        drop = _dropout(self, self.attention_drop_ratio, self.linear_after_att_drop_ratio, 0.0)
         if _wants_grad(self, q, k, v):
-            self._check_dropout()
             names = ("q_for_heads", "k_for_heads", "v_for_heads", "linear_projection")
             prm = [t for n in names for t in (getattr(self, n).weight, getattr(self, n).bias)]
-            return _WindowAttentionFunction.apply(self, q, k, v, self.relative_position_bias_table, *prm)
-        return self._forward_nograd(q, k, v)
+            return _WindowAttentionFunction.apply(self, drop, q, k, v, self.relative_position_bias_table, *prm)
+        return self._forward_nograd(q, k, v, drop)
 
-    def _forward_nograd(self, q: Tensor, k: Tensor, v: Tensor) -> Tensor:
+    def _forward_nograd(self, q: Tensor, k: Tensor, v: Tensor, drop: Optional[L.Dropout] = None) -> Tensor:
         _check_forward_only(self, q, k, v)
-        self._check_dropout()
         if q.shape != k.shape or q.shape != v.shape:
             raise ValueError(f"q, k, v must share one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
         b, c, h, w = q.shape
@@ -226,8 +252,13 @@ class WindowAttention(_FwdAlias, nn.Module):
         out = torch.empty((b, h, w, c), dtype=torch.float32, device=q.device)
         desc = self._desc()
         lib = L.lib()
-        ws, wsn = _workspace(lib.swf_window_attention_workspace_bytes(C.byref(desc), b, h, w), q.device)
         prm = self._params()
+        if drop is not None:
+            ws, wsn = _workspace(lib.swf_window_attention_drop_workspace_bytes(C.byref(desc), b, h, w), q.device)
+            L.check(lib.swf_window_attention_fwd_drop(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), None, _ptr(out), b, h, w,
+                                                      C.byref(drop), 0, ws, wsn, _stream(q.device)))
+            return _to_nchw(out)
+        ws, wsn = _workspace(lib.swf_window_attention_workspace_bytes(C.byref(desc), b, h, w), q.device)
         L.check(lib.swf_window_attention_fwd_prec(C.byref(desc), _precision_code(self.precision), C.byref(prm), _ptr(qn), _ptr(kn),
                                                   _ptr(vn), None, _ptr(out), b, h, w, ws, wsn, _stream(q.device)))
         return _to_nchw(out)
@@ -235,14 +266,15 @@ class WindowAttention(_FwdAlias, nn.Module):
 
 class _WindowAttentionFunction(torch.autograd.Function):
     """WindowAttention.forward under torch.autograd: forward = the module's own forward (its precision tier), backward =
-    swf_window_attention_bwd.  q, k, v may be one tensor: autograd adds the three input gradients."""
+    swf_window_attention_bwd.  q, k, v may be one tensor: autograd adds the three input gradients.  With dropout (`drop` not None)
+    both directions run the *_drop entries with the seed saved here."""
 
     @staticmethod
-    def forward(ctx, module, q, k, v, table, *params):
-        ctx.module = module
+    def forward(ctx, module, drop, q, k, v, table, *params):
+        ctx.module, ctx.drop = module, drop
         ctx.save_for_backward(q, k, v)
         with torch.no_grad():
-            return module._forward_nograd(q.detach(), k.detach(), v.detach())
+            return module._forward_nograd(q.detach(), k.detach(), v.detach(), drop)
 
     @staticmethod
     def backward(ctx, g):
@@ -264,22 +296,28 @@ class _WindowAttentionFunction(torch.autograd.Function):
             gt = new(m.relative_position_bias_table)
             grads = L.AttnParams(lin(gw[0], gb[0]), lin(gw[1], gb[1]), lin(gw[2], gb[2]), lin(gw[3], gb[3]), gt.data_ptr())
             lib, desc, prm = L.lib(), m._desc(), m._params()
-            ws, wsn = _workspace(lib.swf_window_attention_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
-            L.check(lib.swf_window_attention_bwd(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk), _ptr(gv),
-                                                 C.byref(grads), b, h, w, ws, wsn, _stream(dev)))
+            if ctx.drop is not None:
+                ws, wsn = _workspace(lib.swf_window_attention_drop_workspace_bytes(C.byref(desc), b, h, w), dev)
+                L.check(lib.swf_window_attention_bwd_drop(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
+                                                          _ptr(gv), C.byref(grads), b, h, w, C.byref(ctx.drop), 0, ws, wsn, _stream(dev)))
+            else:
+                ws, wsn = _workspace(lib.swf_window_attention_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
+                L.check(lib.swf_window_attention_bwd(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
+                                                     _ptr(gv), C.byref(grads), b, h, w, ws, wsn, _stream(dev)))
             flat = [t for pair in zip(gw, gb) for t in pair]
-            return (None, _to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *flat)
+            return (None, None, _to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *flat)
 
 
 class _MlpFunction(torch.autograd.Function):
-    """One stream of AutoPathMLP.forward (a003:46-50) under torch.autograd: forward swf_mlp_fwd, backward swf_mlp_bwd."""
+    """One stream of AutoPathMLP.forward (a003:46-50) under torch.autograd: forward swf_mlp_fwd, backward swf_mlp_bwd (with dropout:
+    swf_mlp_{fwd,bwd}_drop with the seed saved here)."""
 
     @staticmethod
-    def forward(ctx, module, s, x, w1, b1, w2, b2):
-        ctx.module, ctx.s = module, s
+    def forward(ctx, module, s, drop, x, w1, b1, w2, b2):
+        ctx.module, ctx.s, ctx.drop = module, s, drop
         ctx.save_for_backward(x)
         with torch.no_grad():
-            return module._one_nograd(x.detach(), s)
+            return module._one_nograd(x.detach(), s) if drop is None else module._one_drop(x.detach(), s, drop)
 
     @staticmethod
     def backward(ctx, g):
@@ -297,10 +335,15 @@ class _MlpFunction(torch.autograd.Function):
             f1, f2 = _lin(c1), _lin(c2)
             gf1, gf2 = L.Linear(ptr(g1w), ptr(g1b)), L.Linear(ptr(g2w), ptr(g2b))
             lib, n = L.lib(), b * h * w
-            ws, wsn = _workspace(lib.swf_mlp_bwd_workspace_bytes(n, c, m.hidden_dims), dev)
-            L.check(lib.swf_mlp_bwd(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, m.hidden_dims,
-                                    ws, wsn, _stream(dev)))
-            return None, None, _to_nchw(gx), g1w, g1b, g2w, g2b
+            if ctx.drop is not None:
+                ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, m.hidden_dims), dev)
+                L.check(lib.swf_mlp_bwd_drop(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c,
+                                             m.hidden_dims, C.byref(ctx.drop), _MASK_STREAM[s], ws, wsn, _stream(dev)))
+            else:
+                ws, wsn = _workspace(lib.swf_mlp_bwd_workspace_bytes(n, c, m.hidden_dims), dev)
+                L.check(lib.swf_mlp_bwd(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, m.hidden_dims,
+                                        ws, wsn, _stream(dev)))
+            return None, None, None, _to_nchw(gx), g1w, g1b, g2w, g2b
 
 
 class _LayerNormFunction(torch.autograd.Function):
@@ -363,6 +406,9 @@ class AutoPathWinAtt(_FwdAlias, nn.Module):
         return self.window_attention_x(q=x, k=x, v=x), self.window_attention_y(q=y, k=y, v=y)
 
 
+_MASK_STREAM = {"x": 0, "y": 1}   # the stream id of the dropout masks (include/swinfuse.h swf_dropout)
+
+
 class AutoPathMLP(_FwdAlias, nn.Module):
     """a003_AutoPathMLP.AutoPathMLP: per-stream 1x1 conv -> activation -> 1x1 conv (a003:21-50)."""
 
@@ -397,25 +443,39 @@ class AutoPathMLP(_FwdAlias, nn.Module):
         L.check(lib.swf_mlp_fwd(prec, C.byref(px), None, _ptr(xn), None, _ptr(ox), None, n, c, self.hidden_dims, ws, wsn, _stream(x.device)))
         return _to_nchw(ox)
 
-    def _one_grad(self, x: Tensor, s: str) -> Tensor:
+    def _one_drop(self, x: Tensor, s: str, drop: L.Dropout) -> Tensor:
+        """One stream with dropout (swf_mlp_fwd_drop, exact fp32): mask stream 0 for x, 1 for y, one seed for both."""
+        b, c, h, w = x.shape
+        xn = _to_nhwc(x)
+        ox = torch.empty_like(xn)
+        lib, n = L.lib(), b * h * w
+        f1, f2 = _lin(getattr(self, f"mlp_{s}_1")), _lin(getattr(self, f"mlp_{s}_2"))
+        ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, self.hidden_dims), x.device)
+        L.check(lib.swf_mlp_fwd_drop(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(ox), n, c, self.hidden_dims, C.byref(drop), _MASK_STREAM[s],
+                                     ws, wsn, _stream(x.device)))
+        return _to_nchw(ox)
+
+    def _one_grad(self, x: Tensor, s: str, drop: Optional[L.Dropout]) -> Tensor:
         c1, c2 = getattr(self, f"mlp_{s}_1"), getattr(self, f"mlp_{s}_2")
-        return _MlpFunction.apply(self, s, x, c1.weight, c1.bias, c2.weight, c2.bias)
+        return _MlpFunction.apply(self, s, drop, x, c1.weight, c1.bias, c2.weight, c2.bias)
 
     def forward(self, x, y=None):
         """a003:46-50 through swf_mlp_fwd: both streams in one call (one launch of the fused kernel's MLP half at level-0 width).  With
-        torch.autograd recording each stream is a differentiable call (swf_mlp_bwd: exact fp32)."""
+        torch.autograd recording each stream is a differentiable call (swf_mlp_bwd: exact fp32).  In train() with drop_ratio > 0 both
+        directions run swf_mlp_{fwd,bwd}_drop (exact fp32), with or without grad."""
+        drop = _dropout(self, 0.0, 0.0, self.drop_ratio)
+        dual = self.use_dual_path or y is not None
         if _wants_grad(self, x, y):
             _require_elu(self.activation_func)
-            if self.training and self.drop_ratio:
-                raise NotImplementedError("dropout > 0 in training mode is outside the HIP path")
-            if self.use_dual_path or y is not None:
-                return self._one_grad(x, "x"), self._one_grad(y, "y")
-            return self._one_grad(x, "x")
+            if dual:
+                return self._one_grad(x, "x", drop), self._one_grad(y, "y", drop)
+            return self._one_grad(x, "x", drop)
         _check_forward_only(self, x, y)
         _require_elu(self.activation_func)
-        if self.training and self.drop_ratio:
-            raise NotImplementedError("dropout > 0 in training mode is outside the forward-only HIP path")
-        dual = self.use_dual_path or y is not None
+        if drop is not None:
+            if dual:
+                return self._one_drop(x, "x", drop), self._one_drop(y, "y", drop)
+            return self._one_drop(x, "x", drop)
         b, c, h, w = x.shape
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
         ox = torch.empty_like(xn)
@@ -449,8 +509,9 @@ class AddAndLayerNormWithOtherModule(_FwdAlias, nn.Module):
     def forward(self, x, y=None):
         om = self.other_module
         dual = self.use_dual_path or y is not None
-        if _wants_grad(self, x, y):
-            # under torch.autograd the wrapper is composed of differentiable calls: LayerNorm, the other module, the residual add
+        if _wants_grad(self, x, y) or (isinstance(om, (AutoPathWinAtt, AutoPathMLP)) and _drops_in_training(om)):
+            # under torch.autograd the wrapper is composed of differentiable calls: LayerNorm, the other module, the residual add (and so
+            # is a train()-mode call whose other module drops: the fused half-block units have no masks)
             if not isinstance(om, (AutoPathWinAtt, AutoPathMLP)):
                 raise NotImplementedError("other_module must be AutoPathWinAtt or AutoPathMLP of this package")
             nx = _LayerNormFunction.apply(self.norm_layer_1, x, self.norm_layer_1.weight, self.norm_layer_1.bias)
@@ -502,15 +563,16 @@ class AddAndLayerNormWithOtherModule(_FwdAlias, nn.Module):
 # a005 / a009 / a012: blocks
 # ----------------------------------------------------------------------------------------------
 class _BasicBlockFunction(torch.autograd.Function):
-    """BasicBlock under torch.autograd: forward = the library's forward, backward = swf_basic_block_bwd (kernels_bwd.hip)."""
+    """BasicBlock under torch.autograd: forward = the library's forward, backward = swf_basic_block_bwd (kernels_bwd.hip).  With dropout
+    (`drop` not None) swf_basic_block_{fwd,bwd}_drop with the seed saved here: the backward regenerates the forward's masks."""
 
     @staticmethod
-    def forward(ctx, block, dual, x, y, *params):
-        ctx.block, ctx.dual = block, dual
+    def forward(ctx, block, dual, drop, x, y, *params):
+        ctx.block, ctx.dual, ctx.drop = block, dual, drop
         ctx.save_for_backward(x, y) if dual else ctx.save_for_backward(x)
         ctx.nparams = len(params)
         with torch.no_grad():
-            ox, oy = block._forward_nograd(x.detach(), y.detach() if dual else None, dual)
+            ox, oy = block._forward_nograd(x.detach(), y.detach() if dual else None, dual, drop)
         return (ox, oy) if dual else (ox,)
 
     @staticmethod
@@ -519,10 +581,10 @@ class _BasicBlockFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, y = saved[0], (saved[1] if dual else None)
         with torch.no_grad():
-            gx, gy, bufs = block._backward(x, y, gouts[0], gouts[1] if dual else None, dual)
+            gx, gy, bufs = block._backward(x, y, gouts[0], gouts[1] if dual else None, dual, ctx.drop)
         streams = ("x", "y") if dual else ("x",)
         pg = [g for s in streams for g in bufs[s]]
-        return (None, None, gx, gy, *pg)
+        return (None, None, None, gx, gy, *pg)
 
 
 class BasicBlock(_FwdAlias, nn.Module):
@@ -602,23 +664,31 @@ class BasicBlock(_FwdAlias, nn.Module):
         g.fc1, g.fc2 = L.Linear(ptr(bufs[13]), ptr(bufs[14])), L.Linear(ptr(bufs[15]), ptr(bufs[16]))
         return g
 
-    def _forward_nograd(self, x, y, dual):
+    def _forward_nograd(self, x, y, dual, drop: Optional[L.Dropout] = None):
         b, c, h, w = x.shape
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
         ox = torch.empty_like(xn)
         oy = torch.empty_like(yn) if dual else None
-        desc = self._desc(self.precision)
         px = self._stream_params("x")
         py = self._stream_params("y") if dual else None
         lib = L.lib()
+        if drop is not None:   # the exact tier whatever self.precision says: the fused fast kernels have no masks
+            desc = self._desc("fp32")
+            ws, wsn = _workspace(lib.swf_basic_block_drop_workspace_bytes(C.byref(desc), b, h, w), x.device)
+            L.check(lib.swf_basic_block_fwd_drop(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn),
+                                                 _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None, b, h, w,
+                                                 C.byref(drop), ws, wsn, _stream(x.device)))
+            return (_to_nchw(ox), _to_nchw(oy)) if dual else (_to_nchw(ox), None)
+        desc = self._desc(self.precision)
         ws, wsn = _workspace(lib.swf_basic_block_workspace_bytes(C.byref(desc), b, h, w), x.device)
         L.check(lib.swf_basic_block_fwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn),
                                         _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None,
                                         b, h, w, ws, wsn, _stream(x.device)))
         return (_to_nchw(ox), _to_nchw(oy)) if dual else (_to_nchw(ox), None)
 
-    def _backward(self, x, y, gox, goy, dual):
-        """dL/d(x, y) and the parameter gradients of both streams through swf_basic_block_bwd (exact fp32, forward recomputed)."""
+    def _backward(self, x, y, gox, goy, dual, drop: Optional[L.Dropout] = None):
+        """dL/d(x, y) and the parameter gradients of both streams through swf_basic_block_bwd (exact fp32, forward recomputed; with
+        dropout swf_basic_block_bwd_drop, the same masks as the forward)."""
         b, c, h, w = x.shape
         dev = x.device
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
@@ -633,31 +703,42 @@ class BasicBlock(_FwdAlias, nn.Module):
         px = self._stream_params("x")
         py = self._stream_params("y") if dual else None
         lib = L.lib()
-        ws, wsn = _workspace(lib.swf_basic_block_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
-        L.check(lib.swf_basic_block_bwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None,
-                                        _ptr(gxo), _ptr(gyo) if dual else None, _ptr(gxi), _ptr(gyi) if dual else None,
-                                        C.byref(gs["x"]), C.byref(gs["y"]) if dual else None, b, h, w, ws, wsn, _stream(dev)))
+        if drop is not None:
+            ws, wsn = _workspace(lib.swf_basic_block_drop_workspace_bytes(C.byref(desc), b, h, w), dev)
+            L.check(lib.swf_basic_block_bwd_drop(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None,
+                                                 _ptr(gxo), _ptr(gyo) if dual else None, _ptr(gxi), _ptr(gyi) if dual else None,
+                                                 C.byref(gs["x"]), C.byref(gs["y"]) if dual else None, b, h, w, C.byref(drop), ws, wsn,
+                                                 _stream(dev)))
+        else:
+            ws, wsn = _workspace(lib.swf_basic_block_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
+            L.check(lib.swf_basic_block_bwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None,
+                                            _ptr(gxo), _ptr(gyo) if dual else None, _ptr(gxi), _ptr(gyi) if dual else None,
+                                            C.byref(gs["x"]), C.byref(gs["y"]) if dual else None, b, h, w, ws, wsn, _stream(dev)))
         return _to_nchw(gxi), (_to_nchw(gyi) if dual else None), bufs
 
     def forward(self, x, y=None):
+        """a005:127-145.  In train() with a dropout ratio > 0 the block runs swf_basic_block_fwd_drop (and under autograd
+        swf_basic_block_bwd_drop) in the exact fp32 tier whatever `precision` says, with or without grad; one seed per call
+        (last_dropout_seed) serves both streams (mask streams 0 and 1) and all four sites."""
         dual = self.use_dual_path or y is not None
+        drop = _dropout(self, self.attention_drop_ratio, self.linear_after_att_drop_ratio, self.mlp_drop_ratio)
         if torch.is_grad_enabled() and (x.requires_grad or (y is not None and y.requires_grad) or
                                         any(p.requires_grad for p in self.parameters())):
-            # autograd path: forward through the library as usual, backward through swf_basic_block_bwd (first stage of the training
-            # side: the block; patch layers, head and loss have no backward yet, so MyModel as a whole still raises)
+            # autograd path: forward through the library as usual, backward through swf_basic_block_bwd (kernels_bwd.hip)
             for t in (x, y):
                 if t is not None and t.dim() != 4:
                     raise ValueError(f"expected a 4-D (batch, channels, height, width) tensor, got shape {tuple(t.shape)}")
-            if self.training and (self.attention_drop_ratio or self.linear_after_att_drop_ratio or self.mlp_drop_ratio):
-                raise NotImplementedError("dropout > 0 in training mode is outside the HIP path")
             _require_elu(self.mlp_activation_func)
             self.check_input_compatibility_with_option(x=x, y=y)
             streams = ("x", "y") if dual else ("x",)
             params = [t for s in streams for t in self._grad_tensors(s)]
-            out = _BasicBlockFunction.apply(self, dual, x, y if dual else None, *params)
+            out = _BasicBlockFunction.apply(self, dual, drop, x, y if dual else None, *params)
             return (out[0], out[1]) if dual else out[0]
         _check_forward_only(self, x, y)
         self.check_input_compatibility_with_option(x=x, y=y)
+        if drop is not None:
+            ox, oy = self._forward_nograd(x, y, dual, drop)
+            return (ox, oy) if dual else ox
         b, c, h, w = x.shape
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
         ox = torch.empty_like(xn)
@@ -729,7 +810,9 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
         dual = self.use_dual_path
         if dual and y is None:
             raise ValueError("use_dual_path=True needs both x and y")
-        if _wants_grad(self, x, y):   # under autograd the four blocks run one by one (each differentiable: BasicBlock.forward)
+        if _wants_grad(self, x, y) or _drops_in_training(self):
+            # under autograd the four blocks run one by one (each differentiable: BasicBlock.forward), and so they do in train() with
+            # dropout (swf_block_pair4_fwd has no masks)
             for blk in blocks:
                 if dual:
                     x, y = blk(x, y)
@@ -1238,8 +1321,9 @@ class MyModel(_FwdAlias, nn.Module):
         """a013:209-230 module by module under torch.autograd (training side): every module's forward is a library
         call and its backward a library call of kernels_bwd.hip (exact fp32).  Both modes of the reference: under model.train() the
         head's BatchNorm normalises with the batch statistics and updates its running statistics (a016:137), under model.eval() it uses
-        the running statistics; dropout must be 0 (the reference's configuration, A000_CONFIG.py).  The one-call fused forward
-        (swf_model_forward) is not differentiable and is not used here."""
+        the running statistics.  Under model.train() the three dropout ratios apply in every block: a block with a ratio
+        > 0 runs the exact fp32 tier whatever the model's `precision` says (BasicBlock.forward), each block with a seed of its own drawn
+        from torch's CPU generator.  The one-call fused forward (swf_model_forward) is not differentiable and is not used here."""
         if in_x.shape != in_y.shape or in_x.shape[1] != self.in_dims_list[0]:
             raise ValueError(f"expected two (B,{self.in_dims_list[0]},H,W) tensors, got {tuple(in_x.shape)} and {tuple(in_y.shape)}")
         self.u_net_intermediate_result_recorder.delete_all()
@@ -1251,7 +1335,8 @@ class MyModel(_FwdAlias, nn.Module):
         # the module-level autograd Functions key on their inputs; an input that requires grad is kept as it is, so it gets its gradient
         x = in_x if in_x.requires_grad else in_x.detach().requires_grad_(True)
         y = in_y if in_y.requires_grad else in_y.detach().requires_grad_(True)
-        # the blocks run in the MODEL's tier here (their own .precision is what they run at when called on their own)
+        # the blocks run in the MODEL's tier here (their own .precision is what they run at when called on their own); a block that
+        # drops in train() ignores it and runs the exact tier (the fused fast kernels have no masks)
         blocks = [m for m in self.modules() if isinstance(m, BasicBlock)]
         own = [blk.precision for blk in blocks]
         for blk in blocks:

@@ -2,7 +2,9 @@
 parameter (exact fp32, atomics-free) + a plain SGD update, model.train() as the reference trains (a016:137).  Prints one JSON line.
 The loss is a smooth stand-in (mean squared distance to max(ir, vis)): the reference's loss needs kornia, absent here.
 
-    python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5]
+    python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5] [--drop P]
+
+--drop P sets the three dropout ratios (attention, projection, MLP) to P: every block then runs the exact-fp32 *_drop entries.
 """
 import argparse
 import json
@@ -23,12 +25,15 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--config", default="win8")
     ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--drop", type=float, default=0.0, help="attention_drop_ratio = linear_after_att_drop_ratio = mlp_drop_ratio")
     args = ap.parse_args()
     entry.build()
     from swin_unet_image_fusion_amd import CONFIGS, MyModel, load_recipe_into, synthetic_pair
     dev = torch.device("cuda:0")
     cfg = CONFIGS[args.config]
-    model = MyModel(**cfg.model_kwargs(nn.ELU(inplace=True)))
+    kw = cfg.model_kwargs(nn.ELU(inplace=True))
+    kw.update(attention_drop_ratio=args.drop, linear_after_att_drop_ratio=args.drop, mlp_drop_ratio=args.drop)
+    model = MyModel(**kw)
     load_recipe_into(model, seed=0, flavor="kaiming")
     model.to(dev).train()
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
@@ -51,7 +56,7 @@ def main():
             times["forward"] += t1 - t0; times["backward"] += t2 - t1; times["update"] += t3 - t2
     ms = {k: round(v / args.iters * 1e3, 2) for k, v in times.items()}
     total = sum(ms.values())
-    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, SGD",
+    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, SGD, dropout {args.drop}",
                       "ms": ms, "ms_per_step": round(total, 2), "pairs_per_s": round(args.batch / total * 1e3, 1),
                       "loss_first_last": [losses[0], losses[-1]]}))
 
