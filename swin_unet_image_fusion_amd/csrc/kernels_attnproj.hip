@@ -24,7 +24,6 @@ namespace swf {
 namespace {
 
 using namespace wf;
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kC = 384, kD = 48, kHeads = 8, kNS = 3, kVRS = 72, kLDO = kC + 8;
 constexpr size_t kVtBytes = size_t(kHeads) * kD * kVRS * 2, kBiasBytes = 2 * 2 * 16 * 64 * 4;
@@ -40,14 +39,6 @@ struct ApDev {
     const float* res[2]; float* out[2];
     int B, H, W, shift;
 };
-
-// position of key `tok` in a V^T image row: the order in which the score accumulators hold the keys (kernels_window.hip)
-__device__ __forceinline__ int vt_pos(int tok) {
-    const int k16 = tok & 15;
-    const int e = ((k16 >> 3) << 2) | (k16 & 3);
-    const int h = (k16 >> 2) & 1;
-    return (tok & 48) | (h << 3) | e;
-}
 
 #ifdef AP_PROBE   // tools/ap_probe.hip: wall-clock stamps (10 ns) of workgroup (AP_PROBE, 0, 0), wave 0
 __device__ unsigned long long ap_probe[16];
@@ -281,11 +272,6 @@ int launch_attnproj(const swf_block_desc& d, const AttnProjArgs& a, int nstream,
     const int ws = d.attn.win_h;
     if (!attnproj_supported(d) || a.H % ws || a.W % ws) return fail(SWF_ERR_UNSUPPORTED, "attnproj: shape not covered");
     if ((int64_t)a.B * a.H * a.W > INT32_MAX / kC) return fail(SWF_ERR_UNSUPPORTED, "attnproj: token count");
-    static hipError_t attr_err = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_proj_kernel<8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_proj_kernel<7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLds);
-    }();
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn_proj): %s", hipGetErrorString(attr_err));
     ApDev dv{};
     for (int s = 0; s < nstream; ++s) {
         if (!a.q[s] || !a.k[s] || !a.v[s] || !a.wp_hi[s] || !a.wp_lo[s] || !a.table[s] || !a.res[s] || !a.out[s])
@@ -296,8 +282,13 @@ int launch_attnproj(const swf_block_desc& d, const AttnProjArgs& a, int nstream,
     }
     dv.B = a.B; dv.H = a.H; dv.W = a.W; dv.shift = a.shift;
     const int nwin = a.B * (a.H / ws) * (a.W / ws);
-    if (ws == 8) hipLaunchKernelGGL((attn_proj_kernel<8>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
-    else hipLaunchKernelGGL((attn_proj_kernel<7>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
+    if (ws == 8) {
+        SWF_TRY(raise_lds_limit<&attn_proj_kernel<8>>((int)kLds, "attn_proj"));
+        hipLaunchKernelGGL((attn_proj_kernel<8>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
+    } else {
+        SWF_TRY(raise_lds_limit<&attn_proj_kernel<7>>((int)kLds, "attn_proj"));
+        hipLaunchKernelGGL((attn_proj_kernel<7>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
+    }
     return check_launch("attn_proj");
 }
 

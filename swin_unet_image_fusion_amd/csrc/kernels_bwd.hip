@@ -1108,8 +1108,6 @@ int add_tensors(const float* a, const float* b, float* out, int64_t n, hipStream
 // form — a pixel sums over every (output pixel, tap) pair whose reflected source it is — so every sum has a fixed order.
 namespace {
 
-__device__ __forceinline__ int reflect2b(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
 __global__ __launch_bounds__(256) void head_t1_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ t1,
                                                        swf_head_params p, int B, int H, int W, int ks) {
     const int64_t total = (int64_t)B * H * W, e = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -1118,9 +1116,9 @@ __global__ __launch_bounds__(256) void head_t1_kernel(const float* __restrict__ 
     const int64_t b = e / ((int64_t)W * H);
     float a0 = p.conv1_b ? p.conv1_b[0] : 0.f, a1 = p.conv1_b ? p.conv1_b[1] : 0.f;
     for (int ky = 0; ky < ks; ++ky) {
-        const int yy = reflect2b(py + ky - r, H);
+        const int yy = reflect2(py + ky - r, H);
         for (int kx = 0; kx < ks; ++kx) {
-            const int xx = reflect2b(px + kx - r, W);
+            const int xx = reflect2(px + kx - r, W);
             const int64_t sidx = (b * H + yy) * W + xx;
             const float vx = x[sidx], vy = y[sidx];
             a0 = fmaf(p.conv1_w[((0 * 2 + 0) * ks + ky) * ks + kx], vx, a0);
@@ -1144,10 +1142,10 @@ __global__ __launch_bounds__(256) void head_conv_adjoint_kernel(const float* __r
     float acc[2] = {0.f, 0.f};
     for (int oy = max(0, py - 2 * r); oy <= min(H - 1, py + 2 * r); ++oy)
         for (int ky = 0; ky < ks; ++ky) {
-            if (reflect2b(oy + ky - r, H) != py) continue;
+            if (reflect2(oy + ky - r, H) != py) continue;
             for (int ox = max(0, px - 2 * r); ox <= min(W - 1, px + 2 * r); ++ox)
                 for (int kx = 0; kx < ks; ++kx) {
-                    if (reflect2b(ox + kx - r, W) != px) continue;
+                    if (reflect2(ox + kx - r, W) != px) continue;
                     const int64_t o = (b * H + oy) * W + ox;
                     for (int co = 0; co < CO; ++co) {
                         const float gv = g[o * CO + co];
@@ -1175,7 +1173,7 @@ __global__ __launch_bounds__(256) void head_rows2_kernel(const float* __restrict
     float* row = rows + e * NC;
     for (int ky = 0; ky < ks; ++ky)
         for (int kx = 0; kx < ks; ++kx) {
-            const int64_t sidx = (b * H + reflect2b(py + ky - r, H)) * W + reflect2b(px + kx - r, W);
+            const int64_t sidx = (b * H + reflect2(py + ky - r, H)) * W + reflect2(px + kx - r, W);
             const float u0 = a0 * t1[2 * sidx] + c0, u1 = a1 * t1[2 * sidx + 1] + c1;
             row[(0 * ks + ky) * ks + kx] = g * (u0 > 0.f ? u0 : expm1f(u0));
             row[(1 * ks + ky) * ks + kx] = g * (u1 > 0.f ? u1 : expm1f(u1));
@@ -1201,7 +1199,7 @@ __global__ __launch_bounds__(256) void head_rows1_kernel(const float* __restrict
     float* row = rows + e * NC;
     for (int ky = 0; ky < ks; ++ky)
         for (int kx = 0; kx < ks; ++kx) {
-            const int64_t sidx = (b * H + reflect2b(py + ky - r, H)) * W + reflect2b(px + kx - r, W);
+            const int64_t sidx = (b * H + reflect2(py + ky - r, H)) * W + reflect2(px + kx - r, W);
             const float vx = x[sidx], vy = y[sidx];
             row[((0 * 2 + 0) * ks + ky) * ks + kx] = g0 * vx;
             row[((0 * 2 + 1) * ks + ky) * ks + kx] = g0 * vy;

@@ -15,9 +15,9 @@
 #include "kernels_window.h"
 #include "kernels_mlp.h"
 #include "kernels_qkvattn.h"
+#include "win_frag.h"
 
 #include <algorithm>
-#include <mutex>
 #include <cstdlib>
 
 #ifndef SWF_GEMM_ABL
@@ -26,25 +26,9 @@
 
 namespace swf {
 
-using bf16 = __bf16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+using namespace wf;
 
 namespace {
-
-// ELU(alpha = 1) with the hardware exp2 (absolute error ~1e-7: fast-tier grade)
-__device__ __forceinline__ float elu_1(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * 1.44269504088896341f) - 1.0f; }
-
-__device__ __forceinline__ void split_f4(const float4 v, bf16x4& hi, bf16x4& lo) {
-    const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        hi[i] = (bf16)f[i];
-        lo[i] = (bf16)(f[i] - (float)hi[i]);
-    }
-}
 
 struct SpProbDev {
     const bf16* a_hi; const bf16* a_lo; const bf16* w_hi; const bf16* w_lo;
@@ -199,20 +183,18 @@ __global__ __launch_bounds__(256) void gemm_sp_kernel(SpBatchDev batch, int M, i
             if (epi == SP_EPI_QKV16) {
                 const int which = prob % 3;
                 if (which == 2) {
-                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
                     const f16x4 h = {(_Float16)v.x, (_Float16)v.y, (_Float16)v.z, (_Float16)v.w};
                     *reinterpret_cast<f16x4*>(pr.o_hi + (int64_t)m * N + n) = h;
                 } else {
                     // Q (pre-scaled) and K in f16 too: the Q.K^T operands are 8x closer to fp32 than in bf16 at the same MFMA rate
-                    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
                     const float sc = which == 0 ? batch.qscale : 1.0f;
                     const f16x4 h = {(_Float16)(v.x * sc), (_Float16)(v.y * sc), (_Float16)(v.z * sc), (_Float16)(v.w * sc)};
                     *reinterpret_cast<f16x4*>(pr.o_hi + (int64_t)m * N + n) = h;
                 }
             } else if (epi == SP_EPI_ELU_SPLIT) {
-                v.x = elu_1(v.x); v.y = elu_1(v.y); v.z = elu_1(v.z); v.w = elu_1(v.w);
+                v.x = elu_fast(v.x); v.y = elu_fast(v.y); v.z = elu_fast(v.z); v.w = elu_fast(v.w);
                 bf16x4 hi, lo;
-                split_f4(v, hi, lo);
+                split4(v, hi, lo);
                 *reinterpret_cast<bf16x4*>(pr.o_hi + (int64_t)m * N + n) = hi;
                 *reinterpret_cast<bf16x4*>(pr.o_lo + (int64_t)m * N + n) = lo;
             } else {
@@ -258,7 +240,7 @@ __global__ __launch_bounds__(256) void split_planes_kernel(const float* __restri
                                                            bf16* __restrict__ lo, int64_t n4) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n4; e += (int64_t)gridDim.x * blockDim.x) {
         bf16x4 h, l;
-        split_f4(reinterpret_cast<const float4*>(src)[e], h, l);
+        split4(reinterpret_cast<const float4*>(src)[e], h, l);
         reinterpret_cast<bf16x4*>(hi)[e] = h;
         reinterpret_cast<bf16x4*>(lo)[e] = l;
     }
@@ -288,14 +270,7 @@ template <int WM, int WN>
 static int launch_sp_cfg(dim3 grid, hipStream_t stream, const SpBatchDev& dev, int M, int N, int K, int ldo, int epi, int splitk,
                          int kchunk) {
     constexpr int lds_bytes = 2 * (2 * 64 * WM * 64 + 2 * 64 * WN * 64);   // two stages
-    static std::once_flag once;   // > 64 KB of dynamic LDS needs the attribute once per kernel (thread-safe)
-    static hipError_t attr_err = hipSuccess;
-    if (lds_bytes > 65536) {
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_sp_kernel<WM, WN>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        });
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "gemm_sp: cannot raise the dynamic LDS limit to %d B", lds_bytes);
-    }
+    if (lds_bytes > 65536) SWF_TRY((raise_lds_limit<&gemm_sp_kernel<WM, WN>>(lds_bytes, "gemm_sp")));
     hipLaunchKernelGGL((gemm_sp_kernel<WM, WN>), grid, dim3(256), lds_bytes, stream, dev, M, N, K, ldo, epi, splitk, kchunk);
     return SWF_OK;
 }

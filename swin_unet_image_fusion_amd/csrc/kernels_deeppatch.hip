@@ -22,7 +22,6 @@ namespace swf {
 namespace {
 
 using namespace wf;
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 struct DpArgs {
     const float* in[2]; float* out[2]; const float* skip[2];
@@ -36,9 +35,6 @@ struct DpArgs {
     // decoder, whole-row form: packed weights of the block that runs next, touched at the end (per-XCD L2 warm-up, kernels_window.hip), or nullptr
     const char* warm[2]; int warm_bytes;
 };
-
-__device__ __forceinline__ int reflect_idx(int i, int n) { return i < n ? i : 2 * n - 2 - i; }   // bottom / right only
-__device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
 
 #ifdef DP_PROBE   // tools/dp_probe.hip: wall-clock stamps (10 ns) of workgroup (DP_PROBE, 0), thread 0
 __device__ unsigned long long dp_probe[16];
@@ -134,8 +130,8 @@ __global__ __launch_bounds__(64 * NW) void deep_patch_kernel(DpArgs a) {
                 src = a.in[s] + ((size_t)(rb * a.H + ry) * a.W + rx) * CIN + col;   // crop: only Hm x Wm of the H x W map is read
             } else {
                 const int pq = col / CIN, c = col - pq * CIN, ph = pq >> 1, pw = pq & 1;   // 2x2 merging: (ph, pw, channel) order
-                const int my = reflect_idx(ry, a.Hm), mx = reflect_idx(rx, a.Wm);            // window pad of the merged map
-                const int iy = reflect_idx(2 * my + ph, a.H), ix = reflect_idx(2 * mx + pw, a.W);   // merge pad of the input
+                const int my = reflect_br(ry, a.Hm), mx = reflect_br(rx, a.Wm);            // window pad of the merged map
+                const int iy = reflect_br(2 * my + ph, a.H), ix = reflect_br(2 * mx + pw, a.W);   // merge pad of the input
                 src = a.in[s] + ((size_t)(rb * a.H + iy) * a.W + ix) * CIN + c;
             }
             v[i] = *reinterpret_cast<const float4*>(src);
@@ -290,7 +286,6 @@ __global__ __launch_bounds__(64 * NW) void deep_patch_kernel(DpArgs a) {
         if (live) {
             const float sc = which == 0 ? a.qscale : 1.0f;
             f16* dst = a.qo[s][which] + (size_t)m * K + 32 * ct0 - which * K;
-            typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
             for (int i = 0; i < NO; ++i) {
                 const f16x4 h = {(f16)(v[i][0] * sc), (f16)(v[i][1] * sc), (f16)(v[i][2] * sc), (f16)(v[i][3] * sc)};
@@ -551,9 +546,7 @@ int launch_t(const DpArgs& a, int nstream, hipStream_t stream) {
     constexpr int KC = K > 384 ? 384 : K, MR = 32 * MT;
     constexpr size_t img = size_t(2) * MR * (KC + 8) * 2, outb = size_t(MR) * (N + 4) * 4, lds = img > outb ? img : outb;
     static_assert(lds <= 160 * 1024, "LDS");
-    static hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&deep_patch_kernel<K, N, MT, NW, DEC, NTOT>),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(deep_patch): %s", hipGetErrorString(attr_err));
+    SWF_TRY((raise_lds_limit<&deep_patch_kernel<K, N, MT, NW, DEC, NTOT>>((int)lds, "deep_patch")));
     hipLaunchKernelGGL((deep_patch_kernel<K, N, MT, NW, DEC, NTOT>), dim3((a.M + MR - 1) / MR, nstream, NTOT / N), dim3(64 * NW), lds, stream, a);
     return check_launch("deep_patch");
 }

@@ -8,9 +8,11 @@
 
 #include <algorithm>
 
+#include "win_frag.h"
+
 namespace swf {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
+using namespace wf;
 
 __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expm1f(v); }
 
@@ -121,19 +123,7 @@ int launch_gemm_f32(const GemmBatch& batch, int nprob, int M, int N, int K, int 
 // relative error — fp32-grade at 3/16 of the f32-MFMA cost; gfx950 has no xf32/tf32).
 // 64x64 tile, K staged 32 at a time, next tile's global loads issued before the MFMAs of the current.
 // ------------------------------------------------------------------------------------------
-using bf16_t = __bf16;
-typedef bf16_t bf16x8_t __attribute__((ext_vector_type(8)));
-typedef bf16_t bf16x4_t __attribute__((ext_vector_type(4)));
 constexpr int XBK = 32, XLD = XBK + 8;   // 80-B rows: conflict-free ds_read_b128
-
-__device__ __forceinline__ void split4(const float4 v, bf16x4_t& hi, bf16x4_t& lo) {
-    const float f[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        hi[i] = (bf16_t)f[i];
-        lo[i] = (bf16_t)(f[i] - (float)hi[i]);
-    }
-}
 
 // split-K: blockIdx.z = problem * splitk + slice; a slice covers kchunk (multiple of 32) of K and, when
 // splitk > 1, writes its raw partial tile to batch.scratch[(z)][M][N]; gemm_splitk_reduce_kernel sums the
@@ -143,7 +133,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M
     const int prob = blockIdx.z / splitk, slice = blockIdx.z % splitk;
     const GemmProb pr = batch.p[prob];
     const int kbeg = slice * kchunk, kend = min(K, kbeg + kchunk);
-    __shared__ __attribute__((aligned(16))) bf16_t As_hi[GBM * XLD], As_lo[GBM * XLD], Ws_hi[GBN * XLD], Ws_lo[GBN * XLD];
+    __shared__ __attribute__((aligned(16))) bf16 As_hi[GBM * XLD], As_lo[GBM * XLD], Ws_hi[GBN * XLD], Ws_lo[GBN * XLD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wr = wave >> 1, wc = wave & 1;
     const int brow = blockIdx.x * GBM, bcol = blockIdx.y * GBN;
@@ -175,15 +165,15 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M
             v1 = make_float4(t[4], t[5], t[6], t[7]);
         }
     };
-    auto stash = [&](bf16_t* hi_img, bf16_t* lo_img, const float4& v0, const float4& v1) {
-        bf16x4_t h0, l0, h1, l1;
+    auto stash = [&](bf16* hi_img, bf16* lo_img, const float4& v0, const float4& v1) {
+        bf16x4 h0, l0, h1, l1;
         split4(v0, h0, l0);
         split4(v1, h1, l1);
-        bf16x8_t h, l;
+        bf16x8 h, l;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { h[i] = h0[i]; h[4 + i] = h1[i]; l[i] = l0[i]; l[4 + i] = l1[i]; }
-        *reinterpret_cast<bf16x8_t*>(hi_img + lr * XLD + lk) = h;
-        *reinterpret_cast<bf16x8_t*>(lo_img + lr * XLD + lk) = l;
+        *reinterpret_cast<bf16x8*>(hi_img + lr * XLD + lk) = h;
+        *reinterpret_cast<bf16x8*>(lo_img + lr * XLD + lk) = l;
     };
 
     float4 a0, a1, w0, w1;
@@ -198,16 +188,16 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M
             load8(pr.A, arow, a_in, vecA, k0 + XBK + lk, a0, a1);
             load8(pr.W, wrow, w_in, vecW, k0 + XBK + lk, w0, w1);
         }
-        bf16x8_t ah[2], al[2], bh[2], bl[2];
+        bf16x8 ah[2], al[2], bh[2], bl[2];
 #pragma unroll
         for (int m = 0; m < 2; ++m) {
-            ah[m] = *reinterpret_cast<const bf16x8_t*>(As_hi + (wr * 32 + m * 16 + fr) * XLD + 8 * fq);
-            al[m] = *reinterpret_cast<const bf16x8_t*>(As_lo + (wr * 32 + m * 16 + fr) * XLD + 8 * fq);
+            ah[m] = *reinterpret_cast<const bf16x8*>(As_hi + (wr * 32 + m * 16 + fr) * XLD + 8 * fq);
+            al[m] = *reinterpret_cast<const bf16x8*>(As_lo + (wr * 32 + m * 16 + fr) * XLD + 8 * fq);
         }
 #pragma unroll
         for (int n = 0; n < 2; ++n) {
-            bh[n] = *reinterpret_cast<const bf16x8_t*>(Ws_hi + (wc * 32 + n * 16 + fr) * XLD + 8 * fq);
-            bl[n] = *reinterpret_cast<const bf16x8_t*>(Ws_lo + (wc * 32 + n * 16 + fr) * XLD + 8 * fq);
+            bh[n] = *reinterpret_cast<const bf16x8*>(Ws_hi + (wc * 32 + n * 16 + fr) * XLD + 8 * fq);
+            bl[n] = *reinterpret_cast<const bf16x8*>(Ws_lo + (wc * 32 + n * 16 + fr) * XLD + 8 * fq);
         }
 #pragma unroll
         for (int m = 0; m < 2; ++m)
@@ -326,10 +316,10 @@ __global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, i
     const LnGemmProb pr = batch.p[blockIdx.z];
     const int KP = (C + 31) / 32 * 32;          // K padded to the MFMA k-step
     const int ALD = KP + 8;                     // A image row stride (bf16): odd multiple of 16 B
-    bf16_t* a_hi = reinterpret_cast<bf16_t*>(lsm);
-    bf16_t* a_lo = a_hi + GBM * ALD;
-    bf16_t* w_hi = a_lo + GBM * ALD;            // [64][LLD] slab
-    bf16_t* w_lo = w_hi + GBN * LLD;
+    bf16* a_hi = reinterpret_cast<bf16*>(lsm);
+    bf16* a_lo = a_hi + GBM * ALD;
+    bf16* w_hi = a_lo + GBM * ALD;            // [64][LLD] slab
+    bf16* w_lo = w_hi + GBN * LLD;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int brow = blockIdx.x * GBM;
 
@@ -356,15 +346,15 @@ __global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, i
         const float4* g4 = reinterpret_cast<const float4*>(pr.gamma);
         const float4* b4 = reinterpret_cast<const float4*>(pr.beta);
         for (int ch = part; ch < (KP >> 2); ch += 4) {
-            bf16x4_t h = {0, 0, 0, 0}, l = {0, 0, 0, 0};
+            bf16x4 h = {0, 0, 0, 0}, l = {0, 0, 0, 0};
             if (live && ch < chunks) {
                 const float4 v = x[ch], gg = g4[ch], bb = b4[ch];
                 const float4 n = make_float4((v.x - mean) * rstd * gg.x + bb.x, (v.y - mean) * rstd * gg.y + bb.y,
                                              (v.z - mean) * rstd * gg.z + bb.z, (v.w - mean) * rstd * gg.w + bb.w);
                 split4(n, h, l);
             }
-            *reinterpret_cast<bf16x4_t*>(a_hi + row * ALD + ch * 4) = h;
-            *reinterpret_cast<bf16x4_t*>(a_lo + row * ALD + ch * 4) = l;
+            *reinterpret_cast<bf16x4*>(a_hi + row * ALD + ch * 4) = h;
+            *reinterpret_cast<bf16x4*>(a_lo + row * ALD + ch * 4) = l;
         }
     }
 
@@ -397,26 +387,26 @@ __global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, i
             __syncthreads();   // previous slab's fragment reads (and, first time, the A image writes) are done
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                bf16x4_t h, l;
+                bf16x4 h, l;
                 split4(wv[i], h, l);
-                *reinterpret_cast<bf16x4_t*>(w_hi + lr * LLD + lk + 4 * i) = h;
-                *reinterpret_cast<bf16x4_t*>(w_lo + lr * LLD + lk + 4 * i) = l;
+                *reinterpret_cast<bf16x4*>(w_hi + lr * LLD + lk + 4 * i) = h;
+                *reinterpret_cast<bf16x4*>(w_lo + lr * LLD + lk + 4 * i) = l;
             }
             __syncthreads();
             if (k0 + LBK < KP) wload(k0 + LBK);
 #pragma unroll
             for (int ks = 0; ks < LBK / 32; ++ks) {
                 if (k0 + ks * 32 >= KP) break;
-                bf16x8_t wh[2], wl[2], ah[2], al[2];
+                bf16x8 wh[2], wl[2], ah[2], al[2];
 #pragma unroll
                 for (int m = 0; m < 2; ++m) {   // MFMA A operand = W rows (output columns)
-                    wh[m] = *reinterpret_cast<const bf16x8_t*>(w_hi + (wr * 32 + m * 16 + fr) * LLD + ks * 32 + 8 * fq);
-                    wl[m] = *reinterpret_cast<const bf16x8_t*>(w_lo + (wr * 32 + m * 16 + fr) * LLD + ks * 32 + 8 * fq);
+                    wh[m] = *reinterpret_cast<const bf16x8*>(w_hi + (wr * 32 + m * 16 + fr) * LLD + ks * 32 + 8 * fq);
+                    wl[m] = *reinterpret_cast<const bf16x8*>(w_lo + (wr * 32 + m * 16 + fr) * LLD + ks * 32 + 8 * fq);
                 }
 #pragma unroll
                 for (int n = 0; n < 2; ++n) {   // MFMA B operand = activation rows
-                    ah[n] = *reinterpret_cast<const bf16x8_t*>(a_hi + (wc * 32 + n * 16 + fr) * ALD + k0 + ks * 32 + 8 * fq);
-                    al[n] = *reinterpret_cast<const bf16x8_t*>(a_lo + (wc * 32 + n * 16 + fr) * ALD + k0 + ks * 32 + 8 * fq);
+                    ah[n] = *reinterpret_cast<const bf16x8*>(a_hi + (wc * 32 + n * 16 + fr) * ALD + k0 + ks * 32 + 8 * fq);
+                    al[n] = *reinterpret_cast<const bf16x8*>(a_lo + (wc * 32 + n * 16 + fr) * ALD + k0 + ks * 32 + 8 * fq);
                 }
 #pragma unroll
                 for (int m = 0; m < 2; ++m)
@@ -471,12 +461,7 @@ int launch_lngemm_bf16x3(const LnGemmBatch& batch, int nprob, int M, int N, int 
     }
     const int KP = (C + 31) / 32 * 32;
     const size_t lds = (size_t)2 * GBM * (KP + 8) * 2 + (size_t)2 * GBN * LLD * 2;
-    static size_t lds_cap = 0;
-    if (lds > 64 * 1024 && lds > lds_cap) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lngemm_bf16x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(lngemm): %s", hipGetErrorString(e));
-        lds_cap = 160 * 1024;
-    }
+    if (lds > 64 * 1024) SWF_TRY(raise_lds_limit<&lngemm_bf16x3_kernel>(160 * 1024, "lngemm"));
     // column tiles per workgroup: walk several while the grid still oversubscribes the chip (amortises the prologue)
     const int row_tiles = cdiv(M, GBM), col_tiles = cdiv(N, GBN);
     int ct = 1;
@@ -560,10 +545,10 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnBatch batch, int64
             r.w = (v[i].w - mean) * rstd * g.w + b.w;
             if (elu) { r.x = elu1(r.x); r.y = elu1(r.y); r.z = elu1(r.z); r.w = elu1(r.w); }
             if (pr.out_hi) {
-                bf16x4_t hi, lo;
+                bf16x4 hi, lo;
                 split4(r, hi, lo);
-                reinterpret_cast<bf16x4_t*>(pr.out_hi + tok * C)[ch] = hi;
-                reinterpret_cast<bf16x4_t*>(pr.out_lo + tok * C)[ch] = lo;
+                reinterpret_cast<bf16x4*>(pr.out_hi + tok * C)[ch] = hi;
+                reinterpret_cast<bf16x4*>(pr.out_lo + tok * C)[ch] = lo;
             } else {
                 y[ch] = r;
             }
@@ -724,8 +709,6 @@ int launch_attn_core(const AttnCoreBatch& batch, int nprob, int ldq, int ldk, in
 // ------------------------------------------------------------------------------------------
 // patch merge gather / crop / unmerge scatter
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect_idx(int i, int n) { return i < n ? i : 2 * n - 2 - i; }  // bottom/right only
-
 // VEC = 4 when Cin % 4 == 0 (a float4 never straddles two source pixels), else 1.  32-bit index arithmetic
 // (the launcher falls back to VEC = 1 / 64-bit only through the generic path below when counts overflow).
 template <int VEC>
@@ -739,9 +722,9 @@ __global__ __launch_bounds__(256) void merge_gather_kernel(PtrPair pp, int B, in
         const int kc = (int)(e % Kv);
         const int n = (int)(e / Kv);                 // output token (fits 32 bits: checked by the launcher)
         const int ox = n % Wo, t = n / Wo, oy = t % Ho, b = t / Ho;
-        const int my = reflect_idx(oy, Hm), mx = reflect_idx(ox, Wm);   // window pad of the merged map
+        const int my = reflect_br(oy, Hm), mx = reflect_br(ox, Wm);   // window pad of the merged map
         const int c = kc % Cv, pq = kc / Cv, pw = pq % mw, ph = pq / mw;
-        const int iy = reflect_idx(my * mh + ph, H), ix = reflect_idx(mx * mw + pw, W);  // merge pad of the input
+        const int iy = reflect_br(my * mh + ph, H), ix = reflect_br(mx * mw + pw, W);  // merge pad of the input
         const int64_t src = (((int64_t)b * H + iy) * W + ix) * Cin + c * VEC;
         if constexpr (VEC == 4) *reinterpret_cast<float4*>(out + e * 4) = *reinterpret_cast<const float4*>(in + src);
         else out[e] = in[src];
@@ -771,7 +754,7 @@ __global__ __launch_bounds__(256) void reflect_pad_kernel(const float* __restric
         const int x = (int)(n % Wo); n /= Wo;
         const int y = (int)(n % Ho);
         const int b = (int)(n / Ho);
-        out[e] = in[(((int64_t)b * H + reflect_idx(y, H)) * W + reflect_idx(x, W)) * C + c];
+        out[e] = in[(((int64_t)b * H + reflect_br(y, H)) * W + reflect_br(x, W)) * C + c];
     }
 }
 
@@ -944,8 +927,6 @@ int launch_unmerge_scatter(const PtrPair& pp, int nprob, int B, int Hm, int Wm, 
 // ------------------------------------------------------------------------------------------
 // final head (a013:126-152); reflect on all four sides ('same' padding, padding_mode='reflect')
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect2(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
-
 __global__ __launch_bounds__(256) void head_conv1_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                          float* __restrict__ tmp, swf_head_params p, int B, int H, int W,
                                                          int ks) {

@@ -19,8 +19,9 @@
 #include "kernels_mlp.h"
 
 #include <algorithm>
-#include <mutex>
 #include <cstdlib>
+
+#include "win_frag.h"
 
 #ifdef SWF_MLP_PROBE   // tools/mlp_probe.hip: wall-clock stamps of workgroup (0,0,0) wave 0 at the phase boundaries
 __device__ unsigned long long swf_mlp_probe[64];
@@ -36,13 +37,7 @@ namespace swf {
 
 namespace {
 
-using bf16 = __bf16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr float kLog2e = 1.4426950408889634f;
-__device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
+using namespace wf;
 
 struct MlpArgs {
     const float* x[2]; float* out[2];
@@ -58,6 +53,7 @@ struct MlpArgs {
     const float* part0[2]; const float* part1[2]; const float* pbias[2]; float* x1[2];
 };
 
+// wf::mma3 on u32x4 fragments schedules this kernel's LDS reads and MFMAs differently (not instruction-identical): kept local
 __device__ __forceinline__ void mma3(f32x16& acc, const bf16x8 wh, const bf16x8 wl, const bf16x8 bh, const bf16x8 bl) {
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, bh, acc, 0, 0, 0);
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, bl, acc, 0, 0, 0);
@@ -560,14 +556,7 @@ int launch_c(const MlpArgs& a, int nstream, hipStream_t stream) {
     // A image + H image (NW = 4, 6) or A image with H laid over it + gamma / beta (NW = 8)
     constexpr int lds = NW == 8 ? TOK * (C + 8) * 2 * 2 + 2 * C * 4 : (TOK * (C + 8) + TOK * (32 * NW + 8)) * 2 * 2;
     if (NW == 8 && a.nchunks != 1) return fail(SWF_ERR_UNSUPPORTED, "mlp_fused: the 8-wave kernel takes one hidden chunk per workgroup");
-    static std::once_flag once;   // > 64 KB of dynamic LDS needs the attribute once per kernel (thread-safe)
-    static hipError_t attr_err = hipSuccess;
-    if (lds > 65536) {
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&mlp_fused_kernel<C, NW, TOK>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "mlp_fused: cannot raise the dynamic LDS limit to %d B", lds);
-    }
+    if (lds > 65536) SWF_TRY((raise_lds_limit<&mlp_fused_kernel<C, NW, TOK>>(lds, "mlp_fused")));
     dim3 grid((a.M + TOK - 1) / TOK, a.splits, nstream);
     hipLaunchKernelGGL((mlp_fused_kernel<C, NW, TOK>), grid, dim3(64 * NW), lds, stream, a);
     SWF_TRY(check_launch("mlp_fused"));

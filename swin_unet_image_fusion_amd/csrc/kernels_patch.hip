@@ -10,21 +10,15 @@
 #include "kernels_patch.h"
 
 #include <algorithm>
-#include <mutex>
 #include <cstdlib>
+
+#include "win_frag.h"
 
 namespace swf {
 
 namespace {
 
-using bf16 = __bf16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLog2e = 1.4426950408889634f;
-__device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
-__device__ __forceinline__ int reflect_br(int i, int n) { return i < n ? i : 2 * n - 2 - i; }   // bottom / right pad only
+using namespace wf;
 
 struct PatchArgs {
     const float* in[2]; float* out[2]; const float* skip[2];
@@ -290,14 +284,7 @@ template <int KS, int NT, int DEC, int VEC>
 int launch_cfg(const PatchArgs& a, int nstream, hipStream_t stream) {
     constexpr int KP = 32 * KS + 8;
     constexpr int lds = (16 * NT + 64) * KP * 2 * 2 + 3 * 16 * NT * 4;
-    static std::once_flag once;   // > 64 KB of dynamic LDS needs the attribute once per kernel (thread-safe)
-    static hipError_t attr_err = hipSuccess;
-    if (lds > 65536) {
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&patch_fused_kernel<KS, NT, DEC, VEC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        });
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "patch_fused: cannot raise the dynamic LDS limit to %d B", lds);
-    }
+    if (lds > 65536) SWF_TRY((raise_lds_limit<&patch_fused_kernel<KS, NT, DEC, VEC>>(lds, "patch_fused")));
     const int ntiles = (a.M + 63) / 64;
     // a few tiles per workgroup amortise the weight staging; at most ~8 resident workgroups per CU
     const int per_cu = std::max(1, std::min(8, 160 * 1024 / lds));

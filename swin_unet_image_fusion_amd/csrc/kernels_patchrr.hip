@@ -35,8 +35,6 @@ struct PRR {
     static constexpr size_t p_total = p_vec + size_t(3) * 2 * NV * 4;
 };
 
-__device__ __forceinline__ int reflect_br(int i, int n) { return i < n ? i : 2 * n - 2 - i; }   // bottom / right pad only
-
 // KS: 16-deep k-steps covering K; NT: 32-row tiles covering N; DEC: 0 merge, 1 unmerge; CIN1: encoder with one input channel
 // (K = 4 scalar gathers); TPW: 32-token tiles a wave carries through one pass over the weight fragments
 template <int KS, int NT, int DEC, int CIN1, int TPW>
@@ -284,15 +282,6 @@ __global__ __launch_bounds__(256) void patch_rr_pack_kernel(PrrPackArgs a) {
     }
 }
 
-int num_cus_prr() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 // the (k-steps, tiles) class of a layer, or false
 bool shape_class(int decoder, int Cin, int Cout, int mh, int mw, int* ks, int* nt) {
     if (mh != 2 || mw != 2 || Cin <= 0 || Cout <= 0) return false;
@@ -313,7 +302,7 @@ bool shape_class(int decoder, int Cin, int Cout, int mh, int mw, int* ks, int* n
 template <int KS, int NT, int DEC, int CIN1, int TPW>
 int launch_t(const PrrArgs& a, int nstream, hipStream_t stream) {
     const int ngroup = (a.M + 32 * TPW - 1) / (32 * TPW);
-    const int gx = std::max(1, std::min((ngroup + 3) / 4, 8 * num_cus_prr() / nstream));
+    const int gx = std::max(1, std::min((ngroup + 3) / 4, 8 * num_cus() / nstream));
     hipLaunchKernelGGL((patch_rr_kernel<KS, NT, DEC, CIN1, TPW>), dim3(gx, nstream), dim3(256), 0, stream, a);
     return check_launch("patch_rr");
 }

@@ -19,24 +19,12 @@
 
 #include <algorithm>
 
+#include "win_frag.h"
+
 namespace swf {
 namespace {
 
-using bf16 = __bf16;
-using f16 = _Float16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr float kLog2e = 1.4426950408889634f;
-
-__host__ __device__ constexpr int rho(int i, int hf) { return (i & 3) + 8 * (i >> 2) + 4 * hf; }
+using namespace wf;
 
 template <int C_>
 struct QA {
@@ -61,55 +49,6 @@ struct QaDev {
     float* part[2][2];   // [head group][stream]: projection partial sums [token][C] fp32 (nullptr: write O planes instead)
     int B, H, W, shift, cross, nstream;
 };
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// split-bf16 x3: small cross terms first
-__device__ __forceinline__ f32x16 mma3(u32x4 ahi, u32x4 alo, u32x4 bhi, u32x4 blo, f32x16 acc) {
-    acc = mfma_bf16(alo, bhi, acc);
-    acc = mfma_bf16(ahi, blo, acc);
-    acc = mfma_bf16(ahi, bhi, acc);
-    return acc;
-}
-__device__ __forceinline__ u32x4 pack8_f16(const float* v) {
-    u32x4 o;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const f16x2 h = {(f16)v[2 * p], (f16)v[2 * p + 1]};
-        o[p] = __builtin_bit_cast(unsigned, h);
-    }
-    return o;
-}
-// 8 fp32 values -> one k-step fragment in split-bf16 (hi = bf16(v), lo = bf16(v - hi))
-__device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo) {
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const bf16x2 h = {(bf16)v[2 * p], (bf16)v[2 * p + 1]};
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-        const bf16x2 l = {(bf16)(v[2 * p] - h0), (bf16)(v[2 * p + 1] - h1)};
-        hi[p] = hu;
-        lo[p] = __builtin_bit_cast(unsigned, l);
-    }
-}
-// a = the value of lanes 0..31 (in both halves), b = the value of lanes 32..63 (kernels_win24.hip)
-__device__ __forceinline__ void halves(float v, float& a, float& b) {
-    a = v;
-    b = v;
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-template <typename T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-#define QA_FENCE() asm volatile("" ::: "memory")
 
 #ifdef QA_PROBE   // diagnostic build: 10-ns wall-clock stamps of workgroup QA_PROBE, wave 0, into a buffer nothing else reads
 __device__ unsigned long long qa_probe[8];
@@ -197,7 +136,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QaDev a) {
         // (12 steps x ~0.7 us); the ring keeps 6 * PD loads (1 KB each) in flight per wave.  Fences pin the issue points.
 #pragma unroll
         for (int s = 0; s < KS; ++s) {
-            QA_FENCE();
+            SWF_WF_FENCE();
             const u32x4 xh = *reinterpret_cast<const u32x4*>(xq + s * 32), xl = *reinterpret_cast<const u32x4*>(xq + G::l_plane + s * 32);
             u32x4 kh = xh, kl = xl;
             if (cross) {
@@ -208,7 +147,7 @@ __global__ __launch_bounds__(512, 2) void qkv_attn_kernel(QaDev a) {
             aq = mma3(ws_[0], ws_[1], xh, xl, aq);   // [virtual channel][token]
             ak = mma3(ws_[2], ws_[3], kh, kl, ak);
             av = mma3(kh, kl, ws_[4], ws_[5], av);   // [token][virtual channel]: the accumulator registers are V^T's key slots
-            QA_FENCE();
+            SWF_WF_FENCE();
             if (s + PD < KS) {
 #pragma unroll
                 for (int m = 0; m < 3; ++m) { ws_[2 * m] = WFRAG(m, s + PD, 0); ws_[2 * m + 1] = WFRAG(m, s + PD, 1); }
@@ -458,11 +397,6 @@ int launch_qkvattn(const swf_block_desc& d, const QkvAttnArgs& a, int nstream, h
     const int wsd = d.attn.win_h;
     if (!qkvattn_supported(d) || a.H % wsd || a.W % wsd) return fail(SWF_ERR_UNSUPPORTED, "qkvattn: shape not covered");
     using G = QA<192>;
-    static hipError_t attr_err = [] {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_attn_kernel<192, 8>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::l_total);
-        return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&qkv_attn_kernel<192, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::l_total);
-    }();
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(qkv_attn): %s", hipGetErrorString(attr_err));
     QaDev dv{};
     for (int s = 0; s < nstream; ++s) {
         dv.packed[s] = static_cast<const char*>(a.packed[s]);
@@ -474,8 +408,13 @@ int launch_qkvattn(const swf_block_desc& d, const QkvAttnArgs& a, int nstream, h
         return fail(SWF_ERR_NULL, "qkvattn: projection partial buffers must be given for both head groups and streams or not at all");
     dv.B = a.B; dv.H = a.H; dv.W = a.W; dv.shift = a.shift; dv.cross = a.cross; dv.nstream = nstream;
     const int nwin = a.B * (a.H / wsd) * (a.W / wsd);
-    if (wsd == 8) hipLaunchKernelGGL((qkv_attn_kernel<192, 8>), dim3(nwin, nstream, 2), dim3(512), G::l_total, stream, dv);
-    else hipLaunchKernelGGL((qkv_attn_kernel<192, 7>), dim3(nwin, nstream, 2), dim3(512), G::l_total, stream, dv);
+    if (wsd == 8) {
+        SWF_TRY((raise_lds_limit<&qkv_attn_kernel<192, 8>>((int)G::l_total, "qkv_attn")));
+        hipLaunchKernelGGL((qkv_attn_kernel<192, 8>), dim3(nwin, nstream, 2), dim3(512), G::l_total, stream, dv);
+    } else {
+        SWF_TRY((raise_lds_limit<&qkv_attn_kernel<192, 7>>((int)G::l_total, "qkv_attn")));
+        hipLaunchKernelGGL((qkv_attn_kernel<192, 7>), dim3(nwin, nstream, 2), dim3(512), G::l_total, stream, dv);
+    }
     return check_launch("qkv_attn");
 }
 

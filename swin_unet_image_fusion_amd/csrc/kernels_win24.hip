@@ -31,39 +31,16 @@
 // v_mfma_f32_32x32x16_f16 (f16 operands are 8x closer to fp32 than bf16 at the same rate); LayerNorm statistics,
 // softmax, ELU, residual stream, accumulators fp32; exp via v_exp_f32 (Wq, bq and the bias matrix carry log2(e)).
 #include "kernels_win24.h"
+#include "win_frag.h"
 
 #include <algorithm>
 
 namespace swf {
 namespace {
 
-using bf16 = __bf16;
-using f16 = _Float16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace wf;
 
-constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-
-#ifndef W24_FOLD_MAX
-#define W24_FOLD_MAX 1   // S - max on the matrix pipe (second S^T MFMA with -max on the head's spare k slot)
-#endif
-#ifndef W24_MED3
-#define W24_MED3 1       // ELU in exp2 units through one v_med3 (fc1 packed with log2 e, fc2 with ln 2)
-#endif
-#ifndef W24_ACT_F16
-#define W24_ACT_F16 0    // A/B: activations of the linear layers as ONE f16 (weights split into f16 hi + lo, 2 MFMAs per k-step) instead of split-bf16 x3
-#endif
-#ifndef W24_WAVES
-#define W24_WAVES 3   // resident workgroups per CU = waves per SIMD (register budget 512 / W24_WAVES)
-#endif
-
-// row of accumulator register i in lane half hf (C/D map of the 32x32 MFMAs) == k index of element i & 7 of k-step i >> 3
-__host__ __device__ constexpr int rho(int i, int hf) { return (i & 3) + 8 * (i >> 2) + 4 * hf; }
+constexpr int W24_WAVES = 3;   // resident workgroups per CU = waves per SIMD (register budget 512 / W24_WAVES)
 
 template <int HID_>
 struct G24 {
@@ -108,87 +85,6 @@ struct Win24Args {
 //   W24_MLP    x + fc2(ELU(fc1(LN2 x))) — AddAndLayerNormWithOtherModule around AutoPathMLP (a004:29-38, a003:46-50); with RAW:
 //              fc2(ELU(fc1 x)) — AutoPathMLP.forward.  Tokens are a flat list (no windows): 64 per workgroup step and stream
 constexpr int W24_BLOCK = 0, W24_ATTN = 1, W24_MLP = 2;
-
-__device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// acc += a . b over one 16-deep k-step with split-bf16 operands (a = a_hi + a_lo, b = b_hi + b_lo): three MFMAs, small cross
-// terms first so they are not absorbed by the large hi.hi partial sums
-template <bool WEIGHT_IS_A = true>
-__device__ __forceinline__ f32x16 mma3(u32x4 ahi, u32x4 alo, u32x4 bhi, u32x4 blo, f32x16 acc) {
-    if constexpr (W24_ACT_F16) {   // the activation operand is a single f16 fragment (its "lo" is unused), the weight f16 hi + lo
-        if constexpr (WEIGHT_IS_A) {
-            acc = mfma_f16(alo, bhi, acc);
-            acc = mfma_f16(ahi, bhi, acc);
-        } else {
-            acc = mfma_f16(ahi, blo, acc);
-            acc = mfma_f16(ahi, bhi, acc);
-        }
-        return acc;
-    }
-    acc = mfma_bf16(alo, bhi, acc);
-    acc = mfma_bf16(ahi, blo, acc);
-    acc = mfma_bf16(ahi, bhi, acc);
-    return acc;
-}
-
-__device__ __forceinline__ u32x4 pack8_f16(const float* v);
-// 8 fp32 values -> one k-step fragment in split-bf16 (hi = bf16(v), lo = bf16(v - hi))
-__device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo) {
-    if constexpr (W24_ACT_F16) {
-        hi = pack8_f16(v);
-        lo = hi;   // unused
-        return;
-    }
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const bf16x2 h = {(bf16)v[2 * p], (bf16)v[2 * p + 1]};
-        const unsigned hu = __builtin_bit_cast(unsigned, h);
-        const float h0 = __builtin_bit_cast(float, hu << 16), h1 = __builtin_bit_cast(float, hu & 0xffff0000u);
-        const bf16x2 l = {(bf16)(v[2 * p] - h0), (bf16)(v[2 * p + 1] - h1)};
-        hi[p] = hu;
-        lo[p] = __builtin_bit_cast(unsigned, l);
-    }
-}
-__device__ __forceinline__ u32x4 pack8_f16(const float* v) {
-    u32x4 o;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const f16x2 h = {(f16)v[2 * p], (f16)v[2 * p + 1]};   // v_cvt_pk_f16_f32 (round to nearest even)
-        o[p] = __builtin_bit_cast(unsigned, h);
-    }
-    return o;
-}
-
-// value of the same register in lane l ^ 32, combined with the own value.  v_permlane32_swap exchanges the upper half of its
-// first operand with the lower half of its second: with both = v, a = [v_lo, v_lo] and b = [v_hi, v_hi] afterwards.
-// (inline asm: hipcc 7.2 folds the builtin's second result into the first; the s_nop covers the VALU-write -> permlane hazard)
-__device__ __forceinline__ void halves(float v, float& a, float& b) {
-    a = v;
-    b = v;
-    asm("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
-}
-__device__ __forceinline__ float sum_halves(float v) { float a, b; halves(v, a, b); return a + b; }
-__device__ __forceinline__ float max_halves(float v) { float a, b; halves(v, a, b); return __builtin_fmaxf(a, b); }
-
-// The weight fragments are loop-invariant loads: without a fence hipcc hoists them out of the window loop (or to the top of
-// an iteration) and spills.  A compiler-only barrier, no instruction.
-#define W24_FENCE() asm volatile("" ::: "memory")
-
-// A pointer that is the same in every lane of the wave but derived from the wave index: made provably uniform so that hipcc
-// keeps it in SGPRs and addresses fragments as (scalar base + lane offset + immediate) instead of holding a 64-bit per-lane
-// address per fragment group in VGPRs across the window loop.
-template <typename T>
-__device__ __forceinline__ T* uniform_ptr(T* p) {
-    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-    return reinterpret_cast<T*>(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
 // LayerNorm (eps 1e-5, biased variance) of the lane's token — 12 of its 24 channels sit in this lane (registers 0..11 of
 // `res`), the other 12 in lane l ^ 32 — straight into the split-bf16 B / A operand fragments of the next linear layer.
@@ -267,7 +163,7 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
         // S - max on the matrix pipe instead of 32 subtractions on the (saturated) vector pipe: the head's spare k slot (virtual
         // channel 4h+3) is 1 in every K row and -max (rounded to f16: softmax is shift-invariant, any per-query constant
         // near the maximum serves) in the Q fragment, and the scores are computed a second time
-        if constexpr (W24_FOLD_MAX) {
+        {
             const u32x4 ka0 = ksrc[(0 * 2 + s) * 64], ka1 = ksrc[(1 * 2 + s) * 64];
             const f16 nm = (f16)(-mx);
             const unsigned nmb = keep ? (unsigned)__builtin_bit_cast(unsigned short, nm) : 0u;
@@ -276,9 +172,6 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
             qm[2 * sub + 1] = (keep ? qf[s][2 * sub + 1] : 0u) | (nmb << 16);
             s0 = mfma_f16(ka0, qm, bias[0]);
             s1 = mfma_f16(ka1, qm, bias[1]);
-        } else {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { s0[i] -= mx; s1[i] -= mx; }
         }
         // O^T tile of this head = V^T . P^T over the 64 keys; P = exp2(S - max) in f16, one pv-step (16 keys = registers
         // 8s'.. of key tile kt) at a time: the exponentials of step ps+1 issue under the MFMA of step ps
@@ -364,7 +257,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
 
     int it = 0;
     for (int win = blockIdx.x; win < nwin; win += gridDim.x, ++it) {
-        W24_FENCE();
+        SWF_WF_FENCE();
         const int b = win / npi, wrem = win - b * npi;
         const int wy = wrem / nwx, wx = wrem - wy * nwx;
         const int buf = it & 1;
@@ -422,7 +315,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
                 qf[0] = pack8_f16(t);
                 qf[1] = pack8_f16(t + 8);
             }
-            W24_FENCE();
+            SWF_WF_FENCE();
             if (!(RAW && ws == 0)) {   // RAW: the query stream's tokens are nobody's keys
                 float t[16];
                 acc = zero16;
@@ -433,11 +326,11 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
                 u32x4* kdst = kimg + (((buf * 2 + kvs) * 2 + qb) * 2) * 64 + lane;
                 kdst[0] = pack8_f16(t);
                 kdst[64] = pack8_f16(t + 8);
-                W24_FENCE();
+                SWF_WF_FENCE();
                 // V: tokens in rows (A = x fragments, B = weight fragments): register i of lane (channel r, hf) is token rho(i, hf)
                 acc = zero16;
 #pragma unroll
-                for (int s = 0; s < 2; ++s) acc = mma3<false>(xh[s], xl[s], WK(G::F_QKV + 8 + 2 * s), WK(G::F_QKV + 9 + 2 * s), acc);
+                for (int s = 0; s < 2; ++s) acc = mma3(xh[s], xl[s], WK(G::F_QKV + 8 + 2 * s), WK(G::F_QKV + 9 + 2 * s), acc);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) t[i] = acc[i];
                 u32x4* vdst = vimg + ((buf * 2 + kvs) * 4 + 2 * qb) * 64 + lane;
@@ -472,7 +365,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
         }
 
         // ---- normalise, output projection + bias + residual: res is the C operand ----
-        W24_FENCE();
+        SWF_WF_FENCE();
         if constexpr (RAW) res = zero16;
         else load_rows(res);
         {
@@ -486,7 +379,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
             u32x4 oh[2], ol[2];
             split8(t, oh[0], ol[0]);
             split8(t + 8, oh[1], ol[1]);
-            W24_FENCE();
+            SWF_WF_FENCE();
 #pragma unroll
             for (int s = 0; s < 2; ++s) res = mma3(WF(G::F_P + 2 * s), WF(G::F_P + 2 * s + 1), oh[s], ol[s], res);
         }
@@ -501,7 +394,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
             else layernorm_frags(res, vec, G::V_LN2G, G::V_LN2B, xh, xl);
 #pragma unroll
             for (int tI = 0; tI < G::NT1; ++tI) {
-                W24_FENCE();
+                SWF_WF_FENCE();
                 f32x16 acc = zero16;
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
@@ -514,12 +407,8 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
 #pragma unroll
                 for (int i = 0; i < 16; ++i) {
                     const float u = acc[i];
-                    if constexpr (W24_MED3) {
-                        const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                        e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                    } else {
-                        e[i] = u > 0.f ? u : __builtin_amdgcn_exp2f(u * kLog2e) - 1.0f;
-                    }
+                    const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
+                    e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
                 }
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
@@ -527,7 +416,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
                     if (u < G::KU) {
                         u32x4 hh, hl;
                         split8(e + 8 * s2, hh, hl);
-                        W24_FENCE();
+                        SWF_WF_FENCE();
                         res = mma3(WF(G::F_W2 + 2 * u), WF(G::F_W2 + 2 * u + 1), hh, hl, res);
                     }
                 }
@@ -608,7 +497,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
     __syncthreads();
 
     for (int win = blockIdx.x; win < nwin; win += gridDim.x) {
-        W24_FENCE();
+        SWF_WF_FENCE();
         const int b = win / npi, wrem = win - b * npi;
         const int wy = wrem / nwx, wx = wrem - wy * nwx;
         // byte offset of the lane's first float4 of its token in tile j: window row 2j + (r >> 4), column r & 15; the cyclic
@@ -667,7 +556,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
                 kdst[64] = pack8_f16(t + 8);
                 acc = zero16;
 #pragma unroll
-                for (int s = 0; s < 2; ++s) acc = mma3<false>(xh[s], xl[s], wv[2 * s], wv[2 * s + 1], acc);
+                for (int s = 0; s < 2; ++s) acc = mma3(xh[s], xl[s], wv[2 * s], wv[2 * s + 1], acc);
 #pragma unroll
                 for (int i = 0; i < 16; ++i) t[i] = acc[i];
                 u32x4* vdst = vimg + (kvs * 16 + 2 * j) * 64 + lane;
@@ -765,7 +654,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
 
             // ---- normalise, output projection + bias + residual ----
             f32x16 res;
-            W24_FENCE();
+            SWF_WF_FENCE();
             load_rows(res, tokoff);
             {
                 float t[16];
@@ -778,7 +667,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
                 u32x4 oh[2], ol[2];
                 split8(t, oh[0], ol[0]);
                 split8(t + 8, oh[1], ol[1]);
-                W24_FENCE();
+                SWF_WF_FENCE();
 #pragma unroll
                 for (int s = 0; s < 2; ++s) res = mma3(WF(G::F_P + 2 * s), WF(G::F_P + 2 * s + 1), oh[s], ol[s], res);
             }
@@ -788,7 +677,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
                 layernorm_frags(res, vec, G::V_LN2G, G::V_LN2B, xh, xl);
 #pragma unroll
                 for (int tI = 0; tI < G::NT1; ++tI) {
-                    W24_FENCE();
+                    SWF_WF_FENCE();
                     f32x16 acc = zero16;
 #pragma unroll
                     for (int s = 0; s < 2; ++s)
@@ -797,12 +686,8 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {
                         const float u = acc[i];
-                        if constexpr (W24_MED3) {
-                            const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                            e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                        } else {
-                            e[i] = u > 0.f ? u : __builtin_amdgcn_exp2f(u * kLog2e) - 1.0f;
-                        }
+                        const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
+                        e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
                     }
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
@@ -810,7 +695,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
                         if (u < G::KU) {
                             u32x4 hh, hl;
                             split8(e + 8 * s2, hh, hl);
-                            W24_FENCE();
+                            SWF_WF_FENCE();
                             res = mma3(WF(G::F_W2 + 2 * u), WF(G::F_W2 + 2 * u + 1), hh, hl, res);
                         }
                     }
@@ -883,21 +768,16 @@ __global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
             const int g = f - G::F_W1, t = g >> 2, st = (g >> 1) & 1;
             hl = g & 1;
             const int k = rho(8 * st + e, hf), hid = 32 * t + r;
-            if (hid < HID) val = (k < 24 ? lin(p.fc1, hid, k, 24) : (k == 24 ? bia(p.fc1, hid) : 0.f)) * (W24_MED3 ? kLog2e : 1.0f);   // exp2 units (ELU in the kernel)
+            if (hid < HID) val = (k < 24 ? lin(p.fc1, hid, k, 24) : (k == 24 ? bia(p.fc1, hid) : 0.f)) * kLog2e;   // exp2 units (ELU in the kernel)
             else if (G::ONES_H && hid == HID && k == 24) val = 1.0f;   // u = 1 -> h' = 1: the constant the fc2 bias rides on
         } else {   // fc2: row r = output channel; k-step u covers hidden units 32(u>>1) + rho(8(u&1) + e, hf)
             const int g = f - G::F_W2, u = g >> 1;
             hl = g & 1;
             const int hid = 32 * (u >> 1) + rho(8 * (u & 1) + e, hf);
-            if (r < 24) val = hid < HID ? lin(p.fc2, r, hid, HID) * (W24_MED3 ? kLn2 : 1.0f) : ((G::ONES_H && hid == HID) ? bia(p.fc2, r) : 0.f);   // h' = ELU log2(e)
+            if (r < 24) val = hid < HID ? lin(p.fc2, r, hid, HID) * kLn2 : ((G::ONES_H && hid == HID) ? bia(p.fc2, r) : 0.f);   // h' = ELU log2(e)
         }
-        if constexpr (W24_ACT_F16) {
-            const f16 hi = (f16)val;
-            reinterpret_cast<f16*>(dst)[idx] = hl ? (f16)(val - (float)hi) : hi;
-        } else {
-            const bf16 hi = (bf16)val;
-            reinterpret_cast<bf16*>(dst)[idx] = hl ? (bf16)(val - (float)hi) : hi;
-        }
+        const bf16 hi = (bf16)val;
+        reinterpret_cast<bf16*>(dst)[idx] = hl ? (bf16)(val - (float)hi) : hi;
     }
     float* vec = reinterpret_cast<float*>(dst + G::p_vec);
     for (int i = gtid; i < 128; i += gsz) {
@@ -934,15 +814,6 @@ __global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
         else if (qy < ws && qx < ws) v = p.attn.bias_table[(ky - qy + ws - 1) * tw + (kx - qx + ws - 1)] * kLog2e;
         bm[i] = v;
     }
-}
-
-int num_cus24() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
 }
 
 }  // namespace
@@ -996,7 +867,7 @@ int launch_win24_half(const swf_block_desc& d, int mode, int raw, const void* pa
         if ((int64_t)std::max(ntok_x, ntok_y) * 24 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win24_half: token count");
         nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
     }
-    const dim3 grid(std::min(nwin, W24_WAVES * num_cus24())), blk(256);
+    const dim3 grid(std::min(nwin, W24_WAVES * num_cus())), blk(256);
 #define W24_LAUNCH(HID_, WS_, MODE_, RAW_) hipLaunchKernelGGL((window24_kernel<HID_, WS_, MODE_, RAW_>), grid, blk, 0, stream, a)
     if (mode == W24_ATTN) {   // the MLP geometry is irrelevant: the hidden-96 image layout serves
         if (wsd == 8) { if (raw) W24_LAUNCH(96, 8, W24_ATTN, true); else W24_LAUNCH(96, 8, W24_ATTN, false); }
@@ -1026,17 +897,17 @@ int launch_win24(const swf_block_desc& d, const void* packed_x, const void* pack
     const int nwin = B * (H / wsd) * (W / wsd);
     if (wsd == 16) {   // 65 KB of LDS per workgroup: dynamic allocation, two workgroups per CU
         constexpr int lds = (int)G24<96>::l_total16;
-        static hipError_t attr_err = [] {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&window24w16_kernel<96>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&window24w16_kernel<4>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        }();
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window24w16): %s", hipGetErrorString(attr_err));
-        const int grid16 = std::min(nwin, 2 * num_cus24());
-        if (d.hidden == 96) hipLaunchKernelGGL((window24w16_kernel<96>), dim3(grid16), dim3(256), lds, stream, a);
-        else hipLaunchKernelGGL((window24w16_kernel<4>), dim3(grid16), dim3(256), lds, stream, a);
+        const int grid16 = std::min(nwin, 2 * num_cus());
+        if (d.hidden == 96) {
+            SWF_TRY(raise_lds_limit<&window24w16_kernel<96>>(lds, "window24w16"));
+            hipLaunchKernelGGL((window24w16_kernel<96>), dim3(grid16), dim3(256), lds, stream, a);
+        } else {
+            SWF_TRY(raise_lds_limit<&window24w16_kernel<4>>(lds, "window24w16"));
+            hipLaunchKernelGGL((window24w16_kernel<4>), dim3(grid16), dim3(256), lds, stream, a);
+        }
         return check_launch("window24w16");
     }
-    const int grid = std::min(nwin, W24_WAVES * num_cus24());   // resident workgroups per CU (register-limited)
+    const int grid = std::min(nwin, W24_WAVES * num_cus());   // resident workgroups per CU (register-limited)
     if (wsd == 8) {
         if (d.hidden == 96) hipLaunchKernelGGL((window24_kernel<96, 8>), dim3(grid), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL((window24_kernel<4, 8>), dim3(grid), dim3(256), 0, stream, a);

@@ -26,9 +26,7 @@ namespace {
 
 using namespace wf;
 
-#ifndef W48_WAVES
-#define W48_WAVES 2   // resident workgroups per CU = waves per SIMD
-#endif
+constexpr int W48_WAVES = 2;   // resident workgroups per CU = waves per SIMD
 
 template <int HID_>
 struct G48 {
@@ -866,15 +864,6 @@ __global__ __launch_bounds__(256) void pack48_kernel(Pack48Args a) {
     }
 }
 
-int num_cus48() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 }  // namespace
 
 bool win48_supported(const swf_block_desc& d) {
@@ -924,7 +913,7 @@ int launch_win48_half(const swf_block_desc& d, int mode, int raw, const void* pa
         if ((int64_t)std::max(ntok_x, ntok_y) * 48 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win48_half: token count");
         nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
     }
-    const dim3 grid(std::min(nwin, W48_WAVES * num_cus48())), blk(256);
+    const dim3 grid(std::min(nwin, W48_WAVES * num_cus())), blk(256);
 #define W48_LAUNCH(HID_, WS_, MODE_, RAW_) hipLaunchKernelGGL((window48_kernel<HID_, WS_, MODE_, RAW_>), grid, blk, 0, stream, a)
     if (mode == W48_ATTN) {   // the MLP geometry is irrelevant: the hidden-192 image layout serves
         if (wsd == 8) { if (raw) W48_LAUNCH(192, 8, W48_ATTN, true); else W48_LAUNCH(192, 8, W48_ATTN, false); }
@@ -953,17 +942,17 @@ int launch_win48(const swf_block_desc& d, const void* packed_x, const void* pack
     a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross;
     const int nwin = B * (H / wsd) * (W / wsd);
     if (wsd == 16) {   // 69 KB of LDS per workgroup (dynamic), two workgroups per CU, grid.y = stream
-        static hipError_t attr_err = [] {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&window48w16_kernel<192>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G48<192>::l_total16);
-            return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&window48w16_kernel<96>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G48<96>::l_total16);
-        }();
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window48w16): %s", hipGetErrorString(attr_err));
-        const int gx = std::min(nwin, num_cus48());
-        if (d.hidden == 192) hipLaunchKernelGGL((window48w16_kernel<192>), dim3(gx, 2), dim3(256), G48<192>::l_total16, stream, a);
-        else hipLaunchKernelGGL((window48w16_kernel<96>), dim3(gx, 2), dim3(256), G48<96>::l_total16, stream, a);
+        const int gx = std::min(nwin, num_cus());
+        if (d.hidden == 192) {
+            SWF_TRY(raise_lds_limit<&window48w16_kernel<192>>((int)G48<192>::l_total16, "window48w16"));
+            hipLaunchKernelGGL((window48w16_kernel<192>), dim3(gx, 2), dim3(256), G48<192>::l_total16, stream, a);
+        } else {
+            SWF_TRY(raise_lds_limit<&window48w16_kernel<96>>((int)G48<96>::l_total16, "window48w16"));
+            hipLaunchKernelGGL((window48w16_kernel<96>), dim3(gx, 2), dim3(256), G48<96>::l_total16, stream, a);
+        }
         return check_launch("window48w16");
     }
-    const int grid = std::min(nwin, W48_WAVES * num_cus48());
+    const int grid = std::min(nwin, W48_WAVES * num_cus());
     if (wsd == 8) {
         if (d.hidden == 192) hipLaunchKernelGGL((window48_kernel<192, 8>), dim3(grid), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL((window48_kernel<96, 8>), dim3(grid), dim3(256), 0, stream, a);

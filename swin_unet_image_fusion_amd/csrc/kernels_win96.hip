@@ -1187,15 +1187,6 @@ __global__ __launch_bounds__(256) void pack96_kernel(Pack96Args a) {
     }
 }
 
-int num_cus96() {
-    static int n = [] {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
-        return v;
-    }();
-    return n;
-}
-
 }  // namespace
 
 bool win96_supported(const swf_block_desc& d) {
@@ -1224,8 +1215,7 @@ int pack_win96(const swf_block_desc& d, const swf_block_stream_params& px, const
 template <int HID, int WS>
 static int launch96_t(const Win96Args& a, int grid, hipStream_t stream) {
     constexpr int lds = (int)G96<HID>::l_total;
-    static hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&window96_kernel<HID, WS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window96): %s", hipGetErrorString(attr_err));
+    SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS>>(lds, "window96")));
     hipLaunchKernelGGL((window96_kernel<HID, WS>), dim3(grid), dim3(256), lds, stream, a);
     return check_launch("window96");
 }
@@ -1233,8 +1223,7 @@ static int launch96_t(const Win96Args& a, int grid, hipStream_t stream) {
 template <int HID, int WS>
 static int launch96x8_t(const Win96Args& a, int grid, hipStream_t stream) {
     constexpr int lds = (int)G96<HID>::l_total8;
-    static hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&window96x8_kernel<HID, WS>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window96x8): %s", hipGetErrorString(attr_err));
+    SWF_TRY((raise_lds_limit<&window96x8_kernel<HID, WS>>(lds, "window96x8")));
     hipLaunchKernelGGL((window96x8_kernel<HID, WS>), dim3(grid), dim3(512), lds, stream, a);
     return check_launch("window96x8");
 }
@@ -1247,8 +1236,7 @@ size_t win96_half_packed_bytes(int channels, int hidden) {
 template <int HID, int WS, int MODE, bool RAW>
 static int launch96_half_t(const Win96Args& a, int grid, hipStream_t stream) {
     constexpr int lds = (int)G96<HID>::l_total;
-    static hipError_t attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&window96_kernel<HID, WS, MODE, RAW>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window96 half): %s", hipGetErrorString(attr_err));
+    SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS, MODE, RAW>>(lds, "window96 half")));
     hipLaunchKernelGGL((window96_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), lds, stream, a);
     return check_launch("window96 (half block)");
 }
@@ -1272,7 +1260,7 @@ int launch_win96_half(const swf_block_desc& d, int mode, int raw, const void* pa
         if ((int64_t)std::max(ntok_x, ntok_y) * 96 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win96_half: token count");
         nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
     }
-    const int grid = std::min(nwin, 2 * num_cus96());
+    const int grid = std::min(nwin, 2 * num_cus());
     if (mode == W96_ATTN) {   // the MLP geometry is irrelevant: the hidden-384 image layout serves
         if (wsd == 8) return raw ? launch96_half_t<384, 8, W96_ATTN, true>(a, grid, stream) : launch96_half_t<384, 8, W96_ATTN, false>(a, grid, stream);
         return raw ? launch96_half_t<384, 7, W96_ATTN, true>(a, grid, stream) : launch96_half_t<384, 7, W96_ATTN, false>(a, grid, stream);
@@ -1296,14 +1284,14 @@ int launch_win96(const swf_block_desc& d, const void* packed_x, const void* pack
     a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross;
     const int nwin = B * (H / wsd) * (W / wsd);
     if (wsd == 16) {   // 138 KB of LDS per workgroup: one per CU, grid.y = stream
-        static hipError_t attr_err = [] {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&window96w16_kernel<384>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G96<384>::l_total16);
-            return e != hipSuccess ? e : hipFuncSetAttribute(reinterpret_cast<const void*>(&window96w16_kernel<192>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G96<192>::l_total16);
-        }();
-        if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(window96w16): %s", hipGetErrorString(attr_err));
-        const int gx = std::min(nwin, (num_cus96() + 1) / 2);
-        if (d.hidden == 384) hipLaunchKernelGGL((window96w16_kernel<384>), dim3(gx, 2), dim3(256), G96<384>::l_total16, stream, a);
-        else hipLaunchKernelGGL((window96w16_kernel<192>), dim3(gx, 2), dim3(256), G96<192>::l_total16, stream, a);
+        const int gx = std::min(nwin, (num_cus() + 1) / 2);
+        if (d.hidden == 384) {
+            SWF_TRY(raise_lds_limit<&window96w16_kernel<384>>((int)G96<384>::l_total16, "window96w16"));
+            hipLaunchKernelGGL((window96w16_kernel<384>), dim3(gx, 2), dim3(256), G96<384>::l_total16, stream, a);
+        } else {
+            SWF_TRY(raise_lds_limit<&window96w16_kernel<192>>((int)G96<192>::l_total16, "window96w16"));
+            hipLaunchKernelGGL((window96w16_kernel<192>), dim3(gx, 2), dim3(256), G96<192>::l_total16, stream, a);
+        }
         return check_launch("window96w16");
     }
     static const bool no_x8 = [] { const char* e = debug_env("SWF_WIN96X8"); return e && e[0] == '0'; }();   // A/B switch (tools)
@@ -1311,11 +1299,11 @@ int launch_win96(const swf_block_desc& d, const void* packed_x, const void* pack
     // (window96x8_kernel).  The rule looks at the map, never at the batch: batch shards stay bit-identical.
     // (THROUGHPUT schedule: four waves per window, two windows per CU hide each other's phase latencies)
     if (!no_x8 && d.schedule != SWF_SCHED_THROUGHPUT && (H / wsd) * (W / wsd) <= 16) {
-        const int gx = std::min(nwin, num_cus96());
+        const int gx = std::min(nwin, num_cus());
         if (wsd == 8) return d.hidden == 384 ? launch96x8_t<384, 8>(a, gx, stream) : launch96x8_t<192, 8>(a, gx, stream);
         return d.hidden == 384 ? launch96x8_t<384, 7>(a, gx, stream) : launch96x8_t<192, 7>(a, gx, stream);
     }
-    const int grid = std::min(nwin, 2 * num_cus96());
+    const int grid = std::min(nwin, 2 * num_cus());
     if (wsd == 8) return d.hidden == 384 ? launch96_t<384, 8>(a, grid, stream) : launch96_t<192, 8>(a, grid, stream);
     return d.hidden == 384 ? launch96_t<384, 7>(a, grid, stream) : launch96_t<192, 7>(a, grid, stream);
 }

@@ -25,6 +25,15 @@ int launch_window_block(const swf_block_desc& d, const void* packed_x, const voi
 // next_packed_*: packed images of the block that runs next with different weights (or nullptr): this launch ends by touching
 // them (next_bytes each; 0 = the size of this block's own image) so that they are L2-resident when that block starts.
 
+// The two halves of the block as launches of their own at C = 24 / 48 / 96 (launch_win24_half has the contract; mode
+// WIN24_HALF_ATTN or WIN24_HALF_MLP).  window_half_packed_bytes: bytes of ONE stream's image for hidden width hid, 0 = not
+// covered.  The two streams' images lie at pk and pk + pb.
+size_t window_half_packed_bytes(int C, int hid);
+int pack_window_half(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, char* pk,
+                     size_t pb, hipStream_t stream);
+int launch_window_half(const swf_block_desc& d, int mode, int raw, const char* pk, size_t pb, const float* x_in, const float* y_in,
+                       float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream);
+
 // Touch a buffer from every XCD so that it is L2-resident for the next launch (a fused stage that follows a deep-level stage).
 int launch_l2_warm(const void* p, size_t bytes, hipStream_t stream);
 

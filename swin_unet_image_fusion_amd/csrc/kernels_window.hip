@@ -1,7 +1,8 @@
 // Fast tier (include/swinfuse.h SWF_PREC_FAST), window-level kernels of gfx950 (MI355X).  This file holds
 //   * the dispatcher of the fused BasicBlock launch (a005:127-145, both streams): window_block_supported / packed_bytes /
 //     pack_window_block / launch_window_block route C = 24, 48, 96 to the register-resident kernels of kernels_win24.hip,
-//     kernels_win48.hip, kernels_win96.hip (8x8, 7x7 and 16x16 windows);
+//     kernels_win48.hip, kernels_win96.hip (8x8, 7x7 and 16x16 windows), and the *_window_half entries route the half-block
+//     launches the same way;
 //     (the round-1 LDS-image block kernel those replaced is gone; DESIGN.md Appendix A keeps its measurements);
 //   * the stand-alone MFMA attention cores on projection buffers: attn_core_mfma_kernel<D, WS> (8x8 / 7x7 windows: the deep
 //     levels' core) and attn_core_mfma16_kernel<D> (16x16 windows, online softmax over key tiles), both with optional 16-bit
@@ -22,61 +23,18 @@
 #include "kernels_win24.h"
 #include "kernels_win48.h"
 #include "kernels_win96.h"
+#include "win_frag.h"
 
 #include <algorithm>
 #include <cstdlib>
-#include <mutex>
 
 namespace swf {
 
-using bf16 = __bf16;
-using f16 = _Float16;
-typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef f16 f16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace wf;
 
-constexpr float kLog2e = 1.4426950408889634f;
 constexpr int cceil(int a, int b) { return (a + b - 1) / b; }
 constexpr int cround(int a, int b) { return cceil(a, b) * b; }
 constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
-
-// ------------------------------------------------------------------------------------------
-// device helpers
-// ------------------------------------------------------------------------------------------
-typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef f16 f16x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-
-// ELU(alpha=1) for the fast tier: exp(v)-1 through v_exp_f32.  Near 0 the subtraction cancels, leaving an
-// ABSOLUTE error of ~1e-7 on activations of order 1 — four orders below the tier's error budget; the exact
-// tier keeps expm1f.
-__device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
-
-// max of three; with -fno-honor-nans hipcc folds this into one v_max3_f32 (and drops the canonicalising
-// v_max it would otherwise put in front of fmaxf on MFMA outputs).  NOT inline asm: an asm statement that
-// reads an MFMA result gets none of the MFMA->VALU wait states and reads stale registers.
-__device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
-
-__device__ __forceinline__ void split4_bf16(const float v[4], bf16x4& hi, bf16x4& lo) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        hi[i] = (bf16)v[i];
-        lo[i] = (bf16)(v[i] - (float)hi[i]);
-    }
-}
-
-// position of key `tok` (0..63) inside a V^T row so that the 8 halves a lane needs for k-step s of
-// key tile T sit contiguously: the S^T accumulator register 8s+e of lane half h is key row
-// 32T + 16s + 8(e>>2) + 4h + (e&3)  (C/D map of the 32x32 MFMA), so pos = 32T + 16s + 8h + e.
-// For tok = 4a .. 4a+3 the positions are consecutive (only e&3 changes): one 8-byte store.
-__device__ __forceinline__ int vt_pos(int tok) {
-    const int k16 = tok & 15;
-    const int e = ((k16 >> 3) << 2) | (k16 & 3);
-    const int h = (k16 >> 2) & 1;
-    return (tok & 48) | (h << 3) | e;
-}
-
 
 // ------------------------------------------------------------------------------------------
 // Stand-alone MFMA attention core for 8x8 windows (levels whose linears run as separate GEMMs):
@@ -547,14 +505,7 @@ template <int D>
 static int launch_attn16_t(const Attn16Args& a, int nprob, hipStream_t stream) {
     constexpr int QS = cround(D, 8);
     constexpr size_t lds = (size_t(2) * 256 * QS * 2 + size_t(D + 1) * (256 + 8) * 2 + 15) / 16 * 16 + size_t(31) * 31 * 4;
-    static std::once_flag once;
-    static hipError_t attr_err = hipSuccess;
-    if (lds > 64 * 1024)
-        std::call_once(once, [] {
-            attr_err = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_core_mfma16_kernel<D>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        });
-    if (attr_err != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn16): %s", hipGetErrorString(attr_err));
+    if (lds > 64 * 1024) SWF_TRY(raise_lds_limit<&attn_core_mfma16_kernel<D>>((int)lds, "attn16"));
     const int nwin = a.B * (a.H / 16) * (a.W / 16);
     hipLaunchKernelGGL((attn_core_mfma16_kernel<D>), dim3(nwin, a.heads, nprob), dim3(512), lds, stream, a);
     return check_launch("attn_core_mfma16");
@@ -663,6 +614,23 @@ int pack_window_block(const swf_block_desc& d, const swf_block_stream_params& px
     if (use_win48(d)) return pack_win48(d, px, py, packed_x, packed_y, stream);
     if (use_win96(d)) return pack_win96(d, px, py, packed_x, packed_y, stream);
     return fail(SWF_ERR_UNSUPPORTED, "pack_window_block: C=%d hidden=%d not covered", d.attn.channels, d.hidden);
+}
+
+size_t window_half_packed_bytes(int C, int hid) {
+    return C == 24 ? win24_half_packed_bytes(C, hid) : C == 48 ? win48_half_packed_bytes(C, hid) : C == 96 ? win96_half_packed_bytes(C, hid) : 0;
+}
+
+int pack_window_half(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, char* pk,
+                     size_t pb, hipStream_t stream) {
+    return d.attn.channels == 24 ? pack_win24(d, px, py, pk, pk + pb, stream)
+         : d.attn.channels == 48 ? pack_win48(d, px, py, pk, pk + pb, stream) : pack_win96(d, px, py, pk, pk + pb, stream);
+}
+
+int launch_window_half(const swf_block_desc& d, int mode, int raw, const char* pk, size_t pb, const float* x_in, const float* y_in,
+                       float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream) {
+    return d.attn.channels == 24 ? launch_win24_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream)
+         : d.attn.channels == 48 ? launch_win48_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream)
+                                 : launch_win96_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream);
 }
 
 // Touch `bytes` at p from every XCD (blocks b, b+8, ... share an XCD under round-robin dealing: speed only), so that the lines

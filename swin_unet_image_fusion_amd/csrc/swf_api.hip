@@ -13,8 +13,6 @@
 #include "kernels_bwd.h"
 #include "kernels_dropout.h"
 #include "kernels_win24.h"
-#include "kernels_win48.h"
-#include "kernels_win96.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
 #include "kernels_patchrr.h"
@@ -988,25 +986,12 @@ static bool half_attn_shape(const swf_attn_desc& a, int H, int W) {
            (a.win_h == 8 || a.win_h == 7) && H % a.win_h == 0 && W % a.win_w == 0;
 }
 static int half_attn_hidden(int C) { return 4 * C; }   // the attention half runs on the wide-MLP image layout (fc sections unused)
-static size_t half_packed_bytes(int C, int hid) {
-    return C == 24 ? win24_half_packed_bytes(C, hid) : C == 48 ? win48_half_packed_bytes(C, hid) : C == 96 ? win96_half_packed_bytes(C, hid) : 0;
-}
-static int half_pack(const swf_block_desc& bd, const swf_block_stream_params& sx, const swf_block_stream_params& sy, char* pk, size_t pb, hipStream_t st) {
-    return bd.attn.channels == 24 ? pack_win24(bd, sx, sy, pk, pk + pb, st)
-         : bd.attn.channels == 48 ? pack_win48(bd, sx, sy, pk, pk + pb, st) : pack_win96(bd, sx, sy, pk, pk + pb, st);
-}
-static int half_launch(const swf_block_desc& bd, int mode, int raw, const char* pk, size_t pb, const float* x_in, const float* y_in, float* x_out,
-                       float* y_out, int B, int H, int W, int nx, int ny, hipStream_t st) {
-    return bd.attn.channels == 24 ? launch_win24_half(bd, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, nx, ny, st)
-         : bd.attn.channels == 48 ? launch_win48_half(bd, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, nx, ny, st)
-                                  : launch_win96_half(bd, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, nx, ny, st);
-}
 
 // MLP half on window24 / window48 / window96_kernel <HID, 8, MLP half, raw>: tokens as flat lists.  Dual path: one list per stream.  Single path: the one
 // list is split between the kernel's two stream slots (same weights).  SWF_ERR_UNSUPPORTED = shape not covered (the caller falls back).
 static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                       const float* y_in, float* x_out, float* y_out, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
-    const size_t pb = half_packed_bytes(C, hid);
+    const size_t pb = window_half_packed_bytes(C, hid);
     if (!pb || N <= 0 || N * C * 4 >= (int64_t(1) << 31) || !workspace || workspace_bytes < 2 * pb) return SWF_ERR_UNSUPPORTED;
     swf_block_desc bd{};
     bd.attn = swf_attn_desc{C, 8, C / 8, 8, 8, 0};
@@ -1016,15 +1001,15 @@ static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px
     sx.ln1 = sy.ln1 = swf_norm{nullptr, nullptr};
     if (raw) sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
     char* pk = static_cast<char*>(workspace);
-    SWF_TRY(half_pack(bd, sx, sy, pk, pb, stream));
-    if (py) return half_launch(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, y_in, x_out, y_out, 1, 1, 1, (int)N, (int)N, stream);
+    SWF_TRY(pack_window_half(bd, sx, sy, pk, pb, stream));
+    if (py) return launch_window_half(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, y_in, x_out, y_out, 1, 1, 1, (int)N, (int)N, stream);
     const int64_t n0 = std::min<int64_t>(N, ((N + 1) / 2 + 63) / 64 * 64);
-    return half_launch(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, x_in + n0 * C, x_out, x_out + n0 * C, 1, 1, 1, (int)n0, (int)(N - n0), stream);
+    return launch_window_half(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, x_in + n0 * C, x_out, x_out + n0 * C, 1, 1, 1, (int)n0, (int)(N - n0), stream);
 }
 
 size_t swf_window_attention_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0) return 0;
-    return std::max(attention_generic_ws(*desc, 1, B, H, W), 2 * half_packed_bytes(desc->channels, half_attn_hidden(desc->channels)) + 512);
+    return std::max(attention_generic_ws(*desc, 1, B, H, W), 2 * window_half_packed_bytes(desc->channels, half_attn_hidden(desc->channels)) + 512);
 }
 
 static int window_attention_impl(const swf_attn_desc* desc, int precision, const swf_attn_params* p, const float* q, const float* k,
@@ -1036,7 +1021,7 @@ static int window_attention_impl(const swf_attn_desc* desc, int precision, const
     if (!p->q.weight || !p->k.weight || !p->v.weight || !p->proj.weight || !p->bias_table)
         return fail(SWF_ERR_NULL, "window_attention: NULL weight");
     const int hid_a = half_attn_hidden(desc->channels);
-    const size_t pbh = half_packed_bytes(desc->channels, hid_a);
+    const size_t pbh = window_half_packed_bytes(desc->channels, hid_a);
     if (precision == SWF_PREC_FAST && k == v && !residual && half_attn_shape(*desc, H, W) && (int64_t)B * H * W * desc->channels * 4 < (int64_t(1) << 31) &&
         pbh && workspace && workspace_bytes >= 2 * pbh && out != q && out != k) {
         // window24/48_kernel<.., attention half, RAW>: stream 0 = the queries and the output, stream 1 = the key / value tensor
@@ -1044,8 +1029,8 @@ static int window_attention_impl(const swf_attn_desc* desc, int precision, const
         swf_block_stream_params sp{};
         sp.attn = *p;
         char* pk = static_cast<char*>(workspace);
-        SWF_TRY(half_pack(bd, sp, sp, pk, pbh, as_stream(stream)));
-        return half_launch(bd, WIN24_HALF_ATTN, 1, pk, pbh, q, k, out, nullptr, B, H, W, 0, 0, as_stream(stream));
+        SWF_TRY(pack_window_half(bd, sp, sp, pk, pbh, as_stream(stream)));
+        return launch_window_half(bd, WIN24_HALF_ATTN, 1, pk, pbh, q, k, out, nullptr, B, H, W, 0, 0, as_stream(stream));
     }
     Carver ws(workspace, workspace_bytes);
     const swf_attn_params* prm[2] = {p, nullptr};
@@ -1073,7 +1058,7 @@ int swf_window_attention_fwd_prec(const swf_attn_desc* desc, int32_t precision, 
 size_t swf_basic_block_workspace_bytes(const swf_block_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0) return 0;
     return std::max(std::max(block_generic_ws(desc, 2, B, H, W), window_block_workspace_bytes(*desc, B, H, W)),
-                    2 * std::max(half_packed_bytes(desc->attn.channels, half_attn_hidden(desc->attn.channels)), half_packed_bytes(desc->attn.channels, desc->hidden)) + 512);
+                    2 * std::max(window_half_packed_bytes(desc->attn.channels, half_attn_hidden(desc->attn.channels)), window_half_packed_bytes(desc->attn.channels, desc->hidden)) + 512);
 }
 
 int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
@@ -1081,7 +1066,7 @@ int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_pa
                            void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     SWF_TRY(check_block(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, true, false));
     const int hid_a = half_attn_hidden(desc->attn.channels);
-    const size_t pbh = half_packed_bytes(desc->attn.channels, hid_a);
+    const size_t pbh = window_half_packed_bytes(desc->attn.channels, hid_a);
     if (desc->precision == SWF_PREC_FAST && half_attn_shape(desc->attn, H, W) && (int64_t)B * H * W * desc->attn.channels * 4 < (int64_t(1) << 31) &&
         pbh && workspace && workspace_bytes >= 2 * pbh) {
         // window24/48_kernel<.., attention half>: LN1 + Q/K/V + attention + projection + residual of both streams in one launch.  A single-path
@@ -1093,8 +1078,8 @@ int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_pa
         sx.fc1 = sx.fc2 = swf_linear{nullptr, nullptr}; sy.fc1 = sy.fc2 = swf_linear{nullptr, nullptr};
         sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
         char* pk = static_cast<char*>(workspace);
-        SWF_TRY(half_pack(bd, sx, sy, pk, pbh, as_stream(stream)));
-        return half_launch(bd, WIN24_HALF_ATTN, 0, pk, pbh, x_in, py ? y_in : x_in, x_out, py ? y_out : nullptr, B, H, W, 0, 0, as_stream(stream));
+        SWF_TRY(pack_window_half(bd, sx, sy, pk, pbh, as_stream(stream)));
+        return launch_window_half(bd, WIN24_HALF_ATTN, 0, pk, pbh, x_in, py ? y_in : x_in, x_out, py ? y_out : nullptr, B, H, W, 0, 0, as_stream(stream));
     }
     Carver ws(workspace, workspace_bytes);
     return attn_halfblock_generic(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, as_stream(stream));
@@ -1117,7 +1102,7 @@ size_t swf_mlp_workspace_bytes(int32_t precision, int64_t tokens, int32_t channe
     if (tokens <= 0 || channels <= 0 || hidden <= 0) return 0;
     size_t generic = carve_bytes({tokens * hidden}) + std::max(swf_linear_workspace_bytes(precision, tokens, channels, hidden),
                                                                swf_linear_workspace_bytes(precision, tokens, hidden, channels));
-    return std::max(generic, 2 * half_packed_bytes(channels, hidden) + 512);
+    return std::max(generic, 2 * window_half_packed_bytes(channels, hidden) + 512);
 }
 
 int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in, const float* y_in,

@@ -1,4 +1,4 @@
-// Shared host-side helpers of libswinfuse (gfx950 only).
+// Shared host-side helpers of libswinfuse (gfx950 only), and the reflect-pad index maps both kernel tiers use.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdarg>
@@ -32,6 +32,30 @@ inline const char* debug_env(const char* name) {
     static const bool on = [] { const char* e = std::getenv("SWF_DEBUG_SWITCHES"); return e && e[0] == '1'; }();
     return on ? std::getenv(name) : nullptr;
 }
+
+// Compute units of the current device (256 if the query fails), queried once.  Inline: the tools/ probes compile kernel files
+// into programs that also link the library.
+inline int num_cus() {
+    static const int n = [] {
+        int dev = 0, v = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+        return v;
+    }();
+    return n;
+}
+
+// Raise kernel K's dynamic-LDS limit to `bytes` (a launch with more than 64 KB needs it).  The attribute is set by the first
+// call only (thread-safe static initialisation); every call returns the status of that attempt.
+template <auto K>
+int raise_lds_limit(int bytes, const char* what) {
+    static const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    return e == hipSuccess ? SWF_OK : fail(SWF_ERR_HIP, "hipFuncSetAttribute(%s): %s", what, hipGetErrorString(e));
+}
+
+// Index maps of 'reflect' padding (F.pad mode="reflect": the edge element is not repeated): reflect_br for a pad on the bottom /
+// right edge only, reflect2 for both edges.
+__device__ __forceinline__ int reflect_br(int i, int n) { return i < n ? i : 2 * n - 2 - i; }
+__device__ __forceinline__ int reflect2(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }

@@ -1,6 +1,6 @@
-// Device helpers shared by the register-resident window kernels (kernels_win48.hip; kernels_win24.hip keeps its own copies):
-// 32x32x16 MFMA wrappers on 16-byte operand fragments, split-bf16 / f16 packing of accumulator registers, the lane-half
-// exchange, wave-uniform pointers.  See kernels_win24.hip for the layout conventions (rho order, lane (column, half)).
+// Device helpers of the fast-tier kernels, defined here and nowhere else: vector types, 32x32x16 MFMA wrappers on 16-byte
+// operand fragments, split-bf16 / f16 packing of accumulator registers, the lane-half exchange, wave-uniform pointers, the fast
+// ELU and the V^T key order.  See kernels_win24.hip for the layout conventions (rho order, lane (column, half)).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,8 +10,10 @@ namespace wf {
 using bf16 = __bf16;
 using f16 = _Float16;
 typedef bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
+typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -28,7 +30,8 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
 __device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
-// acc += a . b over one 16-deep k-step with split-bf16 operands: three MFMAs, small cross terms first
+// acc += a . b over one 16-deep k-step with split-bf16 operands (a = a_hi + a_lo, b = b_hi + b_lo): three MFMAs, small cross
+// terms first so they are not absorbed by the large hi.hi partial sums
 __device__ __forceinline__ f32x16 mma3(u32x4 ahi, u32x4 alo, u32x4 bhi, u32x4 blo, f32x16 acc) {
     acc = mfma_bf16(alo, bhi, acc);
     acc = mfma_bf16(ahi, blo, acc);
@@ -45,6 +48,15 @@ __device__ __forceinline__ void split8(const float* v, u32x4& hi, u32x4& lo) {
         const bf16x2 l = {(bf16)(v[2 * p] - h0), (bf16)(v[2 * p + 1] - h1)};
         hi[p] = hu;
         lo[p] = __builtin_bit_cast(unsigned, l);
+    }
+}
+// 4 fp32 values -> split-bf16 hi / lo vectors (the plane formats of the deep-level GEMMs)
+__device__ __forceinline__ void split4(const float4 v, bf16x4& hi, bf16x4& lo) {
+    const float f[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        hi[i] = (bf16)f[i];
+        lo[i] = (bf16)(f[i] - (float)hi[i]);
     }
 }
 __device__ __forceinline__ u32x4 pack8_f16(const float* v) {
@@ -66,8 +78,29 @@ __device__ __forceinline__ void halves(float v, float& a, float& b) {
 }
 __device__ __forceinline__ float sum_halves(float v) { float a, b; halves(v, a, b); return a + b; }
 __device__ __forceinline__ float max_halves(float v) { float a, b; halves(v, a, b); return __builtin_fmaxf(a, b); }
+// max of three; with -fno-honor-nans hipcc folds this into one v_max3_f32 (and drops the canonicalising v_max it would otherwise
+// put in front of fmaxf on MFMA outputs).  NOT inline asm: an asm statement that reads an MFMA result gets none of the
+// MFMA->VALU wait states and reads stale registers.
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
+// ELU(alpha = 1) for the fast tier: exp(v) - 1 through v_exp_f32.  Near 0 the subtraction cancels, leaving an ABSOLUTE error of
+// ~1e-7 on activations of order 1 — four orders below the tier's error budget; the exact tier keeps expm1f.
+__device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
+
+// Position of key `tok` (0..63) inside a V^T row, the order in which the S^T accumulators hold the keys (a layout the writer of a
+// V^T image and the P.V MFMAs must agree on): the 8 halves a lane needs for k-step s of key tile T sit contiguously.  Register
+// 8s+e of lane half h is key row 32T + 16s + 8(e>>2) + 4h + (e&3) (C/D map of the 32x32 MFMA), so pos = 32T + 16s + 8h + e.
+// For tok = 4a .. 4a+3 the positions are consecutive (only e&3 changes): one 8-byte store.
+__device__ __forceinline__ int vt_pos(int tok) {
+    const int k16 = tok & 15;
+    const int e = ((k16 >> 3) << 2) | (k16 & 3);
+    const int h = (k16 >> 2) & 1;
+    return (tok & 48) | (h << 3) | e;
+}
+
+// A pointer that is the same in every lane of the wave but derived from the wave index: made provably uniform so that hipcc
+// keeps it in SGPRs and addresses fragments as (scalar base + lane offset + immediate) instead of holding a 64-bit per-lane
+// address per fragment group in VGPRs across the window loop.
 template <typename T>
 __device__ __forceinline__ T* uniform_ptr(T* p) {
     const unsigned long long v = reinterpret_cast<unsigned long long>(p);
@@ -98,5 +131,6 @@ __device__ __forceinline__ void fill_vectors(float* lvec, const char* vec0, cons
 }  // namespace wf
 }  // namespace swf
 
-// compiler-only barrier: the loop-invariant weight fragment loads must not be hoisted (they would spill)
+// Compiler-only barrier, no instruction: the loop-invariant weight fragment loads must not be hoisted out of the window loop (or
+// to the top of an iteration), where they would spill.
 #define SWF_WF_FENCE() asm volatile("" ::: "memory")
