@@ -418,6 +418,28 @@ int swf_gray8_to_unit_fwd(const uint8_t* gray, float* out, int64_t count, swf_st
 int swf_ycrcb_to_rgb_fwd(const float* fused_y, const float* crcb, float* rgb_f, uint8_t* rgb8,
                          int32_t B, int32_t H, int32_t W, swf_stream_t stream);
 
+/* ---- the reference's fusion loss (a008_loss.py MyLoss), value and d total / d fusion in one call -----------------
+ * total = ssim_ratio*ssim_scale*S + texture_ratio*texture_scale*T + intensity_ratio*intensity_scale*I + psnr_ratio*psnr_scale*P on
+ * single-channel fp32 images: S = MS-SSIM + L1 (five Gaussian scales, 33 taps, zero border) or single-scale SSIM (11 taps, sigma
+ * 1.5, reflect border) of (fusion, ir) and (fusion, vis); T = mean |Sobel(fusion) - max(Sobel(ir), Sobel(vis))|; I = mean
+ * |fusion - max(ir, vis)|; P = 10 log10(mse).  The operators are restated from the published definitions of the kornia classes the
+ * reference calls (kornia is not available to this build): PARITY WITH KORNIA ITSELF IS UNPINNED.  Canny is not provided. */
+typedef struct swf_loss_desc {
+    int32_t ssim_mode;          /* 0 = MS-SSIM + L1 (CHOOSE_MS_SSIM), 1 = single-scale SSIM, window 11 */
+    int32_t use_psnr;
+    float ir_ssim_weight, ir_psnr_weight;
+    float ssim_scale, texture_scale, intensity_scale, psnr_scale;
+    float ssim_ratio, texture_ratio, intensity_ratio, psnr_ratio;
+} swf_loss_desc;
+/* 0 for arguments swf_fusion_loss would refuse */
+size_t swf_fusion_loss_workspace_bytes(const swf_loss_desc* desc, int32_t B, int32_t H, int32_t W, int32_t with_grad);
+/* fusion, ir, vis: [B][H][W].  terms: device float[5] = S, T, I, P (unscaled, as the four calcu_*_loss methods return them; P = 0
+ * when use_psnr = 0) and total.  grad_fusion: NULL, or [B][H][W] <- d total / d fusion, computed in the same call (a term whose
+ * ratio*scale is 0 contributes nothing).  Fixed-order reductions, no atomics: results are bit-reproducible; nothing is allocated
+ * and the host is not synchronised, so the call can be captured into a hipGraph.  ssim_mode 1 needs H, W >= 6 (SWF_ERR_PAD). */
+int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float* ir, const float* vis, float* terms, float* grad_fusion,
+                    int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 int swf_version(void);                     /* major*1000 + minor */
 const char* swf_last_error_string(void);   /* thread-local, never NULL */

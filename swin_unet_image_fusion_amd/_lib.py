@@ -73,6 +73,12 @@ class ModelDesc(C.Structure):
                 ("head_ksize", C.c_int32), ("precision", C.c_int32), ("schedule", C.c_int32)]
 
 
+class LossDesc(C.Structure):
+    _fields_ = [("ssim_mode", C.c_int32), ("use_psnr", C.c_int32), ("ir_ssim_weight", C.c_float), ("ir_psnr_weight", C.c_float),
+                ("ssim_scale", C.c_float), ("texture_scale", C.c_float), ("intensity_scale", C.c_float), ("psnr_scale", C.c_float),
+                ("ssim_ratio", C.c_float), ("texture_ratio", C.c_float), ("intensity_ratio", C.c_float), ("psnr_ratio", C.c_float)]
+
+
 P = C.POINTER
 _i32, _i64, _sz, _vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
 
@@ -152,6 +158,8 @@ SIGNATURES = {
     "swf_model_forward_checked": (C.c_int, [P(ModelDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "swf_model_forward_profiled": (C.c_int, [P(ModelDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, P(C.c_float), _i32, _vp]),
     "swf_tensors_equal": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
+    "swf_fusion_loss_workspace_bytes": (_sz, [P(LossDesc), _i32, _i32, _i32, _i32]),
+    "swf_fusion_loss": (C.c_int, [P(LossDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

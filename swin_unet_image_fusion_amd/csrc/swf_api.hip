@@ -12,6 +12,7 @@
 #include "kernels_window.h"
 #include "kernels_bwd.h"
 #include "kernels_dropout.h"
+#include "kernels_loss.h"
 #include "kernels_win24.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
@@ -1762,6 +1763,32 @@ int swf_tensors_equal(const float* a, const float* b, int64_t count, int32_t* fl
     hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(flag), 1, 1, as_stream(stream));
     if (e != hipSuccess) return fail(SWF_ERR_HIP, "tensors_equal: memset: %s", hipGetErrorString(e));
     return launch_all_equal(a, b, count, flag, as_stream(stream));
+}
+
+// a008 MyLoss.  Every argument check comes before the first HIP call.
+static int check_fusion_loss(const swf_loss_desc* desc, int32_t B, int32_t H, int32_t W) {
+    if (!desc) return fail(SWF_ERR_NULL, "fusion_loss: NULL descriptor");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_loss: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (desc->ssim_mode != 0 && desc->ssim_mode != 1)
+        return fail(SWF_ERR_UNSUPPORTED, "fusion_loss: ssim_mode %d (0 = MS-SSIM + L1, 1 = single-scale SSIM)", desc->ssim_mode);
+    if (desc->ssim_mode == 1 && (H < 6 || W < 6))
+        return fail(SWF_ERR_PAD, "fusion_loss: the 11-tap SSIM window reflects 5 pixels, the map is %dx%d", H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_loss_workspace_bytes(const swf_loss_desc* desc, int32_t B, int32_t H, int32_t W, int32_t with_grad) {
+    if (check_fusion_loss(desc, B, H, W) != SWF_OK) return 0;
+    return fusion_loss_workspace_bytes(*desc, B, H, W, with_grad != 0);
+}
+
+int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float* ir, const float* vis, float* terms, float* grad_fusion,
+                    int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !terms) return fail(SWF_ERR_NULL, "fusion_loss: NULL descriptor, image or terms");
+    SWF_TRY(check_fusion_loss(desc, B, H, W));
+    const size_t need = fusion_loss_workspace_bytes(*desc, B, H, W, grad_fusion != nullptr);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "fusion_loss: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return fusion_loss(*desc, fusion, ir, vis, terms, grad_fusion, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 }  // extern "C"

@@ -1,8 +1,9 @@
 """Time of one training step of the module-by-module autograd path: forward under autograd + backward of every
 parameter (exact fp32, atomics-free) + a plain SGD update, model.train() as the reference trains (a016:137).  Prints one JSON line.
-The loss is a smooth stand-in (mean squared distance to max(ir, vis)): the reference's loss needs kornia, absent here.
+--loss standin (default) is a smooth stand-in, the mean squared distance to max(ir, vis); --loss fusion is the reference's step
+(a016:150-165): clamp_(0, 1), then MyLoss().calcu_total_loss on the fused HIP loss.
 
-    python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5] [--drop P]
+    python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5] [--drop P] [--loss standin|fusion]
 
 --drop P sets the three dropout ratios (attention, projection, MLP) to P: every block then runs the exact-fp32 *_drop entries.
 """
@@ -26,9 +27,10 @@ def main():
     ap.add_argument("--config", default="win8")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--drop", type=float, default=0.0, help="attention_drop_ratio = linear_after_att_drop_ratio = mlp_drop_ratio")
+    ap.add_argument("--loss", choices=["standin", "fusion"], default="standin")
     args = ap.parse_args()
     entry.build()
-    from swin_unet_image_fusion_amd import CONFIGS, MyModel, load_recipe_into, synthetic_pair
+    from swin_unet_image_fusion_amd import CONFIGS, MyLoss, MyModel, load_recipe_into, synthetic_pair
     dev = torch.device("cuda:0")
     cfg = CONFIGS[args.config]
     kw = cfg.model_kwargs(nn.ELU(inplace=True))
@@ -39,12 +41,16 @@ def main():
     opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     ir, vis = (torch.from_numpy(a).to(dev) for a in synthetic_pair(args.batch, args.size, args.size, seed_ir=1, seed_vis=2))
     tgt = torch.maximum(ir, vis)
+    fusion_loss = MyLoss() if args.loss == "fusion" else None
     times = {"forward": 0.0, "backward": 0.0, "update": 0.0}
     losses = []
     for it in range(args.iters + 1):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(ir, vis)
-        loss = (out - tgt).square().mean()
+        if fusion_loss is None:
+            loss = (out - tgt).square().mean()
+        else:
+            loss, _ = fusion_loss.calcu_total_loss(out.clamp_(0, 1), ir, vis)
         torch.cuda.synchronize(); t1 = time.perf_counter()
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -56,7 +62,7 @@ def main():
             times["forward"] += t1 - t0; times["backward"] += t2 - t1; times["update"] += t3 - t2
     ms = {k: round(v / args.iters * 1e3, 2) for k, v in times.items()}
     total = sum(ms.values())
-    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, SGD, dropout {args.drop}",
+    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, SGD, dropout {args.drop}, loss {args.loss}",
                       "ms": ms, "ms_per_step": round(total, 2), "pairs_per_s": round(args.batch / total * 1e3, 1),
                       "loss_first_last": [losses[0], losses[-1]]}))
 
