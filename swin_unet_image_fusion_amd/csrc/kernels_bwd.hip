@@ -649,39 +649,30 @@ int64_t bwd_scratch_floats(int64_t M, int64_t mx, int64_t C) {
 
 }  // namespace
 
-size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, int W) {
-    const int64_t N = (int64_t)B * H * W, C = d.attn.channels, HD = (int64_t)d.attn.heads * d.attn.head_dim, hid = d.hidden;
-    const int64_t nwin = (int64_t)B * (H / d.attn.win_h) * (W / d.attn.win_w), tsz = (int64_t)(2 * d.attn.win_h - 1) * (2 * d.attn.win_w - 1);
-    const int64_t mx = std::max(std::max(C, HD), hid);
-    size_t t = 0;
-    for (int s = 0; s < nstream; ++s)
-        t += carve_bytes({N * C, N * HD, N * HD, N * HD, N * HD, N * C, N * C, N * hid,      // xn, q, k, v, o, x1, xn2, h
-                          N * hid, N * C, N * C, N * HD, N * HD, N * HD, N * HD, N * C,      // dh, dxn2, gx1, do, dq, dk, dv, dxn
-                          tree_rows(nwin * d.attn.heads) * tsz});
-    t += carve_bytes({bwd_scratch_floats(N, mx, C)});
-    return t;
-}
-
-// the dropout entries carve one more buffer per stream: the dropped hidden activation (h itself stays undropped for ELU')
-size_t basic_block_drop_ws(const swf_block_desc& d, int nstream, int B, int H, int W) {
-    return basic_block_bwd_ws(d, nstream, B, H, W) + (size_t)nstream * carve_bytes({(int64_t)B * H * W * d.hidden});
-}
-
 namespace {
 
 struct BlockBufs { float *xn, *q, *k, *v, *o, *x1, *xn2, *h, *hd, *dh, *dxn2, *gx1, *dO, *dq, *dk, *dv, *dxn, *dtab; };
 
-// carves the buffers of basic_block_bwd_ws (with `drop`: basic_block_drop_ws) and returns the scratch of the weight gradients
-float* carve_block(Carver& ws, BlockBufs* b, int nstream, int64_t N, int C, int HD, int hid, int64_t tab_floats, int64_t scratch_floats, bool drop) {
+// carves the buffers of the block entries and returns the scratch of the weight gradients; with `drop` one more buffer per stream:
+// the dropped hidden activation (h itself stays undropped for ELU')
+float* carve_block(Carver& ws, BlockBufs* b, const swf_block_desc& d, int nstream, int B, int H, int W, bool drop) {
+    const int64_t N = (int64_t)B * H * W, C = d.attn.channels, HD = (int64_t)d.attn.heads * d.attn.head_dim, hid = d.hidden;
+    const int64_t nwin = (int64_t)B * (H / d.attn.win_h) * (W / d.attn.win_w), tsz = (int64_t)(2 * d.attn.win_h - 1) * (2 * d.attn.win_w - 1);
     for (int s = 0; s < nstream; ++s) {
         b[s].xn = ws.floats(N * C); b[s].q = ws.floats(N * HD); b[s].k = ws.floats(N * HD); b[s].v = ws.floats(N * HD); b[s].o = ws.floats(N * HD);
         b[s].x1 = ws.floats(N * C); b[s].xn2 = ws.floats(N * C); b[s].h = ws.floats(N * hid);
         b[s].dh = ws.floats(N * hid); b[s].dxn2 = ws.floats(N * C); b[s].gx1 = ws.floats(N * C); b[s].dO = ws.floats(N * HD);
         b[s].dq = ws.floats(N * HD); b[s].dk = ws.floats(N * HD); b[s].dv = ws.floats(N * HD); b[s].dxn = ws.floats(N * C);
-        b[s].dtab = ws.floats(tab_floats);
+        b[s].dtab = ws.floats(tree_rows(nwin * d.attn.heads) * tsz);
         b[s].hd = drop ? ws.floats(N * hid) : b[s].h;
     }
-    return ws.floats(scratch_floats);
+    return ws.floats(bwd_scratch_floats(N, std::max(std::max(C, HD), hid), C));
+}
+size_t block_ws(const swf_block_desc& d, int nstream, int B, int H, int W, bool drop) {
+    Carver m = Carver::measure();
+    BlockBufs b[2];
+    carve_block(m, b, d, nstream, B, H, W, drop);
+    return m.bytes();
 }
 
 // The forward intermediates of both streams in the exact tier: xn, q, k, v, o, x1, xn2, h (and hd).  With `drop` (stream s = mask
@@ -740,9 +731,8 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
     if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_bwd: token count");
     Carver ws(workspace, workspace_bytes);
     BlockBufs b[2];
-    const int64_t mx = std::max(std::max(C, HD), hid);
-    float* scratch = carve_block(ws, b, nstream, N, C, HD, hid, tree_rows(nwin * d.attn.heads) * tsz, bwd_scratch_floats(N, mx, C), drop != nullptr);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_bwd workspace too small (need %zu B)", ws.used);
+    float* scratch = carve_block(ws, b, d, nstream, B, H, W, drop != nullptr);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_bwd workspace too small (need %zu B)", ws.bytes());
     const swf_block_stream_params* pp[2] = {px, py};
     const swf_block_stream_grads* gp[2] = {gx, gy};
     const float* xin[2] = {x_in, y_in};
@@ -804,6 +794,9 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
 
 }  // namespace
 
+size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, int W) { return block_ws(d, nstream, B, H, W, false); }
+size_t basic_block_drop_ws(const swf_block_desc& d, int nstream, int B, int H, int W) { return block_ws(d, nstream, B, H, W, true); }
+
 int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                     const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
                     const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t st) {
@@ -824,12 +817,11 @@ int basic_block_fwd_drop(const swf_block_desc& d, const swf_block_stream_params*
     const int nstream = py ? 2 : 1;
     const int64_t N = (int64_t)B * H * W;
     const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
-    const int64_t nwin = (int64_t)B * (H / d.attn.win_h) * (W / d.attn.win_w), tsz = (int64_t)(2 * d.attn.win_h - 1) * (2 * d.attn.win_w - 1);
     if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_fwd_drop: token count");
     Carver ws(workspace, workspace_bytes);
     BlockBufs b[2];
-    carve_block(ws, b, nstream, N, C, HD, hid, tree_rows(nwin * d.attn.heads) * tsz, bwd_scratch_floats(N, std::max(std::max(C, HD), hid), C), true);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_fwd_drop workspace too small (need %zu B)", ws.used);
+    carve_block(ws, b, d, nstream, B, H, W, true);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "basic_block_fwd_drop workspace too small (need %zu B)", ws.bytes());
     const swf_block_stream_params* pp[2] = {px, py};
     const float* xin[2] = {x_in, y_in};
     float* out[2] = {x_out, y_out};
@@ -844,17 +836,6 @@ int basic_block_fwd_drop(const swf_block_desc& d, const swf_block_stream_params*
 }
 
 // ---- the inner modules on their own (a001 / a003 / a004 under autograd): WindowAttention, one MLP stream, one LayerNorm ---------------
-size_t window_attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W) {
-    const int64_t N = (int64_t)B * H * W, C = d.channels, HD = (int64_t)d.heads * d.head_dim;
-    const int64_t nwin = (int64_t)B * (H / d.win_h) * (W / d.win_w), tsz = (int64_t)(2 * d.win_h - 1) * (2 * d.win_w - 1);
-    return carve_bytes({N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, N * HD, tree_rows(nwin * d.heads) * tsz}) +
-           carve_bytes({bwd_scratch_floats(N, std::max(C, HD), C)});
-}
-// the dropout entries: one more [tokens][C] buffer (the output gradient through site 1)
-size_t window_attention_drop_ws(const swf_attn_desc& d, int B, int H, int W) {
-    return window_attention_bwd_ws(d, B, H, W) + carve_bytes({(int64_t)B * H * W * d.channels});
-}
-
 namespace {
 
 // Q / K / V projections and the attention core of WindowAttention in exact fp32; with dropout O holds the DROPPED values (site 0)
@@ -874,6 +855,26 @@ int window_attention_core(const swf_attn_desc& d, const swf_attn_params& p, cons
     return SWF_OK;
 }
 
+struct AttnBwdBufs { float *Q, *K, *V, *O, *dO, *dQ, *dK, *dV, *dtab, *scratch, *g1; };
+// `bwd` false: the forward with dropout (Q, K, V, O only); `drop`: one more [tokens][C] buffer, the output gradient through site 1
+AttnBwdBufs carve_attention_bwd(Carver& ws, const swf_attn_desc& d, int B, int H, int W, bool bwd, bool drop) {
+    const int64_t N = (int64_t)B * H * W, C = d.channels, HD = (int64_t)d.heads * d.head_dim;
+    const int64_t nwin = (int64_t)B * (H / d.win_h) * (W / d.win_w), tsz = (int64_t)(2 * d.win_h - 1) * (2 * d.win_w - 1);
+    AttnBwdBufs b{};
+    b.Q = ws.floats(N * HD); b.K = ws.floats(N * HD); b.V = ws.floats(N * HD); b.O = ws.floats(N * HD);
+    if (!bwd) return b;
+    b.dO = ws.floats(N * HD); b.dQ = ws.floats(N * HD); b.dK = ws.floats(N * HD); b.dV = ws.floats(N * HD);
+    b.dtab = ws.floats(tree_rows(nwin * d.heads) * tsz);
+    b.scratch = ws.floats(bwd_scratch_floats(N, std::max(C, HD), C));
+    b.g1 = drop ? ws.floats(N * C) : nullptr;
+    return b;
+}
+size_t attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W, bool bwd, bool drop) {
+    Carver m = Carver::measure();
+    carve_attention_bwd(m, d, B, H, W, bwd, drop);
+    return m.bytes();
+}
+
 // WindowAttention.forward (a001:448-474) under autograd: out = proj(attention(q_in Wq, k_in Wk, v_in Wv)).  Q / K / V and the attention
 // output are recomputed in exact fp32; gq / gk / gv are the gradients of the three inputs (separate buffers: the caller adds them where
 // one tensor was passed more than once).  With dropout the output gradient goes through site 1 and dO through site 0.
@@ -885,12 +886,9 @@ int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, 
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(C, HD)) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd: token count");
     Carver ws(workspace, workspace_bytes);
-    float* Q = ws.floats(N * HD); float* K = ws.floats(N * HD); float* V = ws.floats(N * HD); float* O = ws.floats(N * HD);
-    float* dO = ws.floats(N * HD); float* dQ = ws.floats(N * HD); float* dK = ws.floats(N * HD); float* dV = ws.floats(N * HD);
-    float* dtab = ws.floats(tree_rows(nwin * d.heads) * tsz);
-    float* scratch = ws.floats(bwd_scratch_floats(N, std::max(C, HD), C));
-    float* g1 = drop ? ws.floats(N * C) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_bwd workspace too small (need %zu B)", ws.used);
+    const AttnBwdBufs b = carve_attention_bwd(ws, d, B, H, W, true, drop != nullptr);
+    float *Q = b.Q, *K = b.K, *V = b.V, *O = b.O, *dO = b.dO, *dQ = b.dQ, *dK = b.dK, *dV = b.dV, *dtab = b.dtab, *scratch = b.scratch, *g1 = b.g1;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_bwd workspace too small (need %zu B)", ws.bytes());
     static const swf_attn_grads none{};
     const swf_attn_grads& g = gp ? *gp : none;
     SWF_TRY(window_attention_core(d, p, q_in, k_in, v_in, Q, K, V, O, B, H, W, drop, stream_id, st));
@@ -912,18 +910,34 @@ int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, 
     return SWF_OK;
 }
 
+struct MlpBwdBufs { float *h, *dh, *scratch, *hd, *gf; };
+// `bwd` false: the forward with dropout (h only); `masks` (mlp_p > 0): the dropped hidden activation and the output gradient through site 3
+MlpBwdBufs carve_mlp_bwd(Carver& ws, int64_t N, int C, int hid, bool bwd, bool masks) {
+    MlpBwdBufs b{};
+    b.h = ws.floats(N * hid);
+    if (!bwd) return b;
+    b.dh = ws.floats(N * hid);
+    b.scratch = ws.floats(bwd_scratch_floats(N, std::max(C, hid), C));
+    b.hd = masks ? ws.floats(N * hid) : b.h;
+    b.gf = masks ? ws.floats(N * C) : nullptr;
+    return b;
+}
+size_t mlp_ws(int64_t N, int C, int hid, bool bwd, bool masks) {
+    Carver m = Carver::measure();
+    carve_mlp_bwd(m, N, C, hid, bwd, masks);
+    return m.bytes();
+}
+
 // one stream of AutoPathMLP.forward (a003:46-50) under autograd: out = fc2(ELU(fc1(x))); with dropout out = d3(fc2(d2(ELU(fc1(x)))))
 int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
                  const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout* drop, int stream_id, void* workspace, size_t workspace_bytes,
                  hipStream_t st) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_bwd: token count");
     Carver ws(workspace, workspace_bytes);
-    float* h = ws.floats(N * hid); float* dh = ws.floats(N * hid);
-    float* scratch = ws.floats(bwd_scratch_floats(N, std::max(C, hid), C));
     const bool pm = drop && drop->mlp_p > 0.f;
-    float* hd = pm ? ws.floats(N * hid) : h;
-    float* gf = pm ? ws.floats(N * C) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_bwd workspace too small (need %zu B)", ws.used);
+    const MlpBwdBufs b = carve_mlp_bwd(ws, N, C, hid, true, pm);
+    float *h = b.h, *dh = b.dh, *scratch = b.scratch, *hd = b.hd, *gf = b.gf;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_bwd workspace too small (need %zu B)", ws.bytes());
     static const swf_linear_grad none{};
     GemmBatch gb{};
     gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
@@ -949,6 +963,12 @@ int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, c
 
 }  // namespace
 
+size_t window_attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W) { return attention_bwd_ws(d, B, H, W, true, false); }
+// shared by the forward and the backward with dropout
+size_t window_attention_drop_ws(const swf_attn_desc& d, int B, int H, int W) {
+    return std::max(attention_bwd_ws(d, B, H, W, false, true), attention_bwd_ws(d, B, H, W, true, true));
+}
+
 int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, const float* gout,
                          float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W, void* workspace, size_t workspace_bytes,
                          hipStream_t st) {
@@ -968,8 +988,9 @@ int window_attention_fwd_drop(const swf_attn_desc& d, const swf_attn_params& p, 
     const int C = d.channels, HD = d.heads * d.head_dim;
     if (N > INT32_MAX / std::max(C, HD)) return fail(SWF_ERR_UNSUPPORTED, "window_attention_fwd_drop: token count");
     Carver ws(workspace, workspace_bytes);
-    float* Q = ws.floats(N * HD); float* K = ws.floats(N * HD); float* V = ws.floats(N * HD); float* O = ws.floats(N * HD);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_fwd_drop workspace too small (need %zu B)", ws.used);
+    const AttnBwdBufs b = carve_attention_bwd(ws, d, B, H, W, false, true);
+    float *Q = b.Q, *K = b.K, *V = b.V, *O = b.O;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "window_attention_fwd_drop workspace too small (need %zu B)", ws.bytes());
     SWF_TRY(window_attention_core(d, p, q_in, k_in, v_in, Q, K, V, O, B, H, W, &drop, stream_id, st));
     const bool pj = drop.proj_p > 0.f;
     GemmBatch pb{};
@@ -982,10 +1003,9 @@ int window_attention_fwd_drop(const swf_attn_desc& d, const swf_attn_params& p, 
     return SWF_OK;
 }
 
-size_t mlp_bwd_ws(int64_t N, int C, int hid) {
-    return carve_bytes({N * hid, N * hid}) + carve_bytes({bwd_scratch_floats(N, std::max(C, hid), C)});
-}
-size_t mlp_drop_ws(int64_t N, int C, int hid) { return mlp_bwd_ws(N, C, hid) + carve_bytes({N * hid, N * C}); }
+size_t mlp_bwd_ws(int64_t N, int C, int hid) { return mlp_ws(N, C, hid, true, false); }
+// shared by the forward and the backward with dropout, whatever the ratios
+size_t mlp_drop_ws(int64_t N, int C, int hid) { return std::max(mlp_ws(N, C, hid, false, true), mlp_ws(N, C, hid, true, true)); }
 
 int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
             int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st) {
@@ -1002,8 +1022,8 @@ int mlp_fwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, f
                  int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_fwd_drop: token count");
     Carver ws(workspace, workspace_bytes);
-    float* h = ws.floats(N * hid);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_fwd_drop workspace too small (need %zu B)", ws.used);
+    float* h = carve_mlp_bwd(ws, N, C, hid, false, true).h;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_fwd_drop workspace too small (need %zu B)", ws.bytes());
     GemmBatch gb{};
     gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
     SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, 1, st));
@@ -1016,24 +1036,41 @@ int mlp_fwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, f
     return SWF_OK;
 }
 
-size_t layernorm_bwd_ws(int64_t N, int C) { return carve_bytes({bwd_scratch_floats(N, 1, C)}); }
+static float* carve_layernorm_bwd(Carver& ws, int64_t N, int C) { return ws.floats(bwd_scratch_floats(N, 1, C)); }
+size_t layernorm_bwd_ws(int64_t N, int C) {
+    Carver m = Carver::measure();
+    carve_layernorm_bwd(m, N, C);
+    return m.bytes();
+}
 
 // my_layer_norm (a004:54-72) under autograd
 int layernorm_bwd(const swf_norm& ln, const float* x, const float* gout, float* gx, const swf_norm_grad* gp, int64_t N, int C, void* workspace,
                   size_t workspace_bytes, hipStream_t st) {
     Carver ws(workspace, workspace_bytes);
-    float* scratch = ws.floats(bwd_scratch_floats(N, 1, C));
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "layernorm_bwd workspace too small (need %zu B)", ws.used);
+    float* scratch = carve_layernorm_bwd(ws, N, C);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "layernorm_bwd workspace too small (need %zu B)", ws.bytes());
     return ln_bwd(x, ln.gamma, gout, nullptr, gx, gp ? gp->gamma : nullptr, gp ? gp->beta : nullptr, N, C, scratch, st);
 }
 
 // ---- PatchMergingAndLinearLayer backward (a011:244-264 under autograd), one stream, no window padding (the module-level layer) ----------
+struct PatchBwdBufs { float *Z, *U, *V, *A, *dV, *dZ, *scratch; };
+// n merged tokens, conv rows of K inputs and Nn outputs
+static PatchBwdBufs carve_patch_bwd(Carver& ws, int64_t n, int64_t K, int64_t Nn) {
+    PatchBwdBufs b;
+    b.Z = ws.floats(n * K);      // encoder: gathered patches; decoder: unused (the input rows are Z)
+    b.U = ws.floats(n * Nn);     // conv output
+    b.V = ws.floats(n * Nn);     // LayerNorm output (decoder: in merged-token order)
+    b.A = ws.floats(n * Nn);     // ELU output in merged-token order
+    b.dV = ws.floats(n * Nn);
+    b.dZ = ws.floats(n * K);
+    b.scratch = ws.floats(bwd_scratch_floats(n, std::max(K, Nn), Nn));
+    return b;
+}
 size_t patch_bwd_ws(int B, int H, int W, int Cin, int Cout, int mh, int mw, int encoder) {
-    const int64_t n = encoder ? (int64_t)B * (H / mh) * (W / mw) : (int64_t)B * H * W;   // merged tokens
-    const int64_t K = encoder ? (int64_t)Cin * mh * mw : Cin, Nn = encoder ? Cout : (int64_t)Cout * mh * mw;
-    const int64_t mx = std::max(K, Nn);
-    return carve_bytes({n * K, n * Nn, n * Nn, n * Nn, n * Nn, n * K}) +
-           carve_bytes({bwd_scratch_floats(n, mx, Nn)});
+    Carver m = Carver::measure();
+    carve_patch_bwd(m, encoder ? (int64_t)B * (H / mh) * (W / mw) : (int64_t)B * H * W, encoder ? (int64_t)Cin * mh * mw : Cin,
+                    encoder ? Cout : (int64_t)Cout * mh * mw);
+    return m.bytes();
 }
 
 int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int B, int H, int W, int Cin,
@@ -1045,15 +1082,9 @@ int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, flo
     const int K = encoder ? Cin * mh * mw : Cin, Nn = encoder ? Cout : Cout * mh * mw;
     if (n > INT32_MAX / std::max(K, Nn)) return fail(SWF_ERR_UNSUPPORTED, "patch backward: token count");
     Carver ws(workspace, workspace_bytes);
-    float* Z = ws.floats(n * K);      // encoder: gathered patches; decoder: unused (the input rows are Z)
-    float* U = ws.floats(n * Nn);     // conv output
-    float* V = ws.floats(n * Nn);     // LayerNorm output (decoder: in merged-token order)
-    float* A = ws.floats(n * Nn);     // ELU output in merged-token order
-    float* dV = ws.floats(n * Nn);
-    float* dZ = ws.floats(n * K);
-    const int64_t mx = std::max(K, Nn);
-    float* scratch = ws.floats(bwd_scratch_floats(n, mx, Nn));
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch backward workspace too small (need %zu B)", ws.used);
+    const PatchBwdBufs b = carve_patch_bwd(ws, n, K, Nn);
+    float *Z = b.Z, *U = b.U, *V = b.V, *A = b.A, *dV = b.dV, *dZ = b.dZ, *scratch = b.scratch;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch backward workspace too small (need %zu B)", ws.bytes());
     const swf_patch_grads none{};
     const swf_patch_grads& g = gp ? *gp : none;
     const unsigned blocks_img = (unsigned)cdiv64(n * (int64_t)mh * mw * (encoder ? Cin : Cout), 256);
@@ -1256,9 +1287,23 @@ __global__ __launch_bounds__(256) void head_split_kernel(const float* __restrict
 
 }  // namespace
 
+struct HeadBufs { float *t1, *dt2, *din, *rows, *part; };
+// `bwd` false: the batch statistics (rows and partial sums of the two conv1 channels only)
+static HeadBufs carve_head(Carver& ws, int64_t n, int ks, bool bwd) {
+    const int64_t nc = bwd ? 4 * ks * ks + 6 : 2;
+    HeadBufs b{};
+    b.t1 = ws.floats(2 * n);
+    if (bwd) { b.dt2 = ws.floats(2 * n); b.din = ws.floats(2 * n); }
+    b.rows = ws.floats(n * nc);
+    b.part = ws.floats(tree_rows(chunks_of(n)) * nc + (bwd ? nc : 0) + 64);
+    return b;
+}
+// shared by swf_final_head_bwd and swf_final_head_batch_stats
 size_t head_bwd_ws(int B, int H, int W, int ks) {
-    const int64_t n = (int64_t)B * H * W, nc = 4 * ks * ks + 6;
-    return carve_bytes({2 * n, 2 * n, 2 * n, n * nc, tree_rows(chunks_of(n)) * nc + nc + 64});
+    Carver s = Carver::measure(), m = Carver::measure();
+    carve_head(s, (int64_t)B * H * W, ks, false);
+    carve_head(m, (int64_t)B * H * W, ks, true);
+    return std::max(s.bytes(), m.bytes());
 }
 
 int head_batch_stats(const swf_head_params& p, const float* x, const float* y, float* mean, float* var, float* running_mean, float* running_var,
@@ -1266,10 +1311,9 @@ int head_batch_stats(const swf_head_params& p, const float* x, const float* y, f
     if (ks < 1 || ks % 2 == 0 || ks / 2 >= H || ks / 2 >= W) return fail(SWF_ERR_PAD, "head statistics: kernel %d on a %dx%d map", ks, H, W);
     const int64_t n = (int64_t)B * H * W;
     Carver ws(workspace, workspace_bytes);
-    float* t1 = ws.floats(2 * n);
-    float* rows = ws.floats(2 * n);
-    float* part = ws.floats(tree_rows(chunks_of(n)) * 2 + 64);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "head statistics workspace too small (need %zu B)", ws.used);
+    const HeadBufs bufs = carve_head(ws, n, ks, false);
+    float *t1 = bufs.t1, *rows = bufs.rows, *part = bufs.part;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "head statistics workspace too small (need %zu B)", ws.bytes());
     const unsigned blocks = (unsigned)cdiv64(n, 256);
     const int ch = chunks_of(n);
     float* sums = part + tree_rows(ch) * 2;
@@ -1292,12 +1336,9 @@ int head_bwd(const swf_head_params& p, const float* x, const float* y, const flo
     const int64_t n = (int64_t)B * H * W;
     const int nc1 = 4 * ks * ks + 6, nc2 = 2 * ks * ks + 1;
     Carver ws(workspace, workspace_bytes);
-    float* t1 = ws.floats(2 * n);
-    float* dt2 = ws.floats(2 * n);
-    float* din = ws.floats(2 * n);
-    float* rows = ws.floats(n * nc1);
-    float* part = ws.floats(tree_rows(chunks_of(n)) * nc1 + nc1 + 64);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "head backward workspace too small (need %zu B)", ws.used);
+    const HeadBufs bufs = carve_head(ws, n, ks, true);
+    float *t1 = bufs.t1, *dt2 = bufs.dt2, *din = bufs.din, *rows = bufs.rows, *part = bufs.part;
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "head backward workspace too small (need %zu B)", ws.bytes());
     // the BatchNorm constants are four scalars per channel: read them on the host once (a 32-byte synchronous copy per call)
     float hg[2], hb[2], hm[2], hv[2];
     if (hipMemcpyAsync(hg, p.bn_gamma, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hb, p.bn_beta, 8, hipMemcpyDeviceToHost, st) != hipSuccess ||

@@ -608,16 +608,16 @@ LossBuffers carve_loss(Carver& cv, const swf_loss_desc& d, int B, int H, int W, 
 }  // namespace
 
 size_t fusion_loss_workspace_bytes(const swf_loss_desc& d, int B, int H, int W, bool with_grad) {
-    Carver cv(nullptr, 0);
+    Carver cv = Carver::measure();
     carve_loss(cv, d, B, H, W, with_grad);
-    return align_up(cv.used, 256);
+    return cv.bytes();
 }
 
 int fusion_loss(const swf_loss_desc& d, const float* fusion, const float* ir, const float* vis, float* terms, float* grad,
                 int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     Carver cv(workspace, workspace_bytes);
     const LossBuffers b = carve_loss(cv, d, B, H, W, grad != nullptr);
-    if (!cv.ok()) return fail(SWF_ERR_WORKSPACE, "fusion_loss: workspace too small (%zu < %zu bytes)", workspace_bytes, cv.used);
+    if (!cv.ok()) return fail(SWF_ERR_WORKSPACE, "fusion_loss: workspace too small (%zu < %zu bytes)", workspace_bytes, cv.bytes());
     const int64_t n = (int64_t)B * H * W;
     const double inv_n = 1.0 / double(n);
     LossCoef k;

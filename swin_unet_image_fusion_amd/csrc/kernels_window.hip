@@ -602,12 +602,6 @@ bool window_block_out_of_place(const swf_block_desc& d) {
     return (use_win48(d) || use_win96(d)) && d.attn.win_h == 16;
 }
 
-size_t window_block_workspace_bytes(const swf_block_desc& d, int B, int H, int W) {
-    if (!window_block_supported(d, B, H, W)) return 0;
-    // packed weights of both streams (callers without a pre-packed image) + two temporary output maps for in-place callers
-    return 2 * window_block_packed_bytes(d) + (window_block_out_of_place(d) ? (size_t)2 * B * H * W * d.attn.channels * 4 + 512 : 0);
-}
-
 int pack_window_block(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py,
                       void* packed_x, void* packed_y, hipStream_t stream) {
     if (use_win24(d)) return pack_win24(d, px, py, packed_x, packed_y, stream);

@@ -55,32 +55,36 @@ static int64_t splitk_need(int K, int64_t nprob_m_n) {
 // ---- generic composition -----------------------------------------------------------------
 // Q/K/V projections (three GEMM problems per stream in one launch), attention core, output
 // projection (+ residual).  qsrc/ksrc/vsrc are [N][C] token-major inputs per stream.
+struct AttnBufs { float *qkv[2][3], *o[2], *sk, *bias16; int64_t sk_floats; };
+static AttnBufs carve_attention(Carver& ws, const swf_attn_desc& d, int nstream, int64_t N, int fast) {
+    const int C = d.channels, HD = d.heads * d.head_dim;
+    AttnBufs b{};
+    for (int s = 0; s < nstream; ++s) {
+        for (int i = 0; i < 3; ++i) b.qkv[s][i] = ws.floats(N * HD);
+        b.o[s] = ws.floats(N * HD);
+    }
+    b.sk_floats = fast ? std::max(splitk_need(C, 3 * nstream * N * HD), splitk_need(HD, nstream * N * C)) : 0;
+    b.sk = fast ? ws.floats(b.sk_floats) : nullptr;
+    const bool win16 = fast && attn_core_mfma16_supported(d.win_h, d.win_w, d.head_dim);
+    b.bias16 = win16 ? ws.floats((int64_t)attn_core_mfma16_scratch_floats(nstream)) : nullptr;
+    return b;
+}
+
 static int attention_generic(const swf_attn_desc& d, int nstream, const swf_attn_params* const* prm,
                              const float* const* qsrc, const float* const* ksrc, const float* const* vsrc,
-                             const float* const* residual, float* const* out, int B, int H, int W, Carver& ws,
+                             const float* const* residual, float* const* out, int B, int H, int W, const AttnBufs& bufs,
                              hipStream_t stream, int fast = 0, const swf_norm* const* qnorm = nullptr,
                              const swf_norm* const* kvnorm = nullptr) {
     // qnorm / kvnorm non-null: q/k/v sources are PRE-LayerNorm tensors and the projections run with the
     // LayerNorm prologue (fast tier only)
     const int64_t N = (int64_t)B * H * W;
     const int C = d.channels, HD = d.heads * d.head_dim;
-    float* qkv[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    float* o[2] = {nullptr, nullptr};
-    for (int s = 0; s < nstream; ++s) {
-        for (int i = 0; i < 3; ++i) qkv[s][i] = ws.floats(N * HD);
-        o[s] = ws.floats(N * HD);
-    }
-    const int64_t sk_floats = fast ? std::max(splitk_need(C, 3 * nstream * N * HD), splitk_need(HD, nstream * N * C)) : 0;
-    float* sk = fast ? ws.floats(sk_floats) : nullptr;
-    const bool win16 = fast && attn_core_mfma16_supported(d.win_h, d.win_w, d.head_dim);
-    float* bias16 = win16 ? ws.floats((int64_t)attn_core_mfma16_scratch_floats(nstream)) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "attention workspace too small (need %zu B)", ws.used);
     GemmBatch gb{};
-    gb.scratch = sk; gb.scratch_floats = sk_floats;
+    gb.scratch = bufs.sk; gb.scratch_floats = bufs.sk_floats;
     for (int s = 0; s < nstream; ++s) {
         const swf_linear* lin[3] = {&prm[s]->q, &prm[s]->k, &prm[s]->v};
         const float* src[3] = {qsrc[s], ksrc[s], vsrc[s]};
-        for (int i = 0; i < 3; ++i) gb.p[s * 3 + i] = GemmProb{src[i], lin[i]->weight, lin[i]->bias, nullptr, qkv[s][i]};
+        for (int i = 0; i < 3; ++i) gb.p[s * 3 + i] = GemmProb{src[i], lin[i]->weight, lin[i]->bias, nullptr, bufs.qkv[s][i]};
     }
     if (qnorm) {
         LnGemmBatch lb{};
@@ -88,44 +92,44 @@ static int attention_generic(const swf_attn_desc& d, int nstream, const swf_attn
             const swf_linear* lin[3] = {&prm[s]->q, &prm[s]->k, &prm[s]->v};
             const float* src[3] = {qsrc[s], ksrc[s], vsrc[s]};
             const swf_norm* nrm[3] = {qnorm[s], kvnorm[s], kvnorm[s]};
-            for (int i = 0; i < 3; ++i) lb.p[s * 3 + i] = LnGemmProb{src[i], nrm[i]->gamma, nrm[i]->beta, lin[i]->weight, lin[i]->bias, qkv[s][i]};
+            for (int i = 0; i < 3; ++i) lb.p[s * 3 + i] = LnGemmProb{src[i], nrm[i]->gamma, nrm[i]->beta, lin[i]->weight, lin[i]->bias, bufs.qkv[s][i]};
         }
         SWF_TRY(launch_lngemm_bf16x3(lb, nstream * 3, (int)N, HD, C, 0, stream));
     } else {
         SWF_TRY(launch_gemm(fast, gb, nstream * 3, (int)N, HD, C, C, HD, 0, stream));
     }
-    if (win16) {
-        const float* qq[2] = {qkv[0][0], qkv[1][0]};
-        const float* kk[2] = {qkv[0][1], qkv[1][1]};
-        const float* vv[2] = {qkv[0][2], qkv[1][2]};
+    if (bufs.bias16) {   // 16x16 windows
+        const float* qq[2] = {bufs.qkv[0][0], bufs.qkv[1][0]};
+        const float* kk[2] = {bufs.qkv[0][1], bufs.qkv[1][1]};
+        const float* vv[2] = {bufs.qkv[0][2], bufs.qkv[1][2]};
         const float* tt[2] = {prm[0]->bias_table, nstream == 2 ? prm[1]->bias_table : nullptr};
-        SWF_TRY(launch_attn_core_mfma16(qq, kk, vv, o, tt, nstream, HD, HD, HD, HD, B, H, W, d.heads, d.head_dim, d.shift, bias16, stream));
+        SWF_TRY(launch_attn_core_mfma16(qq, kk, vv, bufs.o, tt, nstream, HD, HD, HD, HD, B, H, W, d.heads, d.head_dim, d.shift, bufs.bias16, stream));
     } else if (fast && attn_core_mfma_supported(d.win_h, d.win_w, d.head_dim)) {
-        const float* qq[2] = {qkv[0][0], qkv[1][0]};
-        const float* kk[2] = {qkv[0][1], qkv[1][1]};
-        const float* vv[2] = {qkv[0][2], qkv[1][2]};
+        const float* qq[2] = {bufs.qkv[0][0], bufs.qkv[1][0]};
+        const float* kk[2] = {bufs.qkv[0][1], bufs.qkv[1][1]};
+        const float* vv[2] = {bufs.qkv[0][2], bufs.qkv[1][2]};
         const float* tt[2] = {prm[0]->bias_table, nstream == 2 ? prm[1]->bias_table : nullptr};
-        SWF_TRY(launch_attn_core_mfma(qq, kk, vv, o, tt, nstream, HD, HD, HD, HD, B, H, W, d.heads, d.head_dim, d.shift, stream, nullptr, nullptr,
+        SWF_TRY(launch_attn_core_mfma(qq, kk, vv, bufs.o, tt, nstream, HD, HD, HD, HD, B, H, W, d.heads, d.head_dim, d.shift, stream, nullptr, nullptr,
                                       nullptr, nullptr, nullptr, d.win_h));
     } else {
         AttnCoreBatch ab{};
-        for (int s = 0; s < nstream; ++s) ab.p[s] = AttnCoreProb{qkv[s][0], qkv[s][1], qkv[s][2], o[s], prm[s]->bias_table};
+        for (int s = 0; s < nstream; ++s) ab.p[s] = AttnCoreProb{bufs.qkv[s][0], bufs.qkv[s][1], bufs.qkv[s][2], bufs.o[s], prm[s]->bias_table};
         SWF_TRY(launch_attn_core(ab, nstream, HD, HD, HD, HD, B, H, W, d.win_h, d.win_w, d.heads, d.head_dim, d.shift, stream));
     }
     GemmBatch pb{};
-    pb.scratch = sk; pb.scratch_floats = sk_floats;
+    pb.scratch = bufs.sk; pb.scratch_floats = bufs.sk_floats;
     for (int s = 0; s < nstream; ++s)
-        pb.p[s] = GemmProb{o[s], prm[s]->proj.weight, prm[s]->proj.bias, residual ? residual[s] : nullptr, out[s]};
+        pb.p[s] = GemmProb{bufs.o[s], prm[s]->proj.weight, prm[s]->proj.bias, residual ? residual[s] : nullptr, out[s]};
     SWF_TRY(launch_gemm(fast, pb, nstream, (int)N, C, HD, HD, C, 0, stream));
     return SWF_OK;
 }
 
+// precision is not an argument of the stand-alone query: the larger of both tiers
 static size_t attention_generic_ws(const swf_attn_desc& d, int nstream, int B, int H, int W) {
-    const int64_t N = (int64_t)B * H * W, HD = (int64_t)d.heads * d.head_dim;
-    size_t total = 0;
-    for (int s = 0; s < nstream; ++s) total += carve_bytes({N * HD, N * HD, N * HD, N * HD});
-    return total + carve_bytes({std::max(splitk_need(d.channels, 3 * nstream * N * HD), splitk_need((int)HD, nstream * N * d.channels))}) +
-           carve_bytes({(int64_t)attn_core_mfma16_scratch_floats(nstream)});
+    Carver exact = Carver::measure(), fast = Carver::measure();
+    carve_attention(exact, d, nstream, (int64_t)B * H * W, 0);
+    carve_attention(fast, d, nstream, (int64_t)B * H * W, 1);
+    return std::max(exact.bytes(), fast.bytes());
 }
 
 static int check_stream_params(const swf_block_stream_params* p, const char* which, bool need_attn, bool need_mlp) {
@@ -136,6 +140,17 @@ static int check_stream_params(const swf_block_stream_params* p, const char* whi
     if (need_mlp && (!p->ln2.gamma || !p->ln2.beta || !p->fc1.weight || !p->fc2.weight))
         return fail(SWF_ERR_NULL, "%s: MLP half has a NULL weight", which);
     return SWF_OK;
+}
+
+// attention half: the LayerNorm output rows (unless the fast tier folds LN1 into the projection GEMMs), then attention_generic's buffers
+struct AttnHalfBufs { float* xn[2]; AttnBufs a; };
+static AttnHalfBufs carve_attn_half(Carver& ws, const swf_block_desc& d, int nstream, int64_t N) {
+    const int fast = d.precision == SWF_PREC_FAST;
+    AttnHalfBufs b{};
+    if (!(fast && lngemm_supported(d.attn.channels)))
+        for (int s = 0; s < nstream; ++s) b.xn[s] = ws.floats(N * d.attn.channels);
+    b.a = carve_attention(ws, d.attn, nstream, N, fast);
+    return b;
 }
 
 static int attn_halfblock_generic(const swf_block_desc* desc, const swf_block_stream_params* px,
@@ -149,6 +164,8 @@ static int attn_halfblock_generic(const swf_block_desc* desc, const swf_block_st
     const swf_attn_params* prm[2] = {&px->attn, py ? &py->attn : nullptr};
     const float* res[2] = {x_in, y_in};
     float* out[2] = {x_out, y_out};
+    const AttnHalfBufs bufs = carve_attn_half(ws, *desc, nstream, N);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "attention half-block workspace too small (need %zu B)", ws.bytes());
     if (fast && lngemm_supported(C)) {
         // LayerNorm folded into the projection GEMMs: K and V of stream s read the OTHER stream's tokens in a
         // cross block, normalised with that stream's LayerNorm (a004:29-38 then a002:67-82)
@@ -157,17 +174,29 @@ static int attn_halfblock_generic(const swf_block_desc* desc, const swf_block_st
         const float* qsrc[2] = {raw[0], raw[1]};
         const float* kvsrc[2] = {cross ? raw[1] : raw[0], cross ? raw[0] : raw[1]};
         const swf_norm* kvn[2] = {cross ? nrm[1] : nrm[0], cross ? nrm[0] : nrm[1]};
-        return attention_generic(desc->attn, nstream, prm, qsrc, kvsrc, kvsrc, res, out, B, H, W, ws, stream, fast, nrm, kvn);
+        return attention_generic(desc->attn, nstream, prm, qsrc, kvsrc, kvsrc, res, out, B, H, W, bufs.a, stream, fast, nrm, kvn);
     }
-    float* xn[2] = {ws.floats(N * C), nstream == 2 ? ws.floats(N * C) : nullptr};
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "attention half-block workspace too small");
+    float* const* xn = bufs.xn;
     LnBatch lb{};
     lb.p[0] = LnProb{x_in, xn[0], px->ln1.gamma, px->ln1.beta};
     if (nstream == 2) lb.p[1] = LnProb{y_in, xn[1], py->ln1.gamma, py->ln1.beta};
     SWF_TRY(launch_layernorm(lb, nstream, N, C, 0, stream));
     const float* qsrc[2] = {xn[0], xn[1]};
     const float* kvsrc[2] = {cross ? xn[1] : xn[0], cross ? xn[0] : xn[1]};
-    return attention_generic(desc->attn, nstream, prm, qsrc, kvsrc, kvsrc, res, out, B, H, W, ws, stream, fast);
+    return attention_generic(desc->attn, nstream, prm, qsrc, kvsrc, kvsrc, res, out, B, H, W, bufs.a, stream, fast);
+}
+
+struct MlpHalfBufs { float *xn[2], *hb[2], *sk; int64_t sk_floats; };
+static MlpHalfBufs carve_mlp_half(Carver& ws, const swf_block_desc& d, int nstream, int64_t N) {
+    const int C = d.attn.channels, hid = d.hidden;
+    const int fast = d.precision == SWF_PREC_FAST;
+    MlpHalfBufs b{};
+    if (!(fast && lngemm_supported(C)))
+        for (int s = 0; s < nstream; ++s) b.xn[s] = ws.floats(N * C);
+    for (int s = 0; s < nstream; ++s) b.hb[s] = ws.floats(N * hid);
+    b.sk_floats = fast ? std::max(splitk_need(C, nstream * N * hid), splitk_need(hid, nstream * N * C)) : 0;
+    b.sk = fast ? ws.floats(b.sk_floats) : nullptr;
+    return b;
 }
 
 static int mlp_halfblock_generic(const swf_block_desc* desc, const swf_block_stream_params* px,
@@ -178,69 +207,36 @@ static int mlp_halfblock_generic(const swf_block_desc* desc, const swf_block_str
     const int C = desc->attn.channels, hid = desc->hidden;
     const int fast = desc->precision == SWF_PREC_FAST;
     const bool fold_ln = fast && lngemm_supported(C);
-    float* xn[2] = {nullptr, nullptr};
-    if (!fold_ln) { xn[0] = ws.floats(N * C); if (nstream == 2) xn[1] = ws.floats(N * C); }
-    float* hb[2] = {ws.floats(N * hid), nstream == 2 ? ws.floats(N * hid) : nullptr};
-    const int64_t sk_floats = fast ? std::max(splitk_need(C, nstream * N * hid), splitk_need(hid, nstream * N * C)) : 0;
-    float* sk = fast ? ws.floats(sk_floats) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "MLP half-block workspace too small");
+    const MlpHalfBufs bufs = carve_mlp_half(ws, *desc, nstream, N);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "MLP half-block workspace too small (need %zu B)", ws.bytes());
     const swf_block_stream_params* pp[2] = {px, py};
     const float* res[2] = {x_in, y_in};
     float* out[2] = {x_out, y_out};
     GemmBatch g2{};
-    g2.scratch = sk; g2.scratch_floats = sk_floats;
-    for (int s = 0; s < nstream; ++s) g2.p[s] = GemmProb{hb[s], pp[s]->fc2.weight, pp[s]->fc2.bias, res[s], out[s]};
+    g2.scratch = bufs.sk; g2.scratch_floats = bufs.sk_floats;
+    for (int s = 0; s < nstream; ++s) g2.p[s] = GemmProb{bufs.hb[s], pp[s]->fc2.weight, pp[s]->fc2.bias, res[s], out[s]};
     if (fold_ln) {
         LnGemmBatch l1{};
-        for (int s = 0; s < nstream; ++s) l1.p[s] = LnGemmProb{res[s], pp[s]->ln2.gamma, pp[s]->ln2.beta, pp[s]->fc1.weight, pp[s]->fc1.bias, hb[s]};
+        for (int s = 0; s < nstream; ++s) l1.p[s] = LnGemmProb{res[s], pp[s]->ln2.gamma, pp[s]->ln2.beta, pp[s]->fc1.weight, pp[s]->fc1.bias, bufs.hb[s]};
         SWF_TRY(launch_lngemm_bf16x3(l1, nstream, (int)N, hid, C, 1, stream));
     } else {
         LnBatch lb{};
-        lb.p[0] = LnProb{x_in, xn[0], px->ln2.gamma, px->ln2.beta};
-        if (nstream == 2) lb.p[1] = LnProb{y_in, xn[1], py->ln2.gamma, py->ln2.beta};
+        lb.p[0] = LnProb{x_in, bufs.xn[0], px->ln2.gamma, px->ln2.beta};
+        if (nstream == 2) lb.p[1] = LnProb{y_in, bufs.xn[1], py->ln2.gamma, py->ln2.beta};
         SWF_TRY(launch_layernorm(lb, nstream, N, C, 0, stream));
         GemmBatch g1{};
-        g1.scratch = sk; g1.scratch_floats = sk_floats;
-        for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{xn[s], pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, hb[s]};
+        g1.scratch = bufs.sk; g1.scratch_floats = bufs.sk_floats;
+        for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{bufs.xn[s], pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, bufs.hb[s]};
         SWF_TRY(launch_gemm(fast, g1, nstream, (int)N, hid, C, C, hid, 1, stream));
     }
     SWF_TRY(launch_gemm(fast, g2, nstream, (int)N, C, hid, hid, C, 0, stream));
     return SWF_OK;
 }
 
-static size_t deep_block_ws(const swf_block_desc* d, int nstream, int B, int H, int W);
-static size_t block_generic_ws(const swf_block_desc* d, int nstream, int B, int H, int W) {
-    const int64_t N = (int64_t)B * H * W;
-    size_t a = 0, m = 0;
-    for (int s = 0; s < nstream; ++s) a += carve_bytes({N * d->attn.channels});
-    a += attention_generic_ws(d->attn, nstream, B, H, W);
-    for (int s = 0; s < nstream; ++s) m += carve_bytes({N * d->attn.channels}) + carve_bytes({N * d->hidden});
-    m += carve_bytes({std::max(splitk_need(d->attn.channels, nstream * N * d->hidden), splitk_need(d->hidden, nstream * N * d->attn.channels))});
-    return std::max(std::max(a, m), deep_block_ws(d, nstream, B, H, W));
-}
-
 // ---- deep-level composition (fast tier, C >= 128): pre-split bf16 planes between the units ----------
 // LN1 -> planes | Q/K/V GEMMs -> fp32 | MFMA attention core -> planes | proj GEMM (+x) | LN2 -> planes |
 // fc1 GEMM + ELU -> planes | fc2 GEMM (+x, split-K when hidden >= 1024).  `packed_*`: pre-split weight images
 // (pack_deep_block) or nullptr, in which case they are derived into the workspace on every call.
-static size_t deep_block_ws(const swf_block_desc* d, int nstream, int B, int H, int W) {
-    if (!deep_block_supported(*d)) return 0;
-    const int64_t N = (int64_t)B * H * W, C = d->attn.channels, HD = (int64_t)d->attn.heads * d->attn.head_dim, hid = d->hidden;
-    size_t t = 0;
-    for (int s = 0; s < nstream; ++s) t += carve_bytes({N * C / 2, N * C / 2});   // LN1 planes first (deep_ln1_planes)
-    for (int s = 0; s < nstream; ++s) {
-        t += carve_bytes({(int64_t)deep_block_packed_bytes(*d) / 4});
-        t += carve_bytes({N * HD / 2, N * HD / 2, N * HD / 2, N * HD / 2, N * HD / 2, N * hid / 2, N * hid / 2});
-    }
-    int64_t sk = std::max((int64_t)gemm_sp_splitk_for((int)HD, SP_EPI_F32), (int64_t)gemm_sp_splitk_for((int)hid, SP_EPI_F32));
-    if (mlp_fused_supported((int)C, (int)hid)) sk = std::max(sk, (int64_t)mlp_fused_splits((int)C, (int)hid));
-    t += carve_bytes({sk > 1 ? sk * nstream * N * C : 0});
-    // projection folded into the attention / MLP launches (deep_block_impl): two head-group partials + the attention-residual rows
-    if (qkvattn_supported(*d) && mlp_fused_supported((int)C, (int)hid) && HD == C)
-        for (int s = 0; s < nstream; ++s) t += carve_bytes({N * C, N * C, N * C});
-    return t;
-}
-
 // The LN1 planes of a deep-level block sit at the START of its workspace, at offsets that depend on the token count and C only:
 // whoever runs before the block on the same workspace (the previous block's MLP reduce, the previous stage's last block, the
 // patch-merging kernel) can leave them there and say so through `ln1_ready`.
@@ -249,6 +245,52 @@ static void deep_ln1_planes(Carver& ws, int64_t N, int C, int nstream, bf16_raw*
         hi[s] = reinterpret_cast<bf16_raw*>(ws.floats(N * C / 2));
         lo[s] = reinterpret_cast<bf16_raw*>(ws.floats(N * C / 2));
     }
+}
+
+// Every buffer of deep_block_impl.  `fused_mlp`: the fused MLP kernel runs (its hidden splits may need more reduce scratch than the GEMMs).
+struct DeepBufs {
+    bf16_raw *xn_hi[2], *xn_lo[2], *o_hi[2], *o_lo[2], *h_hi[2], *h_lo[2];
+    bf16_raw* qkv[2][3];   // Q (bf16, pre-scaled), K (bf16), V (fp16): the attention core's operand formats
+    void* wbuf[2];         // the packed weight images when the caller has none
+    float *sk, *part[2][2], *x1[2];
+    int64_t sk_floats;
+};
+static DeepBufs carve_deep_block(Carver& ws, const swf_block_desc& d, int nstream, int64_t N, bool fused_mlp) {
+    const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
+    auto planes = [&](int64_t n) { return reinterpret_cast<bf16_raw*>(ws.floats(n / 2)); };
+    DeepBufs b{};
+    deep_ln1_planes(ws, N, C, nstream, b.xn_hi, b.xn_lo);
+    for (int s = 0; s < nstream; ++s) {
+        b.wbuf[s] = ws.floats((int64_t)deep_block_packed_bytes(d) / 4);
+        for (int i = 0; i < 3; ++i) b.qkv[s][i] = planes(N * HD);
+        b.o_hi[s] = planes(N * HD); b.o_lo[s] = planes(N * HD);
+        b.h_hi[s] = planes(N * hid); b.h_lo[s] = planes(N * hid);
+    }
+    int64_t skn = std::max((int64_t)gemm_sp_splitk_for(HD, SP_EPI_F32), (int64_t)gemm_sp_splitk_for(hid, SP_EPI_F32));
+    if (fused_mlp) skn = std::max(skn, (int64_t)mlp_fused_splits(C, hid));
+    b.sk_floats = skn > 1 ? skn * nstream * N * C : 0;
+    b.sk = ws.floats(b.sk_floats);
+    // Output projection folded into its neighbours (C = 192 levels): qkv_attn writes the two head-group partial sums of
+    // O . Wp^T, the fused MLP kernel's prologue adds x + bias + both and normalises — no projection GEMM launch, O never
+    // reaches HBM.  (Carved last, and by shape alone, so the LN1 planes keep their offsets from block to block.)
+    if (qkvattn_supported(d) && mlp_fused_supported(C, hid) && HD == C)
+        for (int s = 0; s < nstream; ++s) { b.part[0][s] = ws.floats(N * C); b.part[1][s] = ws.floats(N * C); b.x1[s] = ws.floats(N * C); }
+    return b;
+}
+// with and without the fused MLP kernel (SWF_NO_FUSED_MLP, token count)
+static size_t deep_block_ws(const swf_block_desc* d, int nstream, int B, int H, int W) {
+    if (!deep_block_supported(*d)) return 0;
+    Carver plain = Carver::measure(), fused = Carver::measure();
+    carve_deep_block(plain, *d, nstream, (int64_t)B * H * W, false);
+    carve_deep_block(fused, *d, nstream, (int64_t)B * H * W, mlp_fused_supported(d->attn.channels, d->hidden));
+    return std::max(plain.bytes(), fused.bytes());
+}
+
+static size_t block_generic_ws(const swf_block_desc* d, int nstream, int B, int H, int W) {
+    Carver a = Carver::measure(), m = Carver::measure();
+    carve_attn_half(a, *d, nstream, (int64_t)B * H * W);
+    carve_mlp_half(m, *d, nstream, (int64_t)B * H * W);
+    return std::max(std::max(a.bytes(), m.bytes()), deep_block_ws(d, nstream, B, H, W));
 }
 
 static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
@@ -268,26 +310,10 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     const float* xin[2] = {x_in, y_in};
     float* xout[2] = {x_out, y_out};
     const void* pk[2] = {packed_x, packed_y};
-    auto planes = [&](int64_t n) { return reinterpret_cast<bf16_raw*>(ws.floats(n / 2)); };
-    bf16_raw *xn_hi[2], *xn_lo[2], *o_hi[2], *o_lo[2], *h_hi[2], *h_lo[2];
-    bf16_raw* qkv[2][3];   // Q (bf16, pre-scaled), K (bf16), V (fp16): the attention core's operand formats
-    void* wbuf[2] = {nullptr, nullptr};
-    deep_ln1_planes(ws, N, C, nstream, xn_hi, xn_lo);
-    for (int s = 0; s < nstream; ++s) {
-        wbuf[s] = ws.floats((int64_t)deep_block_packed_bytes(*desc) / 4);
-        for (int i = 0; i < 3; ++i) qkv[s][i] = planes(N * HD);
-        o_hi[s] = planes(N * HD); o_lo[s] = planes(N * HD);
-        h_hi[s] = planes(N * hid); h_lo[s] = planes(N * hid);
-    }
-    int64_t skn = std::max((int64_t)gemm_sp_splitk_for(HD, SP_EPI_F32), (int64_t)gemm_sp_splitk_for(hid, SP_EPI_F32));
     static const bool no_fused_mlp = debug_env("SWF_NO_FUSED_MLP") != nullptr;   // A/B switch
     const bool fused_mlp = !no_fused_mlp && mlp_fused_supported(C, hid) && N <= INT32_MAX / 2;
-    if (fused_mlp) skn = std::max(skn, (int64_t)mlp_fused_splits(C, hid));
-    const int64_t sk_floats = skn > 1 ? skn * nstream * N * C : 0;
-    float* sk = ws.floats(sk_floats);
-    // Output projection folded into its neighbours (C = 192 levels): qkv_attn writes the two head-group partial sums of
-    // O . Wp^T, the fused MLP kernel's prologue adds x + bias + both and normalises — no projection GEMM launch, O never
-    // reaches HBM.  (Carved last so the LN1 planes keep their offsets from block to block.)
+    const DeepBufs b = carve_deep_block(ws, *desc, nstream, N, fused_mlp);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "deep block workspace too small (need %zu B)", ws.bytes());
     static const bool no_qkvattn = debug_env("SWF_NO_QKVATTN") != nullptr;     // A/B switches
     static const bool no_projfuse = debug_env("SWF_NO_PROJFUSE") != nullptr;
     const bool fused_attn_shape = !no_qkvattn && qkvattn_supported(*desc) && N <= INT32_MAX / 256;
@@ -295,19 +321,15 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     // pulls per workgroup only pay while its grid under-fills the chip.  The rule looks at the map size, never at the batch, so
     // batch shards keep taking the same path (bit-identical rows across shard sizes).
     const bool proj_fused = fused_attn_shape && fused_mlp && !no_projfuse && HD == C && (int64_t)H * W <= 256;
-    float *part[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}}, *x1[2] = {nullptr, nullptr};
-    if (qkvattn_supported(*desc) && mlp_fused_supported(C, hid) && HD == C)
-        for (int s = 0; s < nstream; ++s) { part[0][s] = ws.floats(N * C); part[1][s] = ws.floats(N * C); x1[s] = ws.floats(N * C); }
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "deep block workspace too small (need %zu B)", ws.used);
     DeepWeights wv[2];
     for (int s = 0; s < nstream; ++s) {
-        if (!pk[s]) { SWF_TRY(pack_deep_block(*desc, *pp[s], wbuf[s], stream)); pk[s] = wbuf[s]; }
+        if (!pk[s]) { SWF_TRY(pack_deep_block(*desc, *pp[s], b.wbuf[s], stream)); pk[s] = b.wbuf[s]; }
         wv[s] = deep_block_views(*desc, pk[s]);
     }
     // attention half (a004:29-38 around a002:58-82)
     if (!ln1_given) {
         LnBatch l1{};
-        for (int s = 0; s < nstream; ++s) l1.p[s] = LnProb{xin[s], nullptr, pp[s]->ln1.gamma, pp[s]->ln1.beta, xn_hi[s], xn_lo[s]};
+        for (int s = 0; s < nstream; ++s) l1.p[s] = LnProb{xin[s], nullptr, pp[s]->ln1.gamma, pp[s]->ln1.beta, b.xn_hi[s], b.xn_lo[s]};
         SWF_TRY(launch_layernorm(l1, nstream, N, C, 0, stream));
     }
     const bool fused_attn = fused_attn_shape && wv[0].qa && (nstream == 1 || wv[1].qa);
@@ -315,8 +337,8 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     if (fused_attn) {   // Q/K/V projections + window attention (+ output projection partials) in one launch
         QkvAttnArgs qa{};
         for (int s = 0; s < nstream; ++s) {
-            qa.packed[s] = wv[s].qa; qa.xn_hi[s] = xn_hi[s]; qa.xn_lo[s] = xn_lo[s]; qa.o_hi[s] = o_hi[s]; qa.o_lo[s] = o_lo[s];
-            if (fold_proj) { qa.part[0][s] = part[0][s]; qa.part[1][s] = part[1][s]; }
+            qa.packed[s] = wv[s].qa; qa.xn_hi[s] = b.xn_hi[s]; qa.xn_lo[s] = b.xn_lo[s]; qa.o_hi[s] = b.o_hi[s]; qa.o_lo[s] = b.o_lo[s];
+            if (fold_proj) { qa.part[0][s] = b.part[0][s]; qa.part[1][s] = b.part[1][s]; }
         }
         qa.B = B; qa.H = H; qa.W = W; qa.shift = desc->attn.shift; qa.cross = cross;
         SWF_TRY(launch_qkvattn(*desc, qa, nstream, stream));
@@ -329,7 +351,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         const bf16_raw* wl[3] = {wv[s].q_lo, wv[s].k_lo, wv[s].v_lo};
         for (int i = 0; i < 3; ++i) {
             const int src = i == 0 ? s : kvs;
-            gq.p[s * 3 + i] = SpGemmProb{xn_hi[src], xn_lo[src], wh[i], wl[i], lin[i]->bias, nullptr, nullptr, qkv[s][i], nullptr};
+            gq.p[s * 3 + i] = SpGemmProb{b.xn_hi[src], b.xn_lo[src], wh[i], wl[i], lin[i]->bias, nullptr, nullptr, b.qkv[s][i], nullptr};
         }
     }
     gq.qscale = 1.4426950408889634f / std::sqrt((float)desc->attn.head_dim);   // d^-0.5 (a001:32-34) and exp -> exp2
@@ -337,9 +359,9 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     if (deep_qkv) {   // level 4: the three projections of both streams in one launch of the rows-times-fragment-major-weights kernel
         DeepQkvArgs dq{};
         for (int s = 0; s < nstream; ++s) {
-            dq.xn_hi[s] = xn_hi[s]; dq.xn_lo[s] = xn_lo[s]; dq.w_hi[s] = wv[s].qkvf_hi; dq.w_lo[s] = wv[s].qkvf_lo;
+            dq.xn_hi[s] = b.xn_hi[s]; dq.xn_lo[s] = b.xn_lo[s]; dq.w_hi[s] = wv[s].qkvf_hi; dq.w_lo[s] = wv[s].qkvf_lo;
             dq.bias[s][0] = pp[s]->attn.q.bias; dq.bias[s][1] = pp[s]->attn.k.bias; dq.bias[s][2] = pp[s]->attn.v.bias;
-            for (int i = 0; i < 3; ++i) dq.out[s][i] = qkv[s][i];
+            for (int i = 0; i < 3; ++i) dq.out[s][i] = b.qkv[s][i];
         }
         dq.qscale = gq.qscale; dq.cross = cross; dq.M = (int)N; dq.C = C;
         SWF_TRY(launch_deep_qkv(dq, nstream, stream));
@@ -350,7 +372,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     if (attn_proj) {
         AttnProjArgs ap{};
         for (int s = 0; s < nstream; ++s) {
-            ap.q[s] = qkv[s][0]; ap.k[s] = qkv[s][1]; ap.v[s] = qkv[s][2];
+            ap.q[s] = b.qkv[s][0]; ap.k[s] = b.qkv[s][1]; ap.v[s] = b.qkv[s][2];
             ap.wp_hi[s] = wv[s].pf_hi; ap.wp_lo[s] = wv[s].pf_lo; ap.pbias[s] = pp[s]->attn.proj.bias; ap.table[s] = pp[s]->attn.bias_table;
             ap.res[s] = xin[s]; ap.out[s] = xout[s];
         }
@@ -358,26 +380,26 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         SWF_TRY(launch_attnproj(*desc, ap, nstream, stream));
     }
     if (!fused_attn && !attn_proj) {
-        const bf16_raw* qq[2] = {qkv[0][0], qkv[1][0]};
-        const bf16_raw* kk[2] = {qkv[0][1], qkv[1][1]};
-        const bf16_raw* vv[2] = {qkv[0][2], qkv[1][2]};
+        const bf16_raw* qq[2] = {b.qkv[0][0], b.qkv[1][0]};
+        const bf16_raw* kk[2] = {b.qkv[0][1], b.qkv[1][1]};
+        const bf16_raw* vv[2] = {b.qkv[0][2], b.qkv[1][2]};
         const float* tt[2] = {pp[0]->attn.bias_table, nstream == 2 ? pp[1]->attn.bias_table : nullptr};
         if (desc->attn.win_h == 16)
             SWF_TRY(launch_attn_core_mfma16(nullptr, nullptr, nullptr, nullptr, tt, nstream, HD, HD, HD, HD, B, H, W, desc->attn.heads,
-                                            desc->attn.head_dim, desc->attn.shift, nullptr, stream, o_hi, o_lo, qq, kk, vv));
+                                            desc->attn.head_dim, desc->attn.shift, nullptr, stream, b.o_hi, b.o_lo, qq, kk, vv));
         else
             SWF_TRY(launch_attn_core_mfma(nullptr, nullptr, nullptr, nullptr, tt, nstream, HD, HD, HD, HD, B, H, W, desc->attn.heads,
-                                          desc->attn.head_dim, desc->attn.shift, stream, o_hi, o_lo, qq, kk, vv, desc->attn.win_h));
+                                          desc->attn.head_dim, desc->attn.shift, stream, b.o_hi, b.o_lo, qq, kk, vv, desc->attn.win_h));
     }
     SpGemmBatch gp{};
-    gp.scratch = sk; gp.scratch_floats = sk_floats;
+    gp.scratch = b.sk; gp.scratch_floats = b.sk_floats;
     for (int s = 0; s < nstream; ++s)
-        gp.p[s] = SpGemmProb{o_hi[s], o_lo[s], wv[s].p_hi, wv[s].p_lo, pp[s]->attn.proj.bias, xin[s], xout[s], nullptr, nullptr};
+        gp.p[s] = SpGemmProb{b.o_hi[s], b.o_lo[s], wv[s].p_hi, wv[s].p_lo, pp[s]->attn.proj.bias, xin[s], xout[s], nullptr, nullptr};
     const bool deep_proj = !fold_proj && !attn_proj && HD == C && deep_proj_supported(*desc) && wv[0].pf_hi && (nstream == 1 || wv[1].pf_hi);
     if (deep_proj) {   // rows x fragment-major Wproj (+ bias + residual) instead of the plane GEMM
         DeepProjArgs dp{};
         for (int s = 0; s < nstream; ++s) {
-            dp.o_hi[s] = o_hi[s]; dp.o_lo[s] = o_lo[s]; dp.w_hi[s] = wv[s].pf_hi; dp.w_lo[s] = wv[s].pf_lo;
+            dp.o_hi[s] = b.o_hi[s]; dp.o_lo[s] = b.o_lo[s]; dp.w_hi[s] = wv[s].pf_hi; dp.w_lo[s] = wv[s].pf_lo;
             dp.bias[s] = pp[s]->attn.proj.bias; dp.res[s] = xin[s]; dp.out[s] = xout[s];
         }
         dp.M = (int)N; dp.C = C;
@@ -389,31 +411,31 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         MlpFusedDesc md{};
         for (int s = 0; s < nstream; ++s) {
             md.x[s] = fold_proj ? xin[s] : xout[s]; md.out[s] = xout[s]; md.gamma[s] = pp[s]->ln2.gamma; md.beta[s] = pp[s]->ln2.beta;
-            if (fold_proj) { md.part0[s] = part[0][s]; md.part1[s] = part[1][s]; md.pbias[s] = pp[s]->attn.proj.bias; md.x1[s] = x1[s]; }
+            if (fold_proj) { md.part0[s] = b.part[0][s]; md.part1[s] = b.part[1][s]; md.pbias[s] = pp[s]->attn.proj.bias; md.x1[s] = b.x1[s]; }
             md.w1_hi[s] = wv[s].w1f_hi; md.w1_lo[s] = wv[s].w1f_lo; md.w2_hi[s] = wv[s].w2f_hi; md.w2_lo[s] = wv[s].w2f_lo;
             md.b1[s] = pp[s]->fc1.bias; md.b2[s] = pp[s]->fc2.bias;
         }
-        md.scratch = sk; md.scratch_floats = sk_floats; md.M = (int)N; md.C = C; md.HID = hid; md.schedule = desc->schedule;
+        md.scratch = b.sk; md.scratch_floats = b.sk_floats; md.M = (int)N; md.C = C; md.HID = hid; md.schedule = desc->schedule;
         const bool ln_next = next_p && ln1_ready && next_p[0] && (nstream == 1 || next_p[1]) && mlp_fused_writes_ln(C, hid);
         if (ln_next)
             for (int s = 0; s < nstream; ++s) {
-                md.ln_gamma[s] = next_p[s]->ln1.gamma; md.ln_beta[s] = next_p[s]->ln1.beta; md.ln_hi[s] = xn_hi[s]; md.ln_lo[s] = xn_lo[s];
+                md.ln_gamma[s] = next_p[s]->ln1.gamma; md.ln_beta[s] = next_p[s]->ln1.beta; md.ln_hi[s] = b.xn_hi[s]; md.ln_lo[s] = b.xn_lo[s];
             }
         SWF_TRY(launch_mlp_fused(md, nstream, stream));
         if (ln_next) *ln1_ready = true;
         return SWF_OK;
     }
     LnBatch l2{};
-    for (int s = 0; s < nstream; ++s) l2.p[s] = LnProb{xout[s], nullptr, pp[s]->ln2.gamma, pp[s]->ln2.beta, xn_hi[s], xn_lo[s]};
+    for (int s = 0; s < nstream; ++s) l2.p[s] = LnProb{xout[s], nullptr, pp[s]->ln2.gamma, pp[s]->ln2.beta, b.xn_hi[s], b.xn_lo[s]};
     SWF_TRY(launch_layernorm(l2, nstream, N, C, 0, stream));
     SpGemmBatch g1{};
     for (int s = 0; s < nstream; ++s)
-        g1.p[s] = SpGemmProb{xn_hi[s], xn_lo[s], wv[s].w1_hi, wv[s].w1_lo, pp[s]->fc1.bias, nullptr, nullptr, h_hi[s], h_lo[s]};
+        g1.p[s] = SpGemmProb{b.xn_hi[s], b.xn_lo[s], wv[s].w1_hi, wv[s].w1_lo, pp[s]->fc1.bias, nullptr, nullptr, b.h_hi[s], b.h_lo[s]};
     SWF_TRY(launch_gemm_sp(g1, nstream, (int)N, hid, C, hid, SP_EPI_ELU_SPLIT, stream));
     SpGemmBatch g2{};
-    g2.scratch = sk; g2.scratch_floats = sk_floats;
+    g2.scratch = b.sk; g2.scratch_floats = b.sk_floats;
     for (int s = 0; s < nstream; ++s)
-        g2.p[s] = SpGemmProb{h_hi[s], h_lo[s], wv[s].w2_hi, wv[s].w2_lo, pp[s]->fc2.bias, xout[s], xout[s], nullptr, nullptr};
+        g2.p[s] = SpGemmProb{b.h_hi[s], b.h_lo[s], wv[s].w2_hi, wv[s].w2_lo, pp[s]->fc2.bias, xout[s], xout[s], nullptr, nullptr};
     return launch_gemm_sp(g2, nstream, (int)N, C, hid, C, SP_EPI_F32, stream);
 }
 
@@ -438,6 +460,32 @@ static int check_block(const swf_block_desc* desc, const swf_block_stream_params
     return SWF_OK;
 }
 
+// Fused window-block route: the packed weight images of both streams (callers without pre-packed ones), then two temporary output maps
+// (`tmp_out`) for a kernel that cannot run a cross block in place (window_block_out_of_place): basic_block_impl copies them to the
+// outputs, block_pair4_impl ping-pongs its two cross blocks through them.
+struct WindowBufs { char* packed; float *ox, *oy; };
+static WindowBufs carve_window_block(Carver& ws, const swf_block_desc& d, int64_t N, bool prepacked, bool tmp_out) {
+    WindowBufs b{};
+    if (!prepacked) b.packed = reinterpret_cast<char*>(ws.floats((int64_t)(2 * window_block_packed_bytes(d) / 4)));
+    if (tmp_out) {
+        b.ox = ws.floats(2 * N * d.attn.channels);
+        b.oy = b.ox ? b.ox + N * d.attn.channels : nullptr;
+    }
+    return b;
+}
+// pre-packed or not, in place or not: the route with both is the largest
+static size_t window_block_ws(const swf_block_desc& d, int B, int H, int W) {
+    if (!window_block_supported(d, B, H, W)) return 0;
+    size_t need = 0;
+    for (int route = 0; route < 4; ++route) {
+        if ((route & 2) && !window_block_out_of_place(d)) continue;
+        Carver m = Carver::measure();
+        carve_window_block(m, d, (int64_t)B * H * W, (route & 1) != 0, (route & 2) != 0);
+        need = std::max(need, m.bytes());
+    }
+    return need;
+}
+
 static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_params* px,
                             const swf_block_stream_params* py, const float* x_in, const float* y_in, float* x_out,
                             float* y_out, int B, int H, int W, void* workspace, size_t workspace_bytes,
@@ -449,20 +497,14 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
         if (ln1_ready) *ln1_ready = false;
         const bool prepacked = prepacked_x && prepacked_y;   // model path: weights were packed once (swf_model_pack_weights)
         const size_t pb = window_block_packed_bytes(*desc);
-        char* w = static_cast<char*>(workspace);
-        size_t used = prepacked ? 0 : 2 * pb;
-        if (!prepacked && (!workspace || workspace_bytes < used)) return fail(SWF_ERR_WORKSPACE, "fused block workspace too small (need %zu B)", used);
         // a kernel whose workgroups read one stream while others write it (kernels_window.h) gets temporary outputs when called in place
-        float *ox = x_out, *oy = y_out;
         const size_t map_bytes = (size_t)B * H * W * desc->attn.channels * 4;
         const bool via_tmp = window_block_out_of_place(*desc) && desc->cross && (x_in == x_out || y_in == y_out || x_in == y_out || y_in == x_out);
-        if (via_tmp) {
-            used = align_up(used, 256);
-            if (!workspace || workspace_bytes < used + 2 * map_bytes)
-                return fail(SWF_ERR_WORKSPACE, "fused block workspace too small (need %zu B)", used + 2 * map_bytes);
-            ox = reinterpret_cast<float*>(w + used);
-            oy = reinterpret_cast<float*>(w + used + map_bytes);
-        }
+        Carver ws(workspace, workspace_bytes);
+        const WindowBufs bufs = carve_window_block(ws, *desc, (int64_t)B * H * W, prepacked, via_tmp);
+        if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "fused block workspace too small (need %zu B)", ws.bytes());
+        char* w = bufs.packed;
+        float *ox = via_tmp ? bufs.ox : x_out, *oy = via_tmp ? bufs.oy : y_out;
         if (prepacked) {
             SWF_TRY(launch_window_block(*desc, prepacked_x, prepacked_y, x_in, y_in, ox, oy, B, H, W, stream, next_x, next_y, next_bytes));
         } else {   // block-level entry: pack this block's weights into the workspace, then one fused launch
@@ -520,6 +562,45 @@ static int merge_shapes(int H, int W, int mh, int mw, int wh, int ww, int* Hm, i
     return SWF_OK;
 }
 
+// Deep-level patch kernels: the LN1 planes of the block that runs next on this workspace (`with_ln`; at its start: deep_ln1_planes), then,
+// for the column-sliced route, `row_floats` conv rows per stream (0: the whole-row route, which keeps its rows on chip).
+struct DeepPatchBufs { bf16_raw *ln_hi[2], *ln_lo[2]; float* zr[2]; };
+static DeepPatchBufs carve_deep_patch(Carver& ws, int nstream, bool with_ln, int64_t N_ln, int C_ln, int64_t row_floats) {
+    DeepPatchBufs b{};
+    if (with_ln) deep_ln1_planes(ws, N_ln, C_ln, nstream, b.ln_hi, b.ln_lo);
+    for (int s = 0; s < nstream && row_floats; ++s) b.zr[s] = ws.floats(row_floats);
+    return b;
+}
+// the kernel's LayerNorm epilogue for the block `blk` (nullptr: none)
+static const DeepPatchExtra* deep_patch_ln(DeepPatchExtra& ex, const DeepPatchBufs& b, const swf_block_stream_params* const* blk, int nstream) {
+    if (!blk) return nullptr;
+    for (int s = 0; s < nstream; ++s) {
+        ex.ln_gamma[s] = blk[s]->ln1.gamma; ex.ln_beta[s] = blk[s]->ln1.beta; ex.ln_hi[s] = b.ln_hi[s]; ex.ln_lo[s] = b.ln_lo[s];
+    }
+    return &ex;
+}
+
+// generic routes: gathered patches and conv rows (merge) / cropped input, conv rows and their LayerNorm (unmerge), split-K partials
+struct PatchBufs { float *a[2], *z[2], *zn[2], *sk; int64_t sk_floats; };
+static PatchBufs carve_merge_generic(Carver& ws, int nstream, int64_t N, int K, int Cout, int fast) {
+    PatchBufs b{};
+    for (int s = 0; s < nstream; ++s) { b.a[s] = ws.floats(N * K); b.z[s] = ws.floats(N * Cout); }
+    b.sk_floats = fast ? splitk_need(K, nstream * N * Cout) : 0;
+    b.sk = fast ? ws.floats(b.sk_floats) : nullptr;
+    return b;
+}
+static PatchBufs carve_unmerge_generic(Carver& ws, int nstream, int64_t N, int Cin, int Kz, bool need_crop, int fast) {
+    PatchBufs b{};
+    for (int s = 0; s < nstream; ++s) {
+        if (need_crop) b.a[s] = ws.floats(N * Cin);
+        b.z[s] = ws.floats(N * Kz);
+        b.zn[s] = ws.floats(N * Kz);
+    }
+    b.sk_floats = fast ? splitk_need(Cin, nstream * N * Kz) : 0;
+    b.sk = fast ? ws.floats(b.sk_floats) : nullptr;
+    return b;
+}
+
 static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const float* const* in, float* const* out,
                             int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww, void* workspace,
                             size_t workspace_bytes, hipStream_t stream, int fast = 0, const void* const* prr = nullptr,
@@ -546,53 +627,33 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
         d.decoder = 0; d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.mh = mh; d.mw = mw; d.Hm = Hm; d.Wm = Wm; d.Ho = Ho; d.Wo = Wo;
         d.K = K; d.N = Cout; d.Cout = Cout; d.M = N;
         if (use_prr) return launch_patch_rr(d, prr, nstream, stream);
-        if (use_dp && deep_patch_raw(0, Cin, Cout, mh, mw)) {   // conv over column slices, then LayerNorm + ELU (+ the next block's LN1) as a second launch
-            Carver wz(workspace, workspace_bytes);
-            DeepPatchExtra ex{};
-            const bool with_ln = first_blk && ln1_ready && first_blk[0] && (nstream == 1 || first_blk[1]);
-            if (with_ln) {   // the planes sit at the start of the workspace (deep_ln1_planes), the conv rows behind them
-                bf16_raw *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
-                deep_ln1_planes(wz, N, Cout, nstream, hi, lo);
-                for (int s = 0; s < nstream; ++s) {
-                    ex.ln_gamma[s] = first_blk[s]->ln1.gamma; ex.ln_beta[s] = first_blk[s]->ln1.beta; ex.ln_hi[s] = hi[s]; ex.ln_lo[s] = lo[s];
-                }
-            }
-            float* zr[2] = {nullptr, nullptr};
-            for (int s = 0; s < nstream; ++s) zr[s] = wz.floats(N * Cout);
-            if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", wz.used);
-            SWF_TRY(launch_deep_patch(d, prr, nstream, stream, zr));
-            SWF_TRY(launch_deep_patch_finish(d, zr, nstream, stream, with_ln ? &ex : nullptr));
-            if (with_ln) *ln1_ready = true;
-            return SWF_OK;
-        }
         if (use_dp) {
+            // column slices: conv rows into the workspace, then LayerNorm + ELU (+ the next block's LN1) as a second launch; else whole rows
+            const bool sliced = deep_patch_raw(0, Cin, Cout, mh, mw);
+            const bool with_ln = first_blk && ln1_ready && first_blk[0] && (nstream == 1 || first_blk[1]) && (sliced || workspace);
+            Carver wz(workspace, workspace_bytes);
+            const DeepPatchBufs b = carve_deep_patch(wz, nstream, with_ln, N, Cout, sliced ? N * Cout : 0);
+            if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", wz.bytes());
             DeepPatchExtra ex{};
-            const bool with_ln = first_blk && ln1_ready && first_blk[0] && (nstream == 1 || first_blk[1]) && workspace;
-            if (with_ln) {
-                Carver wl(workspace, workspace_bytes);
-                bf16_raw *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
-                deep_ln1_planes(wl, N, Cout, nstream, hi, lo);
-                if (!wl.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small for the LN1 planes (need %zu B)", wl.used);
-                for (int s = 0; s < nstream; ++s) {
-                    ex.ln_gamma[s] = first_blk[s]->ln1.gamma; ex.ln_beta[s] = first_blk[s]->ln1.beta; ex.ln_hi[s] = hi[s]; ex.ln_lo[s] = lo[s];
-                }
+            const DeepPatchExtra* ln = deep_patch_ln(ex, b, with_ln ? first_blk : nullptr, nstream);
+            if (sliced) {
+                SWF_TRY(launch_deep_patch(d, prr, nstream, stream, b.zr));
+                SWF_TRY(launch_deep_patch_finish(d, b.zr, nstream, stream, ln));
+            } else {
+                SWF_TRY(launch_deep_patch(d, prr, nstream, stream, nullptr, ln));
             }
-            SWF_TRY(launch_deep_patch(d, prr, nstream, stream, nullptr, with_ln ? &ex : nullptr));
             if (with_ln) *ln1_ready = true;
             return SWF_OK;
         }
         return launch_patch_fused(d, nstream, stream);
     }
     Carver ws(workspace, workspace_bytes);
-    float* a[2];
-    float* z[2];
-    for (int s = 0; s < nstream; ++s) { a[s] = ws.floats(N * K); z[s] = ws.floats(N * Cout); }
-    const int64_t sk_floats = fast ? splitk_need(K, nstream * N * Cout) : 0;
-    float* sk = fast ? ws.floats(sk_floats) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", ws.used);
+    const PatchBufs bufs = carve_merge_generic(ws, nstream, N, K, Cout, fast);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", ws.bytes());
+    float* const *a = bufs.a, *const *z = bufs.z;
     PtrPair pp{};
     GemmBatch gb{};
-    gb.scratch = sk; gb.scratch_floats = sk_floats;
+    gb.scratch = bufs.sk; gb.scratch_floats = bufs.sk_floats;
     LnBatch lb{};
     for (int s = 0; s < nstream; ++s) {
         pp.in[s] = in[s]; pp.out[s] = a[s];
@@ -637,47 +698,32 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
         d.K = Cin; d.N = Kz; d.Cout = Cout; d.M = N;
         if (use_prr) return launch_patch_rr(d, prr, nstream, stream);
         if (use_dp && deep_patch_raw(1, Cin, Cout, mh, mw)) {   // conv over column slices, then LayerNorm + scatter + ELU (+ skip) (+ the next block's LN1)
-            Carver wz(workspace, workspace_bytes);
-            DeepPatchExtra ex{};
             const bool with_ln = next_blk && ln1_ready && next_blk[0] && (nstream == 1 || next_blk[1]);
-            if (with_ln) {
-                bf16_raw *hi[2] = {nullptr, nullptr}, *lo[2] = {nullptr, nullptr};
-                deep_ln1_planes(wz, (int64_t)B * Hout * Wout, Cout, nstream, hi, lo);
-                for (int s = 0; s < nstream; ++s) {
-                    ex.ln_gamma[s] = next_blk[s]->ln1.gamma; ex.ln_beta[s] = next_blk[s]->ln1.beta; ex.ln_hi[s] = hi[s]; ex.ln_lo[s] = lo[s];
-                }
-            }
-            float* zr[2] = {nullptr, nullptr};
-            for (int s = 0; s < nstream; ++s) zr[s] = wz.floats(N * Kz);
-            if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", wz.used);
-            SWF_TRY(launch_deep_patch(d, prr, nstream, stream, zr));
-            SWF_TRY(launch_deep_patch_finish(d, zr, nstream, stream, with_ln ? &ex : nullptr));
+            Carver wz(workspace, workspace_bytes);
+            const DeepPatchBufs b = carve_deep_patch(wz, nstream, with_ln, (int64_t)B * Hout * Wout, Cout, N * Kz);
+            if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", wz.bytes());
+            DeepPatchExtra ex{};
+            SWF_TRY(launch_deep_patch(d, prr, nstream, stream, b.zr));
+            SWF_TRY(launch_deep_patch_finish(d, b.zr, nstream, stream, deep_patch_ln(ex, b, with_ln ? next_blk : nullptr, nstream)));
             if (with_ln) *ln1_ready = true;
             return SWF_OK;
-        } else if (use_dp) {
+        }
+        if (use_dp) {   // whole rows: no workspace
             DeepPatchExtra ex{};
             if (warm && warm_pb && nstream == 2) { ex.warm[0] = warm; ex.warm[1] = warm + warm_pb; ex.warm_bytes = warm_pb; }
             SWF_TRY(launch_deep_patch(d, prr, nstream, stream, nullptr, ex.warm[0] ? &ex : nullptr));
             if (warmed && ex.warm[0]) *warmed = true;
             return SWF_OK;
         }
-        if (!use_dp) return launch_patch_fused(d, nstream, stream);
+        return launch_patch_fused(d, nstream, stream);
     }
     Carver ws(workspace, workspace_bytes);
-    float* cr[2] = {nullptr, nullptr};
-    float* z[2];
-    float* zn[2];
-    for (int s = 0; s < nstream; ++s) {
-        if (need_crop) cr[s] = ws.floats(N * Cin);
-        z[s] = ws.floats(N * Kz);
-        zn[s] = ws.floats(N * Kz);
-    }
-    const int64_t sk_floats = fast ? splitk_need(Cin, nstream * N * Kz) : 0;
-    float* sk = fast ? ws.floats(sk_floats) : nullptr;
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", ws.used);
+    const PatchBufs bufs = carve_unmerge_generic(ws, nstream, N, Cin, Kz, need_crop, fast);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", ws.bytes());
+    float* const *cr = bufs.a, *const *z = bufs.z, *const *zn = bufs.zn;
     PtrPair cp{}, sp{};
     GemmBatch gb{};
-    gb.scratch = sk; gb.scratch_floats = sk_floats;
+    gb.scratch = bufs.sk; gb.scratch_floats = bufs.sk_floats;
     LnBatch lb{};
     for (int s = 0; s < nstream; ++s) {
         cp.in[s] = in[s]; cp.out[s] = cr[s];
@@ -693,20 +739,39 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
     return launch_unmerge_scatter(sp, nstream, B, Hm, Wm, Cout, mh, mw, Hout, Wout, stream);
 }
 
-static size_t patch_ws(int nstream, int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww, int encoder) {
-    size_t total = 0;
-    if (encoder) {
-        int Hm, Wm, Ho, Wo;
-        if (merge_shapes(H, W, mh, mw, wh, ww, &Hm, &Wm, &Ho, &Wo) != SWF_OK) return 0;
-        const int64_t N = (int64_t)B * Ho * Wo;
-        for (int s = 0; s < nstream; ++s) total += carve_bytes({N * mh * mw * Cin, N * Cout});
-        total += carve_bytes({splitk_need(mh * mw * Cin, nstream * N * Cout)});
-    } else {
-        const int64_t N = (int64_t)B * H * W;   // upper bound: uncropped map
-        for (int s = 0; s < nstream; ++s) total += carve_bytes({N * Cin, N * mh * mw * Cout, N * mh * mw * Cout});
-        total += carve_bytes({splitk_need(Cin, (int64_t)nstream * N * mh * mw * Cout)});
-    }
-    return total;
+// Every route of the two impls that the shape admits: the generic one in both tiers, and the deep-level kernels with the LN1 planes of
+// the block behind them (the single-launch fused and register-resident kernels take no workspace).
+static size_t merge_ws(int nstream, int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww) {
+    int Hm, Wm, Ho, Wo;
+    if (Cin <= 0 || Cout <= 0 || merge_shapes(H, W, mh, mw, wh, ww, &Hm, &Wm, &Ho, &Wo) != SWF_OK) return 0;
+    const int64_t N = (int64_t)B * Ho * Wo;
+    Carver exact = Carver::measure(), fast = Carver::measure(), deep = Carver::measure();
+    carve_merge_generic(exact, nstream, N, mh * mw * Cin, Cout, 0);
+    carve_merge_generic(fast, nstream, N, mh * mw * Cin, Cout, 1);
+    if (deep_patch_supported(0, Cin, Cout, mh, mw)) carve_deep_patch(deep, nstream, true, N, Cout, deep_patch_raw(0, Cin, Cout, mh, mw) ? N * Cout : 0);
+    return std::max(std::max(exact.bytes(), fast.bytes()), deep.bytes());
+}
+static size_t unmerge_ws(int nstream, int B, int Hp, int Wp, int Hm, int Wm, int Cin, int Cout, int mh, int mw, int Hout, int Wout) {
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || mh <= 0 || mw <= 0 || Hm <= 0 || Wm <= 0 || Hm > Hp || Wm > Wp) return 0;
+    const int64_t N = (int64_t)B * Hm * Wm;
+    const int Kz = mh * mw * Cout;
+    Carver exact = Carver::measure(), fast = Carver::measure(), deep = Carver::measure();
+    carve_unmerge_generic(exact, nstream, N, Cin, Kz, Hm != Hp || Wm != Wp, 0);
+    carve_unmerge_generic(fast, nstream, N, Cin, Kz, Hm != Hp || Wm != Wp, 1);
+    if (deep_patch_supported(1, Cin, Cout, mh, mw) && deep_patch_raw(1, Cin, Cout, mh, mw))
+        carve_deep_patch(deep, nstream, true, (int64_t)B * Hout * Wout, Cout, N * Kz);
+    return std::max(std::max(exact.bytes(), fast.bytes()), deep.bytes());
+}
+// The stand-alone query does not know the crop (Hm x Wm of Hp x Wp) nor the output size: the maximum over the three crops that can be
+// the largest, each measured with its whole unmerged map as output.  Every buffer of the unmerge carves is a multiple of Hm * Wm, and
+// only a real crop adds the cropped copy, so the largest need is either no crop or the crop by one row or one column; a carve that
+// stops being monotone in the kept map has to widen this list (tests/test_workspace_host.py probes other crops against it).  The
+// stand-alone entry has no packed images and never takes the deep routes; they are measured all the same.
+static size_t unmerge_ws_any_crop(int nstream, int B, int Hp, int Wp, int Cin, int Cout, int mh, int mw) {
+    size_t need = 0;
+    const int crops[3][2] = {{Hp, Wp}, {Hp - 1, Wp}, {Hp, Wp - 1}};
+    for (const auto& c : crops) need = std::max(need, unmerge_ws(nstream, B, Hp, Wp, c[0], c[1], Cin, Cout, mh, mw, c[0] * mh, c[1] * mw));
+    return need;
 }
 
 // ---- model layout ---------------------------------------------------------------------------
@@ -883,19 +948,23 @@ static int block_pair4_impl(const swf_block_desc* desc, const swf_block_stream_p
     const size_t pb = packed ? block_packed_bytes(*desc) : 0;
     bool ln1_ready = ln1_io ? *ln1_io : false;   // deep levels: block i's MLP reduce also writes block i+1's LN1 planes
     // Kernels that cannot run a cross block in place (window_block_out_of_place): the two cross blocks ping-pong through two
-    // temporary maps at the END of the workspace (block 2: maps -> temporaries, block 3: temporaries -> outputs) instead of
+    // temporary maps of carve_window_block (block 2: maps -> temporaries, block 3: temporaries -> outputs) instead of
     // each going through basic_block_impl's temporary-and-copy route
     float *tx = nullptr, *ty = nullptr;
     size_t ws_left = workspace_bytes;
     {
         swf_block_desc dc = *desc;
         dc.cross = 1;
-        const size_t map_bytes = (size_t)B * H * W * desc->attn.channels * 4;
-        if (desc->precision == SWF_PREC_FAST && py && window_block_supported(dc, B, H, W) && window_block_out_of_place(dc) && workspace &&
-            workspace_bytes >= 2 * map_bytes + 512 + 2 * window_block_packed_bytes(dc)) {
-            ws_left = (workspace_bytes - 2 * map_bytes) & ~size_t(255);
-            tx = reinterpret_cast<float*>(static_cast<char*>(workspace) + ws_left);
-            ty = tx + map_bytes / 4;
+        if (desc->precision == SWF_PREC_FAST && py && window_block_supported(dc, B, H, W) && window_block_out_of_place(dc)) {
+            Carver ws(workspace, workspace_bytes);
+            const WindowBufs bufs = carve_window_block(ws, dc, (int64_t)B * H * W, packed != nullptr, true);
+            if (workspace && ws.ok()) {   // (otherwise each cross block takes basic_block_impl's temporary-and-copy route, or fails there)
+                tx = bufs.ox; ty = bufs.oy;
+                // The blocks themselves get what lies before the maps, i.e. room for their packed images and nothing else.  That is
+                // all they carve: window_block_supported ignores cross and shift, so all four blocks of the stage take the fused route,
+                // none of them in place.  A block that could fall back to the deep or generic route here would have to be measured in.
+                ws_left = reinterpret_cast<char*>(tx) - static_cast<char*>(workspace);
+            }
         }
     }
     for (int i = 0; i < 4; ++i) {
@@ -982,6 +1051,19 @@ const char* swf_status_string(int status) {
 
 // ---- fast tier of the stand-alone module entries at level-0 width (C = 24): the block kernel with the other half compiled out ----
 // (levels 0-2: C = 24 / 48 / 96, 8 heads of C / 8, 8x8 or 7x7 windows; hidden widths of the encoder / decoder blocks)
+// the packed images of both streams of a half-block kernel (0 bytes where no kernel covers the width)
+static char* carve_window_half(Carver& ws, int C, int hid) { return reinterpret_cast<char*>(ws.floats((int64_t)(2 * window_half_packed_bytes(C, hid) / 4))); }
+// ... at the start of a workspace, or nullptr when it has no room for them (the caller then takes its generic route)
+static char* window_half_images(void* workspace, size_t workspace_bytes, int C, int hid) {
+    Carver ws(workspace, workspace_bytes);
+    char* pk = carve_window_half(ws, C, hid);
+    return ws.ok() ? pk : nullptr;
+}
+static size_t window_half_ws(int C, int hid) {
+    Carver m = Carver::measure();
+    carve_window_half(m, C, hid);
+    return m.bytes();
+}
 static bool half_attn_shape(const swf_attn_desc& a, int H, int W) {
     return (a.channels == 24 || a.channels == 48 || a.channels == 96) && a.heads == 8 && a.head_dim * 8 == a.channels && a.win_h == a.win_w &&
            (a.win_h == 8 || a.win_h == 7) && H % a.win_h == 0 && W % a.win_w == 0;
@@ -993,7 +1075,8 @@ static int half_attn_hidden(int C) { return 4 * C; }   // the attention half run
 static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                       const float* y_in, float* x_out, float* y_out, int64_t N, void* workspace, size_t workspace_bytes, hipStream_t stream) {
     const size_t pb = window_half_packed_bytes(C, hid);
-    if (!pb || N <= 0 || N * C * 4 >= (int64_t(1) << 31) || !workspace || workspace_bytes < 2 * pb) return SWF_ERR_UNSUPPORTED;
+    char* pk = window_half_images(workspace, workspace_bytes, C, hid);
+    if (!pb || N <= 0 || N * C * 4 >= (int64_t(1) << 31) || !pk) return SWF_ERR_UNSUPPORTED;
     swf_block_desc bd{};
     bd.attn = swf_attn_desc{C, 8, C / 8, 8, 8, 0};
     bd.hidden = hid; bd.cross = 0; bd.precision = SWF_PREC_FAST;
@@ -1001,7 +1084,6 @@ static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px
     sx.attn = swf_attn_params{}; sy.attn = swf_attn_params{};
     sx.ln1 = sy.ln1 = swf_norm{nullptr, nullptr};
     if (raw) sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
-    char* pk = static_cast<char*>(workspace);
     SWF_TRY(pack_window_half(bd, sx, sy, pk, pb, stream));
     if (py) return launch_window_half(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, y_in, x_out, y_out, 1, 1, 1, (int)N, (int)N, stream);
     const int64_t n0 = std::min<int64_t>(N, ((N + 1) / 2 + 63) / 64 * 64);
@@ -1010,7 +1092,7 @@ static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px
 
 size_t swf_window_attention_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0) return 0;
-    return std::max(attention_generic_ws(*desc, 1, B, H, W), 2 * window_half_packed_bytes(desc->channels, half_attn_hidden(desc->channels)) + 512);
+    return std::max(attention_generic_ws(*desc, 1, B, H, W), window_half_ws(desc->channels, half_attn_hidden(desc->channels)));
 }
 
 static int window_attention_impl(const swf_attn_desc* desc, int precision, const swf_attn_params* p, const float* q, const float* k,
@@ -1023,13 +1105,13 @@ static int window_attention_impl(const swf_attn_desc* desc, int precision, const
         return fail(SWF_ERR_NULL, "window_attention: NULL weight");
     const int hid_a = half_attn_hidden(desc->channels);
     const size_t pbh = window_half_packed_bytes(desc->channels, hid_a);
+    char* pk = window_half_images(workspace, workspace_bytes, desc->channels, hid_a);
     if (precision == SWF_PREC_FAST && k == v && !residual && half_attn_shape(*desc, H, W) && (int64_t)B * H * W * desc->channels * 4 < (int64_t(1) << 31) &&
-        pbh && workspace && workspace_bytes >= 2 * pbh && out != q && out != k) {
+        pbh && pk && out != q && out != k) {
         // window24/48_kernel<.., attention half, RAW>: stream 0 = the queries and the output, stream 1 = the key / value tensor
         swf_block_desc bd{*desc, hid_a, 1, SWF_PREC_FAST};
         swf_block_stream_params sp{};
         sp.attn = *p;
-        char* pk = static_cast<char*>(workspace);
         SWF_TRY(pack_window_half(bd, sp, sp, pk, pbh, as_stream(stream)));
         return launch_window_half(bd, WIN24_HALF_ATTN, 1, pk, pbh, q, k, out, nullptr, B, H, W, 0, 0, as_stream(stream));
     }
@@ -1040,8 +1122,10 @@ static int window_attention_impl(const swf_attn_desc* desc, int precision, const
     const float* vs[2] = {v, nullptr};
     const float* rs[2] = {residual, nullptr};
     float* os[2] = {out, nullptr};
-    return attention_generic(*desc, 1, prm, qs, ks, vs, residual ? rs : nullptr, os, B, H, W, ws, as_stream(stream),
-                             precision == SWF_PREC_FAST ? 1 : 0);
+    const int fast = precision == SWF_PREC_FAST ? 1 : 0;
+    const AttnBufs bufs = carve_attention(ws, *desc, 1, (int64_t)B * H * W, fast);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "attention workspace too small (need %zu B)", ws.bytes());
+    return attention_generic(*desc, 1, prm, qs, ks, vs, residual ? rs : nullptr, os, B, H, W, bufs, as_stream(stream), fast);
 }
 
 int swf_window_attention_fwd(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k,
@@ -1058,8 +1142,8 @@ int swf_window_attention_fwd_prec(const swf_attn_desc* desc, int32_t precision, 
 
 size_t swf_basic_block_workspace_bytes(const swf_block_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0) return 0;
-    return std::max(std::max(block_generic_ws(desc, 2, B, H, W), window_block_workspace_bytes(*desc, B, H, W)),
-                    2 * std::max(window_half_packed_bytes(desc->attn.channels, half_attn_hidden(desc->attn.channels)), window_half_packed_bytes(desc->attn.channels, desc->hidden)) + 512);
+    return std::max(std::max(block_generic_ws(desc, 2, B, H, W), window_block_ws(*desc, B, H, W)),
+                    std::max(window_half_ws(desc->attn.channels, half_attn_hidden(desc->attn.channels)), window_half_ws(desc->attn.channels, desc->hidden)));
 }
 
 int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
@@ -1068,8 +1152,9 @@ int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_pa
     SWF_TRY(check_block(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, true, false));
     const int hid_a = half_attn_hidden(desc->attn.channels);
     const size_t pbh = window_half_packed_bytes(desc->attn.channels, hid_a);
+    char* pk = window_half_images(workspace, workspace_bytes, desc->attn.channels, hid_a);
     if (desc->precision == SWF_PREC_FAST && half_attn_shape(desc->attn, H, W) && (int64_t)B * H * W * desc->attn.channels * 4 < (int64_t(1) << 31) &&
-        pbh && workspace && workspace_bytes >= 2 * pbh) {
+        pbh && pk) {
         // window24/48_kernel<.., attention half>: LN1 + Q/K/V + attention + projection + residual of both streams in one launch.  A single-path
         // block runs its stream as stream 0; stream 1 mirrors it with its stores dropped.
         swf_block_desc bd = *desc;
@@ -1078,7 +1163,6 @@ int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_pa
         swf_block_stream_params sx = *px, sy = py ? *py : *px;
         sx.fc1 = sx.fc2 = swf_linear{nullptr, nullptr}; sy.fc1 = sy.fc2 = swf_linear{nullptr, nullptr};
         sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
-        char* pk = static_cast<char*>(workspace);
         SWF_TRY(pack_window_half(bd, sx, sy, pk, pbh, as_stream(stream)));
         return launch_window_half(bd, WIN24_HALF_ATTN, 0, pk, pbh, x_in, py ? y_in : x_in, x_out, py ? y_out : nullptr, B, H, W, 0, 0, as_stream(stream));
     }
@@ -1099,11 +1183,21 @@ int swf_mlp_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_par
     return mlp_halfblock_generic(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, as_stream(stream));
 }
 
+// generic MLP: the hidden activations, then the scratch of the two linear layers (they run one after the other)
+struct MlpBufs { float *hid, *rest; size_t rest_bytes; };
+static MlpBufs carve_mlp(Carver& ws, int32_t precision, int64_t tokens, int32_t channels, int32_t hidden) {
+    MlpBufs b{};
+    b.hid = ws.floats(tokens * hidden);
+    b.rest_bytes = std::max(swf_linear_workspace_bytes(precision, tokens, channels, hidden), swf_linear_workspace_bytes(precision, tokens, hidden, channels));
+    b.rest = ws.floats((int64_t)(b.rest_bytes / 4));
+    return b;
+}
+
 size_t swf_mlp_workspace_bytes(int32_t precision, int64_t tokens, int32_t channels, int32_t hidden) {
     if (tokens <= 0 || channels <= 0 || hidden <= 0) return 0;
-    size_t generic = carve_bytes({tokens * hidden}) + std::max(swf_linear_workspace_bytes(precision, tokens, channels, hidden),
-                                                               swf_linear_workspace_bytes(precision, tokens, hidden, channels));
-    return std::max(generic, 2 * window_half_packed_bytes(channels, hidden) + 512);
+    Carver m = Carver::measure();
+    carve_mlp(m, precision, tokens, channels, hidden);
+    return std::max(m.bytes(), window_half_ws(channels, hidden));
 }
 
 int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in, const float* y_in,
@@ -1119,10 +1213,10 @@ int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_
     }
     // two linear layers per stream through the hidden activations in the workspace
     Carver ws(workspace, workspace_bytes);
-    float* hid = ws.floats(tokens * hidden);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp: workspace too small (need %zu B)", (size_t)swf_mlp_workspace_bytes(precision, tokens, channels, hidden));
-    char* rest = static_cast<char*>(workspace) + align_up(ws.used, 256);
-    const size_t rest_bytes = workspace_bytes > align_up(ws.used, 256) ? workspace_bytes - align_up(ws.used, 256) : 0;
+    const MlpBufs bufs = carve_mlp(ws, precision, tokens, channels, hidden);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp: workspace too small (need %zu B)", ws.bytes());
+    float *hid = bufs.hid, *rest = bufs.rest;
+    const size_t rest_bytes = bufs.rest_bytes;
     const swf_block_stream_params* pp[2] = {px, py};
     const float* in[2] = {x_in, y_in};
     float* out[2] = {x_out, y_out};
@@ -1383,7 +1477,8 @@ int swf_merge_out_shape(int32_t H, int32_t W, int32_t merge_h, int32_t merge_w, 
 size_t swf_patch_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h,
                                  int32_t merge_w, int32_t win_h, int32_t win_w, int32_t encoder) {
     if (B <= 0 || H <= 0 || W <= 0) return 0;
-    return patch_ws(1, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w, encoder);
+    if (encoder) return merge_ws(1, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w);
+    return unmerge_ws_any_crop(1, B, H, W, Cin, Cout, merge_h, merge_w);
 }
 
 int swf_patch_merge_fwd(const swf_patch_params* p, const float* in, float* out, int32_t B, int32_t H, int32_t W, int32_t Cin,
@@ -1411,6 +1506,8 @@ int swf_patch_unmerge_fwd(const swf_patch_params* p, const float* in, const floa
                               workspace, workspace_bytes, as_stream(stream));
 }
 
+static float* carve_head_fwd(Carver& ws, int B, int H, int W) { return ws.floats((int64_t)B * H * W * 2); }   // conv1's two channels
+
 int swf_final_head_fwd(const swf_head_params* p, const float* x, const float* y, float* out, int32_t B, int32_t H, int32_t W,
                        int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     if (!p || !x || !y || !out) return fail(SWF_ERR_NULL, "final_head: NULL argument");
@@ -1418,8 +1515,9 @@ int swf_final_head_fwd(const swf_head_params* p, const float* x, const float* y,
     if (ksize <= 0 || ksize % 2 == 0) return fail(SWF_ERR_UNSUPPORTED, "final_head: even kernel size %d", ksize);
     if (ksize / 2 >= H || ksize / 2 >= W) return fail(SWF_ERR_PAD, "final_head: reflect pad %d >= map %dx%d", ksize / 2, H, W);
     Carver ws(workspace, workspace_bytes);
-    float* tmp = ws.floats((int64_t)B * H * W * 2);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "final_head workspace too small (need %zu B)", ws.used);
+    float* tmp = carve_head_fwd(ws, B, H, W);
+    // no size query: swinfuse.h documents 2*B*H*W floats, so exactly that many bytes are enough, aligned or not
+    if (!workspace || ws.used > workspace_bytes) return fail(SWF_ERR_WORKSPACE, "final_head workspace too small (need %zu B)", ws.used);
     return launch_head(x, y, tmp, out, *p, B, H, W, ksize, as_stream(stream));
 }
 
@@ -1433,9 +1531,18 @@ int swf_linear_fwd(const swf_linear* lin, const float* in, const float* residual
     return launch_gemm_f32(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, act, as_stream(stream));
 }
 
+static GemmBatch carve_linear(Carver& ws, int64_t tokens, int32_t n_in, int32_t n_out) {   // fast tier: the split-K partials
+    GemmBatch gb{};
+    gb.scratch_floats = splitk_need(n_in, tokens * n_out);
+    gb.scratch = ws.floats(gb.scratch_floats);
+    return gb;
+}
+
 size_t swf_linear_workspace_bytes(int32_t precision, int64_t tokens, int32_t n_in, int32_t n_out) {
     if (precision != SWF_PREC_FAST || tokens <= 0 || n_in <= 0 || n_out <= 0) return 0;
-    return carve_bytes({splitk_need(n_in, tokens * n_out)});
+    Carver m = Carver::measure();
+    carve_linear(m, tokens, n_in, n_out);
+    return m.bytes();
 }
 
 int swf_linear_fwd_prec(const swf_linear* lin, int32_t precision, const float* in, const float* residual, float* out, int64_t tokens,
@@ -1446,10 +1553,8 @@ int swf_linear_fwd_prec(const swf_linear* lin, int32_t precision, const float* i
     if (tokens <= 0 || tokens > INT32_MAX || n_in <= 0 || n_out <= 0) return fail(SWF_ERR_BAD_SHAPE, "linear: bad sizes");
     if (act != 0 && act != 1) return fail(SWF_ERR_UNSUPPORTED, "linear: activation %d", act);
     Carver ws(workspace, workspace_bytes);
-    GemmBatch gb{};
-    gb.scratch_floats = splitk_need(n_in, tokens * n_out);
-    gb.scratch = ws.floats(gb.scratch_floats);
-    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "linear: workspace too small (need %zu B)", ws.used);
+    GemmBatch gb = carve_linear(ws, tokens, n_in, n_out);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "linear: workspace too small (need %zu B)", ws.bytes());
     gb.p[0] = GemmProb{in, lin->weight, lin->bias, residual, out};
     return launch_gemm_bf16x3(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, act, as_stream(stream));
 }
@@ -1513,28 +1618,39 @@ int swf_model_param_info(const swf_model_desc* desc, int32_t index, char* name_b
 }
 
 // workspace layout: per level two activation maps (x, y), two full-resolution decoder outputs,
-// then one scratch region shared by every unit.
+// then one scratch region shared by every unit: the largest of their measured needs.
 static size_t model_scratch_bytes(const swf_model_desc* d, int B, const LevelShape* ls) {
     size_t scratch = 0;
     for (int s = 0; s < d->levels; ++s) {
         swf_block_desc be = level_block_desc(d, s, true), bd = level_block_desc(d, s, false);
         scratch = std::max(scratch, std::max(block_generic_ws(&be, 2, B, ls[s].Ho, ls[s].Wo), block_generic_ws(&bd, 2, B, ls[s].Ho, ls[s].Wo)));
-        scratch = std::max(scratch, std::max(window_block_workspace_bytes(be, B, ls[s].Ho, ls[s].Wo), window_block_workspace_bytes(bd, B, ls[s].Ho, ls[s].Wo)));
-        scratch = std::max(scratch, patch_ws(2, B, ls[s].Hin, ls[s].Win, d->in_dims[s], d->out_dims[s], d->merge_h, d->merge_w, d->win_h, d->win_w, 1));
-        scratch = std::max(scratch, patch_ws(2, B, ls[s].Ho, ls[s].Wo, d->out_dims[s], d->in_dims[s], d->merge_h, d->merge_w, d->win_h, d->win_w, 0));
+        scratch = std::max(scratch, std::max(window_block_ws(be, B, ls[s].Ho, ls[s].Wo), window_block_ws(bd, B, ls[s].Ho, ls[s].Wo)));
+        scratch = std::max(scratch, merge_ws(2, B, ls[s].Hin, ls[s].Win, d->in_dims[s], d->out_dims[s], d->merge_h, d->merge_w, d->win_h, d->win_w));
+        scratch = std::max(scratch, unmerge_ws(2, B, ls[s].Ho, ls[s].Wo, ls[s].Hm, ls[s].Wm, d->out_dims[s], d->in_dims[s], d->merge_h, d->merge_w,
+                                               ls[s].Hin, ls[s].Win));
     }
-    scratch = std::max(scratch, carve_bytes({(int64_t)B * ls[0].Hin * ls[0].Win * 2}));
-    return scratch;
+    Carver head = Carver::measure();
+    carve_head_fwd(head, B, ls[0].Hin, ls[0].Win);
+    return std::max(scratch, head.bytes());
+}
+struct ModelBufs { float *act[SWF_MAX_LEVELS][2], *full[2], *scratch; size_t scratch_bytes; };
+static ModelBufs carve_model(Carver& ws, const swf_model_desc* d, int B, int H, int W, const LevelShape* ls) {
+    ModelBufs b{};
+    for (int s = 0; s < d->levels; ++s)
+        for (int t = 0; t < 2; ++t) b.act[s][t] = ws.floats((int64_t)B * ls[s].Ho * ls[s].Wo * d->out_dims[s]);
+    for (int t = 0; t < 2; ++t) b.full[t] = ws.floats((int64_t)B * H * W * d->in_dims[0]);
+    b.scratch_bytes = model_scratch_bytes(d, B, ls);
+    b.scratch = ws.floats((int64_t)(b.scratch_bytes / 4));
+    return b;
 }
 
 size_t swf_model_workspace_bytes(const swf_model_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (check_model_desc(desc) != SWF_OK || B <= 0) return 0;
     LevelShape ls[SWF_MAX_LEVELS];
     if (model_shapes(desc, H, W, ls) != SWF_OK) return 0;
-    size_t total = 0;
-    for (int s = 0; s < desc->levels; ++s) total += 2 * carve_bytes({(int64_t)B * ls[s].Ho * ls[s].Wo * desc->out_dims[s]});
-    total += 2 * carve_bytes({(int64_t)B * H * W * desc->in_dims[0]});
-    return total + model_scratch_bytes(desc, B, ls) + 256;
+    Carver m = Carver::measure();
+    carve_model(m, desc, B, H, W, ls);
+    return m.bytes();
 }
 
 size_t swf_model_packed_bytes(const swf_model_desc* desc) {
@@ -1611,15 +1727,8 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
     hipStream_t stream = as_stream(stream_);
     const int n = desc->levels;
     Carver ws(workspace, workspace_bytes);
-    float* act[SWF_MAX_LEVELS][2];
-    for (int s = 0; s < n; ++s)
-        for (int t = 0; t < 2; ++t) act[s][t] = ws.floats((int64_t)B * ls[s].Ho * ls[s].Wo * desc->out_dims[s]);
-    float* full[2] = {ws.floats((int64_t)B * H * W * desc->in_dims[0]), ws.floats((int64_t)B * H * W * desc->in_dims[0])};
-    const size_t scratch_bytes = model_scratch_bytes(desc, B, ls);
-    size_t scratch_off = align_up(ws.used, 256);
-    if (!workspace || scratch_off + scratch_bytes > workspace_bytes)
-        return fail(SWF_ERR_WORKSPACE, "model workspace too small: have %zu B, need %zu B", workspace_bytes, scratch_off + scratch_bytes);
-    void* scratch = static_cast<char*>(workspace) + scratch_off;
+    const ModelBufs bufs = carve_model(ws, desc, B, H, W, ls);
+    if (!workspace || !ws.ok()) return fail(SWF_ERR_WORKSPACE, "model workspace too small: have %zu B, need %zu B", workspace_bytes, ws.bytes());
 
     auto patch_params = [&](const PatchOff& o) { return swf_patch_params{{arena + o.w, arena + o.b}, {arena + o.g, arena + o.bt}}; };
 
@@ -1644,8 +1753,8 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
         const swf_block_stream_params* first_blk[2] = {&px[0], &py[0]};
         const bool deep_stage = packed && desc->precision == SWF_PREC_FAST && window_block_packed_bytes(bd) == 0 && deep_block_supported(bd);
         ln1_carry = false;
-        SWF_TRY(patch_merge_impl(pmp, 2, cur, act[s], B, ls[s].Hin, ls[s].Win, desc->in_dims[s], desc->out_dims[s], desc->merge_h,
-                                 desc->merge_w, desc->win_h, desc->win_w, scratch, scratch_bytes, stream, desc->precision == SWF_PREC_FAST,
+        SWF_TRY(patch_merge_impl(pmp, 2, cur, bufs.act[s], B, ls[s].Hin, ls[s].Win, desc->in_dims[s], desc->out_dims[s], desc->merge_h,
+                                 desc->merge_w, desc->win_h, desc->win_w, bufs.scratch, bufs.scratch_bytes, stream, desc->precision == SWF_PREC_FAST,
                                  (packed && plan.penc_b[s]) ? prr_enc : nullptr, deep_stage ? first_blk : nullptr, deep_stage ? &ln1_carry : nullptr));
         SWF_TRY(mark());
         // the first block of the next fused-kernel stage is warmed by this stage's last block
@@ -1657,12 +1766,12 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
         }
         // the deepest stage hands the LN1 planes of the decoder's first block (same level, same map, same workspace) to it
         const bool chain = deep_stage && s == n - 1;
-        SWF_TRY(block_pair4_impl(&bd, px, py, act[s][0], act[s][1], act[s][0], act[s][1], B, ls[s].Ho, ls[s].Wo, scratch, scratch_bytes, stream,
+        SWF_TRY(block_pair4_impl(&bd, px, py, bufs.act[s][0], bufs.act[s][1], bufs.act[s][0], bufs.act[s][1], B, ls[s].Ho, ls[s].Wo, bufs.scratch, bufs.scratch_bytes, stream,
                                  (packed && plan.enc_on[s]) ? packed + plan.enc[s] : nullptr, after, after_pb,
                                  equal_flags ? equal_flags + 2 * s : nullptr, chain ? dec_first : nullptr, deep_stage ? &ln1_carry : nullptr));
         if (!chain) ln1_carry = false;
         SWF_TRY(mark());
-        cur[0] = act[s][0]; cur[1] = act[s][1];
+        cur[0] = bufs.act[s][0]; cur[1] = bufs.act[s][1];
     }
     // decoder (a013:221-227): the skip add of stage j+1 is folded into stage j's unmerge epilogue,
     // written in place over the encoder activation of the level below.
@@ -1678,7 +1787,7 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
             if (window_block_packed_bytes(nb) && plan.dec_on[j + 1]) { after = packed + plan.dec[j + 1]; after_pb = window_block_packed_bytes(nb); }
         }
         bool ln1_in = ln1_carry;   // planes left by the deepest encoder stage (j == 0) or by the unmerge layer of the stage before
-        SWF_TRY(block_pair4_impl(&bd, px, py, act[lvl][0], act[lvl][1], act[lvl][0], act[lvl][1], B, ls[lvl].Ho, ls[lvl].Wo, scratch, scratch_bytes, stream,
+        SWF_TRY(block_pair4_impl(&bd, px, py, bufs.act[lvl][0], bufs.act[lvl][1], bufs.act[lvl][0], bufs.act[lvl][1], B, ls[lvl].Ho, ls[lvl].Wo, bufs.scratch, bufs.scratch_bytes, stream,
                                  (packed && plan.dec_on[j]) ? packed + plan.dec[j] : nullptr, after, after_pb,
                                  equal_flags ? equal_flags + 2 * (n + j) : nullptr, nullptr, &ln1_in));
         SWF_TRY(mark());
@@ -1698,13 +1807,13 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
         ln1_carry = false;
         swf_patch_params pm[2] = {patch_params(L->dec_patch[j][0]), patch_params(L->dec_patch[j][1])};
         const swf_patch_params* pmp[2] = {&pm[0], &pm[1]};
-        const float* ins[2] = {act[lvl][0], act[lvl][1]};
-        const float* skip[2] = {lvl > 0 ? act[lvl - 1][0] : nullptr, lvl > 0 ? act[lvl - 1][1] : nullptr};
-        float* outs[2] = {lvl > 0 ? act[lvl - 1][0] : full[0], lvl > 0 ? act[lvl - 1][1] : full[1]};
+        const float* ins[2] = {bufs.act[lvl][0], bufs.act[lvl][1]};
+        const float* skip[2] = {lvl > 0 ? bufs.act[lvl - 1][0] : nullptr, lvl > 0 ? bufs.act[lvl - 1][1] : nullptr};
+        float* outs[2] = {lvl > 0 ? bufs.act[lvl - 1][0] : bufs.full[0], lvl > 0 ? bufs.act[lvl - 1][1] : bufs.full[1]};
         const void* prr_dec[2] = {packed ? packed + plan.pdec[j] : nullptr, packed ? packed + plan.pdec[j] + plan.pdec_b[j] : nullptr};
         SWF_TRY(patch_unmerge_impl(pmp, 2, ins, lvl > 0 ? skip : nullptr, outs, B, ls[lvl].Ho, ls[lvl].Wo, ls[lvl].Hm, ls[lvl].Wm,
                                    desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w, ls[lvl].Hin, ls[lvl].Win,
-                                   scratch, scratch_bytes, stream, desc->precision == SWF_PREC_FAST, (packed && plan.pdec_b[j]) ? prr_dec : nullptr,
+                                   bufs.scratch, bufs.scratch_bytes, stream, desc->precision == SWF_PREC_FAST, (packed && plan.pdec_b[j]) ? prr_dec : nullptr,
                                    warm_next ? after : nullptr, warm_next ? after_pb : 0, &warmed, next_deep ? next_first : nullptr,
                                    next_deep ? &ln1_carry : nullptr));
         if (warm_next && !warmed) SWF_TRY(launch_l2_warm(after, 2 * after_pb, stream));
@@ -1712,8 +1821,9 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
     }
     swf_head_params hp{arena + L->h_c1w, arena + L->h_c1b, arena + L->h_g, arena + L->h_b, arena + L->h_m, arena + L->h_v,
                        arena + L->h_c2w, arena + L->h_c2b};
-    float* tmp = static_cast<float*>(scratch);
-    SWF_TRY(launch_head(full[0], full[1], tmp, out, hp, B, H, W, desc->head_ksize, stream));
+    Carver hw(bufs.scratch, bufs.scratch_bytes);
+    float* tmp = carve_head_fwd(hw, B, H, W);
+    SWF_TRY(launch_head(bufs.full[0], bufs.full[1], tmp, out, hp, B, H, W, desc->head_ksize, stream));
     return mark();
 }
 

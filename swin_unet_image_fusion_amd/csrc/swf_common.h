@@ -61,23 +61,23 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
-// Bump allocator over the caller's workspace; every carve is 256-byte aligned.
+// Bump allocator over the caller's workspace; every carve is 256-byte aligned.  A unit carves its buffers in ONE function that takes a
+// Carver&; its implementation runs that function on the real workspace, its size query runs the same function on Carver::measure()
+// and returns bytes(), so one byte less than the query is refused.  While measuring, floats() returns nullptr and no pointer is formed.
 struct Carver {
     char* base;
     size_t cap, used;
-    Carver(void* p, size_t bytes) : base(static_cast<char*>(p)), cap(bytes), used(0) {}
+    bool measuring;
+    Carver(void* p, size_t bytes, bool measure_only = false) : base(static_cast<char*>(p)), cap(bytes), used(0), measuring(measure_only) {}
+    static Carver measure() { return Carver(nullptr, 0, true); }
     float* floats(int64_t n) {
-        size_t off = align_up(used, 256);
+        const size_t off = align_up(used, 256);
         used = off + static_cast<size_t>(n) * sizeof(float);
-        return reinterpret_cast<float*>(base + off);
+        return (measuring || !base) ? nullptr : reinterpret_cast<float*>(base + off);
     }
-    bool ok() const { return base != nullptr ? used <= cap : used == 0; }
+    size_t bytes() const { return align_up(used, 256); }   // what a size query returns, and what ok() asks of a real workspace
+    bool ok() const { return base != nullptr ? bytes() <= cap : used == 0; }   // no workspace is fine when nothing was carved
 };
-inline size_t carve_bytes(std::initializer_list<int64_t> floats) {
-    size_t used = 0;
-    for (int64_t n : floats) used = align_up(used, 256) + static_cast<size_t>(n) * sizeof(float);
-    return align_up(used, 256);
-}
 
 }  // namespace swf
 
