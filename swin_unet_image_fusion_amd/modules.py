@@ -11,6 +11,10 @@ no CPU fallback: without the built library, or on a CPU tensor, forward raises.
 The eval() forward is the hot path (fused kernels, one C call for MyModel).  Under torch.autograd every module is differentiable
 through exact-fp32 backward entries, and in train() the reference's three dropout ratios apply: a module with a ratio
 > 0 runs the exact-fp32 *_drop entries of the library, with or without grad.
+
+Each entry family of the library is marshalled in one place: WindowAttention, AutoPathMLP and BasicBlock each have one `_fwd` and one
+`_bwd`, which pick the plain or the *_drop entry (with its workspace query and its mask arguments) from `drop is None`.  The no-grad
+forward, the dropout forward and the torch.autograd.Function of a module all go through those two.
 """
 from __future__ import annotations
 
@@ -87,10 +91,22 @@ def _workspace_tensor(device, stream_handle: int) -> Optional[Tensor]:
     return _WS.get((torch.device(device).index, stream_handle))
 
 
-def _check_forward_only(module: nn.Module, *tensors: Optional[Tensor]) -> None:
-    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in tensors):
-        raise RuntimeError("libswinfuse provides the forward pass only; call it under torch.no_grad() "
-                           "with inputs that do not require grad")
+def _raw(t: Optional[Tensor]) -> Optional[int]:
+    """Raw pointer of a buffer this module allocated itself (fp32, contiguous, on the GPU by construction), or None."""
+    return None if t is None else t.data_ptr()
+
+
+def _ref(struct):
+    """C.byref of a ctypes structure, or None (NULL) for an absent second stream."""
+    return None if struct is None else C.byref(struct)
+
+
+def _new_like(p: Optional[Tensor]) -> Optional[Tensor]:
+    """An empty fp32 tensor shaped like the parameter `p` (the buffer its gradient is written to), or None where a layer has no bias."""
+    return None if p is None else torch.empty(p.shape, dtype=torch.float32, device=p.device)
+
+
+def _check_4d(*tensors: Optional[Tensor]) -> None:
     for t in tensors:
         if t is not None and (t.dim() != 4):
             raise ValueError(f"expected a 4-D (batch, channels, height, width) tensor, got shape {tuple(t.shape)}")
@@ -147,6 +163,26 @@ def _to_nchw(t: Tensor) -> Tensor:
     out = torch.empty((b, c, h, w), dtype=torch.float32, device=t.device)
     L.check(L.lib().swf_nhwc_to_nchw(_ptr(t), _ptr(out), b, c, h, w, _stream(t.device)))
     return out
+
+
+def _nhwc_in_out(x: Tensor, y: Optional[Tensor], dual: bool):
+    """(xn, yn, ox, oy) of a one- or two-stream call: NHWC copies of the inputs and empty outputs of their shapes.  yn and oy are None
+    without a second stream, and _ptr(None) is the NULL the library expects for them."""
+    xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
+    return xn, yn, torch.empty_like(xn), (torch.empty_like(yn) if dual else None)
+
+
+def _nchw_out(ox: Tensor, oy: Optional[Tensor]):
+    """What a one- or two-stream forward returns: one NCHW tensor, or the pair."""
+    return _to_nchw(ox) if oy is None else (_to_nchw(ox), _to_nchw(oy))
+
+
+def _qkv_nhwc(q: Tensor, k: Tensor, v: Tensor) -> Tuple[Tensor, Tensor, Tensor]:
+    """NHWC copies of q, k, v.  They may be one tensor (self attention passes x three times): each distinct tensor is converted once."""
+    qn = _to_nhwc(q)
+    kn = qn if k is q else _to_nhwc(k)
+    vn = kn if v is k else (qn if v is q else _to_nhwc(v))
+    return qn, kn, vn
 
 
 def _lin(mod: nn.Module) -> L.Linear:
@@ -236,32 +272,55 @@ class WindowAttention(_FwdAlias, nn.Module):
             names = ("q_for_heads", "k_for_heads", "v_for_heads", "linear_projection")
             prm = [t for n in names for t in (getattr(self, n).weight, getattr(self, n).bias)]
             return _WindowAttentionFunction.apply(self, drop, q, k, v, self.relative_position_bias_table, *prm)
-        return self._forward_nograd(q, k, v, drop)
+        return self._fwd(q, k, v, drop)
 
-    def _forward_nograd(self, q: Tensor, k: Tensor, v: Tensor, drop: Optional[L.Dropout] = None) -> Tensor:
-        _check_forward_only(self, q, k, v)
+    def _fwd(self, q: Tensor, k: Tensor, v: Tensor, drop: Optional[L.Dropout]) -> Tensor:
+        """The one forward call of this module, with and without grad: swf_window_attention_fwd_prec in the module's tier, or with
+        dropout swf_window_attention_fwd_drop (mask stream 0)."""
+        _check_4d(q, k, v)
         if q.shape != k.shape or q.shape != v.shape:
             raise ValueError(f"q, k, v must share one shape, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
         b, c, h, w = q.shape
         if c != self.in_out_dims:
             raise RuntimeError(f"expected {self.in_out_dims} channels, got {c}")
         self.feature_shape_hw = (h, w)
-        qn = _to_nhwc(q)
-        kn = qn if k is q else _to_nhwc(k)
-        vn = kn if v is k else (qn if v is q else _to_nhwc(v))
+        qn, kn, vn = _qkv_nhwc(q, k, v)
         out = torch.empty((b, h, w, c), dtype=torch.float32, device=q.device)
-        desc = self._desc()
-        lib = L.lib()
-        prm = self._params()
-        if drop is not None:
-            ws, wsn = _workspace(lib.swf_window_attention_drop_workspace_bytes(C.byref(desc), b, h, w), q.device)
-            L.check(lib.swf_window_attention_fwd_drop(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), None, _ptr(out), b, h, w,
-                                                      C.byref(drop), 0, ws, wsn, _stream(q.device)))
-            return _to_nchw(out)
-        ws, wsn = _workspace(lib.swf_window_attention_workspace_bytes(C.byref(desc), b, h, w), q.device)
-        L.check(lib.swf_window_attention_fwd_prec(C.byref(desc), _precision_code(self.precision), C.byref(prm), _ptr(qn), _ptr(kn),
-                                                  _ptr(vn), None, _ptr(out), b, h, w, ws, wsn, _stream(q.device)))
+        lib, desc, prm = L.lib(), self._desc(), self._params()
+        # the two entries differ in their one extra argument: the tier behind the descriptor, or the masks behind the sizes
+        if drop is None:
+            size, entry = lib.swf_window_attention_workspace_bytes, lib.swf_window_attention_fwd_prec
+            tier, masks = (_precision_code(self.precision),), ()
+        else:
+            size, entry = lib.swf_window_attention_drop_workspace_bytes, lib.swf_window_attention_fwd_drop
+            tier, masks = (), (C.byref(drop), 0)
+        ws, wsn = _workspace(size(C.byref(desc), b, h, w), q.device)
+        L.check(entry(C.byref(desc), *tier, C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), None, _ptr(out), b, h, w, *masks,
+                      ws, wsn, _stream(q.device)))
         return _to_nchw(out)
+
+    def _bwd(self, q: Tensor, k: Tensor, v: Tensor, g: Tensor, drop: Optional[L.Dropout]):
+        """dL/d(q, k, v) and the parameter gradients (bias table, then weight and bias of q, k, v, projection) through
+        swf_window_attention_bwd, with dropout swf_window_attention_bwd_drop and the forward's masks."""
+        b, c, h, w = q.shape
+        dev = q.device
+        qn, kn, vn = _qkv_nhwc(q, k, v)
+        gn = _to_nhwc(g.contiguous())
+        gq, gk, gv = torch.empty_like(qn), torch.empty_like(qn), torch.empty_like(qn)
+        mods = (self.q_for_heads, self.k_for_heads, self.v_for_heads, self.linear_projection)
+        gw = [_new_like(md.weight) for md in mods]
+        gb = [_new_like(md.bias) for md in mods]
+        gt = _new_like(self.relative_position_bias_table)
+        grads = L.AttnParams(*[L.Linear(_raw(wt), _raw(bs)) for wt, bs in zip(gw, gb)], _raw(gt))
+        lib, desc, prm = L.lib(), self._desc(), self._params()
+        if drop is None:
+            size, entry, masks = lib.swf_window_attention_bwd_workspace_bytes, lib.swf_window_attention_bwd, ()
+        else:
+            size, entry, masks = lib.swf_window_attention_drop_workspace_bytes, lib.swf_window_attention_bwd_drop, (C.byref(drop), 0)
+        ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
+        L.check(entry(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk), _ptr(gv), C.byref(grads),
+                      b, h, w, *masks, ws, wsn, _stream(dev)))
+        return (_to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *[t for pair in zip(gw, gb) for t in pair])
 
 
 class _WindowAttentionFunction(torch.autograd.Function):
@@ -274,38 +333,12 @@ class _WindowAttentionFunction(torch.autograd.Function):
         ctx.module, ctx.drop = module, drop
         ctx.save_for_backward(q, k, v)
         with torch.no_grad():
-            return module._forward_nograd(q.detach(), k.detach(), v.detach(), drop)
+            return module._fwd(q.detach(), k.detach(), v.detach(), drop)
 
     @staticmethod
     def backward(ctx, g):
-        m = ctx.module
-        q, k, v = ctx.saved_tensors
-        b, c, h, w = q.shape
-        dev = q.device
         with torch.no_grad():
-            qn = _to_nhwc(q)
-            kn = qn if k is q else _to_nhwc(k)
-            vn = kn if v is k else (qn if v is q else _to_nhwc(v))
-            gn = _to_nhwc(g.contiguous())
-            gq, gk, gv = torch.empty_like(qn), torch.empty_like(qn), torch.empty_like(qn)
-            new = lambda t: None if t is None else torch.empty(t.shape, dtype=torch.float32, device=dev)
-            lin = lambda wt, bs: L.Linear(wt.data_ptr(), None if bs is None else bs.data_ptr())
-            mods = (m.q_for_heads, m.k_for_heads, m.v_for_heads, m.linear_projection)
-            gw = [new(md.weight) for md in mods]
-            gb = [new(md.bias) for md in mods]
-            gt = new(m.relative_position_bias_table)
-            grads = L.AttnParams(lin(gw[0], gb[0]), lin(gw[1], gb[1]), lin(gw[2], gb[2]), lin(gw[3], gb[3]), gt.data_ptr())
-            lib, desc, prm = L.lib(), m._desc(), m._params()
-            if ctx.drop is not None:
-                ws, wsn = _workspace(lib.swf_window_attention_drop_workspace_bytes(C.byref(desc), b, h, w), dev)
-                L.check(lib.swf_window_attention_bwd_drop(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
-                                                          _ptr(gv), C.byref(grads), b, h, w, C.byref(ctx.drop), 0, ws, wsn, _stream(dev)))
-            else:
-                ws, wsn = _workspace(lib.swf_window_attention_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
-                L.check(lib.swf_window_attention_bwd(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
-                                                     _ptr(gv), C.byref(grads), b, h, w, ws, wsn, _stream(dev)))
-            flat = [t for pair in zip(gw, gb) for t in pair]
-            return (None, None, _to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *flat)
+            return (None, None, *ctx.module._bwd(*ctx.saved_tensors, g, ctx.drop))
 
 
 class _MlpFunction(torch.autograd.Function):
@@ -317,33 +350,12 @@ class _MlpFunction(torch.autograd.Function):
         ctx.module, ctx.s, ctx.drop = module, s, drop
         ctx.save_for_backward(x)
         with torch.no_grad():
-            return module._one_nograd(x.detach(), s) if drop is None else module._one_drop(x.detach(), s, drop)
+            return module._fwd(drop, x.detach(), None, False, s)
 
     @staticmethod
     def backward(ctx, g):
-        m, s = ctx.module, ctx.s
-        (x,) = ctx.saved_tensors
-        b, c, h, w = x.shape
-        dev = x.device
-        c1, c2 = getattr(m, f"mlp_{s}_1"), getattr(m, f"mlp_{s}_2")
         with torch.no_grad():
-            xn, gn = _to_nhwc(x), _to_nhwc(g.contiguous())
-            gx = torch.empty_like(xn)
-            new = lambda t: None if t is None else torch.empty(t.shape, dtype=torch.float32, device=dev)
-            g1w, g1b, g2w, g2b = new(c1.weight), new(c1.bias), new(c2.weight), new(c2.bias)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            f1, f2 = _lin(c1), _lin(c2)
-            gf1, gf2 = L.Linear(ptr(g1w), ptr(g1b)), L.Linear(ptr(g2w), ptr(g2b))
-            lib, n = L.lib(), b * h * w
-            if ctx.drop is not None:
-                ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, m.hidden_dims), dev)
-                L.check(lib.swf_mlp_bwd_drop(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c,
-                                             m.hidden_dims, C.byref(ctx.drop), _MASK_STREAM[s], ws, wsn, _stream(dev)))
-            else:
-                ws, wsn = _workspace(lib.swf_mlp_bwd_workspace_bytes(n, c, m.hidden_dims), dev)
-                L.check(lib.swf_mlp_bwd(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, m.hidden_dims,
-                                        ws, wsn, _stream(dev)))
-            return None, None, None, _to_nchw(gx), g1w, g1b, g2w, g2b
+            return (None, None, None, *ctx.module._bwd(ctx.s, ctx.drop, ctx.saved_tensors[0], g))
 
 
 class _LayerNormFunction(torch.autograd.Function):
@@ -428,32 +440,58 @@ class AutoPathMLP(_FwdAlias, nn.Module):
             setattr(self, f"dropout_{s}_2", d2)
             setattr(self, f"sequence_{s}", nn.Sequential(c1, activation_func, d1, c2, d2))
 
+    def _fcs(self, s: str) -> Tuple[L.Linear, L.Linear]:
+        return _lin(getattr(self, f"mlp_{s}_1")), _lin(getattr(self, f"mlp_{s}_2"))
+
     def _params(self, s: str) -> L.BlockStreamParams:
         p = L.BlockStreamParams()
-        p.fc1, p.fc2 = _lin(getattr(self, f"mlp_{s}_1")), _lin(getattr(self, f"mlp_{s}_2"))
+        p.fc1, p.fc2 = self._fcs(s)
         return p
 
-    def _one_nograd(self, x: Tensor, s: str) -> Tensor:
+    def _fwd(self, drop: Optional[L.Dropout], x: Tensor, y: Optional[Tensor], dual: bool, s: str = "x"):
+        """The MLP on one stream (`x` through the parameters of stream `s`) or on both (`dual`: x and y).  Without dropout that is ONE
+        swf_mlp_fwd call whichever it is; with dropout one swf_mlp_fwd_drop call per stream (exact fp32; mask stream 0 for x, 1 for y,
+        one seed for both)."""
         b, c, h, w = x.shape
-        xn = _to_nhwc(x)
-        ox = torch.empty_like(xn)
-        lib, prec, n = L.lib(), _precision_code(self.precision), b * h * w
-        px = self._params(s)
-        ws, wsn = _workspace(lib.swf_mlp_workspace_bytes(prec, n, c, self.hidden_dims), x.device)
-        L.check(lib.swf_mlp_fwd(prec, C.byref(px), None, _ptr(xn), None, _ptr(ox), None, n, c, self.hidden_dims, ws, wsn, _stream(x.device)))
-        return _to_nchw(ox)
+        lib, n, hid, dev = L.lib(), b * h * w, self.hidden_dims, x.device
+        if drop is None:
+            xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
+            prec = _precision_code(self.precision)
+            px, py = self._params(s), (self._params("y") if dual else None)
+            ws, wsn = _workspace(lib.swf_mlp_workspace_bytes(prec, n, c, hid), dev)
+            L.check(lib.swf_mlp_fwd(prec, _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), n, c, hid, ws, wsn, _stream(dev)))
+            return _nchw_out(ox, oy)
+        outs = []
+        for name, t in (("x", x), ("y", y)) if dual else ((s, x),):
+            tn = _to_nhwc(t)
+            out = torch.empty_like(tn)
+            f1, f2 = self._fcs(name)
+            ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, hid), dev)
+            L.check(lib.swf_mlp_fwd_drop(C.byref(f1), C.byref(f2), _ptr(tn), _ptr(out), n, c, hid, C.byref(drop), _MASK_STREAM[name],
+                                         ws, wsn, _stream(dev)))
+            outs.append(_to_nchw(out))
+        return tuple(outs) if dual else outs[0]
 
-    def _one_drop(self, x: Tensor, s: str, drop: L.Dropout) -> Tensor:
-        """One stream with dropout (swf_mlp_fwd_drop, exact fp32): mask stream 0 for x, 1 for y, one seed for both."""
+    def _bwd(self, s: str, drop: Optional[L.Dropout], x: Tensor, g: Tensor):
+        """dL/dx of stream `s` and the gradients of its fc1 / fc2 weight and bias through swf_mlp_bwd, with dropout swf_mlp_bwd_drop and
+        the forward's masks."""
         b, c, h, w = x.shape
-        xn = _to_nhwc(x)
-        ox = torch.empty_like(xn)
-        lib, n = L.lib(), b * h * w
-        f1, f2 = _lin(getattr(self, f"mlp_{s}_1")), _lin(getattr(self, f"mlp_{s}_2"))
-        ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, self.hidden_dims), x.device)
-        L.check(lib.swf_mlp_fwd_drop(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(ox), n, c, self.hidden_dims, C.byref(drop), _MASK_STREAM[s],
-                                     ws, wsn, _stream(x.device)))
-        return _to_nchw(ox)
+        dev = x.device
+        c1, c2 = getattr(self, f"mlp_{s}_1"), getattr(self, f"mlp_{s}_2")
+        xn, gn = _to_nhwc(x), _to_nhwc(g.contiguous())
+        gx = torch.empty_like(xn)
+        g1w, g1b, g2w, g2b = _new_like(c1.weight), _new_like(c1.bias), _new_like(c2.weight), _new_like(c2.bias)
+        f1, f2 = self._fcs(s)
+        gf1, gf2 = L.Linear(_raw(g1w), _raw(g1b)), L.Linear(_raw(g2w), _raw(g2b))
+        lib, n, hid = L.lib(), b * h * w, self.hidden_dims
+        if drop is None:
+            size, entry, masks = lib.swf_mlp_bwd_workspace_bytes, lib.swf_mlp_bwd, ()
+        else:
+            size, entry, masks = lib.swf_mlp_drop_workspace_bytes, lib.swf_mlp_bwd_drop, (C.byref(drop), _MASK_STREAM[s])
+        ws, wsn = _workspace(size(n, c, hid), dev)
+        L.check(entry(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, hid, *masks,
+                      ws, wsn, _stream(dev)))
+        return _to_nchw(gx), g1w, g1b, g2w, g2b
 
     def _one_grad(self, x: Tensor, s: str, drop: Optional[L.Dropout]) -> Tensor:
         c1, c2 = getattr(self, f"mlp_{s}_1"), getattr(self, f"mlp_{s}_2")
@@ -467,27 +505,11 @@ class AutoPathMLP(_FwdAlias, nn.Module):
         dual = self.use_dual_path or y is not None
         if _wants_grad(self, x, y):
             _require_elu(self.activation_func)
-            if dual:
-                return self._one_grad(x, "x", drop), self._one_grad(y, "y", drop)
-            return self._one_grad(x, "x", drop)
-        _check_forward_only(self, x, y)
+            ox = self._one_grad(x, "x", drop)
+            return (ox, self._one_grad(y, "y", drop)) if dual else ox
+        _check_4d(x, y)
         _require_elu(self.activation_func)
-        if drop is not None:
-            if dual:
-                return self._one_drop(x, "x", drop), self._one_drop(y, "y", drop)
-            return self._one_drop(x, "x", drop)
-        b, c, h, w = x.shape
-        xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        ox = torch.empty_like(xn)
-        oy = torch.empty_like(yn) if dual else None
-        lib, prec, n = L.lib(), _precision_code(self.precision), b * h * w
-        px, py = self._params("x"), (self._params("y") if dual else None)
-        ws, wsn = _workspace(lib.swf_mlp_workspace_bytes(prec, n, c, self.hidden_dims), x.device)
-        L.check(lib.swf_mlp_fwd(prec, C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None, _ptr(ox),
-                                _ptr(oy) if dual else None, n, c, self.hidden_dims, ws, wsn, _stream(x.device)))
-        if dual:
-            return _to_nchw(ox), _to_nchw(oy)
-        return _to_nchw(ox)
+        return self._fwd(drop, x, y, dual)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -506,57 +528,51 @@ class AddAndLayerNormWithOtherModule(_FwdAlias, nn.Module):
         if use_dual_path:
             self.norm_layer_2 = nn.LayerNorm(normalized_shape=normalized_shape)
 
+    def _wraps_mlp(self) -> bool:
+        """Which half of a block this is: True around an AutoPathMLP (ln2 + fc1 + fc2), False around an AutoPathWinAtt (ln1 + attn)."""
+        if not isinstance(self.other_module, (AutoPathWinAtt, AutoPathMLP)):
+            raise NotImplementedError("other_module must be AutoPathWinAtt or AutoPathMLP of this package")
+        return isinstance(self.other_module, AutoPathMLP)
+
+    def _fill(self, p: L.BlockStreamParams, s: str) -> L.BlockStreamParams:
+        """Write this half's fields of stream `s` into `p` (BasicBlock._stream_params fills one struct from both of its halves)."""
+        om, ln = self.other_module, _norm(self.norm_layer_1 if s == "x" else self.norm_layer_2)
+        if self._wraps_mlp():
+            p.ln2 = ln
+            p.fc1, p.fc2 = om._fcs(s)
+        else:
+            p.ln1, p.attn = ln, getattr(om, f"window_attention_{s}")._params()
+        return p
+
     def forward(self, x, y=None):
-        om = self.other_module
+        om, mlp = self.other_module, self._wraps_mlp()
         dual = self.use_dual_path or y is not None
-        if _wants_grad(self, x, y) or (isinstance(om, (AutoPathWinAtt, AutoPathMLP)) and _drops_in_training(om)):
+        if _wants_grad(self, x, y) or _drops_in_training(om):
             # under torch.autograd the wrapper is composed of differentiable calls: LayerNorm, the other module, the residual add (and so
             # is a train()-mode call whose other module drops: the fused half-block units have no masks)
-            if not isinstance(om, (AutoPathWinAtt, AutoPathMLP)):
-                raise NotImplementedError("other_module must be AutoPathWinAtt or AutoPathMLP of this package")
             nx = _LayerNormFunction.apply(self.norm_layer_1, x, self.norm_layer_1.weight, self.norm_layer_1.bias)
             if not dual:
-                return _AddFunction.apply(x, om(nx, None) if isinstance(om, AutoPathMLP) else om(nx, nx))
+                return _AddFunction.apply(x, om(nx, None) if mlp else om(nx, nx))
             ny = _LayerNormFunction.apply(self.norm_layer_2, y, self.norm_layer_2.weight, self.norm_layer_2.bias)
             ox, oy = om(nx, ny)
             return _AddFunction.apply(x, ox), _AddFunction.apply(y, oy)
-        _check_forward_only(self, x, y)
+        _check_4d(x, y)
         b, c, h, w = x.shape
-        xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        ox = torch.empty_like(xn)
-        oy = torch.empty_like(yn) if dual else None
-        lib = L.lib()
-        streams = ("x", "y") if dual else ("x",)
-        prec = _precision_code(self.precision)
-        norms = {"x": self.norm_layer_1, "y": getattr(self, "norm_layer_2", None)}
-        prm = {}
-        if isinstance(om, AutoPathWinAtt):
-            wa0 = om.window_attention_x
-            desc = L.BlockDesc(wa0._desc(), 1, int(bool(om.use_cross_att)), prec)
-            for s in streams:
-                p = L.BlockStreamParams()
-                p.ln1 = _norm(norms[s])
-                p.attn = getattr(om, f"window_attention_{s}")._params()
-                prm[s] = p
-            fn = lib.swf_attn_halfblock_fwd
-        elif isinstance(om, AutoPathMLP):
+        xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
+        lib, prec = L.lib(), _precision_code(self.precision)
+        if mlp:
             _require_elu(om.activation_func)
             desc = L.BlockDesc(L.AttnDesc(om.in_out_dims, 1, 1, 1, 1, 0), om.hidden_dims, 0, prec)
-            for s in streams:
-                p = L.BlockStreamParams()
-                p.ln2 = _norm(norms[s])
-                p.fc1, p.fc2 = _lin(getattr(om, f"mlp_{s}_1")), _lin(getattr(om, f"mlp_{s}_2"))
-                prm[s] = p
-            fn = lib.swf_mlp_halfblock_fwd
+            entry = lib.swf_mlp_halfblock_fwd
         else:
-            raise NotImplementedError("other_module must be AutoPathWinAtt or AutoPathMLP of this package")
+            desc = L.BlockDesc(om.window_attention_x._desc(), 1, int(bool(om.use_cross_att)), prec)
+            entry = lib.swf_attn_halfblock_fwd
+        px = self._fill(L.BlockStreamParams(), "x")
+        py = self._fill(L.BlockStreamParams(), "y") if dual else None
         ws, wsn = _workspace(lib.swf_basic_block_workspace_bytes(
             C.byref(L.BlockDesc(desc.attn, max(desc.hidden, 1), 0, prec)), b, h, w), x.device)
-        L.check(fn(C.byref(desc), C.byref(prm["x"]), C.byref(prm["y"]) if dual else None, _ptr(xn),
-                   _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None, b, h, w, ws, wsn, _stream(x.device)))
-        if dual:
-            return _to_nchw(ox), _to_nchw(oy)
-        return _to_nchw(ox)
+        L.check(entry(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), b, h, w, ws, wsn, _stream(x.device)))
+        return _nchw_out(ox, oy)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -572,8 +588,8 @@ class _BasicBlockFunction(torch.autograd.Function):
         ctx.save_for_backward(x, y) if dual else ctx.save_for_backward(x)
         ctx.nparams = len(params)
         with torch.no_grad():
-            ox, oy = block._forward_nograd(x.detach(), y.detach() if dual else None, dual, drop)
-        return (ox, oy) if dual else (ox,)
+            out = block._fwd(x.detach(), y.detach() if dual else None, dual, drop)
+        return out if dual else (out,)
 
     @staticmethod
     def backward(ctx, *gouts):
@@ -581,7 +597,7 @@ class _BasicBlockFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, y = saved[0], (saved[1] if dual else None)
         with torch.no_grad():
-            gx, gy, bufs = block._backward(x, y, gouts[0], gouts[1] if dual else None, dual, ctx.drop)
+            gx, gy, bufs = block._bwd(x, y, gouts[0], gouts[1] if dual else None, dual, ctx.drop)
         streams = ("x", "y") if dual else ("x",)
         pg = [g for s in streams for g in bufs[s]]
         return (None, None, None, gx, gy, *pg)
@@ -630,20 +646,12 @@ class BasicBlock(_FwdAlias, nn.Module):
 
     def _stream_params(self, s: str) -> L.BlockStreamParams:
         _require_elu(self.mlp_activation_func)
-        p = L.BlockStreamParams()
-        idx = "1" if s == "x" else "2"
-        p.ln1 = _norm(getattr(self.stage_1, f"norm_layer_{idx}"))
-        p.attn = getattr(self.auto_path_win_att, f"window_attention_{s}")._params()
-        p.ln2 = _norm(getattr(self.stage_2, f"norm_layer_{idx}"))
-        p.fc1, p.fc2 = _lin(getattr(self.auto_path_mlp, f"mlp_{s}_1")), _lin(getattr(self.auto_path_mlp, f"mlp_{s}_2"))
-        return p
+        return self.stage_2._fill(self.stage_1._fill(L.BlockStreamParams(), s), s)
 
     # ---- training side (first stage): the block under torch.autograd --------------------------------------------
-    _GRAD_FIELDS = ("ln1.weight", "ln1.bias", "q.weight", "q.bias", "k.weight", "k.bias", "v.weight", "v.bias", "proj.weight",
-                    "proj.bias", "table", "ln2.weight", "ln2.bias", "fc1.weight", "fc1.bias", "fc2.weight", "fc2.bias")
-
     def _grad_tensors(self, s: str) -> List[Optional[Tensor]]:
-        """The stream's parameter tensors in the order of _GRAD_FIELDS (None where a layer has no bias)."""
+        """The stream's parameter tensors in the field order of swf_block_stream_params: ln1, q, k, v, proj (weight then bias each), the
+        bias table, ln2, fc1, fc2 (None where a layer has no bias)."""
         idx = "1" if s == "x" else "2"
         wa = getattr(self.auto_path_win_att, f"window_attention_{s}")
         ln1, ln2 = getattr(self.stage_1, f"norm_layer_{idx}"), getattr(self.stage_2, f"norm_layer_{idx}")
@@ -656,64 +664,54 @@ class BasicBlock(_FwdAlias, nn.Module):
     def _grads_struct(bufs: List[Optional[Tensor]]) -> L.BlockStreamParams:
         """swf_block_stream_grads over freshly allocated gradient buffers (same field order as swf_block_stream_params)."""
         g = L.BlockStreamParams()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        g.ln1 = L.Norm(ptr(bufs[0]), ptr(bufs[1]))
-        g.attn = L.AttnParams(L.Linear(ptr(bufs[2]), ptr(bufs[3])), L.Linear(ptr(bufs[4]), ptr(bufs[5])), L.Linear(ptr(bufs[6]), ptr(bufs[7])),
-                              L.Linear(ptr(bufs[8]), ptr(bufs[9])), ptr(bufs[10]))
-        g.ln2 = L.Norm(ptr(bufs[11]), ptr(bufs[12]))
-        g.fc1, g.fc2 = L.Linear(ptr(bufs[13]), ptr(bufs[14])), L.Linear(ptr(bufs[15]), ptr(bufs[16]))
+        p = [_raw(t) for t in bufs]
+        g.ln1 = L.Norm(p[0], p[1])
+        g.attn = L.AttnParams(L.Linear(p[2], p[3]), L.Linear(p[4], p[5]), L.Linear(p[6], p[7]), L.Linear(p[8], p[9]), p[10])
+        g.ln2 = L.Norm(p[11], p[12])
+        g.fc1, g.fc2 = L.Linear(p[13], p[14]), L.Linear(p[15], p[16])
         return g
 
-    def _forward_nograd(self, x, y, dual, drop: Optional[L.Dropout] = None):
+    def _fwd(self, x, y, dual, drop: Optional[L.Dropout]):
+        """The one forward call of a block, with and without grad: swf_basic_block_fwd in the block's tier, or with dropout
+        swf_basic_block_fwd_drop in the exact tier whatever self.precision says (the fused fast kernels have no masks)."""
         b, c, h, w = x.shape
-        xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        ox = torch.empty_like(xn)
-        oy = torch.empty_like(yn) if dual else None
+        xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
         px = self._stream_params("x")
         py = self._stream_params("y") if dual else None
         lib = L.lib()
-        if drop is not None:   # the exact tier whatever self.precision says: the fused fast kernels have no masks
-            desc = self._desc("fp32")
-            ws, wsn = _workspace(lib.swf_basic_block_drop_workspace_bytes(C.byref(desc), b, h, w), x.device)
-            L.check(lib.swf_basic_block_fwd_drop(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn),
-                                                 _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None, b, h, w,
-                                                 C.byref(drop), ws, wsn, _stream(x.device)))
-            return (_to_nchw(ox), _to_nchw(oy)) if dual else (_to_nchw(ox), None)
-        desc = self._desc(self.precision)
-        ws, wsn = _workspace(lib.swf_basic_block_workspace_bytes(C.byref(desc), b, h, w), x.device)
-        L.check(lib.swf_basic_block_fwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn),
-                                        _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None,
-                                        b, h, w, ws, wsn, _stream(x.device)))
-        return (_to_nchw(ox), _to_nchw(oy)) if dual else (_to_nchw(ox), None)
+        if drop is None:
+            size, entry, masks = lib.swf_basic_block_workspace_bytes, lib.swf_basic_block_fwd, ()
+        else:
+            size, entry, masks = lib.swf_basic_block_drop_workspace_bytes, lib.swf_basic_block_fwd_drop, (C.byref(drop),)
+        desc = self._desc(self.precision if drop is None else "fp32")
+        ws, wsn = _workspace(size(C.byref(desc), b, h, w), x.device)
+        L.check(entry(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), b, h, w, *masks,
+                      ws, wsn, _stream(x.device)))
+        return _nchw_out(ox, oy)
 
-    def _backward(self, x, y, gox, goy, dual, drop: Optional[L.Dropout] = None):
+    def _bwd(self, x, y, gox, goy, dual, drop: Optional[L.Dropout]):
         """dL/d(x, y) and the parameter gradients of both streams through swf_basic_block_bwd (exact fp32, forward recomputed; with
         dropout swf_basic_block_bwd_drop, the same masks as the forward)."""
         b, c, h, w = x.shape
         dev = x.device
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        zeros = lambda t: torch.zeros_like(t) if t is None else t
         gxo = _to_nhwc(gox.contiguous() if gox is not None else torch.zeros_like(x))
         gyo = _to_nhwc(goy.contiguous() if goy is not None else torch.zeros_like(y)) if dual else None
         gxi, gyi = torch.empty_like(xn), (torch.empty_like(yn) if dual else None)
         streams = ("x", "y") if dual else ("x",)
-        bufs = {s: [None if t is None else torch.empty(t.shape, dtype=torch.float32, device=dev) for t in self._grad_tensors(s)] for s in streams}
-        gs = {s: self._grads_struct(bufs[s]) for s in streams}
+        bufs = {s: [_new_like(t) for t in self._grad_tensors(s)] for s in streams}
+        gsx, gsy = self._grads_struct(bufs["x"]), (self._grads_struct(bufs["y"]) if dual else None)
         desc = self._desc("fp32")
         px = self._stream_params("x")
         py = self._stream_params("y") if dual else None
         lib = L.lib()
-        if drop is not None:
-            ws, wsn = _workspace(lib.swf_basic_block_drop_workspace_bytes(C.byref(desc), b, h, w), dev)
-            L.check(lib.swf_basic_block_bwd_drop(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None,
-                                                 _ptr(gxo), _ptr(gyo) if dual else None, _ptr(gxi), _ptr(gyi) if dual else None,
-                                                 C.byref(gs["x"]), C.byref(gs["y"]) if dual else None, b, h, w, C.byref(drop), ws, wsn,
-                                                 _stream(dev)))
+        if drop is None:
+            size, entry, masks = lib.swf_basic_block_bwd_workspace_bytes, lib.swf_basic_block_bwd, ()
         else:
-            ws, wsn = _workspace(lib.swf_basic_block_bwd_workspace_bytes(C.byref(desc), b, h, w), dev)
-            L.check(lib.swf_basic_block_bwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn), _ptr(yn) if dual else None,
-                                            _ptr(gxo), _ptr(gyo) if dual else None, _ptr(gxi), _ptr(gyi) if dual else None,
-                                            C.byref(gs["x"]), C.byref(gs["y"]) if dual else None, b, h, w, ws, wsn, _stream(dev)))
+            size, entry, masks = lib.swf_basic_block_drop_workspace_bytes, lib.swf_basic_block_bwd_drop, (C.byref(drop),)
+        ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
+        L.check(entry(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(gxo), _ptr(gyo), _ptr(gxi), _ptr(gyi), _ref(gsx), _ref(gsy),
+                      b, h, w, *masks, ws, wsn, _stream(dev)))
         return _to_nchw(gxi), (_to_nchw(gyi) if dual else None), bufs
 
     def forward(self, x, y=None):
@@ -722,36 +720,17 @@ class BasicBlock(_FwdAlias, nn.Module):
         (last_dropout_seed) serves both streams (mask streams 0 and 1) and all four sites."""
         dual = self.use_dual_path or y is not None
         drop = _dropout(self, self.attention_drop_ratio, self.linear_after_att_drop_ratio, self.mlp_drop_ratio)
-        if torch.is_grad_enabled() and (x.requires_grad or (y is not None and y.requires_grad) or
-                                        any(p.requires_grad for p in self.parameters())):
+        _check_4d(x, y)
+        if _wants_grad(self, x, y):
             # autograd path: forward through the library as usual, backward through swf_basic_block_bwd (kernels_bwd.hip)
-            for t in (x, y):
-                if t is not None and t.dim() != 4:
-                    raise ValueError(f"expected a 4-D (batch, channels, height, width) tensor, got shape {tuple(t.shape)}")
             _require_elu(self.mlp_activation_func)
             self.check_input_compatibility_with_option(x=x, y=y)
             streams = ("x", "y") if dual else ("x",)
             params = [t for s in streams for t in self._grad_tensors(s)]
             out = _BasicBlockFunction.apply(self, dual, drop, x, y if dual else None, *params)
             return (out[0], out[1]) if dual else out[0]
-        _check_forward_only(self, x, y)
         self.check_input_compatibility_with_option(x=x, y=y)
-        if drop is not None:
-            ox, oy = self._forward_nograd(x, y, dual, drop)
-            return (ox, oy) if dual else ox
-        b, c, h, w = x.shape
-        xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        ox = torch.empty_like(xn)
-        oy = torch.empty_like(yn) if dual else None
-        desc = self._desc(self.precision)
-        px = self._stream_params("x")
-        py = self._stream_params("y") if dual else None
-        lib = L.lib()
-        ws, wsn = _workspace(lib.swf_basic_block_workspace_bytes(C.byref(desc), b, h, w), x.device)
-        L.check(lib.swf_basic_block_fwd(C.byref(desc), C.byref(px), C.byref(py) if dual else None, _ptr(xn),
-                                        _ptr(yn) if dual else None, _ptr(ox), _ptr(oy) if dual else None,
-                                        b, h, w, ws, wsn, _stream(x.device)))
-        return (_to_nchw(ox), _to_nchw(oy)) if dual else _to_nchw(ox)
+        return self._fwd(x, y, dual, drop)
 
 
 class NormalAndShiftWinsBlockPair(_FwdAlias, nn.Module):
@@ -819,36 +798,47 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
                 else:
                     x = blk(x)
             return (x, y) if dual else x
-        _check_forward_only(self, x, y)
+        _check_4d(x, y)
         blocks[2].check_input_compatibility_with_option(x=x, y=y if dual else None)
         b, c, h, w = x.shape
-        xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
-        ox = torch.empty_like(xn)
-        oy = torch.empty_like(yn) if dual else None
+        xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
         desc = blocks[0]._desc(self.precision)
         px = (L.BlockStreamParams * 4)(*[blk._stream_params("x") for blk in blocks])
         py = (L.BlockStreamParams * 4)(*[blk._stream_params("y") for blk in blocks]) if dual else None
         lib = L.lib()
         ws, wsn = _workspace(lib.swf_basic_block_workspace_bytes(C.byref(desc), b, h, w), x.device)
-        L.check(lib.swf_block_pair4_fwd(C.byref(desc), px, py, _ptr(xn), _ptr(yn) if dual else None, _ptr(ox),
-                                        _ptr(oy) if dual else None, b, h, w, ws, wsn, _stream(x.device)))
-        return (_to_nchw(ox), _to_nchw(oy)) if dual else _to_nchw(ox)
+        L.check(lib.swf_block_pair4_fwd(C.byref(desc), px, py, _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), b, h, w, ws, wsn, _stream(x.device)))
+        return _nchw_out(ox, oy)
 
 
 # ----------------------------------------------------------------------------------------------
 # a006 / a011: padding and patch (un)merging
 # ----------------------------------------------------------------------------------------------
+def _reflect_pad_nchw(t: Tensor, ph: int, pw: int) -> Tensor:
+    """Reflect-pad an NCHW tensor at the bottom / right; to the library it is B*C single-channel maps in its NHWC convention."""
+    b, c, h, w = t.shape
+    t = t.contiguous()
+    out = torch.empty((b, c, h + ph, w + pw), dtype=torch.float32, device=t.device)
+    L.check(L.lib().swf_reflect_pad_fwd(_ptr(t), _ptr(out), b * c, h, w, 1, ph, pw, _stream(t.device)))
+    return out
+
+
+def _crop_nchw(t: Tensor, ph: int, pw: int) -> Tensor:
+    """Drop the bottom `ph` rows and the right `pw` columns of an NCHW tensor."""
+    b, c, h, w = t.shape
+    t = t.contiguous()
+    out = torch.empty((b, c, h - ph, w - pw), dtype=torch.float32, device=t.device)
+    L.check(L.lib().swf_crop_fwd(_ptr(t), _ptr(out), b * c, h, w, h - ph, w - pw, 1, _stream(t.device)))
+    return out
+
+
 class _ReflectPadFunction(torch.autograd.Function):
     """MyPadding encoder side under autograd: forward swf_reflect_pad_fwd, backward its adjoint swf_reflect_pad_bwd."""
 
     @staticmethod
     def forward(ctx, t, ph, pw):
-        b, c, h, w = t.shape
-        ctx.shape, ctx.pad = (b, c, h, w), (ph, pw)
-        t = t.contiguous()
-        out = torch.empty((b, c, h + ph, w + pw), dtype=torch.float32, device=t.device)
-        L.check(L.lib().swf_reflect_pad_fwd(_ptr(t), _ptr(out), b * c, h, w, 1, ph, pw, _stream(t.device)))
-        return out
+        ctx.shape, ctx.pad = tuple(t.shape), (ph, pw)
+        return _reflect_pad_nchw(t, ph, pw)
 
     @staticmethod
     def backward(ctx, g):
@@ -864,12 +854,8 @@ class _CropFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, t, ph, pw):
-        b, c, h, w = t.shape
-        ctx.shape = (b, c, h, w)
-        t = t.contiguous()
-        out = torch.empty((b, c, h - ph, w - pw), dtype=torch.float32, device=t.device)
-        L.check(L.lib().swf_crop_fwd(_ptr(t), _ptr(out), b * c, h, w, h - ph, w - pw, 1, _stream(t.device)))
-        return out
+        ctx.shape = tuple(t.shape)
+        return _crop_nchw(t, ph, pw)
 
     @staticmethod
     def backward(ctx, g):
@@ -918,12 +904,7 @@ class MyPadding(_FwdAlias, nn.Module):
             if ph >= t.shape[2] or pw >= t.shape[3]:
                 raise RuntimeError(f"reflect pad ({ph},{pw}) must be smaller than the map {tuple(t.shape[2:])} (a006:128)")
             return _ReflectPadFunction.apply(t, ph, pw)
-        b, c, h, w = t.shape
-        t = t.contiguous()
-        out = torch.empty((b, c, h + ph, w + pw), dtype=torch.float32, device=t.device)
-        # an NCHW tensor is B*C single-channel maps in the library's NHWC convention
-        L.check(L.lib().swf_reflect_pad_fwd(_ptr(t), _ptr(out), b * c, h, w, 1, ph, pw, _stream(t.device)))
-        return out
+        return _reflect_pad_nchw(t, ph, pw)
 
     def _crop(self, t: Tensor) -> Tensor:
         ph, pw = self.padding_size
@@ -931,15 +912,11 @@ class MyPadding(_FwdAlias, nn.Module):
             return t
         if torch.is_grad_enabled() and t.requires_grad:
             return _CropFunction.apply(t, ph, pw)
-        b, c, h, w = t.shape
-        t = t.contiguous()
-        out = torch.empty((b, c, h - ph, w - pw), dtype=torch.float32, device=t.device)
-        L.check(L.lib().swf_crop_fwd(_ptr(t), _ptr(out), b * c, h, w, h - ph, w - pw, 1, _stream(t.device)))
-        return out
+        return _crop_nchw(t, ph, pw)
 
     def forward(self, x, y):
         if not _wants_grad(self, x, y):
-            _check_forward_only(self, x, y)
+            _check_4d(x, y)
         if self.belongs_to_encoder:
             h, w = x.shape[-2:]
             if not (self.training and self.feature_shape_hw):   # a006:38-52: refreshed every call in eval
@@ -981,11 +958,9 @@ class _PatchLayerFunction(torch.autograd.Function):
         with torch.no_grad():
             tn, gn = _to_nhwc(t), _to_nhwc(g.contiguous())
             gin = torch.empty_like(tn)
-            gw = torch.empty(conv.weight.shape, dtype=torch.float32, device=dev)
-            gb = torch.empty(conv.bias.shape, dtype=torch.float32, device=dev) if conv.bias is not None else None
-            gg, gbe = torch.empty_like(ln.weight), torch.empty_like(ln.bias)
+            gw, gb, gg, gbe = _new_like(conv.weight), _new_like(conv.bias), _new_like(ln.weight), _new_like(ln.bias)
             prm = L.PatchParams(_lin(conv), _norm(ln))
-            grads = L.PatchParams(L.Linear(gw.data_ptr(), gb.data_ptr() if gb is not None else None), L.Norm(gg.data_ptr(), gbe.data_ptr()))
+            grads = L.PatchParams(L.Linear(_raw(gw), _raw(gb)), L.Norm(_raw(gg), _raw(gbe)))
             lib, enc = L.lib(), int(layer.belongs_to_encoder)
             ws, wsn = _workspace(lib.swf_patch_layer_bwd_workspace_bytes(b, h, w, layer.in_dims, layer.out_dims, mh, mw, enc), dev)
             L.check(lib.swf_patch_layer_bwd(C.byref(prm), _ptr(tn), _ptr(gn), _ptr(gin), C.byref(grads), b, h, w, layer.in_dims, layer.out_dims,
@@ -1043,7 +1018,7 @@ class PatchMergingAndLinearLayer(_FwdAlias, nn.Module):
     def forward(self, x, y=None):
         grad = _wants_grad(self, x, y)
         if not grad:
-            _check_forward_only(self, x, y)
+            _check_4d(x, y)
         if x.shape[1] != self.in_dims:
             raise RuntimeError(f"expected {self.in_dims} channels, got {x.shape[1]}")
         one = self._one_grad if grad else self._one
@@ -1099,17 +1074,15 @@ class _HeadFunction(torch.autograd.Function):
         with torch.no_grad():
             x, y, gout = x.contiguous(), y.contiguous(), gout.contiguous()
             gx, gy = torch.empty_like(x), torch.empty_like(y)
-            new = lambda t: None if t is None else torch.empty(t.shape, dtype=torch.float32, device=dev)
-            g1w, g1b, gg, gb, g2w, g2b = new(conv1.weight), new(conv1.bias), new(bn.weight), new(bn.bias), new(conv2.weight), new(conv2.bias)
-            ptr = lambda t: None if t is None else t.data_ptr()
-            grads = L.HeadGrads(ptr(g1w), ptr(g1b), ptr(gg), ptr(gb), ptr(g2w), ptr(g2b))
+            bufs = [_new_like(p) for p in (conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias)]
+            grads = L.HeadGrads(*map(_raw, bufs))
             lib, hp, ks = L.lib(), model._head_params(), model.final_layer_conv_kernel_size
             if ctx.train:
                 hp.bn_mean, hp.bn_var = stats.data_ptr(), stats.data_ptr() + 8
             ws, wsn = _workspace(lib.swf_final_head_bwd_workspace_bytes(b, h, w, ks), dev)
             L.check(lib.swf_final_head_bwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), _ptr(gx), _ptr(gy), C.byref(grads), b, h, w, ks,
                                            int(ctx.train), ws, wsn, _stream(dev)))
-        return None, gx, gy, g1w, g1b, gg, gb, g2w, g2b
+        return (None, gx, gy, *bufs)
 
 
 def get_encoder_or_decoder_block(mode: str, window_size: tuple, feature_shape_recorder: StateRecorder,
@@ -1224,11 +1197,10 @@ class MyModel(_FwdAlias, nn.Module):
         hand after an edit that bypasses those counters: through `p.data` (`p.data.copy_(...)`), through a raw pointer, of a
         buffer (BatchNorm running statistics), or after replacing a Parameter object."""
         self._arena, self._arena_key, self._packed, self._fp_params = None, None, None, None
-        self.weights_epoch += 1
+        self.weights_epoch = getattr(self, "weights_epoch", 0) + 1   # _apply() lands here too and does not assume __init__ has set the counter
 
     def _apply(self, fn, *a, **kw):
-        self._arena, self._arena_key, self._packed, self._fp_params = None, None, None, None
-        self.weights_epoch = getattr(self, "weights_epoch", 0) + 1
+        self.refresh_weights()
         return super()._apply(fn, *a, **kw)
 
     _version_of = staticmethod(attrgetter("_version"))
@@ -1313,9 +1285,8 @@ class MyModel(_FwdAlias, nn.Module):
 
     def _head_params(self) -> L.HeadParams:
         conv1, bn, conv2 = self.final_layer[0], self.final_layer[1], self.final_layer[3]
-        ptr = lambda t: None if t is None else _ptr(t)
-        return L.HeadParams(_ptr(conv1.weight), ptr(conv1.bias), _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var),
-                            _ptr(conv2.weight), ptr(conv2.bias))
+        return L.HeadParams(_ptr(conv1.weight), _ptr(conv1.bias), _ptr(bn.weight), _ptr(bn.bias), _ptr(bn.running_mean), _ptr(bn.running_var),
+                            _ptr(conv2.weight), _ptr(conv2.bias))
 
     def _forward_autograd(self, in_x: Tensor, in_y: Tensor) -> Tensor:
         """a013:209-230 module by module under torch.autograd (training side): every module's forward is a library
@@ -1377,7 +1348,7 @@ class MyModel(_FwdAlias, nn.Module):
         instead and is differentiable (_forward_autograd)."""
         if _wants_grad(self, in_x, in_y):
             return self._forward_autograd(in_x, in_y)
-        _check_forward_only(self, in_x, in_y)
+        _check_4d(in_x, in_y)
         if self.training:
             raise RuntimeError("MyModel's HIP path is the eval() forward (BatchNorm running statistics, "
                                "a013:133); call model.eval()")
