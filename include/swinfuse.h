@@ -440,6 +440,45 @@ size_t swf_fusion_loss_workspace_bytes(const swf_loss_desc* desc, int32_t B, int
 int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float* ir, const float* vis, float* terms, float* grad_fusion,
                     int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
+ * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);
+ * v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps), IEEE sqrt and division, no atomics.
+ * The tensors are described by a TABLE the caller builds in pinned host memory with swf_adam_table_fill: n_tensors rows, then a chunk
+ * map (chunk -> row; a chunk is 4096 consecutive elements of one tensor), then room the device side uses for the norm's per-chunk
+ * partial sums.  swf_adam_step copies rows and map to table_device with ONE asynchronous copy on `stream` and launches; the host
+ * table must stay untouched until that copy has run (the caller double-buffers it or guards it with an event).  No synchronisation,
+ * no read-back.  Launches: 1, plus 2 when the call computes the gradient norm. */
+typedef struct swf_adam_desc {
+    double beta1, beta2, eps, weight_decay;   /* doubles: 1 - beta is formed in double and rounded once, as torch forms it from Python floats */
+    double max_grad_norm;                     /* > 0: clip the gradients' global L2 norm (torch.nn.utils.clip_grad_norm_); <= 0: off */
+    int32_t norm_ready;                       /* != 0 (with max_grad_norm > 0): norm_out_device already holds this step's norm and coefficient
+                                                 (swf_adam_grad_norm over a table that spans several groups); the norm launches are skipped */
+} swf_adam_desc;
+typedef struct swf_adam_tensor {              /* one table row; device pointers, fp32, contiguous, numel > 0 */
+    float* param; const float* grad; float* exp_avg; float* exp_avg_sq;
+    int64_t numel;
+    float step_size;                          /* lr / (1 - beta1^t), t = this tensor's own step count, computed in double */
+    float bc2_sqrt;                           /* sqrt(1 - beta2^t) */
+    int32_t first_chunk;                      /* index of the tensor's first chunk (written by swf_adam_table_fill) */
+    int32_t reserved;
+} swf_adam_tensor;
+/* Bytes of a table (host and device buffers alike) for n_tensors tensors of total_elems elements in all; 0 for arguments
+ * swf_adam_table_fill would refuse. */
+size_t swf_adam_table_bytes(int32_t n_tensors, int64_t total_elems);
+/* Host only: write the rows and the chunk map from plain arrays of n_tensors entries (param .. exp_avg_sq: device addresses). */
+int swf_adam_table_fill(void* table_host, size_t table_bytes, int32_t n_tensors, const void* const* param, const void* const* grad,
+                        const void* const* exp_avg, const void* const* exp_avg_sq, const int64_t* numel, const float* step_size,
+                        const float* bc2_sqrt);
+/* norm_out_device[0] <- the L2 norm of every gradient of the table (two-level fixed-order fp64 reduction: bit-reproducible, and independent of
+ * the gradients' alignment),
+ * norm_out_device[1] <- min(1, max_grad_norm / (norm + 1e-6)).  Uploads the table as swf_adam_step does. */
+int swf_adam_grad_norm(double max_grad_norm, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                       float* norm_out_device, swf_stream_t stream);
+/* One Adam step of every row.  norm_out_device: 2 floats (norm, clip coefficient), written first unless desc->norm_ready, then read
+ * by the update; may be NULL when clipping is off.  The gradients themselves are never written. */
+int swf_adam_step(const swf_adam_desc* desc, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                  float* norm_out_device, swf_stream_t stream);
+
 /* ---- misc ------------------------------------------------------------------------------------ */
 int swf_version(void);                     /* major*1000 + minor */
 const char* swf_last_error_string(void);   /* thread-local, never NULL */

@@ -10,4 +10,7 @@ from .modules import (AddAndLayerNormWithOtherModule, AutoPathMLP, AutoPathWinAt
                       MyPadding, NormalAndShiftWinsBlockPair, PatchMergingAndLinearLayer, SelfAndCrossBlockPair,
                       StateRecorder, WindowAttention, get_encoder_or_decoder_block)
 
+from .optim import FusedAdam  # noqa: F401
+from .training import fractional_epoch, load_training_state, save_training_state, train_step  # noqa: F401
+
 __version__ = "0.1.0"

@@ -79,6 +79,16 @@ class LossDesc(C.Structure):
                 ("ssim_ratio", C.c_float), ("texture_ratio", C.c_float), ("intensity_ratio", C.c_float), ("psnr_ratio", C.c_float)]
 
 
+class AdamDesc(C.Structure):
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+                ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
+
+
+class AdamTensor(C.Structure):   # one table row (swf_adam_tensor); written by swf_adam_table_fill, declared here for its size
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("numel", C.c_int64),
+                ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("first_chunk", C.c_int32), ("reserved", C.c_int32)]
+
+
 P = C.POINTER
 _i32, _i64, _sz, _vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
 
@@ -160,6 +170,10 @@ SIGNATURES = {
     "swf_tensors_equal": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "swf_fusion_loss_workspace_bytes": (_sz, [P(LossDesc), _i32, _i32, _i32, _i32]),
     "swf_fusion_loss": (C.c_int, [P(LossDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_adam_table_bytes": (_sz, [_i32, _i64]),
+    "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),
+    "swf_adam_step": (C.c_int, [P(AdamDesc), _vp, _vp, _sz, _i32, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

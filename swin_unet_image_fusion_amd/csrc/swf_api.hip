@@ -13,6 +13,7 @@
 #include "kernels_bwd.h"
 #include "kernels_dropout.h"
 #include "kernels_loss.h"
+#include "kernels_optim.h"
 #include "kernels_win24.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
@@ -1899,6 +1900,126 @@ int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float*
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "fusion_loss: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return fusion_loss(*desc, fusion, ir, vis, terms, grad_fusion, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.
+static int64_t adam_max_chunks(int32_t n_tensors, int64_t total_elems) { return total_elems / kAdamChunk + n_tensors; }
+
+size_t swf_adam_table_bytes(int32_t n_tensors, int64_t total_elems) {
+    if (n_tensors <= 0 || total_elems < n_tensors || adam_max_chunks(n_tensors, total_elems) > INT32_MAX) return 0;
+    return adam_layout(n_tensors, adam_max_chunks(n_tensors, total_elems)).total_bytes;
+}
+
+int swf_adam_table_fill(void* table_host, size_t table_bytes, int32_t n_tensors, const void* const* param, const void* const* grad,
+                        const void* const* exp_avg, const void* const* exp_avg_sq, const int64_t* numel, const float* step_size,
+                        const float* bc2_sqrt) {
+    if (!table_host || !param || !grad || !exp_avg || !exp_avg_sq || !numel || !step_size || !bc2_sqrt)
+        return fail(SWF_ERR_NULL, "adam_table_fill: NULL table or array");
+    if (n_tensors <= 0) return fail(SWF_ERR_BAD_SHAPE, "adam_table_fill: %d tensors", n_tensors);
+    int64_t n_chunks = 0;
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        if (!param[i] || !grad[i] || !exp_avg[i] || !exp_avg_sq[i]) return fail(SWF_ERR_NULL, "adam_table_fill: tensor %d has a NULL pointer", i);
+        if (numel[i] <= 0) return fail(SWF_ERR_BAD_SHAPE, "adam_table_fill: tensor %d has %lld elements", i, (long long)numel[i]);
+        n_chunks += cdiv64(numel[i], kAdamChunk);
+    }
+    if (n_chunks > INT32_MAX) return fail(SWF_ERR_UNSUPPORTED, "adam_table_fill: %lld chunks", (long long)n_chunks);
+    const AdamLayout lay = adam_layout(n_tensors, n_chunks);
+    if (table_bytes < lay.total_bytes)
+        return fail(SWF_ERR_WORKSPACE, "adam_table_fill: table of %zu bytes, %zu needed", table_bytes, lay.total_bytes);
+    swf_adam_tensor* rows = static_cast<swf_adam_tensor*>(table_host);
+    int32_t* map = reinterpret_cast<int32_t*>(static_cast<char*>(table_host) + lay.map_off);
+    int32_t c = 0;
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        swf_adam_tensor r;
+        r.param = static_cast<float*>(const_cast<void*>(param[i]));
+        r.grad = static_cast<const float*>(grad[i]);
+        r.exp_avg = static_cast<float*>(const_cast<void*>(exp_avg[i]));
+        r.exp_avg_sq = static_cast<float*>(const_cast<void*>(exp_avg_sq[i]));
+        r.numel = numel[i];
+        r.step_size = step_size[i];
+        r.bc2_sqrt = bc2_sqrt[i];
+        r.first_chunk = c;
+        r.reserved = 0;
+        rows[i] = r;
+        for (int64_t k = cdiv64(numel[i], kAdamChunk); k > 0; --k) map[c++] = i;
+    }
+    return SWF_OK;
+}
+
+// Validate a filled host table against the buffer size, -> the number of chunks.  Reads host memory only.
+static int check_adam_table(const char* who, const void* table_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                            int64_t* n_chunks_out) {
+    if (!table_host || !table_device) return fail(SWF_ERR_NULL, "%s: NULL table", who);
+    if (n_tensors <= 0) return fail(SWF_ERR_BAD_SHAPE, "%s: %d tensors", who, n_tensors);
+    if (table_bytes < (size_t)n_tensors * sizeof(swf_adam_tensor))
+        return fail(SWF_ERR_WORKSPACE, "%s: table of %zu bytes cannot hold %d rows", who, table_bytes, n_tensors);
+    const swf_adam_tensor* rows = static_cast<const swf_adam_tensor*>(table_host);
+    int64_t c = 0;
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        const swf_adam_tensor& r = rows[i];
+        if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq) return fail(SWF_ERR_NULL, "%s: row %d has a NULL pointer", who, i);
+        if (r.numel <= 0 || r.first_chunk != c)
+            return fail(SWF_ERR_BAD_SHAPE, "%s: row %d is not what swf_adam_table_fill writes (numel %lld, first chunk %d, expected %lld)", who, i,
+                        (long long)r.numel, r.first_chunk, (long long)c);
+        c += cdiv64(r.numel, kAdamChunk);
+        if (c > INT32_MAX) return fail(SWF_ERR_UNSUPPORTED, "%s: too many chunks", who);
+    }
+    const AdamLayout lay = adam_layout(n_tensors, c);
+    if (table_bytes < lay.total_bytes) return fail(SWF_ERR_WORKSPACE, "%s: table of %zu bytes, %zu needed", who, table_bytes, lay.total_bytes);
+    const int32_t* map = reinterpret_cast<const int32_t*>(static_cast<const char*>(table_host) + lay.map_off);
+    for (int64_t k = 0; k < c; ++k)   // the kernels index the rows with these: keep them inside the table
+        if (map[k] < 0 || map[k] >= n_tensors || k < rows[map[k]].first_chunk ||
+            k >= rows[map[k]].first_chunk + cdiv64(rows[map[k]].numel, kAdamChunk))
+            return fail(SWF_ERR_BAD_SHAPE, "%s: chunk %lld maps to row %d, which does not cover it", who, (long long)k, map[k]);
+    *n_chunks_out = c;
+    return SWF_OK;
+}
+
+struct AdamTable {
+    const swf_adam_tensor* rows;
+    const int32_t* map;
+    double* partials;
+    int n_chunks;
+};
+static int upload_adam_table(const char* who, const void* table_host, void* table_device, int32_t n_tensors, int64_t n_chunks,
+                             hipStream_t stream, AdamTable* t) {
+    const AdamLayout lay = adam_layout(n_tensors, n_chunks);
+    hipError_t e = hipMemcpyAsync(table_device, table_host, lay.copy_bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return fail(SWF_ERR_HIP, "%s: table copy: %s", who, hipGetErrorString(e));
+    char* base = static_cast<char*>(table_device);
+    t->rows = reinterpret_cast<const swf_adam_tensor*>(base);
+    t->map = reinterpret_cast<const int32_t*>(base + lay.map_off);
+    t->partials = reinterpret_cast<double*>(base + lay.partial_off);
+    t->n_chunks = (int)n_chunks;
+    return SWF_OK;
+}
+
+int swf_adam_grad_norm(double max_grad_norm, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                       float* norm_out_device, swf_stream_t stream) {
+    if (!norm_out_device) return fail(SWF_ERR_NULL, "adam_grad_norm: NULL norm_out_device");
+    if (!(max_grad_norm > 0)) return fail(SWF_ERR_BAD_SHAPE, "adam_grad_norm: max_grad_norm %g is not positive", max_grad_norm);
+    int64_t n_chunks = 0;
+    SWF_TRY(check_adam_table("adam_grad_norm", table_pinned_host, table_device, table_bytes, n_tensors, &n_chunks));
+    AdamTable t;
+    SWF_TRY(upload_adam_table("adam_grad_norm", table_pinned_host, table_device, n_tensors, n_chunks, as_stream(stream), &t));
+    return launch_gradnorm(t.rows, t.map, t.n_chunks, t.partials, (float)max_grad_norm, norm_out_device, as_stream(stream));
+}
+
+int swf_adam_step(const swf_adam_desc* desc, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                  float* norm_out_device, swf_stream_t stream) {
+    if (!desc) return fail(SWF_ERR_NULL, "adam_step: NULL descriptor");
+    if (!(desc->beta1 >= 0 && desc->beta1 < 1 && desc->beta2 >= 0 && desc->beta2 < 1 && desc->eps >= 0 && desc->weight_decay >= 0))
+        return fail(SWF_ERR_UNSUPPORTED, "adam_step: betas (%g, %g) must lie in [0, 1), eps %g and weight_decay %g must not be negative",
+                    desc->beta1, desc->beta2, desc->eps, desc->weight_decay);
+    const bool clip = desc->max_grad_norm > 0;
+    if (clip && !norm_out_device) return fail(SWF_ERR_NULL, "adam_step: clipping is on and norm_out_device is NULL");
+    int64_t n_chunks = 0;
+    SWF_TRY(check_adam_table("adam_step", table_pinned_host, table_device, table_bytes, n_tensors, &n_chunks));
+    AdamTable t;
+    SWF_TRY(upload_adam_table("adam_step", table_pinned_host, table_device, n_tensors, n_chunks, as_stream(stream), &t));
+    if (clip && !desc->norm_ready)
+        SWF_TRY(launch_gradnorm(t.rows, t.map, t.n_chunks, t.partials, (float)desc->max_grad_norm, norm_out_device, as_stream(stream)));
+    return launch_adam_multi(t.rows, t.map, t.n_chunks, *desc, clip ? norm_out_device : nullptr, as_stream(stream));
 }
 
 }  // extern "C"

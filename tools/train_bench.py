@@ -1,9 +1,12 @@
 """Time of one training step of the module-by-module autograd path: forward under autograd + backward of every
-parameter (exact fp32, atomics-free) + a plain SGD update, model.train() as the reference trains (a016:137).  Prints one JSON line.
+parameter (exact fp32, atomics-free) + the optimiser's update, model.train() as the reference trains (a016:137).  Prints one JSON line.
+--opt sgd (default) is plain SGD at lr 1e-3, adam is torch.optim.Adam() with its defaults, fused-adam is this package's FusedAdam (the
+reference's optimiser, a016:67, as one HIP launch).
 --loss standin (default) is a smooth stand-in, the mean squared distance to max(ir, vis); --loss fusion is the reference's step
 (a016:150-165): clamp_(0, 1), then MyLoss().calcu_total_loss on the fused HIP loss.
 
     python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5] [--drop P] [--loss standin|fusion]
+                                [--opt sgd|adam|fused-adam]
 
 --drop P sets the three dropout ratios (attention, projection, MLP) to P: every block then runs the exact-fp32 *_drop entries.
 """
@@ -28,9 +31,10 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--drop", type=float, default=0.0, help="attention_drop_ratio = linear_after_att_drop_ratio = mlp_drop_ratio")
     ap.add_argument("--loss", choices=["standin", "fusion"], default="standin")
+    ap.add_argument("--opt", choices=["sgd", "adam", "fused-adam"], default="sgd")
     args = ap.parse_args()
     entry.build()
-    from swin_unet_image_fusion_amd import CONFIGS, MyLoss, MyModel, load_recipe_into, synthetic_pair
+    from swin_unet_image_fusion_amd import CONFIGS, FusedAdam, MyLoss, MyModel, load_recipe_into, synthetic_pair
     dev = torch.device("cuda:0")
     cfg = CONFIGS[args.config]
     kw = cfg.model_kwargs(nn.ELU(inplace=True))
@@ -38,7 +42,11 @@ def main():
     model = MyModel(**kw)
     load_recipe_into(model, seed=0, flavor="kaiming")
     model.to(dev).train()
-    opt = torch.optim.SGD(model.parameters(), lr=1e-3)
+    if args.opt == "sgd":
+        opt = torch.optim.SGD(model.parameters(), lr=1e-3)
+    else:
+        opt = torch.optim.Adam(model.parameters()) if args.opt == "adam" else FusedAdam(model.parameters())
+    bumps_versions = args.opt == "fused-adam"   # FusedAdam.step() bumps the version counters itself: no refresh_weights() needed
     ir, vis = (torch.from_numpy(a).to(dev) for a in synthetic_pair(args.batch, args.size, args.size, seed_ir=1, seed_vis=2))
     tgt = torch.maximum(ir, vis)
     fusion_loss = MyLoss() if args.loss == "fusion" else None
@@ -55,14 +63,17 @@ def main():
         opt.zero_grad(set_to_none=True)
         loss.backward()
         torch.cuda.synchronize(); t2 = time.perf_counter()
-        opt.step(); model.refresh_weights()
+        opt.step()
+        if not bumps_versions:
+            model.refresh_weights()
         torch.cuda.synchronize(); t3 = time.perf_counter()
         losses.append(float(loss))
         if it:
             times["forward"] += t1 - t0; times["backward"] += t2 - t1; times["update"] += t3 - t2
     ms = {k: round(v / args.iters * 1e3, 2) for k, v in times.items()}
+    label = "SGD" if args.opt == "sgd" else args.opt
     total = sum(ms.values())
-    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, SGD, dropout {args.drop}, loss {args.loss}",
+    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, {label}, dropout {args.drop}, loss {args.loss}",
                       "ms": ms, "ms_per_step": round(total, 2), "pairs_per_s": round(args.batch / total * 1e3, 1),
                       "loss_first_last": [losses[0], losses[-1]]}))
 
