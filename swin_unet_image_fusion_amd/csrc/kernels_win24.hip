@@ -30,10 +30,7 @@
 // Arithmetic (SWF_PREC_FAST): linear layers split-bf16 x3 (fp32-grade) on v_mfma_f32_32x32x16_bf16; Q.K^T and P.V on
 // v_mfma_f32_32x32x16_f16 (f16 operands are 8x closer to fp32 than bf16 at the same rate); LayerNorm statistics,
 // softmax, ELU, residual stream, accumulators fp32; exp via v_exp_f32 (Wq, bq and the bias matrix carry log2(e)).
-#include "kernels_win24.h"
-#include "win_frag.h"
-
-#include <algorithm>
+#include "win_host.h"
 
 namespace swf {
 namespace {
@@ -67,24 +64,6 @@ struct G24 {
     // LDS: K images [stream 2][key tile 8][k-step 2] x 1 KB, V^T images [stream 2][pv-step 16] x 1 KB (single-buffered), vectors
     static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_total16 = l_vec16 + 2 * 2 * 64 * 4;
 };
-
-struct Win24Args {
-    const float* in[2];
-    float* out[2];       // half-block modes: a NULL out[s] drops that stream's stores (its waves only feed K / V to the other stream)
-    const char* packed[2];
-    const char* warm[2];
-    int B, H, W, shift, cross, warm_bytes;
-    int ntok[2];         // MLP half (W24_MLP): token count of each stream's flat token list
-};
-
-// What one launch computes (template parameter MODE of window24_kernel):
-//   W24_BLOCK  the whole BasicBlock (a005:127-145)
-//   W24_ATTN   x + proj(attention(LN1 ...)) — AddAndLayerNormWithOtherModule around AutoPathWinAtt (a004:29-38, a002:58-82); with
-//              RAW: proj(attention(q, k, v)) on un-normalised inputs and no residual — WindowAttention.forward (a001:448-474),
-//              stream 0 = the query tensor and the output, stream 1 = the key / value tensor (its waves stop after K / V)
-//   W24_MLP    x + fc2(ELU(fc1(LN2 x))) — AddAndLayerNormWithOtherModule around AutoPathMLP (a004:29-38, a003:46-50); with RAW:
-//              fc2(ELU(fc1 x)) — AutoPathMLP.forward.  Tokens are a flat list (no windows): 64 per workgroup step and stream
-constexpr int W24_BLOCK = 0, W24_ATTN = 1, W24_MLP = 2;
 
 // LayerNorm (eps 1e-5, biased variance) of the lane's token — 12 of its 24 channels sit in this lane (registers 0..11 of
 // `res`), the other 12 in lane l ^ 32 — straight into the split-bf16 B / A operand fragments of the next linear layer.
@@ -199,13 +178,13 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
 // 15 padding tokens (row 7 / column 7) load zeros and store nothing (buffer addressing: an offset beyond the descriptor's
 // range reads 0 and drops the store), and as keys they carry -inf in the packed bias matrix, so their probabilities are 0.
 // The shift seam of the last window row / column sits at WS - WS/2 = 4 for both sizes: the structural masks are unchanged.
-template <int HID, int WS, int MODE = W24_BLOCK, bool RAW = false>
-__global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args) {
+template <int HID, int WS, int MODE = WIN_BLOCK, bool RAW = false>
+__global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) {
     using G = G24<HID>;
     static_assert(WS == 7 || WS == 8, "window side");
-    static_assert(MODE == W24_BLOCK || MODE == W24_ATTN || MODE == W24_MLP, "mode");
-    static_assert(!RAW || MODE != W24_BLOCK, "RAW belongs to the half-block modes");
-    constexpr bool ATT = MODE != W24_MLP, MLP = MODE != W24_ATTN;
+    static_assert(MODE == WIN_BLOCK || MODE == WIN_ATTN || MODE == WIN_MLP, "mode");
+    static_assert(!RAW || MODE != WIN_BLOCK, "RAW belongs to the half-block modes");
+    constexpr bool ATT = MODE != WIN_MLP, MLP = MODE != WIN_ATTN;
     __shared__ __attribute__((aligned(16))) char smem[G::l_total];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem + G::l_k);   // [buf][stream][key tile][k-step][lane]
     u32x4* vimg = reinterpret_cast<u32x4*>(smem + G::l_v);   // [buf][stream][pv-step][lane]
@@ -230,7 +209,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
     const int act_bytes = ATT ? args.B * H * W * 24 * 4 : args.ntok[ws] * 24 * 4;   // < 2^31 (launch_win24)
     const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uniform_ptr(args.in[ws])), 0, act_bytes, 0x00020000);
     // a NULL output (half-block modes) becomes an empty descriptor: every store is out of range and dropped
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == W24_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == WIN_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
     const unsigned loff = (unsigned)lane * 16u;
     auto WF = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, f * 1024, 0)); };   // own stream: Q, proj, MLP
     auto WK = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, loff, f * 1024, 0)); };   // K / V weights
@@ -468,7 +447,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(Win24Args args
 // the column seam (column 8) is bit 2 of the accumulator register index against bit 3 of the lane's query column: -inf added
 // to those bias registers of the chunk's two tiles.
 template <int HID>
-__global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
+__global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
     using G = G24<HID>;
     extern __shared__ __attribute__((aligned(16))) char smem16[];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem16 + G::l_k16);   // [stream][key tile 8][k-step 2][lane]
@@ -722,23 +701,15 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(Win24Args args) {
 // ---------------------------------------------------------------------------------------------------------------
 // weight packing: fp32 nn.Parameter tensors -> fragment-major split-bf16 images with their k columns in rho order
 // ---------------------------------------------------------------------------------------------------------------
-struct Pack24Args {
-    swf_block_stream_params p[2];
-    char* dst[2];
-    int ws;   // window side (7 or 8)
-};
-
 template <int HID>
-__global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
+__global__ __launch_bounds__(256) void pack24_kernel(WinPackArgs a) {
     using G = G24<HID>;
     const int s = blockIdx.y;
     const swf_block_stream_params& p = a.p[s];
     char* dst = a.dst[s];
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
     const float qscale = kLog2e / sqrtf(3.0f);   // d^-0.5 (a001:32-34) and exp -> exp2
-    // (the half-block entries pack only the half they run: a missing layer packs as zeros)
-    auto lin = [](const swf_linear& l, int n, int k, int ld) { return l.weight ? l.weight[n * ld + k] : 0.f; };
-    auto bia = [](const swf_linear& l, int n) { return (l.weight && l.bias) ? l.bias[n] : 0.f; };
+    auto lin = [](const swf_linear& l, int n, int k, int ld) { return pack_wgt(l, n * ld + k); };
 
     for (int idx = gtid; idx < G::NFRAG * 512; idx += gsz) {
         const int f = idx >> 9, lane = (idx >> 3) & 63, e = idx & 7;
@@ -752,7 +723,7 @@ __global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
             const swf_linear& l = t == 0 ? p.attn.q : t == 1 ? p.attn.k : p.attn.v;
             if (c < 3) {
                 const int row = 3 * head + c;
-                val = k < 24 ? lin(l, row, k, 24) : (k == 24 ? bia(l, row) : 0.f);
+                val = k < 24 ? lin(l, row, k, 24) : (k == 24 ? pack_bia(l, row) : 0.f);
                 if (t == 0) val *= qscale;
             } else if (t != 0 && k == 24) {
                 // virtual channel 4*head+3: the constant 1 (zero weights, bias 1).  V: its O^T row is the softmax denominator.
@@ -763,18 +734,18 @@ __global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
             const int st = ((f - G::F_P) >> 1) & 1;
             hl = f & 1;
             const int k = rho(8 * st + e, hf), head = k >> 2, c = k & 3;
-            if (r < 24) val = c < 3 ? lin(p.attn.proj, r, 3 * head + c, 24) : (k == 3 ? bia(p.attn.proj, r) : 0.f);
+            if (r < 24) val = c < 3 ? lin(p.attn.proj, r, 3 * head + c, 24) : (k == 3 ? pack_bia(p.attn.proj, r) : 0.f);
         } else if (f < G::F_W2) {   // fc1: row = hidden unit; k = input channel in rho order, slot 24 = bias
             const int g = f - G::F_W1, t = g >> 2, st = (g >> 1) & 1;
             hl = g & 1;
             const int k = rho(8 * st + e, hf), hid = 32 * t + r;
-            if (hid < HID) val = (k < 24 ? lin(p.fc1, hid, k, 24) : (k == 24 ? bia(p.fc1, hid) : 0.f)) * kLog2e;   // exp2 units (ELU in the kernel)
+            if (hid < HID) val = (k < 24 ? lin(p.fc1, hid, k, 24) : (k == 24 ? pack_bia(p.fc1, hid) : 0.f)) * kLog2e;   // exp2 units (ELU in the kernel)
             else if (G::ONES_H && hid == HID && k == 24) val = 1.0f;   // u = 1 -> h' = 1: the constant the fc2 bias rides on
         } else {   // fc2: row r = output channel; k-step u covers hidden units 32(u>>1) + rho(8(u&1) + e, hf)
             const int g = f - G::F_W2, u = g >> 1;
             hl = g & 1;
             const int hid = 32 * (u >> 1) + rho(8 * (u & 1) + e, hf);
-            if (r < 24) val = hid < HID ? lin(p.fc2, r, hid, HID) * kLn2 : ((G::ONES_H && hid == HID) ? bia(p.fc2, r) : 0.f);   // h' = ELU log2(e)
+            if (r < 24) val = hid < HID ? lin(p.fc2, r, hid, HID) * kLn2 : ((G::ONES_H && hid == HID) ? pack_bia(p.fc2, r) : 0.f);   // h' = ELU log2(e)
         }
         const bf16 hi = (bf16)val;
         reinterpret_cast<bf16*>(dst)[idx] = hl ? (bf16)(val - (float)hi) : hi;
@@ -791,131 +762,37 @@ __global__ __launch_bounds__(256) void pack24_kernel(Pack24Args a) {
         else if (which == 4) v = (p.fc2.weight && p.fc2.bias) ? p.fc2.bias[c] : 0.f;
         vec[i] = v;
     }
-    // relative-position bias (a001:113-144), exp2 units, the S^T accumulator registers of each lane: [query block][lane][key tile][register]
-    float* bm = reinterpret_cast<float*>(dst + G::p_bias);
-    if (!p.attn.bias_table) return;   // MLP half: no attention, the bias section is never read
-    if (a.ws == 16) {
-        // 16x16 windows: one S^T tile per distance d = kt - qb + 7 between the key tile and the query tile (a tile = two window
-        // rows): [d][lane][reg], key = rho(reg, lane half), query = lane & 31, row = index >> 4, column = index & 15
-        for (int i = gtid; i < 15 * 64 * 16; i += gsz) {
-            const int reg = i & 15, lane = (i >> 4) & 63, d = i >> 10;
-            const int key = rho(reg, lane >> 5), q = lane & 31;
-            const int dy = 2 * (d - 7) + (key >> 4) - (q >> 4), dx = (key & 15) - (q & 15);
-            bm[i] = (dy >= -15 && dy <= 15) ? p.attn.bias_table[(dy + 15) * 31 + (dx + 15)] * kLog2e : 0.f;
-        }
-        return;
-    }
-    for (int i = gtid; i < 2 * 2 * 16 * 64; i += gsz) {
-        const int reg = i & 15, kt = (i >> 4) & 1, lane = (i >> 5) & 63, qb = i >> 11;
-        const int key = 32 * kt + rho(reg, lane >> 5), q = 32 * qb + (lane & 31);
-        const int ky = key >> 3, kx = key & 7, qy = q >> 3, qx = q & 7, ws = a.ws, tw = 2 * ws - 1;
-        float v = 0.f;
-        if (ky >= ws || kx >= ws) v = -INFINITY;   // padding token of a 7x7 window as key: probability 0
-        else if (qy < ws && qx < ws) v = p.attn.bias_table[(ky - qy + ws - 1) * tw + (kx - qx + ws - 1)] * kLog2e;
-        bm[i] = v;
-    }
+    // relative-position bias: [query block][lane][key tile][register] (MLP half: no attention, the section is never read)
+    if (p.attn.bias_table) pack_rel_bias<true>(reinterpret_cast<float*>(dst + G::p_bias), p.attn.bias_table, a.ws, gtid, gsz);
 }
+
+// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 65 KB of LDS per workgroup (dynamic
+// allocation), two workgroups per CU, 1-D grid.
+struct L24 {
+    static constexpr int C = 24, D = 3, HID_WIDE = 96, HID_NARROW = 4, PACK_GRID = 32, WAVES = W24_WAVES;
+    static constexpr const char *name = "win24", *pack_name = "pack_win24";
+    template <int HID> using G = G24<HID>;
+    template <int HID>
+    static void pack(dim3 grid, const WinPackArgs& a, hipStream_t stream) { hipLaunchKernelGGL((pack24_kernel<HID>), grid, dim3(256), 0, stream, a); }
+    template <int HID, int WS, int MODE, bool RAW>
+    static int launch(const swf_block_desc&, const WinArgs& a, int grid, hipStream_t stream) {
+        hipLaunchKernelGGL((window24_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), 0, stream, a);
+        return check_launch(MODE == WIN_BLOCK ? "window24" : "window24 (half block)");
+    }
+    template <int HID>
+    static int launch16(const WinArgs& a, int nwin, hipStream_t stream) {
+        constexpr int lds = (int)G24<HID>::l_total16;
+        SWF_TRY(raise_lds_limit<&window24w16_kernel<HID>>(lds, "window24w16"));
+        hipLaunchKernelGGL((window24w16_kernel<HID>), dim3(std::min(nwin, 2 * num_cus())), dim3(256), lds, stream, a);
+        return check_launch("window24w16");
+    }
+};
 
 }  // namespace
 
-bool win24_supported(const swf_block_desc& d) {
-    return d.attn.channels == 24 && d.attn.heads == 8 && d.attn.head_dim == 3 && d.attn.win_h == d.attn.win_w &&
-           (d.attn.win_h == 8 || d.attn.win_h == 7 || d.attn.win_h == 16) && (d.hidden == 96 || d.hidden == 4);
-}
-
-size_t win24_packed_bytes(const swf_block_desc& d) {
-    if (!win24_supported(d)) return 0;
-    if (d.attn.win_h == 16) return align_up(d.hidden == 96 ? G24<96>::p_total16 : G24<4>::p_total16, 256);
-    return align_up(d.hidden == 96 ? G24<96>::p_total : G24<4>::p_total, 256);
-}
-
-int pack_win24(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, void* packed_x,
-               void* packed_y, hipStream_t stream) {
-    if (!win24_supported(d)) return fail(SWF_ERR_UNSUPPORTED, "pack_win24: shape not covered");
-    Pack24Args a;
-    a.p[0] = px; a.p[1] = py;
-    a.dst[0] = static_cast<char*>(packed_x); a.dst[1] = static_cast<char*>(packed_y);
-    a.ws = d.attn.win_h;
-    if (d.hidden == 96) hipLaunchKernelGGL((pack24_kernel<96>), dim3(32, 2), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((pack24_kernel<4>), dim3(32, 2), dim3(256), 0, stream, a);
-    return check_launch("pack_win24");
-}
-
-size_t win24_half_packed_bytes(int channels, int hidden) {
-    if (channels != 24 || (hidden != 96 && hidden != 4)) return 0;
-    return align_up(hidden == 96 ? G24<96>::p_total : G24<4>::p_total, 256);
-}
-
-// Half-block launches (8x8 / 7x7 windows).  mode W24_ATTN: x_out = x + proj(attention(LN1 ...)) for both streams (raw = 0), or
-// out = proj(attention(q, kv, kv)) with q = x_in, kv = y_in, y_out = NULL (raw = 1; packed_y = packed_x).  mode W24_MLP: tokens as
-// flat lists of ntok_x / ntok_y rows (H, W ignored).  A NULL output drops that stream's stores.
-int launch_win24_half(const swf_block_desc& d, int mode, int raw, const void* packed_x, const void* packed_y, const float* x_in,
-                      const float* y_in, float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream) {
-    const int wsd = d.attn.win_h;
-    if (mode != W24_ATTN && mode != W24_MLP) return fail(SWF_ERR_UNSUPPORTED, "win24_half: mode %d", mode);
-    if (d.attn.channels != 24 || (d.hidden != 96 && d.hidden != 4)) return fail(SWF_ERR_UNSUPPORTED, "win24_half: shape not covered");
-    Win24Args a{};
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross; a.ntok[0] = ntok_x; a.ntok[1] = ntok_y;
-    int nwin;
-    if (mode == W24_ATTN) {
-        if (!win24_supported(d) || wsd == 16 || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win24_half: shape not covered");
-        if ((int64_t)B * H * W * 24 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win24_half: map exceeds the 2 GB buffer window");
-        nwin = B * (H / wsd) * (W / wsd);
-    } else {
-        if ((int64_t)std::max(ntok_x, ntok_y) * 24 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win24_half: token count");
-        nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
-    }
-    const dim3 grid(std::min(nwin, W24_WAVES * num_cus())), blk(256);
-#define W24_LAUNCH(HID_, WS_, MODE_, RAW_) hipLaunchKernelGGL((window24_kernel<HID_, WS_, MODE_, RAW_>), grid, blk, 0, stream, a)
-    if (mode == W24_ATTN) {   // the MLP geometry is irrelevant: the hidden-96 image layout serves
-        if (wsd == 8) { if (raw) W24_LAUNCH(96, 8, W24_ATTN, true); else W24_LAUNCH(96, 8, W24_ATTN, false); }
-        else { if (raw) W24_LAUNCH(96, 7, W24_ATTN, true); else W24_LAUNCH(96, 7, W24_ATTN, false); }
-    } else if (d.hidden == 96) {
-        if (raw) W24_LAUNCH(96, 8, W24_MLP, true); else W24_LAUNCH(96, 8, W24_MLP, false);
-    } else {
-        if (raw) W24_LAUNCH(4, 8, W24_MLP, true); else W24_LAUNCH(4, 8, W24_MLP, false);
-    }
-#undef W24_LAUNCH
-    return check_launch("window24 (half block)");
-}
-
-int launch_win24(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in, const float* y_in,
-                 float* x_out, float* y_out, int B, int H, int W, hipStream_t stream, const void* next_packed_x,
-                 const void* next_packed_y, size_t next_bytes) {
-    const int wsd = d.attn.win_h;
-    if (!win24_supported(d) || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win24: shape not covered");
-    if ((int64_t)B * H * W * 24 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win24: a stream of %d x %d x %d tokens exceeds the 2 GB buffer window", B, H, W);
-    Win24Args a;
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.warm[0] = static_cast<const char*>(next_packed_x); a.warm[1] = static_cast<const char*>(next_packed_y);
-    if (!a.warm[1]) a.warm[0] = nullptr;
-    a.warm_bytes = (int)(next_bytes ? next_bytes : win24_packed_bytes(d));
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross;
-    const int nwin = B * (H / wsd) * (W / wsd);
-    if (wsd == 16) {   // 65 KB of LDS per workgroup: dynamic allocation, two workgroups per CU
-        constexpr int lds = (int)G24<96>::l_total16;
-        const int grid16 = std::min(nwin, 2 * num_cus());
-        if (d.hidden == 96) {
-            SWF_TRY(raise_lds_limit<&window24w16_kernel<96>>(lds, "window24w16"));
-            hipLaunchKernelGGL((window24w16_kernel<96>), dim3(grid16), dim3(256), lds, stream, a);
-        } else {
-            SWF_TRY(raise_lds_limit<&window24w16_kernel<4>>(lds, "window24w16"));
-            hipLaunchKernelGGL((window24w16_kernel<4>), dim3(grid16), dim3(256), lds, stream, a);
-        }
-        return check_launch("window24w16");
-    }
-    const int grid = std::min(nwin, W24_WAVES * num_cus());   // resident workgroups per CU (register-limited)
-    if (wsd == 8) {
-        if (d.hidden == 96) hipLaunchKernelGGL((window24_kernel<96, 8>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((window24_kernel<4, 8>), dim3(grid), dim3(256), 0, stream, a);
-    } else {
-        if (d.hidden == 96) hipLaunchKernelGGL((window24_kernel<96, 7>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((window24_kernel<4, 7>), dim3(grid), dim3(256), 0, stream, a);
-    }
-    return check_launch("window24");
+const WinLevel& win24_level() {
+    static const WinLevel level = win_level<L24>();
+    return level;
 }
 
 }  // namespace swf

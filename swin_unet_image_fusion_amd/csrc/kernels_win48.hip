@@ -16,10 +16,7 @@
 //
 // Arithmetic as kernels_win24.hip: linear layers split-bf16 x3 on v_mfma_f32_32x32x16_bf16, Q.K^T and P.V on ..._f16, fp32
 // LayerNorm / softmax / ELU / residual; ELU in exp2 units through v_med3 (fc1 packed with log2 e, fc2 with ln 2).
-#include "kernels_win48.h"
-#include "win_frag.h"
-
-#include <algorithm>
+#include "win_host.h"
 
 namespace swf {
 namespace {
@@ -53,18 +50,7 @@ struct G48 {
     static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_total16 = l_vec16 + size_t(2) * VSTREAM * 4;
 };
 
-struct Win48Args {
-    const float* in[2];
-    float* out[2];       // half-block modes: a NULL out[s] drops that stream's stores
-    const char* packed[2];
-    const char* warm[2];
-    int B, H, W, shift, cross, warm_bytes;
-    int ntok[2];         // MLP half (W48_MLP): token count of each stream's flat token list
-};
-
-// launch modes of window48_kernel: the whole block, or one half of it as a launch of its own (kernels_win24.hip: W24_*; RAW = no
-// LayerNorm, no residual; RAW attention: stream 0 = queries and output, stream 1 = key / value tensor)
-constexpr int W48_BLOCK = 0, W48_ATTN = 1, W48_MLP = 2;
+// launch modes of window48_kernel: win_level.h (WIN_BLOCK, WIN_ATTN, WIN_MLP; RAW = no LayerNorm, no residual)
 
 // RAW modes: the un-normalised row as the operand fragments of the next linear layer
 __device__ __forceinline__ void raw48(const f32x16& x0, const f32x16& x1, u32x4 (&xh)[3], u32x4 (&xl)[3]) {
@@ -170,12 +156,12 @@ __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc
 // WS = window side, 8 or 7 (the reference's default, A000_CONFIG.py:55).  A 7x7 window runs on the same 8x8 token grid, as in
 // kernels_win24.hip: the 15 padding tokens load zeros and store nothing (an offset beyond the buffer descriptor's range) and
 // carry -inf in the packed bias matrix as keys; the shift seam sits at WS - WS/2 = 4 for both sizes.
-template <int HID, int WS, int MODE = W48_BLOCK, bool RAW = false>
-__global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(Win48Args args) {
+template <int HID, int WS, int MODE = WIN_BLOCK, bool RAW = false>
+__global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) {
     using G = G48<HID>;
     static_assert(WS == 7 || WS == 8, "window side");
-    static_assert(!RAW || MODE != W48_BLOCK, "RAW belongs to the half-block modes");
-    constexpr bool ATT = MODE != W48_MLP, MLP = MODE != W48_ATTN;
+    static_assert(!RAW || MODE != WIN_BLOCK, "RAW belongs to the half-block modes");
+    constexpr bool ATT = MODE != WIN_MLP, MLP = MODE != WIN_ATTN;
     __shared__ __attribute__((aligned(16))) char smem[G::l_total];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem + G::l_k);   // [stream][key tile][vch tile][k-step][lane]
     u32x4* vimg = reinterpret_cast<u32x4*>(smem + G::l_v);   // [stream][vch tile][pv-step][lane]
@@ -192,7 +178,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(Win48Args args
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(uniform_ptr(args.packed[kvs])), 0, (int)G::p_total, 0x00020000);
     const int act_bytes = ATT ? args.B * H * W * 48 * 4 : args.ntok[ws] * 48 * 4;   // < 2^31 (launch_win48)
     const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uniform_ptr(args.in[ws])), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == W48_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == WIN_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
     const unsigned loff = (unsigned)lane * 16u;
     auto WF = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, f * 1024, 0)); };   // own stream: Q, proj, MLP
     auto WK = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, loff, f * 1024, 0)); };   // K / V weights
@@ -464,7 +450,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(Win48Args args
 // 8x8 kernel's attention as a chunk, running maximum kept as the f16 value the second S^T pass subtracts; bias tiles by tile
 // distance; row-seam chunks skipped, column seam = register bit 2 against lane bit 3: kernels_win24.hip), projection, LN2, MLP.
 template <int HID>
-__global__ __launch_bounds__(256, 2) void window48w16_kernel(Win48Args args) {
+__global__ __launch_bounds__(256, 2) void window48w16_kernel(WinArgs args) {
     using G = G48<HID>;
     extern __shared__ __attribute__((aligned(16))) char smem48[];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem48 + G::l_k16);   // [key tile][vch tile][k-step][lane]
@@ -762,27 +748,14 @@ __global__ __launch_bounds__(256, 2) void window48w16_kernel(Win48Args args) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct Pack48Args {
-    swf_block_stream_params p[2];
-    char* dst[2];
-    int ws;   // window side (7 or 8)
-};
-
-// k index (input channel / virtual channel / hidden unit offset) of element e of k-step s in lane half hf, for an operand
-// produced as accumulator tiles: step s covers registers 8(s&1).. of tile s>>1
-__host__ __device__ constexpr int kslot(int s, int hf, int e) { return 32 * (s >> 1) + rho(8 * (s & 1) + e, hf); }
-
 template <int HID>
-__global__ __launch_bounds__(256) void pack48_kernel(Pack48Args a) {
+__global__ __launch_bounds__(256) void pack48_kernel(WinPackArgs a) {
     using G = G48<HID>;
     const int st = blockIdx.y;
     const swf_block_stream_params& p = a.p[st];
     char* dst = a.dst[st];
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
     const float qscale = kLog2e / sqrtf(6.0f);   // d^-0.5 (a001:32-34) and exp -> exp2
-    // (the half-block entries pack only the half they run: a missing layer packs as zeros, a missing norm as identity)
-    auto bia = [](const swf_linear& l, int n) { return (l.weight && l.bias) ? l.bias[n] : 0.f; };
-    auto wgt = [](const swf_linear& l, int i) { return l.weight ? l.weight[i] : 0.f; };
 
     for (int idx = gtid; idx < G::NFRAG * 512; idx += gsz) {
         const int f = idx >> 9, lane = (idx >> 3) & 63, e = idx & 7, r = lane & 31, hf = lane >> 5;
@@ -794,24 +767,24 @@ __global__ __launch_bounds__(256) void pack48_kernel(Pack48Args a) {
             const int k = kslot(s, hf, e), head = 4 * T + (r >> 3), c = r & 7;
             const swf_linear& l = m == 0 ? p.attn.q : m == 1 ? p.attn.k : p.attn.v;
             if (c < 6 && k < 48) {
-                val = wgt(l, (head * 6 + c) * 48 + k);
+                val = pack_wgt(l, (head * 6 + c) * 48 + k);
                 if (m == 0) val *= qscale;
             }
         } else if (f < G::F_W1) {   // projection: row = output channel 32To + r; k = virtual channel of O, head 0's row 6 (= 1) carries the bias
             const int g = (f - G::F_P) >> 1, ks = g & 3, To = g >> 2;
             hl = f & 1;
             const int n = 32 * To + r, v = kslot(ks, hf, e), head = v >> 3, c = v & 7;
-            if (n < 48) val = c < 6 ? wgt(p.attn.proj, n * 48 + head * 6 + c) : (v == 6 ? bia(p.attn.proj, n) : 0.f);
+            if (n < 48) val = c < 6 ? pack_wgt(p.attn.proj, n * 48 + head * 6 + c) : (v == 6 ? pack_bia(p.attn.proj, n) : 0.f);
         } else if (f < G::F_W2) {   // fc1 (exp2 units): row = hidden unit
             const int g = (f - G::F_W1) >> 1, s = g % 3, tI = g / 3;
             hl = f & 1;
             const int k = kslot(s, hf, e), hid = 32 * tI + r;
-            if (k < 48) val = wgt(p.fc1, hid * 48 + k) * kLog2e;
+            if (k < 48) val = pack_wgt(p.fc1, hid * 48 + k) * kLog2e;
         } else {   // fc2 (x ln 2): row = output channel; k = hidden unit in accumulator order
             const int g = (f - G::F_W2) >> 1, u = g % G::KU, To = g / G::KU;
             hl = f & 1;
             const int n = 32 * To + r, hid = kslot(u, hf, e);
-            if (n < 48) val = wgt(p.fc2, n * HID + hid) * kLn2;
+            if (n < 48) val = pack_wgt(p.fc2, n * HID + hid) * kLn2;
         }
         const bf16 hi = (bf16)val;
         reinterpret_cast<bf16*>(dst)[idx] = hl ? (bf16)(val - (float)hi) : hi;
@@ -825,142 +798,53 @@ __global__ __launch_bounds__(256) void pack48_kernel(Pack48Args a) {
                 const int which = j / 24, k = j % 24;
                 const int c = k < 16 ? rho(k, hf) : 32 + rho(k - 16, hf);
                 v = which == 0 ? (p.ln1.gamma ? p.ln1.gamma[c] : 1.f) : which == 1 ? (p.ln1.beta ? p.ln1.beta[c] : 0.f)
-                  : which == 2 ? (p.ln2.gamma ? p.ln2.gamma[c] : 1.f) : which == 3 ? (p.ln2.beta ? p.ln2.beta[c] : 0.f) : bia(p.fc2, c);
+                  : which == 2 ? (p.ln2.gamma ? p.ln2.gamma[c] : 1.f) : which == 3 ? (p.ln2.beta ? p.ln2.beta[c] : 0.f) : pack_bia(p.fc2, c);
             } else if (j < G::V_B1) {   // Q / K bias in accumulator order; K's spare row 7 is the constant 1
                 const int isk = j >= G::V_BK, k = (j - (isk ? G::V_BK : G::V_BQ)), T = k >> 4, vch = 32 * T + rho(k & 15, hf);
                 const int head = vch >> 3, c = vch & 7;
-                if (c < 6) v = isk ? bia(p.attn.k, head * 6 + c) : bia(p.attn.q, head * 6 + c) * qscale;
+                if (c < 6) v = isk ? pack_bia(p.attn.k, head * 6 + c) : pack_bia(p.attn.q, head * 6 + c) * qscale;
                 else if (isk && c == 7) v = 1.0f;
             } else if (j < G::V_B1 + 16 * G::NT1) {
                 const int k = j - G::V_B1, hid = 32 * (k >> 4) + rho(k & 15, hf);
-                v = bia(p.fc1, hid) * kLog2e;
+                v = pack_bia(p.fc1, hid) * kLog2e;
             }
         } else {   // V bias by virtual channel; spare row 6 is the constant 1 (softmax denominator)
             const int vch = i - 2 * G::VHF, head = vch >> 3, c = vch & 7;
-            v = c < 6 ? bia(p.attn.v, head * 6 + c) : (c == 6 ? 1.0f : 0.f);
+            v = c < 6 ? pack_bia(p.attn.v, head * 6 + c) : (c == 6 ? 1.0f : 0.f);
         }
         vec[i] = v;
     }
-    // relative-position bias (a001:113-144), exp2 units: [query block][key tile][register / 4][lane][register % 4]
-    float* bm = reinterpret_cast<float*>(dst + G::p_bias);
-    if (!p.attn.bias_table) return;   // MLP half: the bias section is never read
-    if (a.ws == 16) {   // [distance kt - qb + 7][register / 4][lane][register % 4]; a tile = two window rows of 16
-        for (int i = gtid; i < 15 * 16 * 64; i += gsz) {
-            const int j = i & 3, lane = (i >> 2) & 63, a4 = (i >> 8) & 3, d = i >> 10;
-            const int key = rho(4 * a4 + j, lane >> 5), q = lane & 31;
-            const int dy = 2 * (d - 7) + (key >> 4) - (q >> 4), dx = (key & 15) - (q & 15);
-            bm[i] = p.attn.bias_table[(dy + 15) * 31 + (dx + 15)] * kLog2e;
-        }
-        return;
-    }
-    for (int i = gtid; i < 2 * 2 * 16 * 64; i += gsz) {
-        const int j = i & 3, lane = (i >> 2) & 63, a4 = (i >> 8) & 3, kt = (i >> 10) & 1, qb = i >> 11;
-        const int key = 32 * kt + rho(4 * a4 + j, lane >> 5), q = 32 * qb + (lane & 31);
-        const int ky = key >> 3, kx = key & 7, qy = q >> 3, qx = q & 7, ws = a.ws, tw = 2 * ws - 1;
-        float v = 0.f;
-        if (ky >= ws || kx >= ws) v = -INFINITY;   // padding token of a 7x7 window as key: probability 0
-        else if (qy < ws && qx < ws) v = p.attn.bias_table[(ky - qy + ws - 1) * tw + (kx - qx + ws - 1)] * kLog2e;
-        bm[i] = v;
-    }
+    // relative-position bias: [query block][key tile][register / 4][lane][register % 4] (MLP half: the section is never read)
+    if (p.attn.bias_table) pack_rel_bias<false>(reinterpret_cast<float*>(dst + G::p_bias), p.attn.bias_table, a.ws, gtid, gsz);
 }
+
+// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 69 KB of LDS per workgroup (dynamic),
+// two workgroups per CU, grid.y = stream.
+struct L48 {
+    static constexpr int C = 48, D = 6, HID_WIDE = 192, HID_NARROW = 96, PACK_GRID = 64, WAVES = W48_WAVES;
+    static constexpr const char *name = "win48", *pack_name = "pack_win48";
+    template <int HID> using G = G48<HID>;
+    template <int HID>
+    static void pack(dim3 grid, const WinPackArgs& a, hipStream_t stream) { hipLaunchKernelGGL((pack48_kernel<HID>), grid, dim3(256), 0, stream, a); }
+    template <int HID, int WS, int MODE, bool RAW>
+    static int launch(const swf_block_desc&, const WinArgs& a, int grid, hipStream_t stream) {
+        hipLaunchKernelGGL((window48_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), 0, stream, a);
+        return check_launch(MODE == WIN_BLOCK ? "window48" : "window48 (half block)");
+    }
+    template <int HID>
+    static int launch16(const WinArgs& a, int nwin, hipStream_t stream) {
+        constexpr int lds = (int)G48<HID>::l_total16;
+        SWF_TRY(raise_lds_limit<&window48w16_kernel<HID>>(lds, "window48w16"));
+        hipLaunchKernelGGL((window48w16_kernel<HID>), dim3(std::min(nwin, num_cus()), 2), dim3(256), lds, stream, a);
+        return check_launch("window48w16");
+    }
+};
 
 }  // namespace
 
-bool win48_supported(const swf_block_desc& d) {
-    return d.attn.channels == 48 && d.attn.heads == 8 && d.attn.head_dim == 6 && d.attn.win_h == d.attn.win_w && (d.attn.win_h == 8 || d.attn.win_h == 7 || d.attn.win_h == 16) &&
-           (d.hidden == 192 || d.hidden == 96);
-}
-
-size_t win48_packed_bytes(const swf_block_desc& d) {
-    if (!win48_supported(d)) return 0;
-    if (d.attn.win_h == 16) return align_up(d.hidden == 192 ? G48<192>::p_total16 : G48<96>::p_total16, 256);
-    return align_up(d.hidden == 192 ? G48<192>::p_total : G48<96>::p_total, 256);
-}
-
-int pack_win48(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, void* packed_x,
-               void* packed_y, hipStream_t stream) {
-    if (!win48_supported(d)) return fail(SWF_ERR_UNSUPPORTED, "pack_win48: shape not covered");
-    Pack48Args a;
-    a.p[0] = px; a.p[1] = py;
-    a.dst[0] = static_cast<char*>(packed_x); a.dst[1] = static_cast<char*>(packed_y);
-    a.ws = d.attn.win_h;
-    if (d.hidden == 192) hipLaunchKernelGGL((pack48_kernel<192>), dim3(64, 2), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((pack48_kernel<96>), dim3(64, 2), dim3(256), 0, stream, a);
-    return check_launch("pack_win48");
-}
-
-size_t win48_half_packed_bytes(int channels, int hidden) {
-    if (channels != 48 || (hidden != 192 && hidden != 96)) return 0;
-    return align_up(hidden == 192 ? G48<192>::p_total : G48<96>::p_total, 256);
-}
-
-// Half-block launches (8x8 / 7x7 windows): see launch_win24_half (kernels_win24.hip) for the contract.
-int launch_win48_half(const swf_block_desc& d, int mode, int raw, const void* packed_x, const void* packed_y, const float* x_in,
-                      const float* y_in, float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream) {
-    const int wsd = d.attn.win_h;
-    if (mode != W48_ATTN && mode != W48_MLP) return fail(SWF_ERR_UNSUPPORTED, "win48_half: mode %d", mode);
-    if (d.attn.channels != 48 || (d.hidden != 192 && d.hidden != 96)) return fail(SWF_ERR_UNSUPPORTED, "win48_half: shape not covered");
-    Win48Args a{};
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross; a.ntok[0] = ntok_x; a.ntok[1] = ntok_y;
-    int nwin;
-    if (mode == W48_ATTN) {
-        if (!win48_supported(d) || wsd == 16 || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win48_half: shape not covered");
-        if ((int64_t)B * H * W * 48 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win48_half: map exceeds the 2 GB buffer window");
-        nwin = B * (H / wsd) * (W / wsd);
-    } else {
-        if ((int64_t)std::max(ntok_x, ntok_y) * 48 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win48_half: token count");
-        nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
-    }
-    const dim3 grid(std::min(nwin, W48_WAVES * num_cus())), blk(256);
-#define W48_LAUNCH(HID_, WS_, MODE_, RAW_) hipLaunchKernelGGL((window48_kernel<HID_, WS_, MODE_, RAW_>), grid, blk, 0, stream, a)
-    if (mode == W48_ATTN) {   // the MLP geometry is irrelevant: the hidden-192 image layout serves
-        if (wsd == 8) { if (raw) W48_LAUNCH(192, 8, W48_ATTN, true); else W48_LAUNCH(192, 8, W48_ATTN, false); }
-        else { if (raw) W48_LAUNCH(192, 7, W48_ATTN, true); else W48_LAUNCH(192, 7, W48_ATTN, false); }
-    } else if (d.hidden == 192) {
-        if (raw) W48_LAUNCH(192, 8, W48_MLP, true); else W48_LAUNCH(192, 8, W48_MLP, false);
-    } else {
-        if (raw) W48_LAUNCH(96, 8, W48_MLP, true); else W48_LAUNCH(96, 8, W48_MLP, false);
-    }
-#undef W48_LAUNCH
-    return check_launch("window48 (half block)");
-}
-
-int launch_win48(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in, const float* y_in,
-                 float* x_out, float* y_out, int B, int H, int W, hipStream_t stream, const void* next_packed_x,
-                 const void* next_packed_y, size_t next_bytes) {
-    const int wsd = d.attn.win_h;
-    if (!win48_supported(d) || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win48: shape not covered");
-    if ((int64_t)B * H * W * 48 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win48: a stream of %d x %d x %d tokens exceeds the 2 GB buffer window", B, H, W);
-    Win48Args a;
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.warm[0] = static_cast<const char*>(next_packed_x); a.warm[1] = static_cast<const char*>(next_packed_y);
-    if (!a.warm[1]) a.warm[0] = nullptr;
-    a.warm_bytes = (int)(next_bytes ? next_bytes : win48_packed_bytes(d));
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross;
-    const int nwin = B * (H / wsd) * (W / wsd);
-    if (wsd == 16) {   // 69 KB of LDS per workgroup (dynamic), two workgroups per CU, grid.y = stream
-        const int gx = std::min(nwin, num_cus());
-        if (d.hidden == 192) {
-            SWF_TRY(raise_lds_limit<&window48w16_kernel<192>>((int)G48<192>::l_total16, "window48w16"));
-            hipLaunchKernelGGL((window48w16_kernel<192>), dim3(gx, 2), dim3(256), G48<192>::l_total16, stream, a);
-        } else {
-            SWF_TRY(raise_lds_limit<&window48w16_kernel<96>>((int)G48<96>::l_total16, "window48w16"));
-            hipLaunchKernelGGL((window48w16_kernel<96>), dim3(gx, 2), dim3(256), G48<96>::l_total16, stream, a);
-        }
-        return check_launch("window48w16");
-    }
-    const int grid = std::min(nwin, W48_WAVES * num_cus());
-    if (wsd == 8) {
-        if (d.hidden == 192) hipLaunchKernelGGL((window48_kernel<192, 8>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((window48_kernel<96, 8>), dim3(grid), dim3(256), 0, stream, a);
-    } else {
-        if (d.hidden == 192) hipLaunchKernelGGL((window48_kernel<192, 7>), dim3(grid), dim3(256), 0, stream, a);
-        else hipLaunchKernelGGL((window48_kernel<96, 7>), dim3(grid), dim3(256), 0, stream, a);
-    }
-    return check_launch("window48");
+const WinLevel& win48_level() {
+    static const WinLevel level = win_level<L48>();
+    return level;
 }
 
 }  // namespace swf

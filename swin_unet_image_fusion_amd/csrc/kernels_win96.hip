@@ -9,12 +9,9 @@
 // 2T + 1 as its k-steps 0 and 1, so the Q / K fragments of a head need no masking and S^T of a head is one MFMA per key tile.
 // Within a head's k-step lane half 0 holds channels 0-3 and 8-11, lane half 1 channels 4-7 and the spare rows 12-15: row 12 is
 // the constant 1 in V (softmax denominator), row 13 the constant 1 in K against -max in Q (S - max on the matrix pipe).
-#include "kernels_win96.h"
+#include "win_host.h"
 
-#include <algorithm>
 #include <cstdlib>
-
-#include "win_frag.h"
 
 namespace swf {
 namespace {
@@ -48,18 +45,7 @@ struct G96 {
     static_assert(l_total16 <= 160 * 1024, "LDS");
 };
 
-struct Win96Args {
-    const float* in[2];
-    float* out[2];       // half-block modes: a NULL out[s] drops that stream's stores
-    const char* packed[2];
-    const char* warm[2];
-    int B, H, W, shift, cross, warm_bytes;
-    int ntok[2];         // MLP half (W96_MLP): token count of each stream's flat token list
-};
-
-// launch modes of window96_kernel: the whole block, or one half of it as a launch of its own (kernels_win24.hip: W24_*; RAW = no
-// LayerNorm, no residual; RAW attention: stream 0 = queries and output, stream 1 = key / value tensor)
-constexpr int W96_BLOCK = 0, W96_ATTN = 1, W96_MLP = 2;
+// launch modes of window96_kernel: win_level.h (WIN_BLOCK, WIN_ATTN, WIN_MLP; RAW = no LayerNorm, no residual)
 
 // LayerNorm (eps 1e-5, biased variance) of the lane's token: 48 of its 96 channels sit in this lane (three tiles x 16 registers),
 // the other 48 in lane l ^ 32.  Output: the six k-step fragments of the next linear layer.
@@ -166,12 +152,12 @@ __device__ __forceinline__ void attention96(const u32x4* ksrc, const u32x4* vsrc
 
 // WS = window side, 8 or 7 (the reference's default): 7x7 windows run on the 8x8 token grid, padding tokens beyond the buffer
 // range (reads 0, stores dropped) and -inf in the packed bias matrix as keys (kernels_win24.hip).
-template <int HID, int WS, int MODE = W96_BLOCK, bool RAW = false>
-__global__ __launch_bounds__(256, 2) void window96_kernel(Win96Args args) {
+template <int HID, int WS, int MODE = WIN_BLOCK, bool RAW = false>
+__global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
     using G = G96<HID>;
     static_assert(WS == 7 || WS == 8, "window side");
-    static_assert(!RAW || MODE != W96_BLOCK, "RAW belongs to the half-block modes");
-    constexpr bool ATT = MODE != W96_MLP, MLP = MODE != W96_ATTN;
+    static_assert(!RAW || MODE != WIN_BLOCK, "RAW belongs to the half-block modes");
+    constexpr bool ATT = MODE != WIN_MLP, MLP = MODE != WIN_ATTN;
     extern __shared__ __attribute__((aligned(16))) char smem96[];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem96 + G::l_k);   // [stream][key tile][vch tile][k-step][lane]
     u32x4* vimg = reinterpret_cast<u32x4*>(smem96 + G::l_v);   // [stream][vch tile][pv-step][lane]
@@ -188,7 +174,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(Win96Args args) {
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(uniform_ptr(args.packed[kvs])), 0, (int)G::p_total, 0x00020000);
     const int act_bytes = ATT ? args.B * H * W * 96 * 4 : args.ntok[ws] * 96 * 4;   // < 2^31 (launch_win96)
     const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uniform_ptr(args.in[ws])), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == W96_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == WIN_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
     const unsigned loff = (unsigned)lane * 16u;
     auto WF = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, f * 1024, 0)); };   // own stream: Q, proj, MLP
     auto WK = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, loff, f * 1024, 0)); };   // K / V weights
@@ -473,7 +459,7 @@ __device__ unsigned long long w96_probe[16];
 #endif
 
 template <int HID, int WS>
-__global__ __launch_bounds__(512) void window96x8_kernel(Win96Args args) {
+__global__ __launch_bounds__(512) void window96x8_kernel(WinArgs args) {
     using G = G96<HID>;
     static_assert(WS == 7 || WS == 8, "window side");
     static_assert(G::NT1 % 2 == 0, "hidden tiles split over the two feature halves");
@@ -779,7 +765,7 @@ __global__ __launch_bounds__(512) void window96x8_kernel(Win96Args args) {
 // distance; row-seam chunks skipped, column seam = register bit 2 against lane bit 3), projection, LN2, MLP.  Not callable in
 // place in cross blocks (window_block_out_of_place).
 template <int HID>
-__global__ __launch_bounds__(256, 1) void window96w16_kernel(Win96Args args) {
+__global__ __launch_bounds__(256, 1) void window96w16_kernel(WinArgs args) {
     using G = G96<HID>;
     extern __shared__ __attribute__((aligned(16))) char smem96w[];
     u32x4* kimg = reinterpret_cast<u32x4*>(smem96w + G::l_k16);   // [key tile][vch tile][k-step][lane]
@@ -1088,27 +1074,14 @@ __global__ __launch_bounds__(256, 1) void window96w16_kernel(Win96Args args) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-struct Pack96Args {
-    swf_block_stream_params p[2];
-    char* dst[2];
-    int ws;   // window side (7 or 8)
-};
-
-// k index of element e of k-step s in lane half hf, for an operand produced as accumulator tiles: step s covers registers
-// 8(s & 1).. of tile s >> 1
-__host__ __device__ constexpr int kslot(int s, int hf, int e) { return 32 * (s >> 1) + rho(8 * (s & 1) + e, hf); }
-
 template <int HID>
-__global__ __launch_bounds__(256) void pack96_kernel(Pack96Args a) {
+__global__ __launch_bounds__(256) void pack96_kernel(WinPackArgs a) {
     using G = G96<HID>;
     const int st = blockIdx.y;
     const swf_block_stream_params& p = a.p[st];
     char* dst = a.dst[st];
     const int gtid = blockIdx.x * blockDim.x + threadIdx.x, gsz = gridDim.x * blockDim.x;
     const float qscale = kLog2e / sqrtf(12.0f);   // d^-0.5 (a001:32-34) and exp -> exp2
-    // (the half-block entries pack only the half they run: a missing layer packs as zeros, a missing norm as identity)
-    auto bia = [](const swf_linear& l, int n) { return (l.weight && l.bias) ? l.bias[n] : 0.f; };
-    auto wgt = [](const swf_linear& l, int i) { return l.weight ? l.weight[i] : 0.f; };
 
     for (int idx = gtid; idx < G::NFRAG * 512; idx += gsz) {
         const int f = idx >> 9, lane = (idx >> 3) & 63, e = idx & 7, r = lane & 31, hf = lane >> 5;
@@ -1119,22 +1092,22 @@ __global__ __launch_bounds__(256) void pack96_kernel(Pack96Args a) {
             const int k = kslot(s, hf, e), vch = 32 * T + r, head = vch >> 4, c = vch & 15;
             const swf_linear& l = m == 0 ? p.attn.q : m == 1 ? p.attn.k : p.attn.v;
             if (c < 12) {
-                val = wgt(l, (head * 12 + c) * 96 + k);
+                val = pack_wgt(l, (head * 12 + c) * 96 + k);
                 if (m == 0) val *= qscale;
             }
         } else if (f < G::F_W1) {   // projection: row = output channel 32To + r; k-step = head, element = the head's row in accumulator order;
                                     // head 0's row 12 (= 1 after normalisation) carries the bias
             const int g = (f - G::F_P) >> 1, ks = g & 7, To = g >> 3;
             const int n = 32 * To + r, row = rho(e, hf);   // rho(8 * 0 + e, hf) of a 16-row head: (e & 3) + 8 (e >> 2) + 4 hf
-            val = row < 12 ? wgt(p.attn.proj, n * 96 + ks * 12 + row) : ((ks == 0 && row == 12) ? bia(p.attn.proj, n) : 0.f);
+            val = row < 12 ? pack_wgt(p.attn.proj, n * 96 + ks * 12 + row) : ((ks == 0 && row == 12) ? pack_bia(p.attn.proj, n) : 0.f);
         } else if (f < G::F_W2) {   // fc1 (exp2 units): row = hidden unit
             const int g = (f - G::F_W1) >> 1, s = g % 6, tI = g / 6;
             const int k = kslot(s, hf, e), hid = 32 * tI + r;
-            val = wgt(p.fc1, hid * 96 + k) * kLog2e;
+            val = pack_wgt(p.fc1, hid * 96 + k) * kLog2e;
         } else {   // fc2 (x ln 2): row = output channel; k = hidden unit in accumulator order
             const int g = (f - G::F_W2) >> 1, u = g % G::KU, To = g / G::KU;
             const int n = 32 * To + r, hid = kslot(u, hf, e);
-            val = wgt(p.fc2, n * HID + hid) * kLn2;
+            val = pack_wgt(p.fc2, n * HID + hid) * kLn2;
         }
         const bf16 hi = (bf16)val;
         reinterpret_cast<bf16*>(dst)[idx] = hl ? (bf16)(val - (float)hi) : hi;
@@ -1148,164 +1121,66 @@ __global__ __launch_bounds__(256) void pack96_kernel(Pack96Args a) {
                 const int which = j / 48, k = j % 48;
                 const int c = 32 * (k >> 4) + rho(k & 15, hf);
                 v = which == 0 ? (p.ln1.gamma ? p.ln1.gamma[c] : 1.f) : which == 1 ? (p.ln1.beta ? p.ln1.beta[c] : 0.f)
-                  : which == 2 ? (p.ln2.gamma ? p.ln2.gamma[c] : 1.f) : which == 3 ? (p.ln2.beta ? p.ln2.beta[c] : 0.f) : bia(p.fc2, c);
+                  : which == 2 ? (p.ln2.gamma ? p.ln2.gamma[c] : 1.f) : which == 3 ? (p.ln2.beta ? p.ln2.beta[c] : 0.f) : pack_bia(p.fc2, c);
             } else if (j < G::V_B1) {   // Q / K bias in accumulator order; K's spare row 13 is the constant 1 (the -max slot)
                 const int isk = j >= G::V_BK, k = j - (isk ? G::V_BK : G::V_BQ), vch = 32 * (k >> 4) + rho(k & 15, hf);
                 const int head = vch >> 4, c = vch & 15;
-                if (c < 12) v = isk ? bia(p.attn.k, head * 12 + c) : bia(p.attn.q, head * 12 + c) * qscale;
+                if (c < 12) v = isk ? pack_bia(p.attn.k, head * 12 + c) : pack_bia(p.attn.q, head * 12 + c) * qscale;
                 else if (isk && c == 13) v = 1.0f;
             } else {
                 const int k = j - G::V_B1, hid = 32 * (k >> 4) + rho(k & 15, hf);
-                v = bia(p.fc1, hid) * kLog2e;
+                v = pack_bia(p.fc1, hid) * kLog2e;
             }
         } else {   // V bias by virtual channel; spare row 12 is the constant 1 (softmax denominator)
             const int vch = i - 2 * G::VHF, head = vch >> 4, c = vch & 15;
-            v = c < 12 ? bia(p.attn.v, head * 12 + c) : (c == 12 ? 1.0f : 0.f);
+            v = c < 12 ? pack_bia(p.attn.v, head * 12 + c) : (c == 12 ? 1.0f : 0.f);
         }
         vec[i] = v;
     }
-    // relative-position bias (a001:113-144), exp2 units: [query block][key tile][register / 4][lane][register % 4]
-    float* bm = reinterpret_cast<float*>(dst + G::p_bias);
-    if (!p.attn.bias_table) return;   // MLP half: the bias section is never read
-    if (a.ws == 16) {   // [distance kt - qb + 7][register / 4][lane][register % 4]; a tile = two window rows of 16
-        for (int i = gtid; i < 15 * 16 * 64; i += gsz) {
-            const int j = i & 3, lane = (i >> 2) & 63, a4 = (i >> 8) & 3, d = i >> 10;
-            const int key = rho(4 * a4 + j, lane >> 5), q = lane & 31;
-            const int dy = 2 * (d - 7) + (key >> 4) - (q >> 4), dx = (key & 15) - (q & 15);
-            bm[i] = p.attn.bias_table[(dy + 15) * 31 + (dx + 15)] * kLog2e;
-        }
-        return;
-    }
-    for (int i = gtid; i < 2 * 2 * 16 * 64; i += gsz) {
-        const int j = i & 3, lane = (i >> 2) & 63, a4 = (i >> 8) & 3, kt = (i >> 10) & 1, qb = i >> 11;
-        const int key = 32 * kt + rho(4 * a4 + j, lane >> 5), q = 32 * qb + (lane & 31);
-        const int ky = key >> 3, kx = key & 7, qy = q >> 3, qx = q & 7, ws = a.ws, tw = 2 * ws - 1;
-        float v = 0.f;
-        if (ky >= ws || kx >= ws) v = -INFINITY;   // padding token of a 7x7 window as key: probability 0
-        else if (qy < ws && qx < ws) v = p.attn.bias_table[(ky - qy + ws - 1) * tw + (kx - qx + ws - 1)] * kLog2e;
-        bm[i] = v;
-    }
+    // relative-position bias: [query block][key tile][register / 4][lane][register % 4] (MLP half: the section is never read)
+    if (p.attn.bias_table) pack_rel_bias<false>(reinterpret_cast<float*>(dst + G::p_bias), p.attn.bias_table, a.ws, gtid, gsz);
 }
+
+// The level as the shared host entries see it (win_host.h).  Every kernel takes its LDS dynamically (more than 64 KB).
+struct L96 {
+    static constexpr int C = 96, D = 12, HID_WIDE = 384, HID_NARROW = 192, PACK_GRID = 128, WAVES = 2;
+    static constexpr const char *name = "win96", *pack_name = "pack_win96";
+    template <int HID> using G = G96<HID>;
+    template <int HID>
+    static void pack(dim3 grid, const WinPackArgs& a, hipStream_t stream) { hipLaunchKernelGGL((pack96_kernel<HID>), grid, dim3(256), 0, stream, a); }
+    template <int HID, int WS, int MODE, bool RAW>
+    static int launch(const swf_block_desc& d, const WinArgs& a, int grid, hipStream_t stream) {
+        if constexpr (MODE == WIN_BLOCK) {
+            static const bool no_x8 = [] { const char* e = debug_env("SWF_WIN96X8"); return e && e[0] == '0'; }();   // A/B switch (tools)
+            // Maps of up to 16 windows (32 x 32 tokens: B=16 256x256 has 256 windows for 256 CUs) take eight waves per window
+            // (window96x8_kernel), one workgroup per CU.  The rule looks at the map, never at the batch: batch shards stay bit-identical.
+            // (THROUGHPUT schedule: four waves per window, two windows per CU hide each other's phase latencies)
+            if (!no_x8 && d.schedule != SWF_SCHED_THROUGHPUT && (a.H / WS) * (a.W / WS) <= 16) {
+                constexpr int lds8 = (int)G96<HID>::l_total8;
+                SWF_TRY((raise_lds_limit<&window96x8_kernel<HID, WS>>(lds8, "window96x8")));
+                hipLaunchKernelGGL((window96x8_kernel<HID, WS>), dim3(std::min(grid, num_cus())), dim3(512), lds8, stream, a);
+                return check_launch("window96x8");
+            }
+        }
+        constexpr int lds = (int)G96<HID>::l_total;
+        SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS, MODE, RAW>>(lds, MODE == WIN_BLOCK ? "window96" : "window96 half")));
+        hipLaunchKernelGGL((window96_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), lds, stream, a);
+        return check_launch(MODE == WIN_BLOCK ? "window96" : "window96 (half block)");
+    }
+    template <int HID>
+    static int launch16(const WinArgs& a, int nwin, hipStream_t stream) {   // 138 KB of LDS per workgroup: one per CU, grid.y = stream
+        constexpr int lds = (int)G96<HID>::l_total16;
+        SWF_TRY(raise_lds_limit<&window96w16_kernel<HID>>(lds, "window96w16"));
+        hipLaunchKernelGGL((window96w16_kernel<HID>), dim3(std::min(nwin, (num_cus() + 1) / 2), 2), dim3(256), lds, stream, a);
+        return check_launch("window96w16");
+    }
+};
 
 }  // namespace
 
-bool win96_supported(const swf_block_desc& d) {
-    return d.attn.channels == 96 && d.attn.heads == 8 && d.attn.head_dim == 12 && d.attn.win_h == d.attn.win_w &&
-           (d.attn.win_h == 8 || d.attn.win_h == 7 || d.attn.win_h == 16) && (d.hidden == 384 || d.hidden == 192);
-}
-
-size_t win96_packed_bytes(const swf_block_desc& d) {
-    if (!win96_supported(d)) return 0;
-    if (d.attn.win_h == 16) return align_up(d.hidden == 384 ? G96<384>::p_total16 : G96<192>::p_total16, 256);
-    return align_up(d.hidden == 384 ? G96<384>::p_total : G96<192>::p_total, 256);
-}
-
-int pack_win96(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, void* packed_x,
-               void* packed_y, hipStream_t stream) {
-    if (!win96_supported(d)) return fail(SWF_ERR_UNSUPPORTED, "pack_win96: shape not covered");
-    Pack96Args a;
-    a.p[0] = px; a.p[1] = py;
-    a.dst[0] = static_cast<char*>(packed_x); a.dst[1] = static_cast<char*>(packed_y);
-    a.ws = d.attn.win_h;
-    if (d.hidden == 384) hipLaunchKernelGGL((pack96_kernel<384>), dim3(128, 2), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((pack96_kernel<192>), dim3(128, 2), dim3(256), 0, stream, a);
-    return check_launch("pack_win96");
-}
-
-template <int HID, int WS>
-static int launch96_t(const Win96Args& a, int grid, hipStream_t stream) {
-    constexpr int lds = (int)G96<HID>::l_total;
-    SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS>>(lds, "window96")));
-    hipLaunchKernelGGL((window96_kernel<HID, WS>), dim3(grid), dim3(256), lds, stream, a);
-    return check_launch("window96");
-}
-
-template <int HID, int WS>
-static int launch96x8_t(const Win96Args& a, int grid, hipStream_t stream) {
-    constexpr int lds = (int)G96<HID>::l_total8;
-    SWF_TRY((raise_lds_limit<&window96x8_kernel<HID, WS>>(lds, "window96x8")));
-    hipLaunchKernelGGL((window96x8_kernel<HID, WS>), dim3(grid), dim3(512), lds, stream, a);
-    return check_launch("window96x8");
-}
-
-size_t win96_half_packed_bytes(int channels, int hidden) {
-    if (channels != 96 || (hidden != 384 && hidden != 192)) return 0;
-    return align_up(hidden == 384 ? G96<384>::p_total : G96<192>::p_total, 256);
-}
-
-template <int HID, int WS, int MODE, bool RAW>
-static int launch96_half_t(const Win96Args& a, int grid, hipStream_t stream) {
-    constexpr int lds = (int)G96<HID>::l_total;
-    SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS, MODE, RAW>>(lds, "window96 half")));
-    hipLaunchKernelGGL((window96_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), lds, stream, a);
-    return check_launch("window96 (half block)");
-}
-
-// Half-block launches (8x8 / 7x7 windows) on the four-wave kernel: see launch_win24_half (kernels_win24.hip) for the contract.
-int launch_win96_half(const swf_block_desc& d, int mode, int raw, const void* packed_x, const void* packed_y, const float* x_in,
-                      const float* y_in, float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream) {
-    const int wsd = d.attn.win_h;
-    if (mode != W96_ATTN && mode != W96_MLP) return fail(SWF_ERR_UNSUPPORTED, "win96_half: mode %d", mode);
-    if (d.attn.channels != 96 || (d.hidden != 384 && d.hidden != 192)) return fail(SWF_ERR_UNSUPPORTED, "win96_half: shape not covered");
-    Win96Args a{};
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross; a.ntok[0] = ntok_x; a.ntok[1] = ntok_y;
-    int nwin;
-    if (mode == W96_ATTN) {
-        if (!win96_supported(d) || wsd == 16 || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win96_half: shape not covered");
-        if ((int64_t)B * H * W * 96 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win96_half: map exceeds the 2 GB buffer window");
-        nwin = B * (H / wsd) * (W / wsd);
-    } else {
-        if ((int64_t)std::max(ntok_x, ntok_y) * 96 * 4 >= (int64_t(1) << 31) || ntok_x <= 0) return fail(SWF_ERR_UNSUPPORTED, "win96_half: token count");
-        nwin = (std::max(ntok_x, ntok_y) + 63) / 64;
-    }
-    const int grid = std::min(nwin, 2 * num_cus());
-    if (mode == W96_ATTN) {   // the MLP geometry is irrelevant: the hidden-384 image layout serves
-        if (wsd == 8) return raw ? launch96_half_t<384, 8, W96_ATTN, true>(a, grid, stream) : launch96_half_t<384, 8, W96_ATTN, false>(a, grid, stream);
-        return raw ? launch96_half_t<384, 7, W96_ATTN, true>(a, grid, stream) : launch96_half_t<384, 7, W96_ATTN, false>(a, grid, stream);
-    }
-    if (d.hidden == 384) return raw ? launch96_half_t<384, 8, W96_MLP, true>(a, grid, stream) : launch96_half_t<384, 8, W96_MLP, false>(a, grid, stream);
-    return raw ? launch96_half_t<192, 8, W96_MLP, true>(a, grid, stream) : launch96_half_t<192, 8, W96_MLP, false>(a, grid, stream);
-}
-
-int launch_win96(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in, const float* y_in,
-                 float* x_out, float* y_out, int B, int H, int W, hipStream_t stream, const void* next_packed_x,
-                 const void* next_packed_y, size_t next_bytes) {
-    const int wsd = d.attn.win_h;
-    if (!win96_supported(d) || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "win96: shape not covered");
-    if ((int64_t)B * H * W * 96 * 4 >= (int64_t(1) << 31)) return fail(SWF_ERR_UNSUPPORTED, "win96: a stream of %d x %d x %d tokens exceeds the 2 GB buffer window", B, H, W);
-    Win96Args a;
-    a.in[0] = x_in; a.in[1] = y_in; a.out[0] = x_out; a.out[1] = y_out;
-    a.packed[0] = static_cast<const char*>(packed_x); a.packed[1] = static_cast<const char*>(packed_y);
-    a.warm[0] = static_cast<const char*>(next_packed_x); a.warm[1] = static_cast<const char*>(next_packed_y);
-    if (!a.warm[1]) a.warm[0] = nullptr;
-    a.warm_bytes = (int)(next_bytes ? next_bytes : win96_packed_bytes(d));
-    a.B = B; a.H = H; a.W = W; a.shift = d.attn.shift; a.cross = d.cross;
-    const int nwin = B * (H / wsd) * (W / wsd);
-    if (wsd == 16) {   // 138 KB of LDS per workgroup: one per CU, grid.y = stream
-        const int gx = std::min(nwin, (num_cus() + 1) / 2);
-        if (d.hidden == 384) {
-            SWF_TRY(raise_lds_limit<&window96w16_kernel<384>>((int)G96<384>::l_total16, "window96w16"));
-            hipLaunchKernelGGL((window96w16_kernel<384>), dim3(gx, 2), dim3(256), G96<384>::l_total16, stream, a);
-        } else {
-            SWF_TRY(raise_lds_limit<&window96w16_kernel<192>>((int)G96<192>::l_total16, "window96w16"));
-            hipLaunchKernelGGL((window96w16_kernel<192>), dim3(gx, 2), dim3(256), G96<192>::l_total16, stream, a);
-        }
-        return check_launch("window96w16");
-    }
-    static const bool no_x8 = [] { const char* e = debug_env("SWF_WIN96X8"); return e && e[0] == '0'; }();   // A/B switch (tools)
-    // Maps of up to 16 windows (32 x 32 tokens: B=16 256x256 has 256 windows for 256 CUs) take eight waves per window
-    // (window96x8_kernel).  The rule looks at the map, never at the batch: batch shards stay bit-identical.
-    // (THROUGHPUT schedule: four waves per window, two windows per CU hide each other's phase latencies)
-    if (!no_x8 && d.schedule != SWF_SCHED_THROUGHPUT && (H / wsd) * (W / wsd) <= 16) {
-        const int gx = std::min(nwin, num_cus());
-        if (wsd == 8) return d.hidden == 384 ? launch96x8_t<384, 8>(a, gx, stream) : launch96x8_t<192, 8>(a, gx, stream);
-        return d.hidden == 384 ? launch96x8_t<384, 7>(a, gx, stream) : launch96x8_t<192, 7>(a, gx, stream);
-    }
-    const int grid = std::min(nwin, 2 * num_cus());
-    if (wsd == 8) return d.hidden == 384 ? launch96_t<384, 8>(a, grid, stream) : launch96_t<192, 8>(a, grid, stream);
-    return d.hidden == 384 ? launch96_t<384, 7>(a, grid, stream) : launch96_t<192, 7>(a, grid, stream);
+const WinLevel& win96_level() {
+    static const WinLevel level = win_level<L96>();
+    return level;
 }
 
 }  // namespace swf

@@ -1,6 +1,6 @@
-// Fused fast tier: one launch = one BasicBlock (both modality streams) on LDS-resident window tiles.
+// Fused fast tier: one launch = one BasicBlock (both modality streams) on register-resident window tiles.
 #pragma once
-#include "swf_common.h"
+#include "win_level.h"
 
 namespace swf {
 
@@ -23,8 +23,8 @@ int launch_window_block(const swf_block_desc& d, const void* packed_x, const voi
 // next_packed_*: packed images of the block that runs next with different weights (or nullptr): this launch ends by touching
 // them (next_bytes each; 0 = the size of this block's own image) so that they are L2-resident when that block starts.
 
-// The two halves of the block as launches of their own at C = 24 / 48 / 96 (launch_win24_half has the contract; mode
-// WIN24_HALF_ATTN or WIN24_HALF_MLP).  window_half_packed_bytes: bytes of ONE stream's image for hidden width hid, 0 = not
+// The two halves of the block as launches of their own at C = 24 / 48 / 96 (WinLevel::launch_half in win_level.h has the
+// contract; mode WIN_ATTN or WIN_MLP).  window_half_packed_bytes: bytes of ONE stream's image for hidden width hid, 0 = not
 // covered.  The two streams' images lie at pk and pk + pb.
 size_t window_half_packed_bytes(int C, int hid);
 int pack_window_half(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, char* pk,

@@ -1,8 +1,8 @@
 // Fast tier (include/swinfuse.h SWF_PREC_FAST), window-level kernels of gfx950 (MI355X).  This file holds
 //   * the dispatcher of the fused BasicBlock launch (a005:127-145, both streams): window_block_supported / packed_bytes /
 //     pack_window_block / launch_window_block route C = 24, 48, 96 to the register-resident kernels of kernels_win24.hip,
-//     kernels_win48.hip, kernels_win96.hip (8x8, 7x7 and 16x16 windows), and the *_window_half entries route the half-block
-//     launches the same way;
+//     kernels_win48.hip, kernels_win96.hip (8x8, 7x7 and 16x16 windows) through their WinLevel tables (win_level.h; the entries
+//     behind them are written once, in win_host.h), and the *_window_half entries route the half-block launches the same way;
 //     (the round-1 LDS-image block kernel those replaced is gone; DESIGN.md Appendix A keeps its measurements);
 //   * the stand-alone MFMA attention cores on projection buffers: attn_core_mfma_kernel<D, WS> (8x8 / 7x7 windows: the deep
 //     levels' core) and attn_core_mfma16_kernel<D> (16x16 windows, online softmax over key tiles), both with optional 16-bit
@@ -20,9 +20,6 @@
 //   exp() runs as v_exp_f32 (exp2): Wq/bq carry d^-0.5*log2(e), the bias matrices carry log2(e).
 //
 #include "kernels_window.h"
-#include "kernels_win24.h"
-#include "kernels_win48.h"
-#include "kernels_win96.h"
 #include "win_frag.h"
 
 #include <algorithm>
@@ -576,55 +573,56 @@ int launch_attn_core_mfma(const float* const* Q, const float* const* K, const fl
 // kernels_win96.hip.  Their token rows travel through 32-bit buffer descriptors, so ONE launch covers at most 2^31 - 1 bytes
 // of a stream's map; images are independent (LayerNorm per token, attention per window), so a larger batch is launched in
 // batch slices (launch_window_block) and only a single image beyond that size is left to the unfused tier.
-static bool use_win24(const swf_block_desc& d) { return win24_supported(d); }
-static bool use_win48(const swf_block_desc& d) { return win48_supported(d); }
-static bool use_win96(const swf_block_desc& d) { return win96_supported(d); }
+// The level is picked once, by channel count; its entries (win_level.h) check the rest of the descriptor.
+static const WinLevel* level_of(int C) { return C == 24 ? &win24_level() : C == 48 ? &win48_level() : C == 96 ? &win96_level() : nullptr; }
+static const WinLevel* level_of(const swf_block_desc& d) {
+    const WinLevel* l = level_of(d.attn.channels);
+    return l && l->supported(d) ? l : nullptr;
+}
 
 static int64_t image_bytes(const swf_block_desc& d, int H, int W) { return (int64_t)H * W * d.attn.channels * 4; }
 constexpr int64_t kMaxLaunchBytes = (int64_t(1) << 31) - 1;
 
 bool window_block_supported(const swf_block_desc& d, int B, int H, int W) {
-    if (B <= 0 || H <= 0 || W <= 0) return false;
-    if (!(use_win24(d) || use_win48(d) || use_win96(d))) return false;
+    if (B <= 0 || H <= 0 || W <= 0 || !level_of(d)) return false;
     return H % d.attn.win_h == 0 && W % d.attn.win_w == 0 && image_bytes(d, H, W) <= kMaxLaunchBytes;
 }
 
 size_t window_block_packed_bytes(const swf_block_desc& d) {
-    if (use_win24(d)) return win24_packed_bytes(d);
-    if (use_win48(d)) return win48_packed_bytes(d);
-    if (use_win96(d)) return win96_packed_bytes(d);
-    return 0;
+    const WinLevel* l = level_of(d);
+    return l ? l->packed_bytes(d) : 0;
 }
 
-// The 16x16-window kernel at C = 48 runs one workgroup per (window, stream): in a cross block the workgroup of one stream reads the
-// other stream's tokens while that stream's workgroup writes its results, so the outputs must not alias the inputs.
+// The 16x16-window kernels at C = 48 and 96 run one workgroup per (window, stream): in a cross block the workgroup of one stream
+// reads the other stream's tokens while that stream's workgroup writes its results, so the outputs must not alias the inputs.
 bool window_block_out_of_place(const swf_block_desc& d) {
-    return (use_win48(d) || use_win96(d)) && d.attn.win_h == 16;
+    return level_of(d) && d.attn.channels != 24 && d.attn.win_h == 16;
 }
 
 int pack_window_block(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py,
                       void* packed_x, void* packed_y, hipStream_t stream) {
-    if (use_win24(d)) return pack_win24(d, px, py, packed_x, packed_y, stream);
-    if (use_win48(d)) return pack_win48(d, px, py, packed_x, packed_y, stream);
-    if (use_win96(d)) return pack_win96(d, px, py, packed_x, packed_y, stream);
-    return fail(SWF_ERR_UNSUPPORTED, "pack_window_block: C=%d hidden=%d not covered", d.attn.channels, d.hidden);
+    const WinLevel* l = level_of(d);
+    if (!l) return fail(SWF_ERR_UNSUPPORTED, "pack_window_block: C=%d hidden=%d not covered", d.attn.channels, d.hidden);
+    return l->pack(d, px, py, packed_x, packed_y, stream);
 }
 
 size_t window_half_packed_bytes(int C, int hid) {
-    return C == 24 ? win24_half_packed_bytes(C, hid) : C == 48 ? win48_half_packed_bytes(C, hid) : C == 96 ? win96_half_packed_bytes(C, hid) : 0;
+    const WinLevel* l = level_of(C);
+    return l ? l->half_packed_bytes(hid) : 0;
 }
 
 int pack_window_half(const swf_block_desc& d, const swf_block_stream_params& px, const swf_block_stream_params& py, char* pk,
                      size_t pb, hipStream_t stream) {
-    return d.attn.channels == 24 ? pack_win24(d, px, py, pk, pk + pb, stream)
-         : d.attn.channels == 48 ? pack_win48(d, px, py, pk, pk + pb, stream) : pack_win96(d, px, py, pk, pk + pb, stream);
+    const WinLevel* l = level_of(d.attn.channels);
+    if (!l) return fail(SWF_ERR_UNSUPPORTED, "pack_window_half: C=%d not covered", d.attn.channels);
+    return l->pack(d, px, py, pk, pk + pb, stream);
 }
 
 int launch_window_half(const swf_block_desc& d, int mode, int raw, const char* pk, size_t pb, const float* x_in, const float* y_in,
                        float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream) {
-    return d.attn.channels == 24 ? launch_win24_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream)
-         : d.attn.channels == 48 ? launch_win48_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream)
-                                 : launch_win96_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream);
+    const WinLevel* l = level_of(d.attn.channels);
+    if (!l) return fail(SWF_ERR_UNSUPPORTED, "launch_window_half: C=%d not covered", d.attn.channels);
+    return l->launch_half(d, mode, raw, pk, pk + pb, x_in, y_in, x_out, y_out, B, H, W, ntok_x, ntok_y, stream);
 }
 
 // Touch `bytes` at p from every XCD (blocks b, b+8, ... share an XCD under round-robin dealing: speed only), so that the lines
@@ -650,6 +648,7 @@ int launch_window_block(const swf_block_desc& d, const void* packed_x, const voi
         return fail(SWF_ERR_UNSUPPORTED, "window_block: C=%d hidden=%d, %d x %d map, window %d not covered", d.attn.channels, d.hidden, H, W, d.attn.win_h);
     // batch slices of at most 2^31 - 1 bytes per stream map (32-bit buffer offsets inside the kernels); the slice size depends on
     // the map size only, and a slice runs exactly the kernel the whole batch would: rows are bit-identical either way
+    const WinLevel* level = level_of(d);
     const int64_t img = image_bytes(d, H, W);
     const int per = (int)std::min<int64_t>(B, kMaxLaunchBytes / img);
     for (int b0 = 0; b0 < B; b0 += per) {
@@ -658,10 +657,7 @@ int launch_window_block(const swf_block_desc& d, const void* packed_x, const voi
         const bool last = b0 + nb >= B;   // only the last slice touches the next block's packed weights (L2 warm-up)
         const void* nx = last ? next_packed_x : nullptr;
         const void* ny = last ? next_packed_y : nullptr;
-        int st;
-        if (use_win24(d)) st = launch_win24(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes);
-        else if (use_win48(d)) st = launch_win48(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes);
-        else st = launch_win96(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes);
+        const int st = level->launch(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes);
         if (st != SWF_OK) return st;
     }
     return SWF_OK;

@@ -14,7 +14,6 @@
 #include "kernels_dropout.h"
 #include "kernels_loss.h"
 #include "kernels_optim.h"
-#include "kernels_win24.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
 #include "kernels_patchrr.h"
@@ -1086,9 +1085,9 @@ static int mlp_half24(int C, int hid, int raw, const swf_block_stream_params* px
     sx.ln1 = sy.ln1 = swf_norm{nullptr, nullptr};
     if (raw) sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
     SWF_TRY(pack_window_half(bd, sx, sy, pk, pb, stream));
-    if (py) return launch_window_half(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, y_in, x_out, y_out, 1, 1, 1, (int)N, (int)N, stream);
+    if (py) return launch_window_half(bd, WIN_MLP, raw, pk, pb, x_in, y_in, x_out, y_out, 1, 1, 1, (int)N, (int)N, stream);
     const int64_t n0 = std::min<int64_t>(N, ((N + 1) / 2 + 63) / 64 * 64);
-    return launch_window_half(bd, WIN24_HALF_MLP, raw, pk, pb, x_in, x_in + n0 * C, x_out, x_out + n0 * C, 1, 1, 1, (int)n0, (int)(N - n0), stream);
+    return launch_window_half(bd, WIN_MLP, raw, pk, pb, x_in, x_in + n0 * C, x_out, x_out + n0 * C, 1, 1, 1, (int)n0, (int)(N - n0), stream);
 }
 
 size_t swf_window_attention_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
@@ -1114,7 +1113,7 @@ static int window_attention_impl(const swf_attn_desc* desc, int precision, const
         swf_block_stream_params sp{};
         sp.attn = *p;
         SWF_TRY(pack_window_half(bd, sp, sp, pk, pbh, as_stream(stream)));
-        return launch_window_half(bd, WIN24_HALF_ATTN, 1, pk, pbh, q, k, out, nullptr, B, H, W, 0, 0, as_stream(stream));
+        return launch_window_half(bd, WIN_ATTN, 1, pk, pbh, q, k, out, nullptr, B, H, W, 0, 0, as_stream(stream));
     }
     Carver ws(workspace, workspace_bytes);
     const swf_attn_params* prm[2] = {p, nullptr};
@@ -1165,7 +1164,7 @@ int swf_attn_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_pa
         sx.fc1 = sx.fc2 = swf_linear{nullptr, nullptr}; sy.fc1 = sy.fc2 = swf_linear{nullptr, nullptr};
         sx.ln2 = sy.ln2 = swf_norm{nullptr, nullptr};
         SWF_TRY(pack_window_half(bd, sx, sy, pk, pbh, as_stream(stream)));
-        return launch_window_half(bd, WIN24_HALF_ATTN, 0, pk, pbh, x_in, py ? y_in : x_in, x_out, py ? y_out : nullptr, B, H, W, 0, 0, as_stream(stream));
+        return launch_window_half(bd, WIN_ATTN, 0, pk, pbh, x_in, py ? y_in : x_in, x_out, py ? y_out : nullptr, B, H, W, 0, 0, as_stream(stream));
     }
     Carver ws(workspace, workspace_bytes);
     return attn_halfblock_generic(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, as_stream(stream));
