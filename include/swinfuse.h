@@ -418,6 +418,35 @@ int swf_gray8_to_unit_fwd(const uint8_t* gray, float* out, int64_t count, swf_st
 int swf_ycrcb_to_rgb_fwd(const float* fused_y, const float* crcb, float* rgb_f, uint8_t* rgb8,
                          int32_t B, int32_t H, int32_t W, swf_stream_t stream);
 
+/* ---- resident paired dataset: the reference's training-time input transform (a015_dataset.py:57-66, :89-103) in one launch --------
+ * The decoded uint8 images of a training set lie in two device arenas (gray [H][W], BGR [H][W][3], cv2.imread layouts).  A batch is
+ * described by B rows; the launch writes ir = u8/255 and vis_y = cv2's uint8 luma/255 (the BGR->YCrCb restatement above) of the crop
+ * box, resized to out_h x out_w as torch.nn.functional.interpolate(mode="bilinear", antialias=True, align_corners=False) resizes the
+ * cropped float image (which is what torchvision's resized_crop does), then mirrored if flip.  Per axis, with in = crop length,
+ * out = output length, scale = in/out, support = max(scale, 1), inv = min(1/scale, 1), output index o: c = scale (o + 0.5),
+ * xmin = max(int(c - support + 0.5), 0), xsize = min(int(c + support + 0.5), in) - xmin, weights max(0, 1 - |(j + xmin - c + 0.5) inv|)
+ * over their sum, j < xsize.  The geometry is evaluated in fp64 and each normalised weight rounded to fp32 once; horizontal pass, then
+ * vertical pass, fp32 fmaf chains in ascending tap order.  Taps never leave the box (crop, then resize); no clamp; no atomics: the
+ * result is bit-reproducible, and a sample's result does not depend on the other rows of its launch.  Both images of a row share
+ * the geometry, which is what the reference's re-seeding before each image of a pair achieves (a015:100-103). */
+typedef struct swf_crop_row {      /* one output sample */
+    uint64_t ir_off;               /* byte offset of the gray image [H][W]    in ir_base  */
+    uint64_t vis_off;              /* byte offset of the BGR  image [H][W][3] in vis_base */
+    int32_t H, W;                  /* source size (both images of a pair have the same) */
+    int32_t top, left, h, w;       /* crop box, inside the source, h, w >= 1 */
+    int32_t flip;                  /* != 0: mirror the OUTPUT columns */
+    int32_t pad_;
+} swf_crop_row;
+/* Bytes of a table of B rows (host and device buffers alike); 0 for B <= 0. */
+size_t swf_paired_crop_rows_bytes(int32_t B);
+/* Host only: the rows live in device memory when the kernel reads them and cannot be checked there, so the caller checks its host copy
+ * before every upload.  SWF_ERR_BAD_SHAPE for a box that leaves its image or an image that passes its arena of ir_bytes / vis_bytes. */
+int swf_paired_crop_rows_check(const swf_crop_row* rows_host, int32_t B, uint64_t ir_bytes, uint64_t vis_bytes);
+/* ir_out, vis_y_out: [B][1][out_h][out_w] fp32.  rows_device: B rows in DEVICE memory that passed swf_paired_crop_rows_check; rows are
+ * per sample, so images of different sizes share one launch.  One launch, no workspace. */
+int swf_paired_crop_resize_fwd(const uint8_t* ir_base, const uint8_t* vis_base, const swf_crop_row* rows_device, int32_t B,
+                               int32_t out_h, int32_t out_w, float* ir_out, float* vis_y_out, swf_stream_t stream);
+
 /* ---- the reference's fusion loss (a008_loss.py MyLoss), value and d total / d fusion in one call -----------------
  * total = ssim_ratio*ssim_scale*S + texture_ratio*texture_scale*T + intensity_ratio*intensity_scale*I + psnr_ratio*psnr_scale*P on
  * single-channel fp32 images: S = MS-SSIM + L1 (five Gaussian scales, 33 taps, zero border) or single-scale SSIM (11 taps, sigma

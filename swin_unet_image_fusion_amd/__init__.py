@@ -5,6 +5,7 @@ a001 `WindowAttention` and the inner modules needed for state_dict compatibility
 by hand-written HIP kernels behind a C-ABI (`include/swinfuse.h`, `libswinfuse.so`).
 """
 from .config import CONFIGS, FusionConfig, load_recipe_into, synthetic_pair  # noqa: F401
+from .data import PairLoader, ResidentPairs, sample_crop_params  # noqa: F401
 from .loss import MyLoss  # noqa: F401
 from .modules import (AddAndLayerNormWithOtherModule, AutoPathMLP, AutoPathWinAtt, BasicBlock, MyModel,  # noqa: F401
                       MyPadding, NormalAndShiftWinsBlockPair, PatchMergingAndLinearLayer, SelfAndCrossBlockPair,

@@ -89,6 +89,11 @@ class AdamTensor(C.Structure):   # one table row (swf_adam_tensor); written by s
                 ("step_size", C.c_float), ("bc2_sqrt", C.c_float), ("first_chunk", C.c_int32), ("reserved", C.c_int32)]
 
 
+class CropRow(C.Structure):      # one table row (swf_crop_row): one output sample of swf_paired_crop_resize_fwd
+    _fields_ = [("ir_off", C.c_uint64), ("vis_off", C.c_uint64), ("H", C.c_int32), ("W", C.c_int32), ("top", C.c_int32),
+                ("left", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("flip", C.c_int32), ("pad_", C.c_int32)]
+
+
 P = C.POINTER
 _i32, _i64, _sz, _vp = C.c_int32, C.c_int64, C.c_size_t, C.c_void_p
 
@@ -157,6 +162,9 @@ SIGNATURES = {
     "swf_bgr8_to_ycrcb_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "swf_gray8_to_unit_fwd": (C.c_int, [_vp, _vp, _i64, _vp]),
     "swf_ycrcb_to_rgb_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "swf_paired_crop_rows_bytes": (_sz, [_i32]),
+    "swf_paired_crop_rows_check": (C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64]),
+    "swf_paired_crop_resize_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
     "swf_model_param_count": (_i32, [P(ModelDesc)]),
     "swf_model_param_info": (C.c_int, [P(ModelDesc), _i32, C.c_char_p, _sz, P(_i64), P(_i64)]),
     "swf_model_arena_elems": (_i64, [P(ModelDesc)]),

@@ -8,21 +8,18 @@
 // its float inverse (1.403, -0.714, -0.344, 1.773, delta 0.5): parity is pinned by formula only ("parity unpinned"
 // against cv2 itself; tests/test_color_gpu.py checks against the same restatement in numpy).
 // Pure HBM-bound byte work: one thread per pixel, planar outputs, no LDS, no MFMA.
-#include "swf_common.h"
+#include "color_fixed.h"
 
 namespace swf {
-
-__device__ __forceinline__ int descale14(int x) { return (x + (1 << 13)) >> 14; }
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // bgr: [B][H][W][3] uint8 (HWC, cv2 layout).  y: [B][1][H][W], crcb: [B][2][H][W] float32 in [0,1].
 __global__ __launch_bounds__(256) void bgr8_to_ycrcb_kernel(const uint8_t* __restrict__ bgr, float* __restrict__ y,
                                                             float* __restrict__ crcb, int64_t pixels_per_image, int64_t total) {
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
         const int b = bgr[e * 3 + 0], g = bgr[e * 3 + 1], r = bgr[e * 3 + 2];
-        const int Y = descale14(b * 1868 + g * 9617 + r * 4899);
-        const int Cr = descale14((r - Y) * 11682 + (128 << 14));
-        const int Cb = descale14((b - Y) * 9241 + (128 << 14));
+        const int Y = bgr_to_y8(b, g, r);
+        const int Cr = descale14((r - Y) * kYCrI + (128 << 14));
+        const int Cb = descale14((b - Y) * kYCbI + (128 << 14));
         const int64_t img = e / pixels_per_image, p = e % pixels_per_image;
         y[e] = (float)sat8(Y) / 255.0f;
         crcb[(img * 2 + 0) * pixels_per_image + p] = (float)sat8(Cr) / 255.0f;
