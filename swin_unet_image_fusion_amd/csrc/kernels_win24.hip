@@ -107,31 +107,36 @@ __device__ __forceinline__ void raw_frags(const f32x16& res, u32x4 (&xh)[2], u32
     split8(n + 8, xh[1], xl[1]);
 }
 
-// Attention of one wave: 32 queries x 64 keys x 8 heads.  ksrc / vsrc: the stream's K and V^T operand images in LDS (+ lane);
-// qf: the wave's own Q fragments; bias: relative-position bias of (stream, query block), C operand of the S^T MFMAs;
-// (with -inf where the shift mask applies).  Returns the O^T accumulator: registers 4a..4a+3 of
-// lane half p = channels 0..2 and softmax denominator of head 2a + p.
-__device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[2], const f32x16 (&bias)[2], bool half1) {
+// Attention of one wave over one chunk of 64 keys: 32 queries x 64 keys x 8 heads.  ksrc / vsrc: the chunk's K and V^T operand
+// images in LDS (+ lane); qf: the wave's own Q fragments; bias: relative-position bias tiles of the chunk, C operand of the S^T
+// MFMAs (with -inf where the shift mask applies).  o is the O^T accumulator: registers 4a..4a+3 of lane half p = channels 0..2
+// and softmax denominator of head 2a + p; passed in and returned.  ONLINE = false (8x8 / 7x7 windows): the chunk is the whole
+// window and o comes in as zero.
+// ONLINE = true (16x16 windows): online softmax over the chunks of a window — the chunk's attention is followed by
+// o = o * 2^(m_old - m_new) + t on the four accumulator rows of the head.  The shift that enters the second S^T pass is -max
+// ROUNDED TO f16, so the running maximum (mrun: register a, lane half p = head 2a + p) is kept as that rounded value: the
+// rescale factor then matches what earlier chunks were shifted by.
+// (Signature: o goes in and out BY VALUE and mrun is a plain pointer, unused when !ONLINE — with reference parameters for the
+// vectors hipcc schedules the kernels differently; attention48 keeps the array reference it always had.)
+template <bool ONLINE>
+__device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[2], const f32x16 (&bias)[2], bool half1,
+                                            f32x16 o, float* mrun = nullptr) {
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 o = zero16;
-    // Register budget (three, ideally four waves per SIMD): the K / V^T fragments are read from LDS where they are used
-    // instead of being held across the head loop, and a head's P tile is exponentiated, packed and multiplied eight keys at a
-    // time, so that at most the bias (32), the score tile (32, shrinking), the product tile (16) and the output tile (16)
-    // are live together.
+    // Register budget (three, ideally four waves per SIMD): the K / V^T fragments are read from LDS per head (a head's two K
+    // fragments serve both S^T passes) instead of being held across the head loop, and a head's P tile is exponentiated, packed
+    // and multiplied eight keys at a time, so that at most the bias (32), the score tile (32, shrinking), the product tile (16)
+    // and the output tile (16) are live together.
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
         const int s = h >> 2, sub = (h >> 1) & 1;
         const bool keep = half1 == ((h & 1) != 0);
-        f32x16 s0, s1;
-        {
-            const u32x4 ka0 = ksrc[(0 * 2 + s) * 64], ka1 = ksrc[(1 * 2 + s) * 64];
-            // the head's three channels are elements 4*sub .. 4*sub+2 of lane half h & 1; every other slot is zeroed
-            u32x4 qm = {0u, 0u, 0u, 0u};
-            qm[2 * sub] = keep ? qf[s][2 * sub] : 0u;
-            qm[2 * sub + 1] = keep ? qf[s][2 * sub + 1] : 0u;
-            s0 = mfma_f16(ka0, qm, bias[0]);   // S^T[key][query] + bias, exp2 units
-            s1 = mfma_f16(ka1, qm, bias[1]);
-        }
+        const u32x4 ka0 = ksrc[(0 * 2 + s) * 64], ka1 = ksrc[(1 * 2 + s) * 64];
+        // the head's three channels are elements 4*sub .. 4*sub+2 of lane half h & 1; every other slot is zeroed
+        u32x4 qm = {0u, 0u, 0u, 0u};
+        qm[2 * sub] = keep ? qf[s][2 * sub] : 0u;
+        qm[2 * sub + 1] = keep ? qf[s][2 * sub + 1] : 0u;
+        f32x16 s0 = mfma_f16(ka0, qm, bias[0]);   // S^T[key][query] + bias, exp2 units
+        f32x16 s1 = mfma_f16(ka1, qm, bias[1]);
         float mx = max3f(s0[0], s0[1], s1[0]);
         mx = max3f(mx, s1[1], s0[2]);
 #pragma unroll
@@ -142,16 +147,19 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
         // S - max on the matrix pipe instead of 32 subtractions on the (saturated) vector pipe: the head's spare k slot (virtual
         // channel 4h+3) is 1 in every K row and -max (rounded to f16: softmax is shift-invariant, any per-query constant
         // near the maximum serves) in the Q fragment, and the scores are computed a second time
-        {
-            const u32x4 ka0 = ksrc[(0 * 2 + s) * 64], ka1 = ksrc[(1 * 2 + s) * 64];
-            const f16 nm = (f16)(-mx);
-            const unsigned nmb = keep ? (unsigned)__builtin_bit_cast(unsigned short, nm) : 0u;
-            u32x4 qm = {0u, 0u, 0u, 0u};
-            qm[2 * sub] = keep ? qf[s][2 * sub] : 0u;
-            qm[2 * sub + 1] = (keep ? qf[s][2 * sub + 1] : 0u) | (nmb << 16);
-            s0 = mfma_f16(ka0, qm, bias[0]);
-            s1 = mfma_f16(ka1, qm, bias[1]);
+        float alpha = 0.f;
+        f16 nm = (f16)(-mx);
+        if constexpr (ONLINE) {
+            const float mold = mrun[h >> 1];
+            nm = (f16)(-__builtin_fmaxf(mold, mx));
+            const float mnew = -(float)nm;                 // the shift the second pass really applies
+            alpha = __builtin_amdgcn_exp2f(mold - mnew);   // first chunk: 2^-inf = 0
+            mrun[h >> 1] = keep ? mnew : mold;
         }
+        const unsigned nmb = keep ? (unsigned)__builtin_bit_cast(unsigned short, nm) : 0u;
+        qm[2 * sub + 1] |= nmb << 16;
+        s0 = mfma_f16(ka0, qm, bias[0]);
+        s1 = mfma_f16(ka1, qm, bias[1]);
         // O^T tile of this head = V^T . P^T over the 64 keys; P = exp2(S - max) in f16, one pv-step (16 keys = registers
         // 8s'.. of key tile kt) at a time: the exponentials of step ps+1 issue under the MFMA of step ps
         f32x16 t;
@@ -167,11 +175,57 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
         }
         // rows 4h .. 4h+3 (3 channels + denominator) = registers 4(h>>1) .. +3 of lane half h & 1
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[4 * (h >> 1) + j] = keep ? t[4 * (h >> 1) + j] : o[4 * (h >> 1) + j];
+        for (int j = 0; j < 4; ++j) {
+            const int i = 4 * (h >> 1) + j;
+            o[i] = keep ? (ONLINE ? __builtin_fmaf(o[i], alpha, t[i]) : t[i]) : o[i];
+        }
         __builtin_amdgcn_sched_barrier(0);   // one head at a time: interleaving heads doubles the live score tiles
     }
     return o;
 }
+
+// The lane's 12 channels of its token (three float4 at byte offset tokoff of the activation buffer, 32 bytes apart) -> registers
+// 0..11 of an accumulator tile; rows 24..31 of every output tile have zero weights: registers 12..15 stay zero
+__device__ __forceinline__ void load_rows24(const __amdgpu_buffer_rsrc_t& irs, unsigned tokoff, f32x16& dstv) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        // (one bit_cast of the whole vector: hipcc 7.2 narrows the load to ONE dword and splats it when the four lanes of
+        // the b128 result are bit_cast element by element)
+        const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irs, tokoff, 32 * a, 0));
+        dstv[4 * a] = v.x; dstv[4 * a + 1] = v.y; dstv[4 * a + 2] = v.z; dstv[4 * a + 3] = v.w;
+    }
+    dstv[12] = dstv[13] = dstv[14] = dstv[15] = 0.f;
+}
+// ... and back (un-shift = the same index map)
+__device__ __forceinline__ void store_rows24(__amdgpu_buffer_rsrc_t ors, unsigned tokoff, f32x16 res) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const f32x4 v = {res[4 * a], res[4 * a + 1], res[4 * a + 2], res[4 * a + 3]};
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, tokoff, 32 * a, 0);
+    }
+}
+
+// Normalise the O^T accumulator of attention24, then output projection + bias + residual: res (the residual rows) is the C operand
+// and the result.
+// WF(f): weight fragment f of the wave's stream.
+template <class G, class WFn>
+__device__ __forceinline__ f32x16 project24(WFn WF, f32x16 o, f32x16 res) {
+    float t[16];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const float inv = __builtin_amdgcn_rcpf(o[4 * a + 3]);
+        t[4 * a] = o[4 * a] * inv; t[4 * a + 1] = o[4 * a + 1] * inv; t[4 * a + 2] = o[4 * a + 2] * inv;
+        t[4 * a + 3] = 1.0f;   // slot rho = 4*head + 3: constant one (the projection bias sits on head 0's)
+    }
+    u32x4 oh[2], ol[2];
+    split8(t, oh[0], ol[0]);
+    split8(t + 8, oh[1], ol[1]);
+    SWF_WF_FENCE();
+#pragma unroll
+    for (int s = 0; s < 2; ++s) res = mma3(WF(G::F_P + 2 * s), WF(G::F_P + 2 * s + 1), oh[s], ol[s], res);
+    return res;
+}
+
 
 // ---------------------------------------------------------------------------------------------------------------
 // WS = window side, 8 or 7 (the reference's default, A000_CONFIG.py:55).  A 7x7 window runs on the same 8x8 token grid: the
@@ -259,17 +313,6 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
                 return tok < args.ntok[ws] ? (unsigned)((tok * 24 + 4 * (lane_w >> 5)) * 4) : 0x80000000u;
             }
         }();
-        // rows 24..31 of every output tile have zero weights: registers 12..15 stay zero
-        auto load_rows = [&](f32x16& dstv) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                // (one bit_cast of the whole vector: hipcc 7.2 narrows the load to ONE dword and splats it when the four lanes of
-                // the b128 result are bit_cast element by element)
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irs, tokoff, 32 * a, 0));
-                dstv[4 * a] = v.x; dstv[4 * a + 1] = v.y; dstv[4 * a + 2] = v.z; dstv[4 * a + 3] = v.w;
-            }
-            dstv[12] = dstv[13] = dstv[14] = dstv[15] = 0.f;
-        };
         const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
         f32x16 res;
@@ -280,7 +323,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
             // the residual rows are NOT kept in registers across the attention phase (16 registers of a 168 budget): they are
             // read again — an L2 hit, the lines were fetched microseconds ago — as the C operand of the projection
             f32x16 x0;
-            load_rows(x0);
+            load_rows24(irs, tokoff, x0);
             u32x4 xh[2], xl[2];
             if constexpr (RAW) raw_frags(x0, xh, xl);
             else layernorm_frags(x0, vec, G::V_LN1G, G::V_LN1B, xh, xl);
@@ -339,31 +382,17 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { bias[0][i] += pen0; bias[1][i] += pen1; }
             }
-            o = attention24(ksrc, vsrc, qf, bias, half1);
+            o = attention24<false>(ksrc, vsrc, qf, bias, half1, zero16);
             if (rowv || colv) load_bias();
         }
 
         // ---- normalise, output projection + bias + residual: res is the C operand ----
         SWF_WF_FENCE();
         if constexpr (RAW) res = zero16;
-        else load_rows(res);
-        {
-            float t[16];
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const float inv = __builtin_amdgcn_rcpf(o[4 * a + 3]);
-                t[4 * a] = o[4 * a] * inv; t[4 * a + 1] = o[4 * a + 1] * inv; t[4 * a + 2] = o[4 * a + 2] * inv;
-                t[4 * a + 3] = 1.0f;   // slot rho = 4*head + 3: constant one (the projection bias sits on head 0's)
-            }
-            u32x4 oh[2], ol[2];
-            split8(t, oh[0], ol[0]);
-            split8(t + 8, oh[1], ol[1]);
-            SWF_WF_FENCE();
-#pragma unroll
-            for (int s = 0; s < 2; ++s) res = mma3(WF(G::F_P + 2 * s), WF(G::F_P + 2 * s + 1), oh[s], ol[s], res);
-        }
+        else load_rows24(irs, tokoff, res);
+        res = project24<G>(WF, o, res);
         } else {   // MLP half: the rows as they are
-            load_rows(res);
+            load_rows24(irs, tokoff, res);
         }
 
         // ---- LN2, MLP: fc1 tile -> ELU -> split -> two k-steps of fc2 accumulating onto the residual ----
@@ -378,17 +407,8 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
 #pragma unroll
                 for (int s = 0; s < 2; ++s)
                     acc = mma3(WF(G::F_W1 + 4 * tI + 2 * s), WF(G::F_W1 + 4 * tI + 2 * s + 1), xh[s], xl[s], acc);
-                // ELU(alpha = 1) in exp2 units: the packed fc1 weights carry log2(e) (acc = u = v log2 e) and the packed fc2
-                // weights ln 2, so the kernel needs h' = ELU(v) log2(e) = u for u > 0, L = log2(e) (2^u - 1) otherwise.  u <= L
-                // everywhere (convexity) and L <= 0 exactly when u <= 0, so h' is the median of (u, L, 0): 3 instructions per
-                // hidden activation (exp, fma, med3) instead of multiply, exp, add, compare, select.
                 float e[16];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const float u = acc[i];
-                    const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                    e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                }
+                elu_tile(acc, e);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     const int u = 2 * tI + s2;
@@ -410,24 +430,10 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
             }
         }
 
-        // ---- store the own rows (un-shift = the same index map) ----
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const f32x4 v = {res[4 * a], res[4 * a + 1], res[4 * a + 2], res[4 * a + 3]};
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, tokoff, 32 * a, 0);
-        }
+        store_rows24(ors, tokoff, res);
     }
 
-    // ---- L2 warm-up of the next block's packed weights (cold since the previous forward; see kernels_window.hip) ----
-    if (args.warm[0]) {
-        const int nsl = max(1, (int)gridDim.x / 8), sl = ((int)blockIdx.x / 8) % nsl;
-        const int lines = (args.warm_bytes + 127) / 128;
-        const int per = (lines + nsl - 1) / nsl, l0 = sl * per, l1 = min(lines, l0 + per);
-        unsigned acc = 0;
-        for (int s2 = 0; s2 < 2; ++s2)
-            for (int l = l0 + tid; l < l1; l += 256) acc ^= *reinterpret_cast<const unsigned*>(args.warm[s2] + (size_t)l * 128);
-        if (acc == 0x9e3779b9u && args.B < 0) args.out[0][0] = 0.f;   // never true: keeps the loads alive
-    }
+    if (args.warm[0]) warm_next_block<256>(args, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -438,14 +444,10 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
 // four —, Q fragments stay in registers, K / V^T images of all 256 keys go to LDS (64 KB for both streams; two workgroups
 // per CU).  One barrier.  Phase B, per tile: attention with an online softmax over four chunks of 64 keys, then projection,
 // LN2, MLP and the store exactly as in window24_kernel.  A second barrier frees the images for the next window.
-//
-// Online softmax in this layout: a chunk is the 8x8 kernel's whole attention (S^T with the bias tile as C operand, row maximum,
-// S^T again with -max on the spare k slot, exp2, V^T.P^T with the constant-one channel), followed by o = o * 2^(m_old - m_new)
-// + t on the four accumulator rows of the head.  The shift that enters the second S^T pass is -max ROUNDED TO f16, so the
-// running maximum is kept as that rounded value: the rescale factor then matches what earlier chunks were shifted by.
+// Online softmax over the chunks: attention24<true>.
 // Shift masks stay structural: the row seam (window row 8) separates key tiles 0..3 from 4..7 — a masked chunk is skipped —,
 // the column seam (column 8) is bit 2 of the accumulator register index against bit 3 of the lane's query column: -inf added
-// to those bias registers of the chunk's two tiles.
+// to those bias registers of the chunk's two tiles (col_seam16).
 template <int HID>
 __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
     using G = G24<HID>;
@@ -489,14 +491,6 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
             ox = ox < ox - (unsigned)W ? ox : ox - (unsigned)W;
             return (unsigned)((((b * H + (int)oy) * W + (int)ox) * 24 + 4 * (lane_w >> 5)) * 4);
         };
-        auto load_rows = [&](f32x16& dstv, unsigned tokoff) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(irs, tokoff, 32 * a, 0));
-                dstv[4 * a] = v.x; dstv[4 * a + 1] = v.y; dstv[4 * a + 2] = v.z; dstv[4 * a + 3] = v.w;
-            }
-            dstv[12] = dstv[13] = dstv[14] = dstv[15] = 0.f;
-        };
 
         // ---- phase A: LN1 + Q/K/V of the wave's four tiles; the weight fragments are fetched once ----
         u32x4 qf[4][2];
@@ -510,7 +504,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
             for (int jj = 0; jj < 4; ++jj) {
                 const int j = 4 * pw + jj;
                 f32x16 x0;
-                load_rows(x0, tokoff_of(j));
+                load_rows24(irs, tokoff_of(j), x0);
                 u32x4 xh[2], xl[2];
                 layernorm_frags(x0, vec, G::V_LN1G, G::V_LN1B, xh, xl);
                 f32x16 acc = zero16;
@@ -570,129 +564,51 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e) bias[kt][q4 * 4 + e] = tb[e];
                         }
-                    if (colv) {   // key column (register bit 2) and query column (lane bit 3) on different sides of column 8
-                        const bool qhi = (r & 8) != 0;
-                        const float pen_lo = qhi ? -INFINITY : 0.f, pen_hi = qhi ? 0.f : -INFINITY;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const float pen = ((i >> 2) & 1) ? pen_hi : pen_lo;
-                            bias[0][i] += pen; bias[1][i] += pen;
-                        }
-                    }
+                    if (colv) col_seam16(bias, r);
                 }
-                const u32x4* kc = ksrc + (2 * c) * 2 * 64;
-                const u32x4* vc = vsrc + (4 * c) * 64;
-#pragma unroll
-                for (int h = 0; h < 8; ++h) {
-                    const int s = h >> 2, sub = (h >> 1) & 1;
-                    const bool keep = half1 == ((h & 1) != 0);
-                    const u32x4 ka0 = kc[(0 * 2 + s) * 64], ka1 = kc[(1 * 2 + s) * 64];
-                    u32x4 qm = {0u, 0u, 0u, 0u};
-                    qm[2 * sub] = keep ? qf[0][s][2 * sub] : 0u;
-                    qm[2 * sub + 1] = keep ? qf[0][s][2 * sub + 1] : 0u;
-                    f32x16 s0 = mfma_f16(ka0, qm, bias[0]);
-                    f32x16 s1 = mfma_f16(ka1, qm, bias[1]);
-                    float mx = max3f(s0[0], s0[1], s1[0]);
-                    mx = max3f(mx, s1[1], s0[2]);
-#pragma unroll
-                    for (int i = 3; i < 16; i += 2) mx = max3f(mx, s0[i], s0[i + 1 < 16 ? i + 1 : i]);
-#pragma unroll
-                    for (int i = 2; i < 16; i += 2) mx = max3f(mx, s1[i], s1[i + 1]);
-                    mx = max_halves(mx);
-                    const float mold = mrun[h >> 1];
-                    const f16 nm = (f16)(-__builtin_fmaxf(mold, mx));
-                    const float mnew = -(float)nm;                      // the shift the second pass really applies
-                    const float alpha = __builtin_amdgcn_exp2f(mold - mnew);   // first chunk: 2^-inf = 0
-                    mrun[h >> 1] = keep ? mnew : mold;
-                    const unsigned nmb = keep ? (unsigned)__builtin_bit_cast(unsigned short, nm) : 0u;
-                    qm[2 * sub + 1] |= nmb << 16;
-                    s0 = mfma_f16(ka0, qm, bias[0]);
-                    s1 = mfma_f16(ka1, qm, bias[1]);
-                    f32x16 t;
-#pragma unroll
-                    for (int ps = 0; ps < 4; ++ps) {
-                        float pe[8];
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) pe[e] = __builtin_amdgcn_exp2f((ps >> 1) ? s1[8 * (ps & 1) + e] : s0[8 * (ps & 1) + e]);
-                        const u32x4 pf = pack8_f16(pe);
-                        const u32x4 va = vc[ps * 64];
-                        t = mfma_f16(va, pf, ps == 0 ? zero16 : t);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const int i = 4 * (h >> 1) + e;
-                        o[i] = keep ? __builtin_fmaf(o[i], alpha, t[i]) : o[i];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                o = attention24<true>(ksrc + (2 * c) * 2 * 64, vsrc + (4 * c) * 64, qf[0], bias, half1, o, mrun);
             }
             // the next tile's Q fragments move up
 #pragma unroll
             for (int q = 0; q < 3; ++q) { qf[q][0] = qf[q + 1][0]; qf[q][1] = qf[q + 1][1]; }
 
-            // ---- normalise, output projection + bias + residual ----
+            // ---- normalise, output projection + bias + residual; LN2, MLP; store ----
             f32x16 res;
             SWF_WF_FENCE();
-            load_rows(res, tokoff);
-            {
-                float t[16];
+            load_rows24(irs, tokoff, res);
+            res = project24<G>(WF, o, res);
+            u32x4 xh[2], xl[2];
+            layernorm_frags(res, vec, G::V_LN2G, G::V_LN2B, xh, xl);
+            // (this loop stays written out in both kernels: as a shared helper it cost window24_kernel<96, *, WIN_BLOCK> VGPR spills)
 #pragma unroll
-                for (int a = 0; a < 4; ++a) {
-                    const float inv = __builtin_amdgcn_rcpf(o[4 * a + 3]);
-                    t[4 * a] = o[4 * a] * inv; t[4 * a + 1] = o[4 * a + 1] * inv; t[4 * a + 2] = o[4 * a + 2] * inv;
-                    t[4 * a + 3] = 1.0f;
-                }
-                u32x4 oh[2], ol[2];
-                split8(t, oh[0], ol[0]);
-                split8(t + 8, oh[1], ol[1]);
+            for (int tI = 0; tI < G::NT1; ++tI) {
                 SWF_WF_FENCE();
+                f32x16 acc = zero16;
 #pragma unroll
-                for (int s = 0; s < 2; ++s) res = mma3(WF(G::F_P + 2 * s), WF(G::F_P + 2 * s + 1), oh[s], ol[s], res);
-            }
-            // ---- LN2, MLP ----
-            {
-                u32x4 xh[2], xl[2];
-                layernorm_frags(res, vec, G::V_LN2G, G::V_LN2B, xh, xl);
+                for (int s = 0; s < 2; ++s)
+                    acc = mma3(WF(G::F_W1 + 4 * tI + 2 * s), WF(G::F_W1 + 4 * tI + 2 * s + 1), xh[s], xl[s], acc);
+                float e[16];
+                elu_tile(acc, e);
 #pragma unroll
-                for (int tI = 0; tI < G::NT1; ++tI) {
-                    SWF_WF_FENCE();
-                    f32x16 acc = zero16;
-#pragma unroll
-                    for (int s = 0; s < 2; ++s)
-                        acc = mma3(WF(G::F_W1 + 4 * tI + 2 * s), WF(G::F_W1 + 4 * tI + 2 * s + 1), xh[s], xl[s], acc);
-                    float e[16];
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) {
-                        const float u = acc[i];
-                        const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                        e[i] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                    }
-#pragma unroll
-                    for (int s2 = 0; s2 < 2; ++s2) {
-                        const int u = 2 * tI + s2;
-                        if (u < G::KU) {
-                            u32x4 hh, hl;
-                            split8(e + 8 * s2, hh, hl);
-                            SWF_WF_FENCE();
-                            res = mma3(WF(G::F_W2 + 2 * u), WF(G::F_W2 + 2 * u + 1), hh, hl, res);
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                if constexpr (!G::ONES_H) {
-#pragma unroll
-                    for (int a = 0; a < 3; ++a) {
-                        const float4 b2 = *reinterpret_cast<const float4*>(vec + G::V_B2 + 4 * a);
-                        res[4 * a] += b2.x; res[4 * a + 1] += b2.y; res[4 * a + 2] += b2.z; res[4 * a + 3] += b2.w;
+                for (int s2 = 0; s2 < 2; ++s2) {
+                    const int u = 2 * tI + s2;
+                    if (u < G::KU) {
+                        u32x4 hh, hl;
+                        split8(e + 8 * s2, hh, hl);
+                        SWF_WF_FENCE();
+                        res = mma3(WF(G::F_W2 + 2 * u), WF(G::F_W2 + 2 * u + 1), hh, hl, res);
                     }
                 }
+                __builtin_amdgcn_sched_barrier(0);
             }
+            if constexpr (!G::ONES_H) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const f32x4 v = {res[4 * a], res[4 * a + 1], res[4 * a + 2], res[4 * a + 3]};
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, tokoff, 32 * a, 0);
+                for (int a = 0; a < 3; ++a) {
+                    const float4 b2 = *reinterpret_cast<const float4*>(vec + G::V_B2 + 4 * a);
+                    res[4 * a] += b2.x; res[4 * a + 1] += b2.y; res[4 * a + 2] += b2.z; res[4 * a + 3] += b2.w;
+                }
             }
+            store_rows24(ors, tokoff, res);
         }
         __syncthreads();   // every wave is done with the K / V^T images: the next window may overwrite them
     }

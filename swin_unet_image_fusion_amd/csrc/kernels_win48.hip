@@ -97,11 +97,15 @@ __device__ __forceinline__ void layernorm48(const f32x16& x0, const f32x16& x1, 
 // qf[tile][k-step]: the wave's own Q fragments; bias: relative-position bias of (stream, query block), with -inf where the shift
 // mask applies (the reference assigns -1e10 to those scores: probability exactly 0).  Returns the two O^T tiles: registers 4q..4q+3 of tile T = head 4T+q:
 // lane half 0 channels 0..3, lane half 1 channels 4, 5, the softmax denominator, 0.
+// ONLINE (16x16 windows): the 64 keys are one chunk of a window's 256 — o is not cleared but rescaled, o = o * 2^(m_old - m_new) + t,
+// with the running maximum mrun[head] kept as the f16 value the second S^T pass subtracts; VSTEPS = pv-steps per V^T tile of the image.
+// (Signature: o stays the array reference this function always took — unlike attention24, whose single tile goes by value; mrun is
+// a plain pointer, unused when !ONLINE.)
+template <bool ONLINE, int VSTEPS = 4>
 __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[2][2], const f32x16 (&bias)[2],
-                                            bool half1, f32x16 (&o)[2]) {
+                                            bool half1, f32x16 (&o)[2], float* mrun = nullptr) {
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    o[0] = zero16;
-    o[1] = zero16;
+    if constexpr (!ONLINE) { o[0] = zero16; o[1] = zero16; }
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
         const int T = h >> 2, hq = h & 3, sp = hq >> 1, sub = hq & 1;
@@ -128,10 +132,16 @@ __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc
         mx = max_halves(mx);
         // Pass 2: S - max on the matrix pipe — the head's spare row 7 (lane half 1, element 4*sub+3) is 1 in K and -max (f16)
         // in Q — then P = exp2(.) in f16 and O^T += V^T . P^T, again one key tile (two pv-steps of 16 keys) at a time
-        {
-            const f16 nm = (f16)(-mx);
-            qm[2 * sub + 1] |= half1 ? ((unsigned)__builtin_bit_cast(unsigned short, nm) << 16) : 0u;
+        f16 nm = (f16)(-mx);
+        float alpha = 0.f;
+        if constexpr (ONLINE) {
+            const float mold = mrun[h];
+            nm = (f16)(-__builtin_fmaxf(mold, mx));
+            const float mnew = -(float)nm;   // the shift the second pass really applies
+            alpha = __builtin_amdgcn_exp2f(mold - mnew);
+            mrun[h] = mnew;
         }
+        qm[2 * sub + 1] |= half1 ? ((unsigned)__builtin_bit_cast(unsigned short, nm) << 16) : 0u;
         f32x16 t;
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
@@ -142,13 +152,13 @@ __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc
 #pragma unroll
                 for (int j = 0; j < 8; ++j) p[j] = __builtin_amdgcn_exp2f(sc[8 * s2 + j]);
                 const u32x4 pf = pack8_f16(p);
-                const u32x4 va = vsrc[(T * 4 + 2 * kt + s2) * 64];
+                const u32x4 va = vsrc[(T * VSTEPS + 2 * kt + s2) * 64];
                 t = mfma_f16(va, pf, (kt == 0 && s2 == 0) ? zero16 : t);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[T][4 * hq + j] = t[4 * hq + j];
+        for (int j = 0; j < 4; ++j) o[T][4 * hq + j] = ONLINE ? __builtin_fmaf(o[T][4 * hq + j], alpha, t[4 * hq + j]) : t[4 * hq + j];
         __builtin_amdgcn_sched_barrier(0);   // one head at a time
     }
 }
@@ -291,13 +301,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
         }
         // the bias tile of (stream, query block) is requested ahead of the barrier: its L2 round trip runs under the wait
         f32x16 bias[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, (int)G::p_bias + ((__builtin_amdgcn_readfirstlane(qb) * 2 + kt) * 4 + a) * 1024, 0));
-                bias[kt][4 * a] = v.x; bias[kt][4 * a + 1] = v.y; bias[kt][4 * a + 2] = v.z; bias[kt][4 * a + 3] = v.w;
-            }
+        load_bias_tiles(wrs, loff, (int)G::p_bias, __builtin_amdgcn_readfirstlane(qb) * 2, bias);
         __syncthreads();   // K / V^T images of both streams complete
         if (RAW && ws == 1) continue;   // RAW: the key / value stream is done with this window
 
@@ -313,7 +317,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
 #pragma unroll
                 for (int i = 0; i < 16; ++i) { bias[0][i] += pen0; bias[1][i] += pen1; }
             }
-            attention48(ksrc, vsrc, qf, bias, half1, o);
+            attention48<false>(ksrc, vsrc, qf, bias, half1, o);
         }
 
         // ---- normalise (denominator: lane half 1, register 4q+2), output projection + bias + residual ----
@@ -391,17 +395,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
 #pragma unroll
                 for (int s = 0; s < 3; ++s) acc = mma3(w[2 * s], w[2 * s + 1], xh[s], xl[s], acc);
                 float e[16];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 b1 = *reinterpret_cast<const float4*>(vec + G::V_B1 + 16 * tI + 4 * g);
-                    const float bb[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // ELU in exp2 units: median of (u, log2 e (2^u - 1), 0)
-                        const float u = acc[4 * g + j] + bb[j];
-                        const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                        e[4 * g + j] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                    }
-                }
+                elu_tile(acc, vec + G::V_B1 + 16 * tI, e);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     u32x4 hh, hl;
@@ -429,15 +423,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
     }
 
     // ---- L2 warm-up of the next block's packed weights (see kernels_window.hip) ----
-    if (args.warm[0]) {
-        const int nsl = max(1, (int)gridDim.x / 8), sl = ((int)blockIdx.x / 8) % nsl;
-        const int lines = (args.warm_bytes + 127) / 128;
-        const int per = (lines + nsl - 1) / nsl, l0 = sl * per, l1 = min(lines, l0 + per);
-        unsigned acc = 0;
-        for (int s2 = 0; s2 < 2; ++s2)
-            for (int l = l0 + tid; l < l1; l += 256) acc ^= *reinterpret_cast<const unsigned*>(args.warm[s2] + (size_t)l * 128);
-        if (acc == 0x9e3779b9u && args.B < 0) args.out[0][0] = 0.f;   // never true: keeps the loads alive
-    }
+    if (args.warm[0]) warm_next_block<256>(args, tid);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -586,70 +572,11 @@ __global__ __launch_bounds__(256, 2) void window48w16_kernel(WinArgs args) {
                 f32x16 bias[2];
                 {
                     const int d0 = __builtin_amdgcn_readfirstlane(2 * c - j + 7);
-#pragma unroll
-                    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, (int)G::p_bias + ((d0 + kt) * 4 + a) * 1024, 0));
-                            bias[kt][4 * a] = v.x; bias[kt][4 * a + 1] = v.y; bias[kt][4 * a + 2] = v.z; bias[kt][4 * a + 3] = v.w;
-                        }
-                    if (colv) {
-                        const bool qhi = (r & 8) != 0;
-                        const float pen_lo = qhi ? -INFINITY : 0.f, pen_hi = qhi ? 0.f : -INFINITY;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const float pen = ((i >> 2) & 1) ? pen_hi : pen_lo;
-                            bias[0][i] += pen; bias[1][i] += pen;
-                        }
-                    }
+                    load_bias_tiles(wrs, loff, (int)G::p_bias, d0, bias);
+                    if (colv) col_seam16(bias, r);
                 }
-                const u32x4* kc = kimg + (2 * c) * 4 * 64 + lane;   // key tiles 2c, 2c + 1: 4 fragments each
-#pragma unroll
-                for (int h = 0; h < 8; ++h) {
-                    const int T = h >> 2, hq = h & 3, sp = hq >> 1, sub = hq & 1;
-                    const u32x4 ka0 = kc[((0 * 2 + T) * 2 + sp) * 64], ka1 = kc[((1 * 2 + T) * 2 + sp) * 64];
-                    u32x4 qm = {0u, 0u, 0u, 0u};
-                    qm[2 * sub] = qf[0][T][sp][2 * sub];
-                    qm[2 * sub + 1] = qf[0][T][sp][2 * sub + 1];
-                    float mx;
-                    {
-                        f32x16 s0 = mfma_f16(ka0, qm, bias[0]);
-                        mx = max3f(s0[0], s0[1], s0[2]);
-#pragma unroll
-                        for (int i = 3; i < 15; i += 2) mx = max3f(mx, s0[i], s0[i + 1]);
-                        mx = __builtin_fmaxf(mx, s0[15]);
-                    }
-                    {
-                        f32x16 s1 = mfma_f16(ka1, qm, bias[1]);
-#pragma unroll
-                        for (int i = 0; i < 16; i += 2) mx = max3f(mx, s1[i], s1[i + 1]);
-                    }
-                    mx = max_halves(mx);
-                    const float mold = mrun[h];
-                    const f16 nm = (f16)(-__builtin_fmaxf(mold, mx));
-                    const float mnew = -(float)nm;   // the shift the second pass really applies
-                    const float alpha = __builtin_amdgcn_exp2f(mold - mnew);
-                    mrun[h] = mnew;
-                    qm[2 * sub + 1] |= half1 ? ((unsigned)__builtin_bit_cast(unsigned short, nm) << 16) : 0u;
-                    f32x16 t;
-#pragma unroll
-                    for (int kt = 0; kt < 2; ++kt) {
-                        f32x16 sc = mfma_f16(kt ? ka1 : ka0, qm, bias[kt]);
-#pragma unroll
-                        for (int s2 = 0; s2 < 2; ++s2) {
-                            float pe[8];
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) pe[e] = __builtin_amdgcn_exp2f(sc[8 * s2 + e]);
-                            const u32x4 pf = pack8_f16(pe);
-                            const u32x4 va = vimg[(T * 16 + 4 * c + 2 * kt + s2) * 64 + lane];
-                            t = mfma_f16(va, pf, (kt == 0 && s2 == 0) ? zero16 : t);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) o[T][4 * hq + e] = __builtin_fmaf(o[T][4 * hq + e], alpha, t[4 * hq + e]);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
+                // key tiles 2c, 2c + 1: 4 K fragments each, 4 pv-steps of each V^T tile
+                attention48<true, 16>(kimg + (2 * c) * 4 * 64 + lane, vimg + (4 * c) * 64 + lane, qf[0], bias, half1, o, mrun);
             }
             // the second tile's Q fragments move up
 #pragma unroll
@@ -709,17 +636,7 @@ __global__ __launch_bounds__(256, 2) void window48w16_kernel(WinArgs args) {
 #pragma unroll
                     for (int s2 = 0; s2 < 3; ++s2) acc = mma3(w[2 * s2], w[2 * s2 + 1], xh[s2], xl[s2], acc);
                     float e[16];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const float4 b1 = *reinterpret_cast<const float4*>(vec + G::V_B1 + 16 * tI + 4 * g);
-                        const float bb[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                        for (int jx = 0; jx < 4; ++jx) {
-                            const float u = acc[4 * g + jx] + bb[jx];
-                            const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                            e[4 * g + jx] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                        }
-                    }
+                    elu_tile(acc, vec + G::V_B1 + 16 * tI, e);
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
                         u32x4 hh, hl;

@@ -98,6 +98,8 @@ __device__ __forceinline__ void raw96(const f32x16 (&x)[3], u32x4 (&xh)[6], u32x
 // the wave's Q fragments (k-step = head within the tile); bias: relative-position bias of (stream, query block) with -inf where the
 // shift mask applies.  Returns the four O^T tiles: registers 8*sp .. 8*sp + 7 of tile T = head 2T + sp (lane half 1: register
 // 8*sp + 4 is the softmax denominator).
+// (window96w16_kernel keeps its own copy of this head loop with the online-softmax rescale: as attention96<ONLINE> it cost that
+// kernel two SGPR spills, kernels_win48.hip's attention48<ONLINE> is the shared form.)
 // (NH < 8: the NH heads whose images start at ksrc / vsrc — window96x8_kernel passes pointers advanced to its first tile.)
 template <int NH = 8>
 __device__ __forceinline__ void attention96(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[NH / 2][2], const f32x16 (&bias)[2],
@@ -292,13 +294,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
         }
         // the bias tile of (stream, query block) is requested ahead of the barrier: its L2 round trip runs under the wait
         f32x16 bias[2];
-#pragma unroll
-        for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-            for (int a = 0; a < 4; ++a) {
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, (int)G::p_bias + ((__builtin_amdgcn_readfirstlane(qb) * 2 + kt) * 4 + a) * 1024, 0));
-                bias[kt][4 * a] = v.x; bias[kt][4 * a + 1] = v.y; bias[kt][4 * a + 2] = v.z; bias[kt][4 * a + 3] = v.w;
-            }
+        load_bias_tiles(wrs, loff, (int)G::p_bias, __builtin_amdgcn_readfirstlane(qb) * 2, bias);
         __syncthreads();   // K / V^T images of both streams complete
         if (RAW && ws == 1) continue;   // RAW: the key / value stream is done with this window
 
@@ -392,17 +388,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
                 if (tI + 1 < G::NT1) req1(tI + 1);   // the next tile's fc1 fragments: in flight during the ELU and fc2
                 SWF_WF_FENCE();
                 float e[16];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 b1 = *reinterpret_cast<const float4*>(vec + G::V_B1 + 16 * tI + 4 * g);
-                    const float bb[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {   // ELU in exp2 units: median of (u, log2 e (2^u - 1), 0)
-                        const float u = acc[4 * g + j] + bb[j];
-                        const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                        e[4 * g + j] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                    }
-                }
+                elu_tile(acc, vec + G::V_B1 + 16 * tI, e);
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
                     u32x4 hh, hl;
@@ -427,15 +413,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
     }
 
     // ---- L2 warm-up of the next block's packed weights (see kernels_window.hip) ----
-    if (args.warm[0]) {
-        const int nsl = max(1, (int)gridDim.x / 8), sl = ((int)blockIdx.x / 8) % nsl;
-        const int lines = (args.warm_bytes + 127) / 128;
-        const int per = (lines + nsl - 1) / nsl, l0 = sl * per, l1 = min(lines, l0 + per);
-        unsigned acc = 0;
-        for (int s2 = 0; s2 < 2; ++s2)
-            for (int l = l0 + tid; l < l1; l += 256) acc ^= *reinterpret_cast<const unsigned*>(args.warm[s2] + (size_t)l * 128);
-        if (acc == 0x9e3779b9u && args.B < 0) args.out[0][0] = 0.f;   // never true: keeps the loads alive
-    }
+    if (args.warm[0]) warm_next_block<256>(args, tid);
 }
 
 
@@ -458,6 +436,8 @@ __device__ unsigned long long w96_probe[16];
 #define W96_STAMP(i) do { } while (0)
 #endif
 
+// (This kernel keeps its own copies of the bias-tile load, the ELU tile and the warm-up tail: with the shared helpers of win_frag.h
+// two of its four block variants measured 1-2 % slower than before, beyond the run-to-run spread.)
 template <int HID, int WS>
 __global__ __launch_bounds__(512) void window96x8_kernel(WinArgs args) {
     using G = G96<HID>;
@@ -908,22 +888,8 @@ __global__ __launch_bounds__(256, 1) void window96w16_kernel(WinArgs args) {
                 f32x16 bias[2];
                 {
                     const int d0 = __builtin_amdgcn_readfirstlane(2 * c - j + 7);
-#pragma unroll
-                    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-                        for (int a = 0; a < 4; ++a) {
-                            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, (int)G::p_bias + ((d0 + kt) * 4 + a) * 1024, 0));
-                            bias[kt][4 * a] = v.x; bias[kt][4 * a + 1] = v.y; bias[kt][4 * a + 2] = v.z; bias[kt][4 * a + 3] = v.w;
-                        }
-                    if (colv) {
-                        const bool qhi = (r & 8) != 0;
-                        const float pen_lo = qhi ? -INFINITY : 0.f, pen_hi = qhi ? 0.f : -INFINITY;
-#pragma unroll
-                        for (int i = 0; i < 16; ++i) {
-                            const float pen = ((i >> 2) & 1) ? pen_hi : pen_lo;
-                            bias[0][i] += pen; bias[1][i] += pen;
-                        }
-                    }
+                    load_bias_tiles(wrs, loff, (int)G::p_bias, d0, bias);
+                    if (colv) col_seam16(bias, r);
                 }
                 const u32x4* kc = kimg + (2 * c) * 8 * 64 + lane;   // key tiles 2c, 2c + 1: 8 fragments each
 #pragma unroll
@@ -1038,17 +1004,7 @@ __global__ __launch_bounds__(256, 1) void window96w16_kernel(WinArgs args) {
                     if (tI + 1 < G::NT1) req1(tI + 1);
                     SWF_WF_FENCE();
                     float e[16];
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        const float4 b1 = *reinterpret_cast<const float4*>(vec + G::V_B1 + 16 * tI + 4 * g);
-                        const float bb[4] = {b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                        for (int jx = 0; jx < 4; ++jx) {
-                            const float u = acc[4 * g + jx] + bb[jx];
-                            const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
-                            e[4 * g + jx] = __builtin_amdgcn_fmed3f(u, L, 0.f);
-                        }
-                    }
+                    elu_tile(acc, vec + G::V_B1 + 16 * tI, e);
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
                         u32x4 hh, hl;

@@ -128,6 +128,67 @@ __device__ __forceinline__ void fill_vectors(float* lvec, const char* vec0, cons
     }
 }
 
+// ---- block stages that are the same at every level of the register-resident block kernels (kernels_win24 / 48 / 96.hip) ----
+
+// One hidden tile of the MLP: ELU(alpha = 1) in exp2 units.  The packed fc1 weights carry log2(e) (acc = u = v log2 e) and the
+// packed fc2 weights ln 2, so the kernel needs h' = ELU(v) log2(e) = u for u > 0, L = log2(e) (2^u - 1) otherwise.  u <= L
+// everywhere (convexity) and L <= 0 exactly when u <= 0, so h' is the median of (u, L, 0): 3 instructions per hidden
+// activation (exp, fma, med3) instead of multiply, exp, add, compare, select.
+__device__ __forceinline__ float elu_exp2(float u) {
+    const float L = __builtin_fmaf(__builtin_amdgcn_exp2f(u), kLog2e, -kLog2e);
+    return __builtin_amdgcn_fmed3f(u, L, 0.f);
+}
+__device__ __forceinline__ void elu_tile(const f32x16& acc, float (&e)[16]) {   // level 0: the fc1 bias rides on a k slot
+#pragma unroll
+    for (int i = 0; i < 16; ++i) e[i] = elu_exp2(acc[i]);
+}
+__device__ __forceinline__ void elu_tile(const f32x16& acc, const float* b1, float (&e)[16]) {   // b1: the tile's 16 fc1 biases of this lane half
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const float4 b = *reinterpret_cast<const float4*>(b1 + 4 * g);
+        const float bb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) e[4 * g + j] = elu_exp2(acc[4 * g + j] + bb[j]);
+    }
+}
+
+// Column seam of a shifted 16x16 window (last window column), on the two bias tiles of a 64-key chunk: key column (register
+// bit 2) and query column (bit 3 of r = lane & 31) on different sides of column 8 -> -inf
+__device__ __forceinline__ void col_seam16(f32x16 (&bias)[2], int r) {
+    const bool qhi = (r & 8) != 0;
+    const float pen_lo = qhi ? -INFINITY : 0.f, pen_hi = qhi ? 0.f : -INFINITY;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const float pen = ((i >> 2) & 1) ? pen_hi : pen_lo;
+        bias[0][i] += pen; bias[1][i] += pen;
+    }
+}
+
+// Two consecutive S^T bias tiles of the [tile][reg/4 4][lane 64][4] fp32 section (levels 1 and 2) that starts at byte p_bias
+// of the packed image behind wrs; tile0 is wave-uniform, loff = lane * 16
+__device__ __forceinline__ void load_bias_tiles(const __amdgpu_buffer_rsrc_t& wrs, unsigned loff, int p_bias, int tile0, f32x16 (&bias)[2]) {
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, p_bias + ((tile0 + kt) * 4 + a) * 1024, 0));
+            bias[kt][4 * a] = v.x; bias[kt][4 * a + 1] = v.y; bias[kt][4 * a + 2] = v.z; bias[kt][4 * a + 3] = v.w;
+        }
+}
+
+// Tail of a block kernel: L2 warm-up of the next block's packed weights (cold since the previous forward; see
+// kernels_window.hip), called when args.warm[0] is set.  Args = WinArgs (warm, warm_bytes; B and out only keep the loads alive).
+template <int NTHREADS, class Args>
+__device__ __forceinline__ void warm_next_block(const Args& args, int tid) {
+    const int nsl = max(1, (int)gridDim.x / 8), sl = ((int)blockIdx.x / 8) % nsl;
+    const int lines = (args.warm_bytes + 127) / 128;
+    const int per = (lines + nsl - 1) / nsl, l0 = sl * per, l1 = min(lines, l0 + per);
+    unsigned acc = 0;
+    for (int s2 = 0; s2 < 2; ++s2)
+        for (int l = l0 + tid; l < l1; l += NTHREADS) acc ^= *reinterpret_cast<const unsigned*>(args.warm[s2] + (size_t)l * 128);
+    if (acc == 0x9e3779b9u && args.B < 0) args.out[0][0] = 0.f;   // never true: keeps the loads alive
+}
+
 }  // namespace wf
 }  // namespace swf
 

@@ -631,6 +631,7 @@ _WIDE = [  # C, heads, d, hidden, (B,H,W), shift, cross
     (48, 8, 6, 96, (1, 24, 16), True, False),      # decoder width (hidden = in_dims * 4)
     (96, 8, 12, 384, (1, 16, 16), True, True),
     (96, 8, 12, 192, (2, 8, 16), False, True),
+    (24, 8, 3, 4, (1, 16, 16), True, True),        # level-0 decoder width: window24_kernel<4, 8> as a single block
     # deep-level fast path (kernels_deep / kernels_mlp): split-bf16 plane GEMMs, MFMA attention core, fused LN2+MLP kernel
     (192, 8, 24, 768, (1, 8, 8), True, True),
     (384, 8, 48, 1536, (2, 8, 8), True, False),
@@ -701,6 +702,10 @@ _WIN7 = [  # 7x7 windows (the reference's default, A000_CONFIG.py:55) at every l
     (48, 8, 6, 96, (1, 21, 14), False, False),
     (96, 8, 12, 384, (1, 14, 14), True, True),
     (96, 8, 12, 192, (2, 7, 14), True, False),
+    (24, 8, 3, 4, (1, 14, 14), True, True),         # level-0 decoder width: window24_kernel<4, 7>
+    # more than 16 windows per map: the four-wave window96_kernel<HID, 7> (smaller maps run window96x8_kernel)
+    (96, 8, 12, 384, (1, 35, 35), True, False),
+    (96, 8, 12, 192, (1, 35, 35), True, True),
     (192, 8, 24, 768, (2, 14, 14), True, True),
     (192, 8, 24, 384, (1, 7, 7), False, True),
     (384, 8, 48, 1536, (2, 7, 7), True, True),      # one window per map: the shift mask covers most of the score tile
