@@ -263,6 +263,42 @@ int swf_patch_unmerge_fwd(const swf_patch_params* p, const float* in, const floa
 size_t swf_patch_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
                                  int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, int32_t encoder);
 
+/* The pair of patch layers of one stage (both modality streams) with the arithmetic mode as an argument.  SWF_PREC_FP32 is
+ * swf_patch_merge_fwd / swf_patch_unmerge_fwd per stream.  SWF_PREC_FAST packs the weight images this shape admits into the workspace
+ * (per call: these entries are for tests and tools, not the hot path) and then takes the route the whole-model forward takes for the
+ * layer, through the same dispatch; *route (host int32, may be NULL) says which kernel that was, so that a caller can tell the kernel it
+ * means to run from a fallback.  py / y_* NULL = one stream (size queries: dual = 0).  Geometry arguments as the single-stream entries above. */
+typedef enum swf_patch_route {
+    SWF_PATCH_ROUTE_GENERIC = 0,      /* gather / crop, GEMM (fast tier: split-bf16, split-K for deep K), LayerNorm, scatter as separate launches */
+    SWF_PATCH_ROUTE_FUSED = 1,        /* one launch, conv operands staged through LDS */
+    SWF_PATCH_ROUTE_RR = 2,           /* one launch, register-resident (two streams, levels 0-2) */
+    SWF_PATCH_ROUTE_DEEP_ROW = 3,     /* deep level, whole rows: one launch */
+    SWF_PATCH_ROUTE_DEEP_SLICED = 4,  /* deep level, conv over column slices, then the finishing launch */
+    SWF_PATCH_ROUTE_LN1 = 0x100       /* flag, OR-ed in: the LN1 planes asked for were written (absent: the route has none, buffers untouched) */
+} swf_patch_route;
+/* Optional: the LN1 of the block that runs behind the layer, as the deep-level kernels leave it for that block: LayerNorm(out) with
+ * `ln` as split-bf16 planes hi / lo, caller-owned uint16 [rows][Cout], rows = the pixels of `out`; value = float(hi) + float(lo).
+ * Written by the encoder whole-row route and by both column-sliced routes (SWF_PATCH_ROUTE_LN1 in *route).  For every stream or none. */
+typedef struct swf_patch_ln1 { swf_norm ln; uint16_t* hi; uint16_t* lo; } swf_patch_ln1;
+size_t swf_patch_merge_prec_workspace_bytes(int32_t precision, int32_t dual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                                            int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w);
+int swf_patch_merge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                             const float* x_in, const float* y_in, float* x_out, float* y_out,
+                             int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                             int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w,
+                             const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
+                             void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* Unlike swf_patch_workspace_bytes this query knows the crop and the output size. */
+size_t swf_patch_unmerge_prec_workspace_bytes(int32_t precision, int32_t dual, int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm,
+                                              int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout);
+int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                               const float* x_in, const float* y_in, const float* x_skip, const float* y_skip,
+                               float* x_out, float* y_out,
+                               int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout,
+                               int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout,
+                               const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
+                               void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- final fusion head (a013:126-152): cat -> conv kxk reflect -> BatchNorm2d(eval) -> ELU -> conv kxk reflect */
 typedef struct swf_head_params {
     const float* conv1_w; const float* conv1_b;   /* final_layer.0: [2][2][k][k], [2] */

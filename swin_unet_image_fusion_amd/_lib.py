@@ -56,6 +56,14 @@ class PatchParams(C.Structure):
     _fields_ = [("conv", Linear), ("ln", Norm)]
 
 
+class PatchLn1(C.Structure):    # swf_patch_ln1: the next block's LN1 and caller-owned uint16 planes
+    _fields_ = [("ln", Norm), ("hi", C.c_void_p), ("lo", C.c_void_p)]
+
+
+# swf_patch_route
+ROUTE_GENERIC, ROUTE_FUSED, ROUTE_RR, ROUTE_DEEP_ROW, ROUTE_DEEP_SLICED, ROUTE_LN1 = 0, 1, 2, 3, 4, 0x100
+
+
 class HeadParams(C.Structure):
     _fields_ = [("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("bn_gamma", C.c_void_p), ("bn_beta", C.c_void_p),
                 ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p)]
@@ -148,6 +156,12 @@ SIGNATURES = {
     "swf_merge_out_shape": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, P(_i32), P(_i32), P(_i32), P(_i32)]),
     "swf_patch_unmerge_fwd": (C.c_int, [P(PatchParams), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_patch_workspace_bytes": (_sz, [_i32] * 10),
+    "swf_patch_merge_prec_workspace_bytes": (_sz, [_i32] * 11),
+    "swf_patch_merge_fwd_prec": (C.c_int, [_i32, P(PatchParams), P(PatchParams), _vp, _vp, _vp, _vp] + [_i32] * 9
+                                 + [P(PatchLn1), P(PatchLn1), P(_i32), _vp, _sz, _vp]),
+    "swf_patch_unmerge_prec_workspace_bytes": (_sz, [_i32] * 13),
+    "swf_patch_unmerge_fwd_prec": (C.c_int, [_i32, P(PatchParams), P(PatchParams), _vp, _vp, _vp, _vp, _vp, _vp] + [_i32] * 11
+                                   + [P(PatchLn1), P(PatchLn1), P(_i32), _vp, _sz, _vp]),
     "swf_final_head_fwd": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_linear_fwd": (C.c_int, [P(Linear), _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "swf_mlp_workspace_bytes": (_sz, [_i32, _i64, _i32, _i32]),

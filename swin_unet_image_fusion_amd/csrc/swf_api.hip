@@ -562,6 +562,24 @@ static int merge_shapes(int H, int W, int mh, int mw, int wh, int ww, int* Hm, i
     return SWF_OK;
 }
 
+// Packed image of ONE stream of a patch layer for the fast-tier kernels that need one: the register-resident kernel's, or the deep-level
+// kernel's where that one does not cover the shape (0 bytes: neither covers it).  The model's pack and the stand-alone tier-selectable
+// entries (swf_patch_*_fwd_prec) size and write their images here.
+static size_t patch_image_bytes(int decoder, int Cin, int Cout, int mh, int mw) {
+    const size_t rr = patch_rr_packed_bytes(decoder, Cin, Cout, mh, mw);
+    return rr ? rr : deep_patch_packed_bytes(decoder, Cin, Cout, mh, mw);
+}
+static int pack_patch_image(int decoder, int Cin, int Cout, int mh, int mw, const swf_patch_params& p, void* dst, hipStream_t stream) {
+    if (patch_rr_packed_bytes(decoder, Cin, Cout, mh, mw))
+        return pack_patch_rr(decoder, Cin, Cout, mh, mw, p.conv.weight, p.conv.bias, p.ln.gamma, p.ln.beta, dst, stream);
+    return pack_deep_patch(decoder, Cin, Cout, mh, mw, p.conv.weight, dst, stream);
+}
+
+// What the two impls report to a caller that asks (swf_patch_*_fwd_prec): the route that ran (swf_patch_route), set in the branch
+// that runs it, and the LN1 planes that route wrote (nullptr: none).
+struct PatchTrace { int route; bf16_raw *ln_hi[2], *ln_lo[2]; };
+static void trace_route(PatchTrace* t, int route) { if (t) t->route = route; }
+
 // Deep-level patch kernels: the LN1 planes of the block that runs next on this workspace (`with_ln`; at its start: deep_ln1_planes), then,
 // for the column-sliced route, `row_floats` conv rows per stream (0: the whole-row route, which keeps its rows on chip).
 struct DeepPatchBufs { bf16_raw *ln_hi[2], *ln_lo[2]; float* zr[2]; };
@@ -604,7 +622,8 @@ static PatchBufs carve_unmerge_generic(Carver& ws, int nstream, int64_t N, int C
 static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const float* const* in, float* const* out,
                             int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww, void* workspace,
                             size_t workspace_bytes, hipStream_t stream, int fast = 0, const void* const* prr = nullptr,
-                            const swf_block_stream_params* const* first_blk = nullptr, bool* ln1_ready = nullptr) {
+                            const swf_block_stream_params* const* first_blk = nullptr, bool* ln1_ready = nullptr,
+                            PatchTrace* trace = nullptr) {
     // prr: per-stream packed images of the register-resident kernel (pack_patch_rr; the model path has them) or nullptr
     // first_blk / ln1_ready: the parameters of the deep-level block that runs next on this workspace; when the whole-row deep patch
     // kernel runs, it also leaves that block's LN1 planes (deep_ln1_planes) and sets *ln1_ready
@@ -626,7 +645,7 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
         }
         d.decoder = 0; d.B = B; d.H = H; d.W = W; d.Cin = Cin; d.mh = mh; d.mw = mw; d.Hm = Hm; d.Wm = Wm; d.Ho = Ho; d.Wo = Wo;
         d.K = K; d.N = Cout; d.Cout = Cout; d.M = N;
-        if (use_prr) return launch_patch_rr(d, prr, nstream, stream);
+        if (use_prr) { trace_route(trace, SWF_PATCH_ROUTE_RR); return launch_patch_rr(d, prr, nstream, stream); }
         if (use_dp) {
             // column slices: conv rows into the workspace, then LayerNorm + ELU (+ the next block's LN1) as a second launch; else whole rows
             const bool sliced = deep_patch_raw(0, Cin, Cout, mh, mw);
@@ -636,6 +655,7 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
             if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", wz.bytes());
             DeepPatchExtra ex{};
             const DeepPatchExtra* ln = deep_patch_ln(ex, b, with_ln ? first_blk : nullptr, nstream);
+            trace_route(trace, sliced ? SWF_PATCH_ROUTE_DEEP_SLICED : SWF_PATCH_ROUTE_DEEP_ROW);
             if (sliced) {
                 SWF_TRY(launch_deep_patch(d, prr, nstream, stream, b.zr));
                 SWF_TRY(launch_deep_patch_finish(d, b.zr, nstream, stream, ln));
@@ -643,10 +663,13 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
                 SWF_TRY(launch_deep_patch(d, prr, nstream, stream, nullptr, ln));
             }
             if (with_ln) *ln1_ready = true;
+            if (with_ln && trace) for (int s = 0; s < nstream; ++s) { trace->ln_hi[s] = b.ln_hi[s]; trace->ln_lo[s] = b.ln_lo[s]; }
             return SWF_OK;
         }
+        trace_route(trace, SWF_PATCH_ROUTE_FUSED);
         return launch_patch_fused(d, nstream, stream);
     }
+    trace_route(trace, SWF_PATCH_ROUTE_GENERIC);
     Carver ws(workspace, workspace_bytes);
     const PatchBufs bufs = carve_merge_generic(ws, nstream, N, K, Cout, fast);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-merge workspace too small (need %zu B)", ws.bytes());
@@ -665,21 +688,26 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
     return launch_layernorm(lb, nstream, N, Cout, 1, stream);
 }
 
+static int unmerge_shapes(int Hp, int Wp, int Hm, int Wm, int mh, int mw, int Hout, int Wout) {
+    if (Hm <= 0 || Wm <= 0 || Hm > Hp || Wm > Wp) return fail(SWF_ERR_BAD_SHAPE, "crop %dx%d of %dx%d", Hm, Wm, Hp, Wp);
+    if (Hout <= 0 || Wout <= 0 || Hout > Hm * mh || Wout > Wm * mw)
+        return fail(SWF_ERR_BAD_SHAPE, "output %dx%d larger than the unmerged map %dx%d", Hout, Wout, Hm * mh, Wm * mw);
+    return SWF_OK;
+}
+
 static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, const float* const* in,
                               const float* const* skip, float* const* out, int B, int Hp, int Wp, int Hm, int Wm, int Cin,
                               int Cout, int mh, int mw, int Hout, int Wout, void* workspace, size_t workspace_bytes,
                               hipStream_t stream, int fast = 0, const void* const* prr = nullptr, const char* warm = nullptr,
                               size_t warm_pb = 0, bool* warmed = nullptr, const swf_block_stream_params* const* next_blk = nullptr,
-                              bool* ln1_ready = nullptr) {
+                              bool* ln1_ready = nullptr, PatchTrace* trace = nullptr) {
     // next_blk / ln1_ready: the first block of the decoder stage that runs next (a deep-level stage on this workspace): the
     // column-sliced layer's second launch also leaves that block's LN1 planes (deep_ln1_planes over the output pixels)
     if (ln1_ready) *ln1_ready = false;
     // warm / warm_pb: packed images (x, then y at + warm_pb) of the block that runs next; the whole-row deep patch kernel touches them
     // at its end and sets *warmed (the caller otherwise spends a launch on it)
     if (warmed) *warmed = false;
-    if (Hm <= 0 || Wm <= 0 || Hm > Hp || Wm > Wp) return fail(SWF_ERR_BAD_SHAPE, "crop %dx%d of %dx%d", Hm, Wm, Hp, Wp);
-    if (Hout <= 0 || Wout <= 0 || Hout > Hm * mh || Wout > Wm * mw)
-        return fail(SWF_ERR_BAD_SHAPE, "output %dx%d larger than the unmerged map %dx%d", Hout, Wout, Hm * mh, Wm * mw);
+    SWF_TRY(unmerge_shapes(Hp, Wp, Hm, Wm, mh, mw, Hout, Wout));
     const int64_t N = (int64_t)B * Hm * Wm;
     const int Kz = mh * mw * Cout;
     const bool need_crop = (Hm != Hp) || (Wm != Wp);
@@ -696,27 +724,32 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
         }
         d.decoder = 1; d.B = B; d.H = Hp; d.W = Wp; d.Cin = Cin; d.mh = mh; d.mw = mw; d.Hm = Hm; d.Wm = Wm; d.Ho = Hout; d.Wo = Wout;
         d.K = Cin; d.N = Kz; d.Cout = Cout; d.M = N;
-        if (use_prr) return launch_patch_rr(d, prr, nstream, stream);
+        if (use_prr) { trace_route(trace, SWF_PATCH_ROUTE_RR); return launch_patch_rr(d, prr, nstream, stream); }
         if (use_dp && deep_patch_raw(1, Cin, Cout, mh, mw)) {   // conv over column slices, then LayerNorm + scatter + ELU (+ skip) (+ the next block's LN1)
             const bool with_ln = next_blk && ln1_ready && next_blk[0] && (nstream == 1 || next_blk[1]);
             Carver wz(workspace, workspace_bytes);
             const DeepPatchBufs b = carve_deep_patch(wz, nstream, with_ln, (int64_t)B * Hout * Wout, Cout, N * Kz);
             if (!wz.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", wz.bytes());
             DeepPatchExtra ex{};
+            trace_route(trace, SWF_PATCH_ROUTE_DEEP_SLICED);
             SWF_TRY(launch_deep_patch(d, prr, nstream, stream, b.zr));
             SWF_TRY(launch_deep_patch_finish(d, b.zr, nstream, stream, deep_patch_ln(ex, b, with_ln ? next_blk : nullptr, nstream)));
             if (with_ln) *ln1_ready = true;
+            if (with_ln && trace) for (int s = 0; s < nstream; ++s) { trace->ln_hi[s] = b.ln_hi[s]; trace->ln_lo[s] = b.ln_lo[s]; }
             return SWF_OK;
         }
         if (use_dp) {   // whole rows: no workspace
+            trace_route(trace, SWF_PATCH_ROUTE_DEEP_ROW);
             DeepPatchExtra ex{};
             if (warm && warm_pb && nstream == 2) { ex.warm[0] = warm; ex.warm[1] = warm + warm_pb; ex.warm_bytes = warm_pb; }
             SWF_TRY(launch_deep_patch(d, prr, nstream, stream, nullptr, ex.warm[0] ? &ex : nullptr));
             if (warmed && ex.warm[0]) *warmed = true;
             return SWF_OK;
         }
+        trace_route(trace, SWF_PATCH_ROUTE_FUSED);
         return launch_patch_fused(d, nstream, stream);
     }
+    trace_route(trace, SWF_PATCH_ROUTE_GENERIC);
     Carver ws(workspace, workspace_bytes);
     const PatchBufs bufs = carve_unmerge_generic(ws, nstream, N, Cin, Kz, need_crop, fast);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch-unmerge workspace too small (need %zu B)", ws.bytes());
@@ -1014,14 +1047,12 @@ static PackedPlan packed_plan(const swf_model_desc* d) {
         p.dec_on[j] = pb > 0; p.dec[j] = off; off += 8 * pb;
     }
     for (int s = 0; s < d->levels; ++s) {
-        p.penc_b[s] = patch_rr_packed_bytes(0, d->in_dims[s], d->out_dims[s], d->merge_h, d->merge_w);
-        if (!p.penc_b[s]) p.penc_b[s] = deep_patch_packed_bytes(0, d->in_dims[s], d->out_dims[s], d->merge_h, d->merge_w);
+        p.penc_b[s] = patch_image_bytes(0, d->in_dims[s], d->out_dims[s], d->merge_h, d->merge_w);
         p.penc[s] = off; off += 2 * p.penc_b[s];
     }
     for (int j = 0; j < d->levels; ++j) {
         const int lvl = d->levels - 1 - j;
-        p.pdec_b[j] = patch_rr_packed_bytes(1, d->out_dims[lvl], d->in_dims[lvl], d->merge_h, d->merge_w);
-        if (!p.pdec_b[j]) p.pdec_b[j] = deep_patch_packed_bytes(1, d->out_dims[lvl], d->in_dims[lvl], d->merge_h, d->merge_w);
+        p.pdec_b[j] = patch_image_bytes(1, d->out_dims[lvl], d->in_dims[lvl], d->merge_h, d->merge_w);
         p.pdec[j] = off; off += 2 * p.pdec_b[j];
     }
     p.total = off;
@@ -1506,6 +1537,138 @@ int swf_patch_unmerge_fwd(const swf_patch_params* p, const float* in, const floa
                               workspace, workspace_bytes, as_stream(stream));
 }
 
+// ---- the pair of patch layers of one stage with the arithmetic tier as an argument -------------------------------------------------
+// The fast tier's packed images (one per stream, where a kernel of this shape takes one), then the room of the impl behind the entry.
+struct PatchPrecBufs { void* packed[2]; void* inner; size_t inner_bytes; };
+static PatchPrecBufs carve_patch_prec(Carver& ws, int nstream, size_t image_bytes, size_t inner_bytes) {
+    PatchPrecBufs b{};
+    for (int s = 0; s < nstream && image_bytes; ++s) b.packed[s] = ws.floats((int64_t)(image_bytes / 4));
+    b.inner = ws.floats((int64_t)(inner_bytes / 4));
+    b.inner_bytes = inner_bytes;
+    return b;
+}
+
+static int check_patch_prec(const char* what, int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in,
+                            const float* y_in, float* x_out, float* y_out, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y,
+                            int B, int Cin, int Cout, int mh, int mw) {
+    if (precision != SWF_PREC_FP32 && precision != SWF_PREC_FAST) return fail(SWF_ERR_BAD_SHAPE, "%s: unknown precision %d", what, precision);
+    if (!px || !x_in || !x_out || !px->conv.weight || !px->ln.gamma || !px->ln.beta) return fail(SWF_ERR_NULL, "%s: NULL x-stream argument", what);
+    if (py && (!y_in || !y_out || !py->conv.weight || !py->ln.gamma || !py->ln.beta))
+        return fail(SWF_ERR_NULL, "%s: NULL y-stream argument with dual-path params", what);
+    if (ln1_y && !py) return fail(SWF_ERR_NULL, "%s: LN1 planes of a y stream that is not there", what);
+    if (ln1_x ? (py && !ln1_y) : ln1_y != nullptr) return fail(SWF_ERR_NULL, "%s: LN1 planes are asked for every stream or for none", what);
+    for (const swf_patch_ln1* l : {ln1_x, ln1_y})
+        if (l && (!l->ln.gamma || !l->ln.beta || !l->hi || !l->lo)) return fail(SWF_ERR_NULL, "%s: NULL pointer in swf_patch_ln1", what);
+    if (B <= 0 || Cin <= 0 || Cout <= 0 || mh <= 0 || mw <= 0) return fail(SWF_ERR_BAD_SHAPE, "%s: non-positive dims", what);
+    return SWF_OK;
+}
+
+// After the impl: the planes its route wrote go to the caller's buffers, and the route code says whether there were any.
+static int finish_patch_prec(const char* what, const PatchTrace& tr, const swf_patch_ln1* const* ln, int nstream, size_t plane_bytes,
+                             int32_t* route, hipStream_t stream) {
+    const bool planes = ln[0] && tr.ln_hi[0];
+    for (int s = 0; s < nstream && planes; ++s)
+        if (hipMemcpyAsync(ln[s]->hi, tr.ln_hi[s], plane_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
+            hipMemcpyAsync(ln[s]->lo, tr.ln_lo[s], plane_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+            return fail(SWF_ERR_HIP, "%s: copy of the LN1 planes failed", what);
+    if (route) *route = tr.route | (planes ? SWF_PATCH_ROUTE_LN1 : 0);
+    return SWF_OK;
+}
+
+static size_t merge_prec_ws(int32_t precision, int nstream, int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww) {
+    Carver m = Carver::measure();
+    carve_patch_prec(m, nstream, precision == SWF_PREC_FAST ? patch_image_bytes(0, Cin, Cout, mh, mw) : 0,
+                     merge_ws(nstream, B, H, W, Cin, Cout, mh, mw, wh, ww));
+    return m.bytes();
+}
+static size_t unmerge_prec_ws(int32_t precision, int nstream, int B, int Hp, int Wp, int Hm, int Wm, int Cin, int Cout, int mh, int mw,
+                              int Hout, int Wout) {
+    Carver m = Carver::measure();
+    carve_patch_prec(m, nstream, precision == SWF_PREC_FAST ? patch_image_bytes(1, Cin, Cout, mh, mw) : 0,
+                     unmerge_ws(nstream, B, Hp, Wp, Hm, Wm, Cin, Cout, mh, mw, Hout, Wout));
+    return m.bytes();
+}
+
+size_t swf_patch_merge_prec_workspace_bytes(int32_t precision, int32_t dual, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                                            int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w) {
+    int Hm, Wm, Ho, Wo;
+    if ((precision != SWF_PREC_FP32 && precision != SWF_PREC_FAST) || B <= 0 || Cin <= 0 || Cout <= 0 ||
+        merge_shapes(H, W, merge_h, merge_w, win_h, win_w, &Hm, &Wm, &Ho, &Wo) != SWF_OK)
+        return 0;
+    return merge_prec_ws(precision, dual ? 2 : 1, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w);
+}
+
+size_t swf_patch_unmerge_prec_workspace_bytes(int32_t precision, int32_t dual, int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm,
+                                              int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout) {
+    if ((precision != SWF_PREC_FP32 && precision != SWF_PREC_FAST) || B <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0 ||
+        unmerge_shapes(Hp, Wp, Hm, Wm, merge_h, merge_w, Hout, Wout) != SWF_OK)
+        return 0;
+    return unmerge_prec_ws(precision, dual ? 2 : 1, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout);
+}
+
+int swf_patch_merge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in, const float* y_in,
+                             float* x_out, float* y_out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h,
+                             int32_t merge_w, int32_t win_h, int32_t win_w, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y,
+                             int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream_) {
+    SWF_TRY(check_patch_prec("patch_merge_prec", precision, px, py, x_in, y_in, x_out, y_out, ln1_x, ln1_y, B, Cin, Cout, merge_h, merge_w));
+    int Hm, Wm, Ho, Wo;
+    SWF_TRY(merge_shapes(H, W, merge_h, merge_w, win_h, win_w, &Hm, &Wm, &Ho, &Wo));
+    const int nstream = py ? 2 : 1, fast = precision == SWF_PREC_FAST;
+    const size_t image = fast ? patch_image_bytes(0, Cin, Cout, merge_h, merge_w) : 0;
+    Carver ws(workspace, workspace_bytes);
+    const PatchPrecBufs bufs = carve_patch_prec(ws, nstream, image, merge_ws(nstream, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w));
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch_merge_prec: workspace too small (need %zu B)", ws.bytes());
+    hipStream_t stream = as_stream(stream_);
+    const swf_patch_params* pp[2] = {px, py};
+    const float* ins[2] = {x_in, y_in};
+    float* outs[2] = {x_out, y_out};
+    const swf_patch_ln1* ln[2] = {ln1_x, ln1_y};
+    swf_block_stream_params blk[2] = {};   // the block behind the layer: only its LN1 is read
+    const swf_block_stream_params* blkp[2] = {&blk[0], &blk[1]};
+    for (int s = 0; s < nstream; ++s) {
+        if (image) SWF_TRY(pack_patch_image(0, Cin, Cout, merge_h, merge_w, *pp[s], bufs.packed[s], stream));
+        if (ln[0]) blk[s].ln1 = ln[s]->ln;
+    }
+    bool ln1_ready = false;
+    PatchTrace tr{};
+    SWF_TRY(patch_merge_impl(pp, nstream, ins, outs, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w, bufs.inner, bufs.inner_bytes, stream,
+                             fast, image ? bufs.packed : nullptr, ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr));
+    return finish_patch_prec("patch_merge_prec", tr, ln, nstream, (size_t)B * Ho * Wo * Cout * sizeof(bf16_raw), route, stream);
+}
+
+int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in,
+                               const float* y_in, const float* x_skip, const float* y_skip, float* x_out, float* y_out, int32_t B, int32_t Hp,
+                               int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t Hout,
+                               int32_t Wout, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route, void* workspace,
+                               size_t workspace_bytes, swf_stream_t stream_) {
+    SWF_TRY(check_patch_prec("patch_unmerge_prec", precision, px, py, x_in, y_in, x_out, y_out, ln1_x, ln1_y, B, Cin, Cout, merge_h, merge_w));
+    if (py && (x_skip != nullptr) != (y_skip != nullptr)) return fail(SWF_ERR_NULL, "patch_unmerge_prec: skip is given for every stream or for none");
+    SWF_TRY(unmerge_shapes(Hp, Wp, Hm, Wm, merge_h, merge_w, Hout, Wout));
+    const int nstream = py ? 2 : 1, fast = precision == SWF_PREC_FAST;
+    const size_t image = fast ? patch_image_bytes(1, Cin, Cout, merge_h, merge_w) : 0;
+    Carver ws(workspace, workspace_bytes);
+    const PatchPrecBufs bufs = carve_patch_prec(ws, nstream, image, unmerge_ws(nstream, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout));
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "patch_unmerge_prec: workspace too small (need %zu B)", ws.bytes());
+    hipStream_t stream = as_stream(stream_);
+    const swf_patch_params* pp[2] = {px, py};
+    const float* ins[2] = {x_in, y_in};
+    const float* sk[2] = {x_skip, y_skip};
+    float* outs[2] = {x_out, y_out};
+    const swf_patch_ln1* ln[2] = {ln1_x, ln1_y};
+    swf_block_stream_params blk[2] = {};   // the block behind the layer: only its LN1 is read
+    const swf_block_stream_params* blkp[2] = {&blk[0], &blk[1]};
+    for (int s = 0; s < nstream; ++s) {
+        if (image) SWF_TRY(pack_patch_image(1, Cin, Cout, merge_h, merge_w, *pp[s], bufs.packed[s], stream));
+        if (ln[0]) blk[s].ln1 = ln[s]->ln;
+    }
+    bool ln1_ready = false;
+    PatchTrace tr{};
+    SWF_TRY(patch_unmerge_impl(pp, nstream, ins, x_skip ? sk : nullptr, outs, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout,
+                               bufs.inner, bufs.inner_bytes, stream, fast, image ? bufs.packed : nullptr, nullptr, 0, nullptr,
+                               ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr));
+    return finish_patch_prec("patch_unmerge_prec", tr, ln, nstream, (size_t)B * Hout * Wout * Cout * sizeof(bf16_raw), route, stream);
+}
+
 static float* carve_head_fwd(Carver& ws, int B, int H, int W) { return ws.floats((int64_t)B * H * W * 2); }   // conv1's two channels
 
 int swf_final_head_fwd(const swf_head_params* p, const float* x, const float* y, float* out, int32_t B, int32_t H, int32_t W,
@@ -1692,21 +1855,15 @@ int swf_model_pack_weights(const swf_model_desc* desc, const float* arena, void*
         for (int st = 0; st < 2; ++st) {
             if (plan.penc_b[k]) {
                 const PatchOff& o = L->enc_patch[k][st];
-                if (patch_rr_packed_bytes(0, desc->in_dims[k], desc->out_dims[k], desc->merge_h, desc->merge_w))
-                    SWF_TRY(pack_patch_rr(0, desc->in_dims[k], desc->out_dims[k], desc->merge_h, desc->merge_w, arena + o.w, arena + o.b, arena + o.g,
-                                          arena + o.bt, base + plan.penc[k] + st * plan.penc_b[k], stream));
-                else
-                    SWF_TRY(pack_deep_patch(0, desc->in_dims[k], desc->out_dims[k], desc->merge_h, desc->merge_w, arena + o.w,
-                                            base + plan.penc[k] + st * plan.penc_b[k], stream));
+                SWF_TRY(pack_patch_image(0, desc->in_dims[k], desc->out_dims[k], desc->merge_h, desc->merge_w,
+                                         swf_patch_params{{arena + o.w, arena + o.b}, {arena + o.g, arena + o.bt}},
+                                         base + plan.penc[k] + st * plan.penc_b[k], stream));
             }
             if (plan.pdec_b[k]) {
                 const PatchOff& o = L->dec_patch[k][st];
-                if (patch_rr_packed_bytes(1, desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w))
-                    SWF_TRY(pack_patch_rr(1, desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w, arena + o.w, arena + o.b,
-                                          arena + o.g, arena + o.bt, base + plan.pdec[k] + st * plan.pdec_b[k], stream));
-                else
-                    SWF_TRY(pack_deep_patch(1, desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w, arena + o.w,
-                                            base + plan.pdec[k] + st * plan.pdec_b[k], stream));
+                SWF_TRY(pack_patch_image(1, desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w,
+                                         swf_patch_params{{arena + o.w, arena + o.b}, {arena + o.g, arena + o.bt}},
+                                         base + plan.pdec[k] + st * plan.pdec_b[k], stream));
             }
         }
     }

@@ -69,6 +69,52 @@ def test_argument_validation_without_gpu():
     assert (hm.value, wm.value) == (3, 2)
 
 
+def test_patch_prec_entries_validate_without_gpu():
+    """swf_patch_merge_fwd_prec / swf_patch_unmerge_fwd_prec refuse bad arguments before anything is packed or launched."""
+    lib = L.lib()
+    P = 4096   # a fake device pointer
+    pp, empty = L.PatchParams(L.Linear(P, P), L.Norm(P, P)), L.PatchParams()
+    ln, ln_null = L.PatchLn1(L.Norm(P, P), P, P), L.PatchLn1(L.Norm(P, P), P, None)
+    route = C.c_int32(-7)
+    merge = lambda prec=L.PREC_FAST, px=pp, py=pp, xi=P, yi=P, xo=P, yo=P, geo=(2, 8, 8, 8, 16, 2, 2, 4, 4), lx=None, ly=None: \
+        lib.swf_patch_merge_fwd_prec(prec, C.byref(px) if px else None, C.byref(py) if py else None, xi, yi, xo, yo, *geo,
+                                     C.byref(lx) if lx else None, C.byref(ly) if ly else None, C.byref(route), None, 0, None)
+    unmerge = lambda prec=L.PREC_FAST, px=pp, py=pp, xi=P, yi=P, sx=None, sy=None, xo=P, yo=P, geo=(2, 8, 8, 5, 7, 16, 8, 2, 2, 9, 14), lx=None, \
+        ly=None: lib.swf_patch_unmerge_fwd_prec(prec, C.byref(px) if px else None, C.byref(py) if py else None, xi, yi, sx, sy, xo, yo, *geo,
+                                                C.byref(lx) if lx else None, C.byref(ly) if ly else None, C.byref(route), None, 0, None)
+    for call in (merge, unmerge):
+        assert call() == L.ERR_WORKSPACE                       # everything else in order: the workspace is what is missing
+        assert call(py=None, yi=None, yo=None) == L.ERR_WORKSPACE   # one stream
+        assert call(px=None) == L.ERR_NULL and call(px=empty) == L.ERR_NULL and call(py=empty) == L.ERR_NULL
+        assert call(xi=None) == L.ERR_NULL and call(xo=None) == L.ERR_NULL and call(yi=None) == L.ERR_NULL and call(yo=None) == L.ERR_NULL
+        assert call(lx=ln) == L.ERR_NULL and call(ly=ln) == L.ERR_NULL          # planes for every stream or for none
+        assert call(lx=ln, ly=ln_null) == L.ERR_NULL
+        assert call(py=None, yi=None, yo=None, ly=ln) == L.ERR_NULL
+        assert call(lx=ln, ly=ln) == L.ERR_WORKSPACE
+        assert call(prec=2) == L.ERR_BAD_SHAPE
+    for bad in ((0, 8, 8, 8, 16, 2, 2, 4, 4), (2, 8, 8, 0, 16, 2, 2, 4, 4), (2, 8, 8, 8, -1, 2, 2, 4, 4), (2, 0, 8, 8, 16, 2, 2, 4, 4),
+                (2, 8, 8, 8, 16, 0, 2, 4, 4), (2, 8, 8, 8, 16, 2, 2, 4, 0)):
+        assert merge(geo=bad) == L.ERR_BAD_SHAPE, bad
+        assert lib.swf_patch_merge_prec_workspace_bytes(L.PREC_FAST, 1, *bad) == 0
+    # reflect pad >= the dimension it pads: before merging (1x8 map, merge 2), and of the merged 4x4 map up to the 8x8 window
+    for pad in ((2, 1, 8, 8, 16, 2, 2, 1, 1), (2, 8, 8, 8, 16, 2, 2, 8, 8)):
+        assert merge(geo=pad) == L.ERR_PAD, pad
+        assert lib.swf_patch_merge_prec_workspace_bytes(L.PREC_FAST, 1, *pad) == 0
+    with pytest.raises(RuntimeError):
+        L.check(merge(geo=(2, 8, 8, 8, 16, 2, 2, 8, 8)))
+    for bad in ((0, 8, 8, 5, 7, 16, 8, 2, 2, 9, 14), (2, 8, 8, 9, 7, 16, 8, 2, 2, 9, 14), (2, 8, 8, 5, 0, 16, 8, 2, 2, 9, 14),
+                (2, 8, 8, 5, 7, 16, 8, 2, 2, 11, 14), (2, 8, 8, 5, 7, 16, 8, 2, 2, 9, 0), (2, 8, 8, 5, 7, 0, 8, 2, 2, 9, 14),
+                (2, 8, 8, 5, 7, 16, 8, 2, 0, 9, 14)):
+        assert unmerge(geo=bad) == L.ERR_BAD_SHAPE, bad
+        assert lib.swf_patch_unmerge_prec_workspace_bytes(L.PREC_FAST, 1, *bad) == 0
+    assert unmerge(sx=P) == L.ERR_NULL and unmerge(sy=P) == L.ERR_NULL      # skip for every stream or for none
+    assert unmerge(sx=P, sy=P) == L.ERR_WORKSPACE
+    for q, geo in ((lib.swf_patch_merge_prec_workspace_bytes, (2, 8, 8, 8, 16, 2, 2, 4, 4)),
+                   (lib.swf_patch_unmerge_prec_workspace_bytes, (2, 8, 8, 5, 7, 16, 8, 2, 2, 9, 14))):
+        assert q(2, 1, *geo) == 0 and q(L.PREC_FP32, 1, *geo) > 0 and q(L.PREC_FAST, 0, *geo) > 0
+    assert route.value == -7   # a refused call reports no route
+
+
 @pytest.mark.parametrize("cfg_name", ["win8", "win7", "tiny", "tiny7", "win8_4stage", "win16"])
 def test_state_dict_matches_reference_key_table(cfg_name):
     with open(os.path.join(G.GOLDEN, f"state_keys_{cfg_name}.json")) as f:

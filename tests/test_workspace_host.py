@@ -177,6 +177,38 @@ def test_patch_layers_generic_route():
     _refuses(lambda ws, n: lib.swf_patch_unmerge_fwd(C.byref(pp), P, None, 2 * P, 2, 8, 8, 8, 7, 16, 8, 2, 2, 16, 14, ws, n, None), need)
 
 
+# (Cin, Cout) of both directions: generic only; register-resident; deep whole-row; deep column-sliced (its conv rows and LN1 planes)
+PREC_WIDTHS = {"merge": [(8, 16), (24, 48), (96, 192), (192, 384)], "unmerge": [(16, 8), (48, 24), (192, 96), (384, 192)]}
+
+
+@pytest.mark.parametrize("dual", [0, 1], ids=["one_stream", "two_streams"])
+@pytest.mark.parametrize("prec", [L.PREC_FP32, L.PREC_FAST], ids=["fp32", "fast"])
+def test_patch_prec_entries_need_exactly_their_query(prec, dual):
+    """swf_patch_merge_fwd_prec / swf_patch_unmerge_fwd_prec: the packed images and the impl's room are one carve, checked before the first
+    launch (the pack).  The un-merge query takes the crop; probed against other crops of the same map it is exact at each, largest at one
+    of the three crops the crop-agnostic swf_patch_workspace_bytes measures, and monotone in the kept map."""
+    lib = L.lib()
+    pp = L.PatchParams(_linear(), L.Norm(P, P))
+    py, y = (C.byref(pp), 3 * P) if dual else (None, None)
+    for cin, cout in PREC_WIDTHS["merge"]:
+        geo = (2, 13, 10, cin, cout, 2, 2, 4, 4)
+        need = lib.swf_patch_merge_prec_workspace_bytes(prec, dual, *geo)
+        _refuses(lambda ws, n: lib.swf_patch_merge_fwd_prec(prec, C.byref(pp), py, P, y, 2 * P, y, *geo, None, None, None, ws, n, None), need)
+        if not dual and prec == L.PREC_FP32:   # no image, one stream: the room of today's entry
+            assert need == lib.swf_patch_workspace_bytes(*geo, 1)
+    for cin, cout in PREC_WIDTHS["unmerge"]:
+        needs = {}
+        for hm, wm in ((8, 8), (7, 8), (8, 7), (5, 5), (5, 8), (8, 3), (1, 1)):
+            geo = (2, 8, 8, hm, wm, cin, cout, 2, 2, 2 * hm - 1, 2 * wm)
+            needs[(hm, wm)] = need = lib.swf_patch_unmerge_prec_workspace_bytes(prec, dual, *geo)
+            _refuses(lambda ws, n: lib.swf_patch_unmerge_fwd_prec(prec, C.byref(pp), py, P, y, None, None, 2 * P, y, *geo, None, None, None, ws, n, None),
+                     need)
+        assert max(needs.values()) == max(needs[(8, 8)], needs[(7, 8)], needs[(8, 7)])
+        assert needs[(1, 1)] <= needs[(5, 5)] <= needs[(5, 8)] <= needs[(7, 8)] and needs[(8, 3)] <= needs[(8, 7)]
+        if not dual and prec == L.PREC_FP32:
+            assert max(needs.values()) <= lib.swf_patch_workspace_bytes(2, 8, 8, cin, cout, 2, 2, 4, 4, 0) < max(needs.values()) + 256
+
+
 def _model_desc(cfg, prec, sched):
     d = L.ModelDesc()
     d.levels = cfg.n_levels
