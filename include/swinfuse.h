@@ -130,6 +130,45 @@ int swf_basic_block_fwd(const swf_block_desc* desc, const swf_block_stream_param
                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
 size_t swf_basic_block_workspace_bytes(const swf_block_desc* desc, int32_t B, int32_t H, int32_t W);
 
+/* Which kernels a block ran: a family in the low byte, OR-ed with the flags of every choice the dispatch made inside that family.  The
+ * code is put together by the branches that launch (never recomputed beside them), so that a caller can tell the kernel it means to run
+ * from a fallback: every fallback of the fast tier is more accurate than the kernel it replaces, and no number would show it. */
+typedef enum swf_block_route {
+    SWF_BLOCK_ROUTE_GENERIC = 0,           /* family: attention half and MLP half composed from separate launches (exact tier; fast tier where no fused kernel covers the block) */
+    SWF_BLOCK_ROUTE_WINDOW = 1,            /* family: one launch of a register-resident window kernel (C = 24 / 48 / 96, two streams) */
+    SWF_BLOCK_ROUTE_DEEP = 2,              /* family: deep-level composition over split-bf16 planes (C >= 128) */
+    SWF_BLOCK_ROUTE_FAMILY_MASK = 0xff,
+    /* window family */
+    SWF_BLOCK_WIN_X8 = 0x100,              /* C = 96, 8x8 / 7x7 windows: the eight-waves-per-window kernel (absent: four waves per window) */
+    SWF_BLOCK_WIN_W16 = 0x200,             /* the level's 16x16-window kernel */
+    SWF_BLOCK_VIA_TMP = 0x400,             /* the outputs went through temporary maps: copied back (an in-place cross block of a kernel that cannot run
+                                              in place), or the ping-pong of a stage's two cross blocks */
+    SWF_BLOCK_PREPACKED = 0x800,           /* window and deep family: the weight images came from the caller, nothing was packed in the call */
+    /* deep family, attention and projection (none of the first four: Q/K/V as plane GEMMs, the 8x8 / 7x7 attention core, the projection as a plane GEMM) */
+    SWF_BLOCK_DEEP_QKVATTN = 0x1000,       /* Q/K/V projections + window attention in one launch (C = 192) */
+    SWF_BLOCK_DEEP_FOLD_PROJ = 0x2000,     /* ... which also left the projection's partial sums: the fused MLP's prologue finishes the attention half */
+    SWF_BLOCK_DEEP_QKV = 0x4000,           /* the three projections of every stream in one launch over fragment-major weights */
+    SWF_BLOCK_DEEP_ATTNPROJ = 0x8000,      /* attention core + output projection + residual in one launch (C = 384) */
+    SWF_BLOCK_DEEP_PROJ = 0x10000,         /* output projection over fragment-major weights (+ bias + residual) */
+    SWF_BLOCK_DEEP_CORE16 = 0x20000,       /* the 16x16-window attention core */
+    /* deep family, MLP (no SWF_BLOCK_MLP_FUSED: LayerNorm, fc1 and fc2 as separate launches) */
+    SWF_BLOCK_MLP_FUSED = 0x40000,         /* LN2 + fc1 + ELU + fc2 + residual in one launch, with exactly one of the three tile variants: */
+    SWF_BLOCK_MLP_TOK32 = 0x80000,         /*   32-token tiles, six waves (C = 192, latency schedule) */
+    SWF_BLOCK_MLP_TOK64 = 0x100000,        /*   64-token tiles, four waves */
+    SWF_BLOCK_MLP_WIDE8 = 0x200000,        /*   64-token tiles, eight waves on one 256-wide hidden chunk (C = 384) */
+    SWF_BLOCK_MLP_SPLIT = 0x400000,        /* the hidden width was split over workgroups and a reduce launch summed the parts */
+    /* deep family, LN1 hand-off between blocks that share a workspace */
+    SWF_BLOCK_LN1_GIVEN = 0x800000,        /* the block found its LN1 planes in place: no LayerNorm launch */
+    SWF_BLOCK_LN1_WRITTEN = 0x1000000      /* the block's MLP also wrote the LN1 planes of the block that runs next */
+} swf_block_route;
+/* swf_basic_block_fwd that also reports the route: *route (host int32, may be NULL) is written when the call succeeds.  Same workspace
+ * query; desc->schedule is honoured as everywhere. */
+int swf_basic_block_fwd_route(const swf_block_desc* desc, const swf_block_stream_params* px,
+                              const swf_block_stream_params* py,
+                              const float* x_in, const float* y_in, float* x_out, float* y_out,
+                              int32_t B, int32_t H, int32_t W, int32_t* route,
+                              void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* Block-level pre-pack for callers that run the same block many times (fast tier): derive the fused kernel's
  * weight images once into a caller-owned buffer of swf_basic_block_packed_bytes(desc) bytes (0 = this shape has no
  * fused kernel; use swf_basic_block_fwd), then launch with swf_basic_block_fwd_packed — exactly one kernel. */
@@ -298,6 +337,22 @@ int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, co
                                int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout,
                                const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
                                void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
+/* One SelfAndCrossBlockPair stage as the whole-model forward runs it (arguments as swf_block_pair4_fwd; desc carries precision and
+ * schedule).  Under SWF_PREC_FAST the images this shape admits (eight, [block][stream]) are packed at the front of the workspace, per call
+ * (this entry is for tests and tools, not the hot path), and the stage then runs from them through the same code as the model's: each
+ * block warms the next block's images, at the deep levels each block's MLP leaves the next block's LN1 planes, and the two cross blocks
+ * of a 16x16-window kernel ping-pong through temporary maps.  route: host int32[4], one swf_block_route per block, or NULL.
+ * ln1_x / ln1_y (for every stream or none; reuse of swf_patch_ln1): the LN1 of the first block of a stage that would run next on the
+ * same map.  Where the last block's route carries SWF_BLOCK_LN1_WRITTEN its MLP wrote LayerNorm(out) with `ln` as split-bf16 planes
+ * and they were copied to hi / lo (uint16 [B*H*W][C]); without the flag the buffers are untouched.  x_out / y_out may alias the
+ * inputs.  The query takes dual = 0 for py == NULL. */
+size_t swf_block_stage_prec_workspace_bytes(const swf_block_desc* desc, int32_t dual, int32_t B, int32_t H, int32_t W);
+int swf_block_stage_fwd_prec(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, float* x_out, float* y_out,
+                             int32_t B, int32_t H, int32_t W,
+                             const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
+                             void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- final fusion head (a013:126-152): cat -> conv kxk reflect -> BatchNorm2d(eval) -> ELU -> conv kxk reflect */
 typedef struct swf_head_params {

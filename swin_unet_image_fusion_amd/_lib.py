@@ -64,6 +64,16 @@ class PatchLn1(C.Structure):    # swf_patch_ln1: the next block's LN1 and caller
 ROUTE_GENERIC, ROUTE_FUSED, ROUTE_RR, ROUTE_DEEP_ROW, ROUTE_DEEP_SLICED, ROUTE_LN1 = 0, 1, 2, 3, 4, 0x100
 
 
+# swf_block_route: a family in the low byte, OR-ed with the flags of every choice the block dispatch made
+BLOCK_GENERIC, BLOCK_WINDOW, BLOCK_DEEP, BLOCK_FAMILY_MASK = 0, 1, 2, 0xFF
+BLOCK_WIN_X8, BLOCK_WIN_W16, BLOCK_VIA_TMP, BLOCK_PREPACKED = 0x100, 0x200, 0x400, 0x800
+BLOCK_DEEP_QKVATTN, BLOCK_DEEP_FOLD_PROJ, BLOCK_DEEP_QKV = 0x1000, 0x2000, 0x4000
+BLOCK_DEEP_ATTNPROJ, BLOCK_DEEP_PROJ, BLOCK_DEEP_CORE16 = 0x8000, 0x10000, 0x20000
+BLOCK_MLP_FUSED, BLOCK_MLP_TOK32, BLOCK_MLP_TOK64, BLOCK_MLP_WIDE8, BLOCK_MLP_SPLIT = 0x40000, 0x80000, 0x100000, 0x200000, 0x400000
+BLOCK_LN1_GIVEN, BLOCK_LN1_WRITTEN = 0x800000, 0x1000000
+SCHED_LATENCY, SCHED_THROUGHPUT = 0, 1
+
+
 class HeadParams(C.Structure):
     _fields_ = [("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("bn_gamma", C.c_void_p), ("bn_beta", C.c_void_p),
                 ("bn_mean", C.c_void_p), ("bn_var", C.c_void_p), ("conv2_w", C.c_void_p), ("conv2_b", C.c_void_p)]
@@ -116,6 +126,8 @@ SIGNATURES = {
     "swf_attn_halfblock_fwd": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_mlp_halfblock_fwd": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_basic_block_fwd": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_basic_block_fwd_route": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                            P(_i32), _vp, _sz, _vp]),
     "swf_basic_block_workspace_bytes": (_sz, [P(BlockDesc), _i32, _i32, _i32]),
     "swf_basic_block_packed_bytes": (_sz, [P(BlockDesc)]),
     "swf_basic_block_pack": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _sz, _vp]),
@@ -152,6 +164,9 @@ SIGNATURES = {
     "swf_final_head_batch_stats": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_add_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp]),
     "swf_block_pair4_fwd": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_block_stage_prec_workspace_bytes": (_sz, [P(BlockDesc), _i32, _i32, _i32, _i32]),
+    "swf_block_stage_fwd_prec": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32,
+                                           P(PatchLn1), P(PatchLn1), P(_i32), _vp, _sz, _vp]),
     "swf_patch_merge_fwd": (C.c_int, [P(PatchParams), _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_merge_out_shape": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, P(_i32), P(_i32), P(_i32), P(_i32)]),
     "swf_patch_unmerge_fwd": (C.c_int, [P(PatchParams), _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),

@@ -26,6 +26,8 @@ struct MlpFusedDesc {
 bool mlp_fused_supported(int C, int HID);
 int mlp_fused_splits(int C, int HID);
 inline bool mlp_fused_writes_ln(int, int) { return true; }
-int launch_mlp_fused(const MlpFusedDesc& d, int nstream, hipStream_t stream);
+// route (or nullptr): the branch that launches ORs in the tile variant (SWF_BLOCK_MLP_TOK32 / _TOK64 / _WIDE8) and, where the reduce over
+// the hidden splits runs, SWF_BLOCK_MLP_SPLIT (swf_block_route).
+int launch_mlp_fused(const MlpFusedDesc& d, int nstream, hipStream_t stream, int* route = nullptr);
 
 }  // namespace swf

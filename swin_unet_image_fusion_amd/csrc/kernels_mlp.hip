@@ -552,7 +552,7 @@ __global__ __launch_bounds__(256) void mlp_reduce_ln_kernel(MlpArgs a, int C, in
 }
 
 template <int C, int NW, int TOK = 64>
-int launch_c(const MlpArgs& a, int nstream, hipStream_t stream) {
+int launch_c(const MlpArgs& a, int nstream, hipStream_t stream, int* route) {
     // A image + H image (NW = 4, 6) or A image with H laid over it + gamma / beta (NW = 8)
     constexpr int lds = NW == 8 ? TOK * (C + 8) * 2 * 2 + 2 * C * 4 : (TOK * (C + 8) + TOK * (32 * NW + 8)) * 2 * 2;
     if (NW == 8 && a.nchunks != 1) return fail(SWF_ERR_UNSUPPORTED, "mlp_fused: the 8-wave kernel takes one hidden chunk per workgroup");
@@ -560,6 +560,8 @@ int launch_c(const MlpArgs& a, int nstream, hipStream_t stream) {
     dim3 grid((a.M + TOK - 1) / TOK, a.splits, nstream);
     hipLaunchKernelGGL((mlp_fused_kernel<C, NW, TOK>), grid, dim3(64 * NW), lds, stream, a);
     SWF_TRY(check_launch("mlp_fused"));
+    trace_block(route, NW == 8 ? SWF_BLOCK_MLP_WIDE8 : TOK == 32 ? SWF_BLOCK_MLP_TOK32 : SWF_BLOCK_MLP_TOK64);
+    if (a.splits > 1) trace_block(route, SWF_BLOCK_MLP_SPLIT);   // one of the two reduce launches below
     MlpArgs ra = a;   // the reduce kernels' residual is the row that entered LN2
     for (int s = 0; s < nstream; ++s)
         if (a.part0[s]) ra.x[s] = a.x1[s];
@@ -609,7 +611,7 @@ int mlp_fused_splits(int C, int HID) {
     return chunks % 2 == 0 ? chunks / 2 : chunks;
 }
 
-int launch_mlp_fused(const MlpFusedDesc& d, int nstream, hipStream_t stream) {
+int launch_mlp_fused(const MlpFusedDesc& d, int nstream, hipStream_t stream, int* route) {
     if (!mlp_fused_supported(d.C, d.HID)) return fail(SWF_ERR_UNSUPPORTED, "mlp_fused: C=%d hidden=%d", d.C, d.HID);
     if (d.M <= 0 || d.M > (1 << 30) / d.C) return fail(SWF_ERR_UNSUPPORTED, "mlp_fused: token count %d", d.M);
     MlpArgs a{};
@@ -641,10 +643,10 @@ int launch_mlp_fused(const MlpFusedDesc& d, int nstream, hipStream_t stream) {
     if (a.splits > 1 && (!d.scratch || (int64_t)nstream * a.splits * d.M * d.C > d.scratch_floats))
         return fail(SWF_ERR_WORKSPACE, "mlp_fused: scratch too small for %d hidden splits", a.splits);
     switch (d.C) {
-        case 128: return launch_c<128, 4>(a, nstream, stream);
-        case 192: return tok32 ? launch_c<192, 6, 32>(a, nstream, stream) : launch_c<192, 4>(a, nstream, stream);
-        case 256: return launch_c<256, 4>(a, nstream, stream);
-        case 384: return wide ? launch_c<384, 8>(a, nstream, stream) : launch_c<384, 4>(a, nstream, stream);
+        case 128: return launch_c<128, 4>(a, nstream, stream, route);
+        case 192: return tok32 ? launch_c<192, 6, 32>(a, nstream, stream, route) : launch_c<192, 4>(a, nstream, stream, route);
+        case 256: return launch_c<256, 4>(a, nstream, stream, route);
+        case 384: return wide ? launch_c<384, 8>(a, nstream, stream, route) : launch_c<384, 4>(a, nstream, stream, route);
     }
     return fail(SWF_ERR_UNSUPPORTED, "mlp_fused: C=%d", d.C);
 }

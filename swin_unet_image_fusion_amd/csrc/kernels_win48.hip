@@ -744,7 +744,7 @@ struct L48 {
     template <int HID>
     static void pack(dim3 grid, const WinPackArgs& a, hipStream_t stream) { hipLaunchKernelGGL((pack48_kernel<HID>), grid, dim3(256), 0, stream, a); }
     template <int HID, int WS, int MODE, bool RAW>
-    static int launch(const swf_block_desc&, const WinArgs& a, int grid, hipStream_t stream) {
+    static int launch(const swf_block_desc&, const WinArgs& a, int grid, hipStream_t stream, int*) {   // one kernel: nothing to report
         hipLaunchKernelGGL((window48_kernel<HID, WS, MODE, RAW>), dim3(grid), dim3(256), 0, stream, a);
         return check_launch(MODE == WIN_BLOCK ? "window48" : "window48 (half block)");
     }

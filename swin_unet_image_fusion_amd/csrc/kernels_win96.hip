@@ -1105,7 +1105,7 @@ struct L96 {
     template <int HID>
     static void pack(dim3 grid, const WinPackArgs& a, hipStream_t stream) { hipLaunchKernelGGL((pack96_kernel<HID>), grid, dim3(256), 0, stream, a); }
     template <int HID, int WS, int MODE, bool RAW>
-    static int launch(const swf_block_desc& d, const WinArgs& a, int grid, hipStream_t stream) {
+    static int launch(const swf_block_desc& d, const WinArgs& a, int grid, hipStream_t stream, int* route) {
         if constexpr (MODE == WIN_BLOCK) {
             static const bool no_x8 = [] { const char* e = debug_env("SWF_WIN96X8"); return e && e[0] == '0'; }();   // A/B switch (tools)
             // Maps of up to 16 windows (32 x 32 tokens: B=16 256x256 has 256 windows for 256 CUs) take eight waves per window
@@ -1114,6 +1114,7 @@ struct L96 {
             if (!no_x8 && d.schedule != SWF_SCHED_THROUGHPUT && (a.H / WS) * (a.W / WS) <= 16) {
                 constexpr int lds8 = (int)G96<HID>::l_total8;
                 SWF_TRY((raise_lds_limit<&window96x8_kernel<HID, WS>>(lds8, "window96x8")));
+                trace_block(route, SWF_BLOCK_WIN_X8);
                 hipLaunchKernelGGL((window96x8_kernel<HID, WS>), dim3(std::min(grid, num_cus())), dim3(512), lds8, stream, a);
                 return check_launch("window96x8");
             }

@@ -19,7 +19,8 @@ int pack_window_block(const swf_block_desc& d, const swf_block_stream_params& px
 int launch_window_block(const swf_block_desc& d, const void* packed_x, const void* packed_y,
                         const float* x_in, const float* y_in, float* x_out, float* y_out, int B, int H, int W,
                         hipStream_t stream, const void* next_packed_x = nullptr, const void* next_packed_y = nullptr,
-                        size_t next_bytes = 0);
+                        size_t next_bytes = 0, int* route = nullptr);
+// route (or nullptr): the branch that launches ORs in which kernel it is (SWF_BLOCK_WIN_X8, SWF_BLOCK_WIN_W16; swf_block_route).
 // next_packed_*: packed images of the block that runs next with different weights (or nullptr): this launch ends by touching
 // them (next_bytes each; 0 = the size of this block's own image) so that they are L2-resident when that block starts.
 

@@ -643,7 +643,7 @@ int launch_l2_warm(const void* p, size_t bytes, hipStream_t stream) {
 
 int launch_window_block(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in,
                         const float* y_in, float* x_out, float* y_out, int B, int H, int W, hipStream_t stream,
-                        const void* next_packed_x, const void* next_packed_y, size_t next_bytes) {
+                        const void* next_packed_x, const void* next_packed_y, size_t next_bytes, int* route) {
     if (!window_block_supported(d, B, H, W))
         return fail(SWF_ERR_UNSUPPORTED, "window_block: C=%d hidden=%d, %d x %d map, window %d not covered", d.attn.channels, d.hidden, H, W, d.attn.win_h);
     // batch slices of at most 2^31 - 1 bytes per stream map (32-bit buffer offsets inside the kernels); the slice size depends on
@@ -657,7 +657,7 @@ int launch_window_block(const swf_block_desc& d, const void* packed_x, const voi
         const bool last = b0 + nb >= B;   // only the last slice touches the next block's packed weights (L2 warm-up)
         const void* nx = last ? next_packed_x : nullptr;
         const void* ny = last ? next_packed_y : nullptr;
-        const int st = level->launch(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes);
+        const int st = level->launch(d, packed_x, packed_y, x_in + off, y_in + off, x_out + off, y_out + off, nb, H, W, stream, nx, ny, next_bytes, route);
         if (st != SWF_OK) return st;
     }
     return SWF_OK;

@@ -296,7 +296,8 @@ static size_t block_generic_ws(const swf_block_desc* d, int nstream, int B, int 
 static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
                            const float* x_in, const float* y_in, float* x_out, float* y_out, int B, int H, int W,
                            Carver& ws, hipStream_t stream, const void* packed_x, const void* packed_y,
-                           const swf_block_stream_params* const* next_p = nullptr, bool* ln1_ready = nullptr) {
+                           const swf_block_stream_params* const* next_p = nullptr, bool* ln1_ready = nullptr, int* route = nullptr) {
+    // `route` (or nullptr): every branch that launches ORs its flag in (swf_block_route)
     // `next_p`: stream parameters of the block that runs next on the same workspace with the same shapes (or nullptr).  When the
     // fused MLP's reduce kernel can, it also writes that block's LN1 planes; `*ln1_ready` reports it, and on entry says whether the
     // previous block did the same for this one (the planes sit at the same workspace offsets: the carve depends on shapes only).
@@ -322,6 +323,8 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
     // batch shards keep taking the same path (bit-identical rows across shard sizes).
     const bool proj_fused = fused_attn_shape && fused_mlp && !no_projfuse && HD == C && (int64_t)H * W <= 256;
     DeepWeights wv[2];
+    trace_block(route, SWF_BLOCK_ROUTE_DEEP);
+    if (pk[0] && (nstream == 1 || pk[1])) trace_block(route, SWF_BLOCK_PREPACKED);
     for (int s = 0; s < nstream; ++s) {
         if (!pk[s]) { SWF_TRY(pack_deep_block(*desc, *pp[s], b.wbuf[s], stream)); pk[s] = b.wbuf[s]; }
         wv[s] = deep_block_views(*desc, pk[s]);
@@ -331,6 +334,8 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         LnBatch l1{};
         for (int s = 0; s < nstream; ++s) l1.p[s] = LnProb{xin[s], nullptr, pp[s]->ln1.gamma, pp[s]->ln1.beta, b.xn_hi[s], b.xn_lo[s]};
         SWF_TRY(launch_layernorm(l1, nstream, N, C, 0, stream));
+    } else {
+        trace_block(route, SWF_BLOCK_LN1_GIVEN);
     }
     const bool fused_attn = fused_attn_shape && wv[0].qa && (nstream == 1 || wv[1].qa);
     const bool fold_proj = proj_fused && fused_attn && pp[0]->attn.proj.bias && (nstream == 1 || pp[1]->attn.proj.bias);
@@ -342,6 +347,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         }
         qa.B = B; qa.H = H; qa.W = W; qa.shift = desc->attn.shift; qa.cross = cross;
         SWF_TRY(launch_qkvattn(*desc, qa, nstream, stream));
+        trace_block(route, SWF_BLOCK_DEEP_QKVATTN | (fold_proj ? SWF_BLOCK_DEEP_FOLD_PROJ : 0));
     }
     SpGemmBatch gq{};
     for (int s = 0; s < nstream; ++s) {
@@ -365,6 +371,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         }
         dq.qscale = gq.qscale; dq.cross = cross; dq.M = (int)N; dq.C = C;
         SWF_TRY(launch_deep_qkv(dq, nstream, stream));
+        trace_block(route, SWF_BLOCK_DEEP_QKV);
     }
     if (!fused_attn && !deep_qkv) SWF_TRY(launch_gemm_sp(gq, 3 * nstream, (int)N, HD, C, HD, SP_EPI_QKV16, stream));
     // level 4 (C = 384): attention core + output projection + residual in one launch
@@ -378,16 +385,18 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         }
         ap.B = B; ap.H = H; ap.W = W; ap.shift = desc->attn.shift;
         SWF_TRY(launch_attnproj(*desc, ap, nstream, stream));
+        trace_block(route, SWF_BLOCK_DEEP_ATTNPROJ);
     }
     if (!fused_attn && !attn_proj) {
         const bf16_raw* qq[2] = {b.qkv[0][0], b.qkv[1][0]};
         const bf16_raw* kk[2] = {b.qkv[0][1], b.qkv[1][1]};
         const bf16_raw* vv[2] = {b.qkv[0][2], b.qkv[1][2]};
         const float* tt[2] = {pp[0]->attn.bias_table, nstream == 2 ? pp[1]->attn.bias_table : nullptr};
-        if (desc->attn.win_h == 16)
+        if (desc->attn.win_h == 16) {
             SWF_TRY(launch_attn_core_mfma16(nullptr, nullptr, nullptr, nullptr, tt, nstream, HD, HD, HD, HD, B, H, W, desc->attn.heads,
                                             desc->attn.head_dim, desc->attn.shift, nullptr, stream, b.o_hi, b.o_lo, qq, kk, vv));
-        else
+            trace_block(route, SWF_BLOCK_DEEP_CORE16);
+        } else
             SWF_TRY(launch_attn_core_mfma(nullptr, nullptr, nullptr, nullptr, tt, nstream, HD, HD, HD, HD, B, H, W, desc->attn.heads,
                                           desc->attn.head_dim, desc->attn.shift, stream, b.o_hi, b.o_lo, qq, kk, vv, desc->attn.win_h));
     }
@@ -404,6 +413,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
         }
         dp.M = (int)N; dp.C = C;
         SWF_TRY(launch_deep_proj(dp, nstream, stream));
+        trace_block(route, SWF_BLOCK_DEEP_PROJ);
     }
     if (!fold_proj && !attn_proj && !deep_proj) SWF_TRY(launch_gemm_sp(gp, nstream, (int)N, C, HD, C, SP_EPI_F32, stream));
     // MLP half (a004:29-38 around a003:46-50)
@@ -421,8 +431,9 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
             for (int s = 0; s < nstream; ++s) {
                 md.ln_gamma[s] = next_p[s]->ln1.gamma; md.ln_beta[s] = next_p[s]->ln1.beta; md.ln_hi[s] = b.xn_hi[s]; md.ln_lo[s] = b.xn_lo[s];
             }
-        SWF_TRY(launch_mlp_fused(md, nstream, stream));
-        if (ln_next) *ln1_ready = true;
+        trace_block(route, SWF_BLOCK_MLP_FUSED);
+        SWF_TRY(launch_mlp_fused(md, nstream, stream, route));
+        if (ln_next) { *ln1_ready = true; trace_block(route, SWF_BLOCK_LN1_WRITTEN); }
         return SWF_OK;
     }
     LnBatch l2{};
@@ -491,8 +502,9 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
                             float* y_out, int B, int H, int W, void* workspace, size_t workspace_bytes,
                             hipStream_t stream, const void* prepacked_x = nullptr, const void* prepacked_y = nullptr,
                             const void* next_x = nullptr, const void* next_y = nullptr, size_t next_bytes = 0,
-                            const swf_block_stream_params* const* next_p = nullptr, bool* ln1_ready = nullptr) {
+                            const swf_block_stream_params* const* next_p = nullptr, bool* ln1_ready = nullptr, int* route = nullptr) {
     // next_p / ln1_ready: see deep_block_impl; every other path ignores the planes and leaves *ln1_ready false
+    // route (or nullptr; the caller zeroes it): the family and the flags of what ran, set where it is launched (swf_block_route)
     if (desc->precision == SWF_PREC_FAST && py && window_block_supported(*desc, B, H, W)) {
         if (ln1_ready) *ln1_ready = false;
         const bool prepacked = prepacked_x && prepacked_y;   // model path: weights were packed once (swf_model_pack_weights)
@@ -505,13 +517,16 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
         if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "fused block workspace too small (need %zu B)", ws.bytes());
         char* w = bufs.packed;
         float *ox = via_tmp ? bufs.ox : x_out, *oy = via_tmp ? bufs.oy : y_out;
+        trace_block(route, SWF_BLOCK_ROUTE_WINDOW);
         if (prepacked) {
-            SWF_TRY(launch_window_block(*desc, prepacked_x, prepacked_y, x_in, y_in, ox, oy, B, H, W, stream, next_x, next_y, next_bytes));
+            SWF_TRY(launch_window_block(*desc, prepacked_x, prepacked_y, x_in, y_in, ox, oy, B, H, W, stream, next_x, next_y, next_bytes, route));
+            trace_block(route, SWF_BLOCK_PREPACKED);
         } else {   // block-level entry: pack this block's weights into the workspace, then one fused launch
             SWF_TRY(pack_window_block(*desc, *px, *py, w, w + pb, stream));
-            SWF_TRY(launch_window_block(*desc, w, w + pb, x_in, y_in, ox, oy, B, H, W, stream));
+            SWF_TRY(launch_window_block(*desc, w, w + pb, x_in, y_in, ox, oy, B, H, W, stream, nullptr, nullptr, 0, route));
         }
         if (via_tmp) {
+            trace_block(route, SWF_BLOCK_VIA_TMP);
             if (hipMemcpyAsync(x_out, ox, map_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
                 hipMemcpyAsync(y_out, oy, map_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess)
                 return fail(SWF_ERR_HIP, "fused block: copy of the temporary outputs failed");
@@ -532,9 +547,10 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
     static const bool no_deep = debug_env("SWF_NO_DEEP") != nullptr;   // A/B switch for tools/profile_block.py
     if (deep_block_supported(*desc) && !no_deep && tbits % 16 == 0 && aligned16(px) && aligned16(py)) {
         Carver ws(workspace, workspace_bytes);
-        return deep_block_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, stream, prepacked_x, prepacked_y, next_p, ln1_ready);
+        return deep_block_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, stream, prepacked_x, prepacked_y, next_p, ln1_ready, route);
     }
     if (ln1_ready) *ln1_ready = false;
+    trace_block(route, SWF_BLOCK_ROUTE_GENERIC);
     {
         Carver ws(workspace, workspace_bytes);
         SWF_TRY(attn_halfblock_generic(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, stream));
@@ -968,7 +984,8 @@ static int block_pair4_impl(const swf_block_desc* desc, const swf_block_stream_p
                             const float* x_in, const float* y_in, float* x_out, float* y_out, int B, int H, int W,
                             void* workspace, size_t workspace_bytes, hipStream_t stream, const char* packed = nullptr,
                             const char* after = nullptr, size_t after_pb = 0, int32_t* equal_flags = nullptr,
-                            const swf_block_stream_params* const* stage_next = nullptr, bool* ln1_io = nullptr) {
+                            const swf_block_stream_params* const* stage_next = nullptr, bool* ln1_io = nullptr, int32_t* routes = nullptr) {
+    // `routes` (host, 4 entries, or nullptr): the swf_block_route of each block
     // `stage_next` / `ln1_io` (deep levels): the first block's parameters of the stage that runs next on the same workspace with the
     // same map (the decoder stage behind the deepest encoder stage), so that this stage's last MLP reduce leaves that block's LN1
     // planes; *ln1_io says on entry whether this stage's first block finds its planes in place, on return whether the next does
@@ -1015,8 +1032,11 @@ static int block_pair4_impl(const swf_block_desc* desc, const swf_block_stream_p
             SWF_TRY(launch_all_equal(xi, yi, (int64_t)B * H * W * desc->attn.channels, equal_flags + (i - 2), stream));
         float* xo = (tx && i == 2) ? tx : x_out;
         float* yo = (tx && i == 2) ? ty : y_out;
+        int route = 0;
         SWF_TRY(basic_block_impl(&d, &px[i], py ? &py[i] : nullptr, xi, yi, xo, yo, B, H, W, workspace, tx ? ws_left : workspace_bytes, stream, pkx, pky,
-                                 nkx, nky, i == 3 ? after_pb : 0, (i < 3 || chain_out) ? nxt : nullptr, &ln1_ready));
+                                 nkx, nky, i == 3 ? after_pb : 0, (i < 3 || chain_out) ? nxt : nullptr, &ln1_ready, routes ? &route : nullptr));
+        if (tx && i >= 2) trace_block(&route, SWF_BLOCK_VIA_TMP);   // block 2 wrote the temporaries, block 3 read them
+        if (routes) routes[i] = route;
         xi = xo; yi = yo;
     }
     if (ln1_io) *ln1_io = ln1_ready;
@@ -1265,6 +1285,17 @@ int swf_basic_block_fwd(const swf_block_desc* desc, const swf_block_stream_param
     return basic_block_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
+int swf_basic_block_fwd_route(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                              const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W,
+                              int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_block(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, true, true));
+    int r = 0;
+    SWF_TRY(basic_block_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, workspace, workspace_bytes, as_stream(stream), nullptr, nullptr,
+                             nullptr, nullptr, 0, nullptr, nullptr, &r));
+    if (route) *route = r;
+    return SWF_OK;
+}
+
 size_t swf_basic_block_packed_bytes(const swf_block_desc* desc) {
     if (!desc || desc->precision != SWF_PREC_FAST) return 0;
     return 2 * window_block_packed_bytes(*desc);
@@ -1497,6 +1528,92 @@ int swf_block_pair4_fwd(const swf_block_desc* desc, const swf_block_stream_param
     for (int i = 0; i < 4; ++i)
         SWF_TRY(check_block(desc, &px[i], py ? &py[i] : nullptr, x_in, y_in, x_out, y_out, B, H, W, true, true));
     return block_pair4_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// ---- one stage as the model runs it: images packed at the front of the workspace, then block_pair4_impl on the rest ----------------
+// Bytes of ONE image of the stage (0: this shape, tier and stream count run without images).  The window kernels need two streams.
+static size_t stage_image_bytes(const swf_block_desc& d, int nstream) {
+    if (d.precision != SWF_PREC_FAST) return 0;
+    if (window_block_packed_bytes(d)) return nstream == 2 ? window_block_packed_bytes(d) : 0;
+    return deep_block_packed_bytes(d);
+}
+// What block_pair4_impl and its four blocks carve when they run from images: a window-kernel stage only the two temporary maps of a
+// kernel that cannot run a cross block in place; every other stage what its largest block needs.
+static size_t stage_inner_ws(const swf_block_desc& d, int nstream, int B, int H, int W) {
+    if (d.precision == SWF_PREC_FAST && nstream == 2 && window_block_supported(d, B, H, W)) {
+        Carver m = Carver::measure();
+        carve_window_block(m, d, (int64_t)B * H * W, true, window_block_out_of_place(d));
+        return m.bytes();
+    }
+    return block_generic_ws(&d, nstream, B, H, W);
+}
+struct StageBufs { char* packed; void* inner; size_t inner_bytes; };
+static StageBufs carve_block_stage(Carver& ws, const swf_block_desc& d, int nstream, int B, int H, int W) {
+    StageBufs b{};
+    const size_t image = stage_image_bytes(d, nstream);
+    if (image) b.packed = reinterpret_cast<char*>(ws.floats((int64_t)(8 * image / 4)));
+    b.inner_bytes = stage_inner_ws(d, nstream, B, H, W);
+    b.inner = ws.floats((int64_t)(b.inner_bytes / 4));
+    return b;
+}
+static bool stage_precision_ok(const swf_block_desc* d) { return d && (d->precision == SWF_PREC_FP32 || d->precision == SWF_PREC_FAST); }
+
+size_t swf_block_stage_prec_workspace_bytes(const swf_block_desc* desc, int32_t dual, int32_t B, int32_t H, int32_t W) {
+    if (!stage_precision_ok(desc) || desc->hidden <= 0 || check_attn_desc(&desc->attn, B, H, W) != SWF_OK) return 0;
+    Carver m = Carver::measure();
+    carve_block_stage(m, *desc, dual ? 2 : 1, B, H, W);
+    return m.bytes();
+}
+
+int swf_block_stage_fwd_prec(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W,
+                             const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route, void* workspace, size_t workspace_bytes,
+                             swf_stream_t stream_) {
+    if (!px) return fail(SWF_ERR_NULL, "block_stage_prec: block params are NULL");
+    for (int i = 0; i < 4; ++i)
+        SWF_TRY(check_block(desc, &px[i], py ? &py[i] : nullptr, x_in, y_in, x_out, y_out, B, H, W, true, true));
+    if (!stage_precision_ok(desc)) return fail(SWF_ERR_BAD_SHAPE, "block_stage_prec: unknown precision %d", desc->precision);
+    if (ln1_y && !py) return fail(SWF_ERR_NULL, "block_stage_prec: LN1 planes of a y stream that is not there");
+    if (ln1_x ? (py && !ln1_y) : ln1_y != nullptr) return fail(SWF_ERR_NULL, "block_stage_prec: LN1 planes are asked for every stream or for none");
+    for (const swf_patch_ln1* l : {ln1_x, ln1_y})
+        if (l && (!l->ln.gamma || !l->ln.beta || !l->hi || !l->lo)) return fail(SWF_ERR_NULL, "block_stage_prec: NULL pointer in swf_patch_ln1");
+    const int nstream = py ? 2 : 1;
+    Carver ws(workspace, workspace_bytes);
+    const StageBufs bufs = carve_block_stage(ws, *desc, nstream, B, H, W);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "block_stage_prec: workspace too small (need %zu B)", ws.bytes());
+    hipStream_t stream = as_stream(stream_);
+    if (bufs.packed) {   // [block 0..3][stream x, y], as swf_model_pack_weights lays a stage out
+        const size_t pb = stage_image_bytes(*desc, nstream);
+        for (int i = 0; i < 4; ++i) {
+            char* dst = bufs.packed + (size_t)(2 * i) * pb;
+            if (window_block_packed_bytes(*desc)) {
+                SWF_TRY(pack_window_block(*desc, px[i], py[i], dst, dst + pb, stream));
+            } else {
+                SWF_TRY(pack_deep_block(*desc, px[i], dst, stream));
+                if (py) SWF_TRY(pack_deep_block(*desc, py[i], dst + pb, stream));
+            }
+        }
+    }
+    const swf_patch_ln1* ln[2] = {ln1_x, ln1_y};
+    swf_block_stream_params nb[2] = {};   // the first block of the stage behind this one: only its LN1 is read
+    const swf_block_stream_params* nbp[2] = {&nb[0], nstream == 2 ? &nb[1] : nullptr};
+    for (int s = 0; s < nstream && ln[0]; ++s) nb[s].ln1 = ln[s]->ln;
+    bool ln1_io = false;
+    int32_t r[4] = {0, 0, 0, 0};
+    SWF_TRY(block_pair4_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, bufs.inner, bufs.inner_bytes, stream, bufs.packed, nullptr, 0, nullptr,
+                             ln[0] ? nbp : nullptr, &ln1_io, r));
+    if (ln[0] && ln1_io) {   // the planes lie where the next block on this workspace would look for them
+        bf16_raw *hi[2], *lo[2];
+        Carver at(bufs.inner, bufs.inner_bytes);
+        deep_ln1_planes(at, (int64_t)B * H * W, desc->attn.channels, nstream, hi, lo);
+        const size_t plane_bytes = (size_t)B * H * W * desc->attn.channels * sizeof(bf16_raw);
+        for (int s = 0; s < nstream; ++s)
+            if (hipMemcpyAsync(ln[s]->hi, hi[s], plane_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess ||
+                hipMemcpyAsync(ln[s]->lo, lo[s], plane_bytes, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+                return fail(SWF_ERR_HIP, "block_stage_prec: copy of the LN1 planes failed");
+    }
+    if (route) std::copy(r, r + 4, route);
+    return SWF_OK;
 }
 
 int swf_merge_out_shape(int32_t H, int32_t W, int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, int32_t* Hm,

@@ -57,6 +57,9 @@ int raise_lds_limit(int bytes, const char* what) {
 __device__ __forceinline__ int reflect_br(int i, int n) { return i < n ? i : 2 * n - 2 - i; }
 __device__ __forceinline__ int reflect2(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
 
+// Route report of a block (swf_block_route): the branch that launches ORs its flag into the caller's code, when there is one.
+inline void trace_block(int* route, int flags) { if (route) *route |= flags; }
+
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }

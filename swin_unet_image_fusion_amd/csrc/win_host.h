@@ -9,7 +9,8 @@
 //   template <int HID> using G = ...;             the level's geometry (p_total, p_total16, ...)
 //   template <int HID> static void pack(dim3 grid, const WinPackArgs&, hipStream_t);   launches the pack kernel
 //   template <int HID, int WS, int MODE, bool RAW>
-//   static int launch(const swf_block_desc&, const WinArgs&, int grid, hipStream_t);   8x8 / 7x7: which kernel, LDS; launch + check
+//   static int launch(const swf_block_desc&, const WinArgs&, int grid, hipStream_t, int* route);   8x8 / 7x7: which kernel, LDS; launch + check
+//                                                 (route: trace_block, where the level has more than one kernel for a block)
 //   template <int HID> static int launch16(const WinArgs&, int nwin, hipStream_t);     16x16: the level's own grid; launch + check
 //
 // and defines winNN_level() to return win_level<L>().
@@ -113,19 +114,19 @@ inline WinArgs win_args(const swf_block_desc& d, const void* packed_x, const voi
 // Which instantiation a descriptor names.  The attention half ignores the MLP geometry (the wide image layout serves), the MLP
 // half has no windows (WS = 8): neither instantiates the other combinations.
 template <class L, int HID, int MODE, bool RAW>
-int win_launch_ws(const swf_block_desc& d, const WinArgs& a, int grid, hipStream_t stream) {
+int win_launch_ws(const swf_block_desc& d, const WinArgs& a, int grid, hipStream_t stream, int* route) {
     if constexpr (MODE != WIN_MLP) {
-        if (d.attn.win_h != 8) return L::template launch<HID, 7, MODE, RAW>(d, a, grid, stream);
+        if (d.attn.win_h != 8) return L::template launch<HID, 7, MODE, RAW>(d, a, grid, stream, route);
     }
-    return L::template launch<HID, 8, MODE, RAW>(d, a, grid, stream);
+    return L::template launch<HID, 8, MODE, RAW>(d, a, grid, stream, route);
 }
 template <class L, int MODE, bool RAW>
-int win_launch_as(const swf_block_desc& d, const WinArgs& a, int nwin, hipStream_t stream) {
+int win_launch_as(const swf_block_desc& d, const WinArgs& a, int nwin, hipStream_t stream, int* route = nullptr) {
     const int grid = std::min(nwin, L::WAVES * num_cus());   // resident workgroups per CU (register-limited)
     if constexpr (MODE != WIN_ATTN) {
-        if (d.hidden != L::HID_WIDE) return win_launch_ws<L, L::HID_NARROW, MODE, RAW>(d, a, grid, stream);
+        if (d.hidden != L::HID_WIDE) return win_launch_ws<L, L::HID_NARROW, MODE, RAW>(d, a, grid, stream, route);
     }
-    return win_launch_ws<L, L::HID_WIDE, MODE, RAW>(d, a, grid, stream);
+    return win_launch_ws<L, L::HID_WIDE, MODE, RAW>(d, a, grid, stream, route);
 }
 
 template <class L>
@@ -151,7 +152,7 @@ int win_launch_half(const swf_block_desc& d, int mode, int raw, const void* pack
 template <class L>
 int win_launch(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in, const float* y_in,
                float* x_out, float* y_out, int B, int H, int W, hipStream_t stream, const void* next_packed_x,
-               const void* next_packed_y, size_t next_bytes) {
+               const void* next_packed_y, size_t next_bytes, int* route) {
     const int wsd = d.attn.win_h;
     if (!win_supported<L>(d) || H % wsd || W % wsd) return fail(SWF_ERR_UNSUPPORTED, "%s: shape not covered", L::name);
     if (!win_rows_fit<L>((int64_t)B * H * W))
@@ -161,7 +162,8 @@ int win_launch(const swf_block_desc& d, const void* packed_x, const void* packed
     if (!a.warm[1]) a.warm[0] = nullptr;
     a.warm_bytes = (int)(next_bytes ? next_bytes : win_packed_bytes<L>(d));
     const int nwin = B * (H / wsd) * (W / wsd);
-    if (wsd != 16) return win_launch_as<L, WIN_BLOCK, false>(d, a, nwin, stream);
+    if (wsd != 16) return win_launch_as<L, WIN_BLOCK, false>(d, a, nwin, stream, route);
+    trace_block(route, SWF_BLOCK_WIN_W16);
     return d.hidden == L::HID_WIDE ? L::template launch16<L::HID_WIDE>(a, nwin, stream) : L::template launch16<L::HID_NARROW>(a, nwin, stream);
 }
 

@@ -46,7 +46,7 @@ struct WinLevel {
                        const float* y_in, float* x_out, float* y_out, int B, int H, int W, int ntok_x, int ntok_y, hipStream_t stream);
     int (*launch)(const swf_block_desc& d, const void* packed_x, const void* packed_y, const float* x_in, const float* y_in,
                   float* x_out, float* y_out, int B, int H, int W, hipStream_t stream, const void* next_packed_x,
-                  const void* next_packed_y, size_t next_bytes);
+                  const void* next_packed_y, size_t next_bytes, int* route);   // route: see launch_window_block
 };
 
 const WinLevel& win24_level();   // C = 24 (kernels_win24.hip)

@@ -199,6 +199,12 @@ def _require_elu(act: nn.Module) -> None:
                                   f"nn.ELU(alpha=1) (A000_CONFIG.py:64); got {act!r}")
 
 
+def _schedule_code(s) -> int:
+    if s not in ("latency", "throughput"):
+        raise ValueError(f"schedule must be 'latency' or 'throughput', got {s!r}")
+    return 1 if s == "throughput" else 0
+
+
 def _precision_code(p) -> int:
     if p in (L.PREC_FP32, "fp32"):
         return L.PREC_FP32
@@ -619,6 +625,7 @@ class BasicBlock(_FwdAlias, nn.Module):
         self.mlp_hidden_dims, self.mlp_activation_func, self.mlp_drop_ratio = mlp_hidden_dims, mlp_activation_func, mlp_drop_ratio
         self.input_compatibility_with_cross_option = None
         self.precision = "fast"
+        self.schedule = "latency"   # swf_schedule: 'latency' | 'throughput' (MyModel.schedule has the meaning)
         self.auto_path_win_att = AutoPathWinAtt(in_out_dims, num_heads, dims_per_head, window_size, use_cyclic_shift,
                                                 use_dual_path, use_cross_attr, use_qkv_bias, attention_drop_ratio,
                                                 linear_after_att_drop_ratio)
@@ -642,7 +649,7 @@ class BasicBlock(_FwdAlias, nn.Module):
 
     def _desc(self, precision) -> L.BlockDesc:
         return L.BlockDesc(self.auto_path_win_att.window_attention_x._desc(), self.mlp_hidden_dims,
-                           int(bool(self.use_cross_attr)), _precision_code(precision))
+                           int(bool(self.use_cross_attr)), _precision_code(precision), _schedule_code(self.schedule))
 
     def _stream_params(self, s: str) -> L.BlockStreamParams:
         _require_elu(self.mlp_activation_func)
@@ -773,6 +780,7 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
         self.attention_drop_ratio, self.linear_after_att_drop_ratio = attention_drop_ratio, linear_after_att_drop_ratio
         self.mlp_hidden_dims, self.mlp_activation_func, self.mlp_drop_ratio = mlp_hidden_dims, mlp_activation_func, mlp_drop_ratio
         self.precision = "fast"
+        self.schedule = "latency"   # swf_schedule of the stage's one call (the blocks' own attribute serves their own calls)
         mk = lambda cross: NormalAndShiftWinsBlockPair(in_out_dims, num_heads, dims_per_head, window_size, use_dual_path,
                                                        cross, use_qkv_bias, attention_drop_ratio,
                                                        linear_after_att_drop_ratio, mlp_hidden_dims, mlp_activation_func,
@@ -787,6 +795,7 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
     def forward(self, x, y=None):
         blocks = self._blocks()
         dual = self.use_dual_path
+        sched = _schedule_code(self.schedule)
         if dual and y is None:
             raise ValueError("use_dual_path=True needs both x and y")
         if _wants_grad(self, x, y) or _drops_in_training(self):
@@ -803,6 +812,7 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
         b, c, h, w = x.shape
         xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
         desc = blocks[0]._desc(self.precision)
+        desc.schedule = sched
         px = (L.BlockStreamParams * 4)(*[blk._stream_params("x") for blk in blocks])
         py = (L.BlockStreamParams * 4)(*[blk._stream_params("y") for blk in blocks]) if dual else None
         lib = L.lib()
@@ -1185,9 +1195,7 @@ class MyModel(_FwdAlias, nn.Module):
         d.merge_h, d.merge_w = self.merging_size
         d.head_ksize = self.final_layer_conv_kernel_size
         d.precision = _precision_code(self.precision)
-        if self.schedule not in ("latency", "throughput"):
-            raise ValueError(f"schedule must be 'latency' or 'throughput', got {self.schedule!r}")
-        d.schedule = 1 if self.schedule == "throughput" else 0
+        d.schedule = _schedule_code(self.schedule)
         return d
 
     def refresh_weights(self) -> None:

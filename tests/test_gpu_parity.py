@@ -631,14 +631,14 @@ _WIDE = [  # C, heads, d, hidden, (B,H,W), shift, cross
     (48, 8, 6, 96, (1, 24, 16), True, False),      # decoder width (hidden = in_dims * 4)
     (96, 8, 12, 384, (1, 16, 16), True, True),
     (96, 8, 12, 192, (2, 8, 16), False, True),
-    (24, 8, 3, 4, (1, 16, 16), True, True),        # level-0 decoder width: window24_kernel<4, 8> as a single block
-    # deep-level fast path (kernels_deep / kernels_mlp): split-bf16 plane GEMMs, MFMA attention core, fused LN2+MLP kernel
+    (24, 8, 3, 4, (1, 16, 16), True, True),        # level-0 decoder width (hidden 4) as a single block
+    # deep-level widths (which kernels serve them is asserted per block by tests/test_gpu_block_fast.py, through the route code)
     (192, 8, 24, 768, (1, 8, 8), True, True),
     (384, 8, 48, 1536, (2, 8, 8), True, False),
-    (192, 8, 24, 384, (2, 8, 8), False, True),      # decoder widths (hidden = in_dims * 4): no hidden split / 3 splits
+    (192, 8, 24, 384, (2, 8, 8), False, True),      # decoder widths (hidden = in_dims * 4)
     (384, 8, 48, 768, (1, 8, 8), True, True),
-    (192, 8, 24, 768, (2, 16, 16), True, False),    # several 64-token tiles per stream
-    (192, 8, 24, 768, (1, 16, 24), True, True),     # map larger than 16x16: the projection runs as its own GEMM (swf_api.hip: proj_fused)
+    (192, 8, 24, 768, (2, 16, 16), True, False),    # 512 tokens per stream
+    (192, 8, 24, 768, (1, 16, 24), True, True),     # map larger than 16x16 (256 tokens)
     (128, 4, 24, 512, (1, 8, 16), True, True),      # heads * d (96) != C: projection K = 96; fused MLP instantiation C = 128
     (256, 8, 24, 1024, (1, 8, 8), False, False),    # heads * d = 192; fused MLP instantiation C = 256
 ]
@@ -668,8 +668,8 @@ def test_basic_block_wide_vs_oracle(case, precision):
 _SINGLE = [  # single-path blocks (use_dual_path=False, a005:54-76): C, heads, d, hidden, (B,H,W), shift
     (24, 8, 3, 96, (2, 16, 16), True),
     (96, 8, 12, 384, (1, 16, 8), False),
-    (192, 8, 24, 768, (2, 8, 16), True),     # deep path with one stream: qkv_attn, fused MLP with a hidden split
-    (384, 8, 48, 1536, (2, 8, 8), True),     # level-4 launches with one stream: rows x fragment-major Q/K/V, attention + projection, 8-wave MLP
+    (192, 8, 24, 768, (2, 8, 16), True),     # deep level 3 with one stream
+    (384, 8, 48, 1536, (2, 8, 8), True),     # level 4 with one stream
     (384, 8, 48, 768, (1, 8, 16), False),
 ]
 
@@ -702,8 +702,8 @@ _WIN7 = [  # 7x7 windows (the reference's default, A000_CONFIG.py:55) at every l
     (48, 8, 6, 96, (1, 21, 14), False, False),
     (96, 8, 12, 384, (1, 14, 14), True, True),
     (96, 8, 12, 192, (2, 7, 14), True, False),
-    (24, 8, 3, 4, (1, 14, 14), True, True),         # level-0 decoder width: window24_kernel<4, 7>
-    # more than 16 windows per map: the four-wave window96_kernel<HID, 7> (smaller maps run window96x8_kernel)
+    (24, 8, 3, 4, (1, 14, 14), True, True),         # level-0 decoder width, 7x7 windows
+    # more than 16 windows per map (tests/test_gpu_block_fast.py asserts which level-2 kernel runs either side of that boundary)
     (96, 8, 12, 384, (1, 35, 35), True, False),
     (96, 8, 12, 192, (1, 35, 35), True, True),
     (192, 8, 24, 768, (2, 14, 14), True, True),

@@ -11,7 +11,6 @@ import ctypes as C
 import faulthandler
 import json
 import os
-import re
 
 import pytest
 import torch
@@ -20,24 +19,14 @@ import __graft_entry__ as entry
 from swin_unet_image_fusion_amd import _lib as L
 from tests import golden_util as G
 from tests import patch_cases as PC
+from tests.gpu_guard import BF16_NAN, DEV, Guarded, planes_to_float as _planes_to_float, record_dir as _record_dir
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL_FP32, TOL_FAST_L2, TOL_FAST_MAX = 2e-5, 1e-3, 1e-3   # the gates of tests/test_gpu_parity.py
-GUARD, PATTERN = 4096, 0xA5
-BF16_NAN = 0x7FC0
 PRECS = [("fp32", L.PREC_FP32), ("fast", L.PREC_FAST)]
 B3_MERGE, B3_UNMERGE = PC.MERGE_MAPS[0][0], PC.UNMERGE_MAPS[0][0]
 
 _LOG = []   # (test id, rel-L2, max-rel)
-
-
-def _record_dir():
-    """The directory tests/test_gpu_parity.py keeps its parity.json in: that module is the one place that names it."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    with open(os.path.join(here, "test_gpu_parity.py")) as f:
-        m = re.search(r'out_dir = os\.path\.join\(.*, "(\w+)"\)', f.read())
-    return os.path.join(os.path.dirname(here), m.group(1))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -69,30 +58,12 @@ def _stream():
     return torch.cuda.current_stream(DEV).cuda_stream
 
 
-class Guarded:
-    """A tensor carved out of a larger allocation whose bytes either side hold a fixed pattern."""
-
-    def __init__(self, shape, dtype=torch.float32):
-        n = int(torch.Size(shape).numel()) * torch.empty((), dtype=dtype).element_size()
-        self.whole = torch.full((n + 2 * GUARD,), PATTERN, dtype=torch.uint8, device=DEV)
-        self.t = self.whole[GUARD:GUARD + n].view(dtype).view(shape)
-        self.n = n
-
-    def intact(self):
-        return bool((self.whole[:GUARD] == PATTERN).all()) and bool((self.whole[GUARD + self.n:] == PATTERN).all())
-
-
 def _nhwc(t):
     return None if t is None else t.permute(0, 2, 3, 1).contiguous().to(DEV)
 
 
 def _nchw(t):
     return t.permute(0, 3, 1, 2).cpu()
-
-
-def _planes_to_float(hi, lo):
-    f = lambda p: ((p.to(torch.int32) & 0xFFFF) << 16).view(torch.float32)
-    return f(hi) + f(lo)
 
 
 _params_cache = {}

@@ -3,8 +3,10 @@ size hold a fixed pattern, an entry gives bitwise the output it gives with twice
 (modules._workspace() over-allocates by a quarter, so the rest of the suite cannot see an under-counting query).
 
 The stand-alone patch entries take the generic route at every level (the deep-level patch kernels need the model's packed images), so
-the column-sliced and whole-row deep patch routes, like the pre-packed window and deep block routes, are exercised by the three model
-cases only.  Every case runs once, under a watchdog of its own that ends the process when a call does not return."""
+here the column-sliced and whole-row deep patch routes, like the pre-packed window and deep block routes, are exercised by the three
+model cases only; per layer and per stage they run in exactly their queried, guarded workspace in tests/test_gpu_patch_fast.py
+(swf_patch_*_fwd_prec) and tests/test_gpu_block_fast.py (swf_block_stage_fwd_prec: pre-packed images, the LN1 chain, the 16x16
+ping-pong).  Every case runs once, under a watchdog of its own that ends the process when a call does not return."""
 import ctypes as C
 import faulthandler
 

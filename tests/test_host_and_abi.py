@@ -115,6 +115,62 @@ def test_patch_prec_entries_validate_without_gpu():
     assert route.value == -7   # a refused call reports no route
 
 
+def test_block_route_entries_validate_without_gpu():
+    """swf_basic_block_fwd_route / swf_block_stage_fwd_prec refuse bad arguments before anything is packed or launched, and a refused
+    call leaves the caller's route untouched."""
+    lib = L.lib()
+    P = 4096   # a fake device pointer
+    lin = lambda: L.Linear(P, P)
+    sp = lambda: L.BlockStreamParams(L.Norm(P, P), L.AttnParams(lin(), lin(), lin(), lin(), P), L.Norm(P, P), lin(), lin())
+    four = lambda: (L.BlockStreamParams * 4)(*[sp() for _ in range(4)])
+    hole = four()
+    hole[2].fc1.weight = None                                # a missing layer in the third block
+    good = L.BlockDesc(L.AttnDesc(192, 8, 24, 8, 8, 0), 768, 0, L.PREC_FAST, 1)
+    ln, ln_null = L.PatchLn1(L.Norm(P, P), P, P), L.PatchLn1(L.Norm(P, None), P, P)
+    route = (C.c_int32 * 4)(-7, -7, -7, -7)
+    block = lambda desc=good, px=four(), py=four(), xi=P, yi=P, xo=P, yo=P, m=(2, 8, 16): \
+        lib.swf_basic_block_fwd_route(C.byref(desc) if desc else None, px, py, xi, yi, xo, yo, *m, route, None, 0, None)
+    stage = lambda desc=good, px=four(), py=four(), xi=P, yi=P, xo=P, yo=P, m=(2, 8, 16), lx=None, ly=None: \
+        lib.swf_block_stage_fwd_prec(C.byref(desc) if desc else None, px, py, xi, yi, xo, yo, *m, C.byref(lx) if lx else None,
+                                     C.byref(ly) if ly else None, route, None, 0, None)
+    for call in (block, stage):
+        assert call() == L.ERR_WORKSPACE                           # everything else in order: the workspace is what is missing
+        assert call(py=None, yi=None, yo=None) == L.ERR_WORKSPACE   # one stream
+        assert call(desc=None) == L.ERR_NULL and call(px=None) == L.ERR_NULL
+        assert call(xi=None) == L.ERR_NULL and call(xo=None) == L.ERR_NULL and call(yi=None) == L.ERR_NULL and call(yo=None) == L.ERR_NULL
+        for m in ((0, 8, 16), (2, 0, 16), (2, 8, 12), (2, 9, 16)):     # empty batch or map, map no multiple of the window
+            assert call(m=m) == L.ERR_BAD_SHAPE, m
+        for bad in (L.BlockDesc(L.AttnDesc(0, 8, 24, 8, 8, 0), 768, 0, L.PREC_FAST, 0), L.BlockDesc(L.AttnDesc(192, 8, 24, 8, 0, 0), 768, 0, L.PREC_FAST, 0),
+                    L.BlockDesc(L.AttnDesc(192, 8, 24, 8, 8, 0), 0, 0, L.PREC_FAST, 0)):
+            assert call(desc=bad) == L.ERR_BAD_SHAPE
+    assert stage(px=hole) == L.ERR_NULL and stage(py=hole) == L.ERR_NULL
+    assert stage(desc=L.BlockDesc(L.AttnDesc(192, 8, 24, 8, 8, 0), 768, 0, 2, 0)) == L.ERR_BAD_SHAPE       # unknown precision
+    assert stage(lx=ln) == L.ERR_NULL and stage(ly=ln) == L.ERR_NULL                                       # planes for every stream or for none
+    assert stage(lx=ln, ly=ln_null) == L.ERR_NULL and stage(py=None, yi=None, yo=None, ly=ln) == L.ERR_NULL
+    assert stage(lx=ln, ly=ln) == L.ERR_WORKSPACE and stage(py=None, yi=None, yo=None, lx=ln) == L.ERR_WORKSPACE
+    q = lib.swf_block_stage_prec_workspace_bytes
+    assert q(C.byref(good), 1, 2, 8, 16) > 0 and q(None, 1, 2, 8, 16) == 0 and q(C.byref(good), 1, 2, 8, 12) == 0
+    assert q(C.byref(L.BlockDesc(L.AttnDesc(192, 8, 24, 8, 8, 0), 768, 0, 2, 0)), 1, 2, 8, 16) == 0
+    assert list(route) == [-7] * 4
+
+
+def test_block_modules_validate_their_schedule():
+    """BasicBlock and SelfAndCrossBlockPair carry the schedule of their own calls (swf_block_desc.schedule), validated like MyModel's."""
+    from swin_unet_image_fusion_amd import BasicBlock
+    blk = BasicBlock(24, 8, 3, (8, 8), True, True, True, True, 0.0, 0.0, 96, nn.ELU(inplace=True), 0.0)
+    assert blk.schedule == "latency" and blk._desc("fast").schedule == 0
+    blk.schedule = "throughput"
+    assert blk._desc("fast").schedule == 1 and blk._desc("fp32").schedule == 1
+    blk.schedule = "fastest"
+    with pytest.raises(ValueError, match="schedule"):
+        blk._desc("fast")
+    pair = SelfAndCrossBlockPair(24, 8, 3, (8, 8), True, True, 0.0, 0.0, 96, nn.ELU(inplace=True), 0.0)
+    assert pair.schedule == "latency"
+    pair.schedule = "fastest"
+    with pytest.raises(ValueError, match="schedule"):      # refused before any tensor is touched
+        pair(torch.zeros(1, 24, 8, 8), torch.ones(1, 24, 8, 8))
+
+
 @pytest.mark.parametrize("cfg_name", ["win8", "win7", "tiny", "tiny7", "win8_4stage", "win16"])
 def test_state_dict_matches_reference_key_table(cfg_name):
     with open(os.path.join(G.GOLDEN, f"state_keys_{cfg_name}.json")) as f:

@@ -209,6 +209,46 @@ def test_patch_prec_entries_need_exactly_their_query(prec, dual):
             assert max(needs.values()) <= lib.swf_patch_workspace_bytes(2, 8, 8, cin, cout, 2, 2, 4, 4, 0) < max(needs.values()) + 256
 
 
+STAGE_SHAPES = {"generic_fp32": GENERIC_FP32, "generic_fast": GENERIC_FAST, "deep3": DEEP, "deep4": DEEP4, "window": WINDOW, "window16": WINDOW16,
+                "window96_16": (_block_desc(96, 8, 12, 16, 384, L.PREC_FAST, cross=1), 2, 32, 16)}
+
+
+@pytest.mark.parametrize("sched", [0, 1], ids=["latency", "throughput"])
+@pytest.mark.parametrize("name", sorted(STAGE_SHAPES))
+def test_block_entries_with_a_route_need_exactly_their_query(name, sched):
+    """swf_basic_block_fwd_route shares swf_basic_block_fwd's query.  swf_block_stage_fwd_prec: the eight packed images and the room of
+    block_pair4_impl are one carve, checked before the first launch (the pack); the query is a multiple of the carve alignment, covers
+    the images plus the largest need of the four blocks, and for the 16x16 kernels that cannot run in place the two temporary maps."""
+    lib = L.lib()
+    d0, b, h, w = STAGE_SHAPES[name]
+    desc = L.BlockDesc(d0.attn, d0.hidden, d0.cross, d0.precision, sched)
+    four = lambda: (L.BlockStreamParams * 4)(*[_stream_params() for _ in range(4)])
+    px, py = four(), four()
+    route = (C.c_int32 * 4)(-7, -7, -7, -7)
+    need1 = lib.swf_basic_block_workspace_bytes(C.byref(desc), b, h, w)
+    block = lambda ws, n: lib.swf_basic_block_fwd_route(C.byref(desc), px, py, P, 2 * P, P, 2 * P, b, h, w, route, ws, n, None)
+    if name == "window96_16":            # (at this map the generic composition, which the query also covers, needs more than the fused route)
+        _named_need_at_most(block, need1)
+    else:
+        _refuses(block, need1)
+    need = lib.swf_block_stage_prec_workspace_bytes(C.byref(desc), 1, b, h, w)
+    assert need % 256 == 0
+    _refuses(lambda ws, n: lib.swf_block_stage_fwd_prec(C.byref(desc), px, py, P, 2 * P, P, 2 * P, b, h, w, None, None, route, ws, n, None), need)
+    assert list(route) == [-7] * 4   # a refused call reports no route
+    fast = desc.precision == L.PREC_FAST
+    images = 8 * max(lib.swf_basic_block_packed_bytes(C.byref(desc)) // 2, 0) if fast else 0
+    maps = 2 * b * h * w * desc.attn.channels * 4
+    if name.startswith("window"):       # the blocks carve nothing when their images are given; the 16x16 kernels at C = 48 / 96: + two maps
+        assert images > 0 and need == images + (maps if "16" in name else 0)
+    elif name.startswith("deep"):       # eight deep-level images (they have no public size query) in front of one block's need
+        assert need > need1 and (need - need1) % 8 == 0
+    else:                                # no images: the room of one block
+        assert need == need1
+    one = lib.swf_block_stage_prec_workspace_bytes(C.byref(desc), 0, b, h, w)
+    assert 0 < one <= need and one % 256 == 0
+    _refuses(lambda ws, n: lib.swf_block_stage_fwd_prec(C.byref(desc), px, None, P, None, P, None, b, h, w, None, None, route, ws, n, None), one)
+
+
 def _model_desc(cfg, prec, sched):
     d = L.ModelDesc()
     d.levels = cfg.n_levels
@@ -240,6 +280,7 @@ def test_invalid_shapes_give_zero_from_every_query():
         for q in (lib.swf_window_attention_workspace_bytes, lib.swf_window_attention_bwd_workspace_bytes, lib.swf_window_attention_drop_workspace_bytes):
             assert q(C.byref(ad), b, h, w) == 0
         assert lib.swf_model_workspace_bytes(C.byref(md), b, h, w) == 0
+        assert lib.swf_block_stage_prec_workspace_bytes(C.byref(bd), 1, b, h, w) == 0
         assert lib.swf_final_head_bwd_workspace_bytes(b, h, w, 3) == 0
         for enc in (0, 1):
             assert lib.swf_patch_workspace_bytes(b, h, w, 8, 16, 2, 2, 4, 4, enc) == 0
