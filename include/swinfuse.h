@@ -560,6 +560,45 @@ size_t swf_fusion_loss_workspace_bytes(const swf_loss_desc* desc, int32_t B, int
 int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float* ir, const float* vis, float* terms, float* grad_fusion,
                     int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- fusion-quality metrics of fused images against their two sources, ten values per image in one call ------------
+ * The numbers the field reports for a fusion method (the reference's README claims them; neither it nor a016 / a017 computes one).
+ * Restated from the published definitions and the common open evaluators; no MATLAB or VIFB toolkit is available to this build:
+ * PARITY WITH ANY OF THEM IS UNPINNED.  VIF and Nabf are not provided; SSIM is the loss's (swf_fusion_loss, ssim_mode 1).
+ * Levels.  Every metric is a function of 8-bit levels, quantised as torchvision save_image does, in fp32 with two roundings:
+ * q = (int) min(max(fadd(fmul(x, 255), 0.5), 0), 255) (never one fused multiply-add; NaN -> 0), so a stored uint8 image passed as
+ * u8 / 255.0f evaluates exactly.  F, A, B = the level images of fusion, ir, vis as reals 0..255, N = H W.
+ *   EN    -sum p_k log2 p_k over F's 256-bin histogram, empty bins skipped (+0 for one bin)
+ *   MI    MI(F, A) + MI(F, B), MI(X, Y) = sum p_xy log2(p_xy / (p_x p_y)) over the 256x256 joint histogram, empty cells skipped
+ *   SD    sqrt(mean (F - mean F)^2)
+ *   SF    sqrt(RF^2 + CF^2), RF^2 = mean of (F[h][w] - F[h][w-1])^2 over the H (W - 1) differences, CF^2 the same down the columns;
+ *         an axis of length 1 contributes 0
+ *   AG    mean over the (H - 1)(W - 1) positions of sqrt((gx^2 + gy^2) / 2), gx = F[h][w+1] - F[h][w], gy = F[h+1][w] - F[h][w];
+ *         0 when H or W is 1
+ *   CC    (r(A, F) + r(B, F)) / 2, r = Pearson's coefficient, defined as 0 when either variance is 0
+ *   SCD   r(F - B, A) + r(F - A, B), same convention
+ *   MSE   (mean (F - A)^2 + mean (F - B)^2) / 2 on levels;   PSNR = 10 log10(255^2 / MSE), +inf at MSE = 0
+ *   QABF  Xydeas & Petrovic: Sobel responses with a zero border, sx with [-1 0 1; -2 0 2; -1 0 1], sy with [1 2 1; 0 0 0; -1 -2 -1];
+ *         g = sqrt(sx^2 + sy^2), alpha = atan(sy / sx), pi/2 where sx = 0; sx, sy are exact integers and every comparison is made on
+ *         them and on the integer sx^2 + sy^2.  For X in {A, B}: G = g_F / g_X where g_X > g_F, g_F where they are equal (the
+ *         published code's convention: 0 on flat pixels), else g_X / g_F; A = 1 - |alpha_X - alpha_F| / (pi/2);
+ *         Q_X = Tg / (1 + e^(kg (G - Dg))) Ta / (1 + e^(ka (A - Da))); QABF = sum(Q_A g_A + Q_B g_B) / sum(g_A + g_B), 0 when the
+ *         denominator is 0.  Usual constants: Tg 0.9994, kg -15, Dg 0.5, Ta 0.9879, ka -22, Da 0.8.
+ * Arithmetic.  Counts and sums of integer products are exact (u32 counters, u64 sums, integer atomics); everything the histograms
+ * determine is derived from them (centred fp64 sums over bins and cells); AG and Qabf per pixel in fp64 (IEEE sqrt and division,
+ * ocml atan and exp), summed through per-tile partials in a fixed order.  No float atomics: results are bit-identical from call to
+ * call, and an image's row does not depend on the rest of its batch. */
+typedef struct swf_metrics_desc { double Tg, kg, Dg, Ta, ka, Da; } swf_metrics_desc;   /* Qabf constants */
+enum { SWF_METRIC_EN, SWF_METRIC_MI, SWF_METRIC_SD, SWF_METRIC_SF, SWF_METRIC_AG, SWF_METRIC_CC,
+       SWF_METRIC_SCD, SWF_METRIC_MSE, SWF_METRIC_PSNR, SWF_METRIC_QABF, SWF_METRIC_COUNT };
+/* 0 for a shape swf_fusion_metrics would refuse */
+size_t swf_fusion_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_METRIC_COUNT], one row per image.  The call zeroes the part of the
+ * workspace it accumulates into, allocates nothing and does not synchronise the host, so it can be captured into a hipGraph.
+ * SWF_ERR_BAD_SHAPE for H W > 2^30 (the pixel indices and u32 counters of the kernels) or B > 65535 (split the batch). */
+int swf_fusion_metrics(const swf_metrics_desc* desc, const float* fusion, const float* ir, const float* vis,
+                       double* out /* device [B][SWF_METRIC_COUNT] */, int32_t B, int32_t H, int32_t W,
+                       void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);
  * v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps), IEEE sqrt and division, no atomics.

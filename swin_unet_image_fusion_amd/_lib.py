@@ -97,6 +97,13 @@ class LossDesc(C.Structure):
                 ("ssim_ratio", C.c_float), ("texture_ratio", C.c_float), ("intensity_ratio", C.c_float), ("psnr_ratio", C.c_float)]
 
 
+class MetricsDesc(C.Structure):   # swf_metrics_desc: the Qabf constants
+    _fields_ = [("Tg", C.c_double), ("kg", C.c_double), ("Dg", C.c_double), ("Ta", C.c_double), ("ka", C.c_double), ("Da", C.c_double)]
+
+
+METRIC_COUNT = 10   # SWF_METRIC_COUNT
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -207,6 +214,8 @@ SIGNATURES = {
     "swf_tensors_equal": (C.c_int, [_vp, _vp, _i64, _vp, _vp]),
     "swf_fusion_loss_workspace_bytes": (_sz, [P(LossDesc), _i32, _i32, _i32, _i32]),
     "swf_fusion_loss": (C.c_int, [P(LossDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_metrics_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_metrics": (C.c_int, [P(MetricsDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

@@ -1,0 +1,98 @@
+"""Fusion-quality metrics on libswinfuse: EN, MI, SD, SF, AG, CC, SCD, MSE, PSNR and Qabf of a batch of fused images against their
+infrared and visible sources in one fused HIP call (swf_fusion_metrics; include/swinfuse.h has every definition).
+
+Every metric is a function of 8-bit levels.  The quantiser is torchvision save_image's, in fp32 with its two roundings,
+`(int) min(max(x * 255 + 0.5, 0), 255)` (never one fused multiply-add; NaN -> level 0), so stored uint8 images passed as `u8 / 255`
+evaluate exactly.  Conventions for degenerate images: EN of a one-level image is +0; an axis of length 1 contributes 0 to SF and makes
+AG 0; Pearson's r (CC, SCD) is 0 when either variance is 0; PSNR is +inf at MSE = 0; Qabf is 0 when no source pixel has a gradient
+(its Sobel responses see a zero border, so a flat non-black image has edges along its frame).
+
+The definitions are restated from the published ones and the common open evaluators; no MATLAB or VIFB toolkit is available to this
+build, so parity with any of them is unpinned.  VIF and Nabf are not provided.  SSIM is already available as
+`MyLoss(choose_ms_ssim=False).calcu_ssim_loss`.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import torch
+from torch import Tensor
+
+from . import _lib as L
+from .modules import _ptr, _stream, _workspace
+
+__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "fusion_metrics", "FusionMetrics"]
+
+METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
+QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
+
+
+def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
+    for name, t in (("fusion_images", fusion), ("ir_images", ir), ("vis_images", vis)):
+        if t.dim() != 4:
+            raise ValueError(f"{name}: expected a 4-D (batch, 1, height, width) tensor, got shape {tuple(t.shape)}")
+        if t.shape[1] != 1:
+            raise NotImplementedError(f"{name}: the metric kernels take single-channel images, got {t.shape[1]} channels")
+        if t.dtype != torch.float32:
+            raise NotImplementedError(f"{name}: the metric kernels are fp32 only, got {t.dtype}")
+        if not t.is_cuda:
+            raise NotImplementedError(f"{name}: the metrics run on the GPU only (there is no CPU path), got a tensor on {t.device}")
+    if not (fusion.shape == ir.shape == vis.shape):
+        raise ValueError(f"shapes differ: fusion {tuple(fusion.shape)}, ir {tuple(ir.shape)}, vis {tuple(vis.shape)}")
+    if torch.is_grad_enabled() and (fusion.requires_grad or ir.requires_grad or vis.requires_grad):
+        raise RuntimeError("the metrics are not differentiable (functions of 8-bit levels): call them under torch.no_grad() or on "
+                           "detached tensors")
+
+
+def _desc(qabf_constants: dict) -> L.MetricsDesc:
+    unknown = set(qabf_constants) - set(QABF_DEFAULTS)
+    if unknown:
+        raise TypeError(f"fusion_metrics: unknown Qabf constant(s) {sorted(unknown)}; the constants are {list(QABF_DEFAULTS)}")
+    c = {**QABF_DEFAULTS, **qabf_constants}
+    return L.MetricsDesc(*(float(c[k]) for k in QABF_DEFAULTS))
+
+
+def fusion_metrics(fusion: Tensor, ir: Tensor, vis: Tensor, **qabf_constants) -> Tensor:
+    """-> (B, 10) float64 tensor on the inputs' device, row b = the METRIC_NAMES values of image b.  Inputs: (B, 1, H, W) fp32 CUDA
+    tensors of one shape.  Keyword arguments replace Qabf constants (Tg, kg, Dg, Ta, ka, Da).  One library call on the current stream,
+    no host synchronisation; bit-identical from call to call."""
+    desc = _desc(qabf_constants)
+    _check_images(fusion, ir, vis)
+    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
+    b, _, h, w = f.shape
+    lib = L.lib()
+    need = lib.swf_fusion_metrics_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
+    out = torch.empty((b, L.METRIC_COUNT), dtype=torch.float64, device=f.device)
+    ws, wsn = _workspace(need, f.device)
+    L.check(lib.swf_fusion_metrics(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
+    return out
+
+
+class FusionMetrics:
+    """Running mean of the ten metrics over every image passed to update().  The sum lives on the device and update() does not
+    synchronise; compute() reads it back once.  The image count is a host int (`count`): the batch size is known on the host, so
+    counting there needs no synchronisation and no device scalar."""
+
+    def __init__(self, **qabf_constants):
+        _desc(qabf_constants)   # refuse a misspelt constant here, not at the first batch
+        self.qabf_constants = qabf_constants
+        self.reset()
+
+    def reset(self) -> None:
+        self._sum: Optional[Tensor] = None
+        self.count = 0
+
+    def update(self, fusion: Tensor, ir: Tensor, vis: Tensor) -> Tensor:
+        """Adds the batch's rows; -> the rows, (B, 10) float64 on the device."""
+        rows = fusion_metrics(fusion, ir, vis, **self.qabf_constants)
+        s = rows.sum(dim=0)
+        self._sum = s if self._sum is None else self._sum + s
+        self.count += rows.shape[0]
+        return rows
+
+    def compute(self) -> Dict[str, float]:
+        """{name: mean over the images seen since reset()}, one device-to-host copy."""
+        if self.count == 0:
+            raise RuntimeError("FusionMetrics.compute(): no image since reset()")
+        return dict(zip(METRIC_NAMES, (self._sum / self.count).tolist()))

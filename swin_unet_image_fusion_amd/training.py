@@ -6,7 +6,7 @@ from __future__ import annotations
 import torch
 from torch import Tensor
 
-__all__ = ["train_step", "fractional_epoch", "save_training_state", "load_training_state"]
+__all__ = ["train_step", "validate", "fractional_epoch", "save_training_state", "load_training_state"]
 
 STATE_KEYS = ("model_state", "optimizer_state", "scheduler_state", "current_epoch")   # a016:243-248
 
@@ -21,6 +21,28 @@ def train_step(model, loss_fn, optimizer, ir: Tensor, vis: Tensor):
     loss.backward()
     optimizer.step()
     return loss, detail
+
+
+def validate(model, loss_fn, loader, metrics=None):
+    """The reference's vali() (a016:198-236) without the figure it saves: remember model.training, eval(), and under no_grad per batch
+    forward, clamp_(0, 1), loss_fn.calcu_total_loss (which feeds the loss's own recorder, as the reference's val_loss_calculator is
+    fed) and, when `metrics` (a FusionMetrics) is given, its update; then restore the mode.  `loader` yields the reference's batch
+    dicts (`ir`, `vis` first: PairLoader) or (ir, vis) pairs, already on the model's device.  -> metrics.compute(), or None."""
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            for batch in loader:
+                ir, vis = list(batch.values())[:2] if isinstance(batch, dict) else batch[:2]
+                fusion = model(ir, vis)
+                fusion = torch.clamp_(fusion, min=0, max=1)
+                loss_fn.calcu_total_loss(fusion_images=fusion, ir_images=ir, vis_images=vis)
+                if metrics is not None:
+                    metrics.update(fusion, ir, vis)
+    finally:
+        if was_training:
+            model.train()
+    return metrics.compute() if metrics is not None else None
 
 
 def fractional_epoch(epoch: int, iter_in_epoch: int, iters_per_epoch: int) -> float:
