@@ -1,0 +1,387 @@
+"""Case table and float64 references of the backward parity tests past the first level of the reduction trees
+(tests/test_gpu_backward_trees.py on the GPU, tests/test_bwd_tree_cases_host.py for the depth, the tails and the conditioning of every
+case on the CPU).
+
+Every parameter gradient of kernels_bwd.hip is a sum over tokens, windows or pixels in a fixed tree: the producing kernel writes partial
+rows, reduce_rows sums GROUP = 32 consecutive rows per level, the intermediate levels live behind the partial rows.  Four trees:
+
+    dw     weight / bias gradients of every linear layer     ceil(tokens / 256) chunk rows
+    ln     d gamma / d beta of every LayerNorm               4 * ceil(tokens / 32) wave rows
+    table  relative-position bias table gradient             windows * heads rows
+    head   conv1 / conv2 / BatchNorm gradients, statistics   ceil(pixels / 256) chunk rows
+
+levels() / tree_rows() restate the tree's shape; rows() gives, per case, the row counts of the sums it exercises, and Case.depth the
+number of reduce_rows launches the table claims for them (held by the host test).  Tree depth depends on the token count only, so the
+cases run at the narrowest widths (C = 8 .. 16), where the float64 oracle costs seconds.
+
+Weights are the `stress` recipe, inputs G.randn (the model: synthetic_pair).  The reference is torch.autograd of the CPU oracle
+(oracle/swin_fusion_oracle.py; with dropout tests/dropout_util.py on the masks of the numpy Philox restatement), for the two direct
+entries plain F.layer_norm and F.linear / F.elu.  Every reference gives two backward passes of one forward: `dense`, the upstream
+gradient a random linear functional of the outputs, and `tail`, the same functional zero everywhere except the last 16 tokens of the
+last image (direct entries: the last token), so that parameter gradients reach the result through the last group of every level."""
+from __future__ import annotations
+
+import functools
+from dataclasses import dataclass, replace
+from typing import Dict, List, Tuple
+
+import torch
+import torch.nn.functional as F
+from torch import nn
+
+from oracle import swin_fusion_oracle as O
+from swin_unet_image_fusion_amd import (CONFIGS, BasicBlock, MyModel, PatchMergingAndLinearLayer, StateRecorder, WindowAttention,
+                                        load_recipe_into, synthetic_pair)
+from swin_unet_image_fusion_amd.config import make_state_arrays
+from tests import dropout_util as D
+from tests import golden_util as G
+
+CHUNK, GROUP, LN_ROWS_PER_BLOCK, LN_WAVES = 256, 32, 32, 4     # kChunk, kGroup, 4 waves x kLnRows, waves per block (kernels_bwd.hip)
+TREES = ("dw", "ln", "table", "head")
+MODES = ("dense", "tail")
+TAIL_TOKENS = 16
+
+
+# ---- the tree, restated ------------------------------------------------------------------------------------------------------------
+def cdiv(a: int, b: int) -> int:
+    return -(-a // b)
+
+
+def level_rows(rows: int) -> List[int]:
+    """Row counts that each reduce_rows launch reads: the partial rows, then every intermediate level."""
+    out = [rows]
+    while rows > GROUP:
+        rows = cdiv(rows, GROUP)
+        out.append(rows)
+    return out
+
+
+def levels(rows: int) -> int:
+    """Number of reduce_rows launches for `rows` partial rows: one more each time the count passes 32, 1 024, 32 768."""
+    return len(level_rows(rows))
+
+
+def tree_rows(rows: int) -> int:
+    """Rows the buffer of a tree holds: the partial rows and every intermediate level behind them."""
+    return sum(level_rows(rows))
+
+
+def last_groups(rows: int) -> List[int]:
+    """Size of the last group of each grouped level (levels that reduce more than GROUP rows)."""
+    return [(r - 1) % GROUP + 1 for r in level_rows(rows) if r > GROUP]
+
+
+def chunks(tokens: int) -> int:
+    return cdiv(tokens, CHUNK)
+
+
+def ln_rows(tokens: int) -> int:
+    return LN_WAVES * cdiv(tokens, LN_ROWS_PER_BLOCK)
+
+
+def workload_depths(batch: int, side: int) -> Dict[str, int]:
+    """Tree depths of a win8_4stage training step on batch x side x side images: level 0 (the 2x2-merged map, 8 heads, 8x8 windows),
+    the head on the full map."""
+    tokens = batch * (side // 2) ** 2
+    return {"dw": levels(chunks(tokens)), "ln": levels(ln_rows(tokens)), "table": levels(batch * (side // 16) ** 2 * 8),
+            "head": levels(chunks(batch * side * side))}
+
+
+# ---- cases -------------------------------------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Case:
+    kind: str                 # "block" | "attention" | "layernorm" | "mlp" | "patch" | "head" | "model"
+    name: str
+    depth: Tuple[Tuple[str, Tuple[int, ...]], ...]   # claimed levels of every sum of rows(case), tree by tree
+    C: int = 0                # block / attention / direct entries: channels; patch: input channels
+    heads: int = 0
+    head_dim: int = 0
+    hidden: int = 0           # block / mlp: hidden width; patch: output channels
+    win: int = 0
+    B: int = 1
+    H: int = 0
+    W: int = 0
+    N: int = 0                # direct entries: tokens
+    drop: float = 0.0         # block: all three drop ratios
+    encoder: bool = True      # patch
+    train: bool = True        # head: batch statistics (train()) or running statistics (eval())
+    cfg: str = "tiny"         # head / model
+    seed: int = 0
+
+    @property
+    def id(self) -> str:
+        return self.name
+
+    @property
+    def metric(self) -> str:
+        """Which criterion of tests/test_gpu_backward.py holds the case: its block test's or its whole-model test's."""
+        return "block" if self.kind in ("block", "layernorm", "mlp", "patch") else "model"
+
+    @property
+    def direct(self) -> bool:
+        return self.kind in ("layernorm", "mlp")
+
+
+def _d(**kw) -> Tuple[Tuple[str, Tuple[int, ...]], ...]:
+    return tuple((t, tuple(v) if isinstance(v, (tuple, list)) else (v,)) for t, v in kw.items())
+
+
+_BLOCK = dict(C=8, heads=2, head_dim=4)
+_TABLE = [
+    # BasicBlock, shift + cross, two streams: one level deeper everywhere (34 chunks, the last of 16 tokens; 1 060 LN rows; 1 058 table rows)
+    Case("block", "block_w4_92x92", _d(dw=2, ln=3, table=3), **_BLOCK, hidden=32, win=4, H=92, W=92),
+    # the training step's depth and beyond: 1 040 chunks -> 33 -> 2 -> 1; 33 280 LN rows; 8 320 table rows
+    Case("block", "block_w8_512x520", _d(dw=3, ln=4, table=3), **_BLOCK, hidden=8, win=8, H=512, W=520),
+    # the first case through swf_basic_block_bwd_drop, which carves a different workspace around the same trees
+    Case("block", "block_w4_92x92_drop", _d(dw=2, ln=3, table=3), **_BLOCK, hidden=32, win=4, H=92, W=92, drop=0.1),
+    # WindowAttention alone, cross mode (k = v = the other stream): 4 160 windows x 8 heads = 33 280 table rows
+    Case("attention", "attention_w4_256x260", _d(dw=2, table=4), C=16, heads=8, head_dim=2, win=4, H=256, W=260),
+    Case("attention", "attention_w4_16x20_control", _d(dw=1, table=2), C=16, heads=8, head_dim=2, win=4, H=16, W=20),
+    # swf_layernorm_bwd / swf_mlp_bwd called directly, on both sides of each boundary
+    Case("layernorm", "layernorm_n8192_control", _d(ln=2), C=8, N=8192),
+    Case("layernorm", "layernorm_n8193", _d(ln=3), C=8, N=8193),            # 1 028 rows -> 33 -> 2: a last group of one row
+    Case("layernorm", "layernorm_n262145", _d(ln=4), C=8, N=262145),        # 32 772 -> 1 025 -> 33 -> 2
+    Case("mlp", "mlp_n8192_control", _d(dw=1), C=8, hidden=16, N=8192),
+    Case("mlp", "mlp_n8193", _d(dw=2), C=8, hidden=16, N=8193),             # 33 chunks: the last chunk and the last group hold one row
+    Case("mlp", "mlp_n262145", _d(dw=3), C=8, hidden=16, N=262145),         # 1 025 -> 33 -> 2
+    # PatchMergingAndLinearLayer: more than 8 192 merged tokens, no multiple of 256 (H x W: the layer's input map)
+    Case("patch", "patch_enc_1to24_184x186", _d(dw=2, ln=3), C=1, hidden=24, H=184, W=186, encoder=True),
+    Case("patch", "patch_dec_16to8_92x93", _d(dw=2, ln=3), C=16, hidden=8, H=92, W=93, encoder=False),
+    # MyModel.do_final_layer of `tiny`, kernel size 3: 264 195 pixels, 1 033 chunks -> 33 -> 2 -> 1
+    Case("head", "head_train_513x515", _d(head=3), H=513, W=515, train=True),
+    Case("head", "head_eval_513x515", _d(head=3), H=513, W=515, train=False),
+    Case("head", "head_train_93x95_control", _d(head=2), H=93, W=95, train=True),
+    # the whole `tiny` model in train(): head, reflect pad, both patch layers and the blocks of both levels at depths none has run at
+    # (per tree: level 0 then level 1; dw and ln: the patch layer's sums, then the blocks')
+    Case("model", "model_tiny_518x514", _d(dw=(2, 2, 2, 2), ln=(3, 3, 3, 3), table=(3, 3), head=3), H=518, W=514),
+]
+
+# Seeds are picked so that the float32 oracle's gradients agree with the float64 oracle's to a quarter of the GPU tolerance
+# (tests/test_bwd_tree_cases_host.py).  Default seed = 5200 + 10 * the case's index; cases that miss with it are listed here by id.
+# Under batch statistics the gradient of the head's conv1 bias vanishes identically (BatchNorm subtracts the mean), so it is compared on
+# the floor of 1e-3 gmax, where the float32 oracle's own rounding of a sum over 264 195 pixels is 2e-4 .. 8e-3 of the floor from seed to
+# seed and with the number of threads the sum is split over (the default seeds gave 3.3e-3 for the head and 6.3e-3 for the model, against
+# the bound of 1.25e-3; the host test evaluates the float32 oracle on a fixed number of threads).
+SEED_OVERRIDE: dict = {"head_train_513x515": 5348, "model_tiny_518x514": 5364}
+
+CASES = [replace(c, seed=SEED_OVERRIDE.get(c.id, 5200 + 10 * i)) for i, c in enumerate(_TABLE)]
+assert len({c.id for c in CASES}) == len(CASES)
+BIT_REPRODUCIBLE = [c for c in CASES if c.id in ("block_w4_92x92", "block_w8_512x520", "layernorm_n262145", "mlp_n262145")]
+DIRECT = [c for c in CASES if c.direct]
+
+
+def find(name: str) -> Case:
+    return next(c for c in CASES if c.id == name)
+
+
+def _model_maps(c: Case) -> List[Tuple[int, int]]:
+    """(merged tokens, window-padded tokens and windows) per level of the model on the case's map"""
+    cfg = CONFIGS[c.cfg]
+    (wh, ww), (mh, mw) = cfg.window_size, cfg.merging_size
+    h, w, out = c.H, c.W, []
+    for _ in cfg.in_dims_list:
+        h, w = cdiv(h, mh), cdiv(w, mw)                       # reflect pad to the merging size, merge
+        merged = c.B * h * w
+        h, w = cdiv(h, wh) * wh, cdiv(w, ww) * ww             # reflect pad to the window size
+        out.append((merged, c.B * h * w, c.B * (h // wh) * (w // ww)))
+    return out
+
+
+def rows(c: Case) -> Dict[str, Tuple[int, ...]]:
+    """Partial rows of every sum the case exercises, tree by tree (the order Case.depth claims levels in)."""
+    if c.kind in ("block", "attention"):
+        n, tab = c.B * c.H * c.W, c.B * (c.H // c.win) * (c.W // c.win) * c.heads
+        return {"dw": (chunks(n),), "table": (tab,), **({"ln": (ln_rows(n),)} if c.kind == "block" else {})}
+    if c.kind == "layernorm":
+        return {"ln": (ln_rows(c.N),)}
+    if c.kind == "mlp":
+        return {"dw": (chunks(c.N),)}
+    if c.kind == "patch":
+        n = c.B * (c.H // 2) * (c.W // 2) if c.encoder else c.B * c.H * c.W
+        return {"dw": (chunks(n),), "ln": (ln_rows(n),)}
+    if c.kind == "head":
+        return {"head": (chunks(c.B * c.H * c.W),)}
+    heads = CONFIGS[c.cfg].att_num_heads
+    maps = _model_maps(c)
+    return {"dw": tuple(chunks(t) for m in maps for t in m[:2]), "ln": tuple(ln_rows(t) for m in maps for t in m[:2]),
+            "table": tuple(m[2] * heads for m in maps), "head": (chunks(c.B * c.H * c.W),)}
+
+
+# ---- criteria (tests/test_gpu_backward.py, unchanged) --------------------------------------------------------------------------------
+# metric -> (bound on the inputs, bound on the parameters).  "block": max|err| <= 2e-4 max(max|ref|, floor), floor = 0 for the inputs and
+# 1e-2 gmax for the parameters.  "model": rel-L2 <= 2e-3 on the inputs; max|err| <= 5e-3 max(max|ref|, 1e-3 gmax) on the parameters.
+# gmax = the largest parameter gradient of this run's own reference.
+BOUNDS = {"block": (2e-4, 2e-4), "model": (2e-3, 5e-3)}
+
+
+def measure(metric: str, got_in, got_par, ref_in, ref_par) -> Tuple[float, float, str]:
+    """(worst input error, worst parameter error, the parameter it belongs to) under the metric's own measure; dicts name -> tensor."""
+    f64 = lambda t: t.detach().cpu().double()
+    assert set(got_in) == set(ref_in) and set(got_par) == set(ref_par) and ref_par, (sorted(got_par), sorted(ref_par))
+    gmax = max(float(f64(r).abs().max()) for r in ref_par.values())
+    worst_in = 0.0
+    for k, r in ref_in.items():
+        g, r = f64(got_in[k]), f64(r)
+        assert g.shape == r.shape and float(r.abs().max()) > 0, k
+        e = float((g - r).abs().max() / r.abs().max()) if metric == "block" else float((g - r).norm() / r.norm())
+        worst_in = max(worst_in, e)
+    worst_par, which = 0.0, ""
+    floor = (1e-2 if metric == "block" else 1e-3) * gmax
+    for k, r in ref_par.items():
+        g, r = f64(got_par[k]), f64(r)
+        assert g.shape == r.shape, k
+        e = float((g - r).abs().max()) / max(float(r.abs().max()), floor)
+        if e >= worst_par:
+            worst_par, which = e, k
+    return worst_in, worst_par, which
+
+
+# ---- weights, inputs ---------------------------------------------------------------------------------------------------------------
+def make_module(c: Case) -> nn.Module:
+    """The package's module of the case with the stress recipe, on the CPU (direct entries have none)."""
+    act = nn.ELU(inplace=True)
+    if c.kind == "block":
+        m = BasicBlock(c.C, c.heads, c.head_dim, (c.win, c.win), True, True, True, True, c.drop, c.drop, c.hidden, act, c.drop)
+    elif c.kind == "attention":
+        m = WindowAttention(c.C, c.heads, c.head_dim, (c.win, c.win), True, True, True, 0.0, 0.0)
+    elif c.kind == "patch":
+        m = PatchMergingAndLinearLayer(belongs_to_encoder=c.encoder, use_dual_path=True, in_dims=c.C, out_dims=c.hidden,
+                                       patch_merging_size_recorder=StateRecorder(), merging_or_unmerging_size=(2, 2), activation_func=act)
+    else:
+        assert c.kind in ("head", "model"), c.kind
+        m = MyModel(**CONFIGS[c.cfg].model_kwargs(act))
+    m.eval()
+    load_recipe_into(m, seed=c.seed, flavor="stress")
+    return m
+
+
+@functools.lru_cache(maxsize=None)
+def state(c: Case) -> Dict[str, torch.Tensor]:
+    if c.direct:    # the recipe's own keys of a LayerNorm / an MLP stream; linear weights [out][in]
+        shapes = ({"norm_layer_1.weight": (c.C,), "norm_layer_1.bias": (c.C,)} if c.kind == "layernorm" else
+                  {"mlp_x_1.weight": (c.hidden, c.C), "mlp_x_1.bias": (c.hidden,), "mlp_x_2.weight": (c.C, c.hidden), "mlp_x_2.bias": (c.C,)})
+        return {k: torch.from_numpy(v) for k, v in make_state_arrays(shapes, {}, seed=c.seed, flavor="stress").items()}
+    return {k: v.detach().clone() for k, v in make_module(c).state_dict().items()}
+
+
+@functools.lru_cache(maxsize=None)
+def param_names(c: Case) -> Tuple[str, ...]:
+    """The parameters whose gradients are compared: every parameter of the module (head: its six)."""
+    if c.direct:
+        return tuple(state(c))
+    names = tuple(k for k, _ in make_module(c).named_parameters())
+    return tuple(k for k in names if k.startswith("final_layer.")) if c.kind == "head" else names
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(c: Case) -> Tuple[torch.Tensor, ...]:
+    """float32; NCHW maps (direct entries: [tokens][C])"""
+    if c.direct:
+        return (G.randn((c.N, c.C), c.seed + 1),)
+    if c.kind == "model":
+        return tuple(torch.from_numpy(a) for a in synthetic_pair(c.B, c.H, c.W, seed_ir=c.seed + 1, seed_vis=c.seed + 2))
+    ch = 1 if c.kind == "head" else c.C
+    return G.randn((c.B, ch, c.H, c.W), c.seed + 1), G.randn((c.B, ch, c.H, c.W), c.seed + 2)
+
+
+INPUT_NAMES = {"block": ("x", "y"), "attention": ("q", "kv"), "patch": ("x", "y"), "head": ("x", "y"), "model": ("ir", "vis"),
+               "layernorm": ("x",), "mlp": ("x",)}
+
+
+def output_shapes(c: Case) -> List[Tuple[int, ...]]:
+    if c.direct:
+        return [(c.N, c.C)]
+    if c.kind in ("head", "model"):
+        return [(c.B, 1, c.H, c.W)]
+    if c.kind == "attention":
+        return [(c.B, c.C, c.H, c.W)]
+    if c.kind == "patch":
+        return [(c.B, c.hidden, c.H // 2, c.W // 2) if c.encoder else (c.B, c.hidden, 2 * c.H, 2 * c.W)] * 2
+    return [(c.B, c.C, c.H, c.W)] * 2
+
+
+@functools.lru_cache(maxsize=None)
+def upstream(c: Case, mode: str) -> Tuple[torch.Tensor, ...]:
+    """dL/d(output) per output, float32: a random linear functional; `tail`: zero except the last 16 tokens of the last image
+    (direct entries: the last token)."""
+    ups = [G.randn(s, c.seed + 5 + i) for i, s in enumerate(output_shapes(c))]
+    if mode == "tail":
+        for i, u in enumerate(ups):
+            keep = torch.zeros_like(u)
+            if c.direct:
+                keep[-1] = 1
+            else:
+                keep[-1, :, -1, -TAIL_TOKENS:] = 1
+            ups[i] = u * keep
+    return tuple(ups)
+
+
+# ---- dropout: the block's seed and masks ---------------------------------------------------------------------------------------------
+def drop_seed(c: Case) -> int:
+    """The seed the block draws in its first train() forward after torch.manual_seed(c.seed) (modules._dropout)."""
+    state_ = torch.random.get_rng_state()
+    torch.manual_seed(c.seed)
+    seed = int(torch.empty((), dtype=torch.int64).random_().item())
+    torch.random.set_rng_state(state_)
+    return seed
+
+
+DROP_SITE_WIDTHS = lambda c: (c.heads * c.head_dim, c.C, c.hidden, c.C)      # sites 0 .. 3 of swf_dropout
+
+
+@functools.lru_cache(maxsize=None)
+def drop_masks(c: Case):
+    """masks(stream, site, width) of tests/dropout_util.block_drop from the numpy Philox restatement (the GPU test holds the library's
+    swf_dropout_mask to exactly these factors before it uses this reference)."""
+    seed, n = drop_seed(c), c.B * c.H * c.W
+    table = {(s, site): D.nchw_mask(D.mask_np(seed, s, site, n * wd, c.drop), c.B, c.H, c.W, wd)
+             for s in (0, 1) for site, wd in enumerate(DROP_SITE_WIDTHS(c))}
+    return lambda s, site, width: table[(s, site)]
+
+
+# ---- reference ---------------------------------------------------------------------------------------------------------------------
+def _forward(c: Case, sd, ins):
+    """outputs (a list) of the oracle on leaves `ins` with weights `sd`, in their dtype"""
+    if c.kind == "block":
+        kw = dict(cross=True, shift=True, num_heads=c.heads, dims_per_head=c.head_dim, window_size=(c.win, c.win))
+        if c.drop:
+            masks = drop_masks(c)
+            return list(D.block_drop(sd, "", *ins, lambda s, site, wd: masks(s, site, wd).to(ins[0].dtype), **kw))
+        return list(O.basic_block(sd, "", *ins, **kw))
+    if c.kind == "attention":
+        q, kv = ins
+        return [O.window_attention(sd, "", q, kv, kv, num_heads=c.heads, dims_per_head=c.head_dim, window_size=(c.win, c.win),
+                                   use_cyclic_shift=True)]
+    if c.kind == "layernorm":
+        return [F.layer_norm(ins[0], (c.C,), sd["norm_layer_1.weight"], sd["norm_layer_1.bias"], 1e-5)]
+    if c.kind == "mlp":
+        return [F.linear(F.elu(F.linear(ins[0], sd["mlp_x_1.weight"], sd["mlp_x_1.bias"])), sd["mlp_x_2.weight"], sd["mlp_x_2.bias"])]
+    if c.kind == "patch":
+        return list(O.patch_layer(sd, "", *ins, encoder=c.encoder, merging_size=(2, 2)))
+    cfg = CONFIGS[c.cfg]
+    if c.kind == "head":
+        return [O.final_head(sd, *ins, cfg.final_conv_layer_kernel_size, training=c.train)]
+    return [O.model_forward(sd, cfg, *ins, training=True)]
+
+
+def reference(c: Case, dtype=torch.float64):
+    """{"out": outputs, "dense" / "tail": (input gradients, parameter gradients) as dicts by name, "running": the head's running
+    statistics after the forward}, evaluated in `dtype`: one forward, one torch.autograd.grad per mode."""
+    cast = lambda t: t.to(dtype, copy=True) if t.is_floating_point() else t.clone()    # (copies: the cached state stays as it is)
+    names = param_names(c)
+    sd = {k: (cast(v).requires_grad_(True) if k in names else cast(v)) for k, v in state(c).items()}
+    ins = [cast(t).requires_grad_(True) for t in inputs(c)]
+    outs = _forward(c, sd, ins)
+    leaves = ins + [sd[k] for k in names]
+    res = {"out": [o.detach() for o in outs],
+           "running": {k: v.detach() for k, v in sd.items() if k.startswith("final_layer.1.running_")}}
+    for mode in MODES:
+        gs = torch.autograd.grad(outs, leaves, [u.to(dtype) for u in upstream(c, mode)], retain_graph=mode != MODES[-1])
+        res[mode] = (dict(zip(INPUT_NAMES[c.kind], gs[:len(ins)])), dict(zip(names, gs[len(ins):])))
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def reference64(c: Case):
+    """The float64 reference, computed once per case and shared by every test that needs it (read-only)."""
+    return reference(c, torch.float64)
