@@ -563,7 +563,8 @@ int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float*
 /* ---- fusion-quality metrics of fused images against their two sources, ten values per image in one call ------------
  * The numbers the field reports for a fusion method (the reference's README claims them; neither it nor a016 / a017 computes one).
  * Restated from the published definitions and the common open evaluators; no MATLAB or VIFB toolkit is available to this build:
- * PARITY WITH ANY OF THEM IS UNPINNED.  VIF and Nabf are not provided; SSIM is the loss's (swf_fusion_loss, ssim_mode 1).
+ * PARITY WITH ANY OF THEM IS UNPINNED.  VIF and Nabf are swf_fusion_fidelity's (below); SSIM is the loss's (swf_fusion_loss,
+ * ssim_mode 1).
  * Levels.  Every metric is a function of 8-bit levels, quantised as torchvision save_image does, in fp32 with two roundings:
  * q = (int) min(max(fadd(fmul(x, 255), 0.5), 0), 255) (never one fused multiply-add; NaN -> 0), so a stored uint8 image passed as
  * u8 / 255.0f evaluates exactly.  F, A, B = the level images of fusion, ir, vis as reals 0..255, N = H W.
@@ -598,6 +599,46 @@ size_t swf_fusion_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int swf_fusion_metrics(const swf_metrics_desc* desc, const float* fusion, const float* ir, const float* vis,
                        double* out /* device [B][SWF_METRIC_COUNT] */, int32_t B, int32_t H, int32_t W,
                        void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
+/* ---- VIF and Nabf: the two remaining numbers of the field's table, five values per image in one call -----------------------------
+ * Restated from the published definitions and the common open evaluators (vifp_mscale; Kumar's objective fusion performance
+ * scheme); no MATLAB, VIFB or sewar copy is available to this build: PARITY WITH ANY OF THEM IS UNPINNED.
+ * Levels.  F, A, B = the level images of fusion, ir, vis of the metrics above (the same quantiser: fp32, two roundings, never one
+ * fused multiply-add, NaN -> 0), taken as reals 0..255.
+ *   VIF   VIF_IR + VIF_VIS, VIF_IR = vifp(A, F), VIF_VIS = vifp(B, F): the multi-scale pixel-domain visual information fidelity of
+ *         Sheikh and Bovik.  vifp(R, D), with sigma_nsq = 2 and eps = 1e-10, keeps running sums num and den over scales s = 1..4:
+ *         N = 2^(5-s) + 1 taps (17, 9, 5, 3); window g[i][j] = exp(-((i-c)^2 + (j-c)^2) / (2 (N/5)^2)), c = (N-1)/2, normalised to
+ *         sum 1 (separable: the 1-D factor is normalised).  For s > 1, R and D are first replaced by their "valid" filtering with
+ *         this scale's window sampled at even rows and even columns (ceil((n - N + 1) / 2) per axis).  Once a scale's input is
+ *         smaller than N in either axis (before or after that step), that scale and all later ones contribute nothing.  With * the
+ *         "valid" filtering: mu1 = g*R, mu2 = g*D, s1 = g*(R R) - mu1^2, s2 = g*(D D) - mu2^2, s12 = g*(R D) - mu1 mu2; s1 and s2
+ *         are clamped below at 0; gg = s12 / (s1 + eps), sv = s2 - gg s12; then in this order (i) where s1 < eps: gg = 0, sv = s2,
+ *         s1 = 0; (ii) where s2 < eps: gg = 0, sv = 0; (iii) where gg < 0: sv = s2, gg = 0; (iv) where sv <= eps: sv = eps;
+ *         (v) num += sum log10(1 + gg^2 s1 / (sv + sigma_nsq)), den += sum log10(1 + s1 / sigma_nsq).  vifp = num / den, and 0 when
+ *         den = 0 (an image under 17 pixels in an axis, a flat source).
+ *   NABF  Kumar's modified fusion-artifact measure, given with its loss term LABF.  Sobel responses with a REPLICATED border, gv with
+ *         [-1 0 1; -2 0 2; -1 0 1] / 8, gh with [-1 -2 -1; 0 0 0; 1 2 1] / 8; g = sqrt(gv^2 + gh^2); alpha = atan(gv / gh),
+ *         sign(gv) pi/2 where gh = 0 (0 where both are 0).  For X in {A, B}: G_XF = 0 where g_X = 0 or g_F = 0, g_F / g_X where
+ *         g_X > g_F, else g_X / g_F; A_XF = | |alpha_X - alpha_F| - pi/2 | 2/pi;
+ *         Q_XF = sqrt(Nrg / (1 + e^(-kg (G_XF - sg))) Nra / (1 + e^(-ka (A_XF - sa)))); w_X = g_X sqrt(g_X) where g_X >= Td, else
+ *         wt_min.  With loss = (1 - Q_AF) w_A + (1 - Q_BF) w_B, na = (g_F > g_A and g_F > g_B), W = sum (w_A + w_B):
+ *         NABF = sum(na loss) / W, LABF = sum((1 - na) loss) / W, so 1 - NABF - LABF = sum(Q_AF w_A + Q_BF w_B) / W.  Every comparison
+ *         between magnitudes, and g >= Td, is made on the exact integers 64 g^2 (the unnormalised Sobel sums squared; Td as
+ *         64 Td^2).  W > 0 always.  Usual constants: Td 2, wt_min 0.001, Nrg 0.9999, kg 19, sg 0.5, Nra 0.9995, ka 22, sa 0.5.
+ * Arithmetic.  fp64 throughout after the quantiser: the variances are differences of sums of products up to 65 025 (an fp32
+ * evaluation is 1e-8 to 3e-6 off, every fp64 order within 3e-13).  Window weights are computed on the host in fp64.  Sums go through
+ * per-tile partials added in a fixed order; no atomics: results are bit-identical from call to call, and an image's row does not
+ * depend on the rest of its batch. */
+typedef struct swf_fidelity_desc { double sigma_nsq, eps, Td, wt_min, Nrg, kg, sg, Nra, ka, sa; } swf_fidelity_desc;
+enum { SWF_FIDELITY_VIF, SWF_FIDELITY_VIF_IR, SWF_FIDELITY_VIF_VIS, SWF_FIDELITY_NABF, SWF_FIDELITY_LABF, SWF_FIDELITY_COUNT };
+/* 0 for a shape swf_fusion_fidelity would refuse */
+size_t swf_fusion_fidelity_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_FIDELITY_COUNT], one row per image.  The call writes every workspace
+ * element it reads, allocates nothing and does not synchronise the host, so it can be captured into a hipGraph.
+ * SWF_ERR_BAD_SHAPE for H W > 2^30 or B > 65535 (the limits of swf_fusion_metrics). */
+int swf_fusion_fidelity(const swf_fidelity_desc* desc, const float* fusion, const float* ir, const float* vis,
+                        double* out /* device [B][SWF_FIDELITY_COUNT] */, int32_t B, int32_t H, int32_t W,
+                        void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);

@@ -104,6 +104,13 @@ class MetricsDesc(C.Structure):   # swf_metrics_desc: the Qabf constants
 METRIC_COUNT = 10   # SWF_METRIC_COUNT
 
 
+class FidelityDesc(C.Structure):   # swf_fidelity_desc: the constants of VIF (sigma_nsq, eps) and Nabf
+    _fields_ = [(n, C.c_double) for n in ("sigma_nsq", "eps", "Td", "wt_min", "Nrg", "kg", "sg", "Nra", "ka", "sa")]
+
+
+FIDELITY_COUNT = 5   # SWF_FIDELITY_COUNT
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -216,6 +223,8 @@ SIGNATURES = {
     "swf_fusion_loss": (C.c_int, [P(LossDesc), _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_fusion_metrics_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "swf_fusion_metrics": (C.c_int, [P(MetricsDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_fidelity_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_fidelity": (C.c_int, [P(FidelityDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

@@ -22,6 +22,7 @@
 //
 // gfx950 cross-compile (hipcc -O3): no scratch in any kernel; VGPRs hist<true> / hist<false> / grad / finish as reported in DESIGN.md 6c.
 #include "kernels_metrics.h"
+#include "levels.h"
 
 #include <algorithm>
 #include <cmath>
@@ -45,15 +46,7 @@ constexpr double kHalfPi = 1.57079632679489661923;
 
 typedef unsigned long long u64;
 
-// Two roundings.  hipcc contracts __fadd_rn(__fmul_rn(x, 255.f), 0.5f) into one v_fma_f32 (the intrinsics are a plain * and + inside
-// its headers, compiled with contraction on), which moves a level about 7 times per million pixels; plain operators under the pragma
-// are what keeps the pair apart (checked in the ISA: no v_fma_f32 / v_fmac_f32 / v_mad_f32 in this file's kernels).
-__device__ __forceinline__ int level(float x) {
-#pragma clang fp contract(off)
-    const float m = x * 255.f;
-    const float v = m + 0.5f;
-    return (int)fminf(fmaxf(v, 0.f), 255.f);   // fmaxf(NaN, 0) = 0
-}
+// level(): the two-rounding quantiser of levels.h, shared with kernels_fidelity.hip.
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll

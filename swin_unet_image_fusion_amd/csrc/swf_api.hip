@@ -13,6 +13,7 @@
 #include "kernels_bwd.h"
 #include "kernels_dropout.h"
 #include "kernels_loss.h"
+#include "kernels_fidelity.h"
 #include "kernels_metrics.h"
 #include "kernels_optim.h"
 #include "kernels_deep.h"
@@ -2197,6 +2198,29 @@ int swf_fusion_metrics(const swf_metrics_desc* desc, const float* fusion, const 
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "fusion_metrics: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return fusion_metrics(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// VIF and Nabf.  Every argument check comes before the first HIP call.
+static int check_fusion_fidelity(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_fidelity: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!fusion_fidelity_shape_ok(B, H, W))
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_fidelity: B=%d H=%d W=%d exceeds the kernels' grids (H W <= 2^30, B <= 65535)", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_fidelity_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    if (check_fusion_fidelity(B, H, W) != SWF_OK) return 0;
+    return fusion_fidelity_workspace_bytes(B, H, W);
+}
+
+int swf_fusion_fidelity(const swf_fidelity_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
+                        int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_fidelity: NULL descriptor, image or output");
+    SWF_TRY(check_fusion_fidelity(B, H, W));
+    const size_t need = fusion_fidelity_workspace_bytes(B, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "fusion_fidelity: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return fusion_fidelity(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

@@ -7,8 +7,12 @@ evaluate exactly.  Conventions for degenerate images: EN of a one-level image is
 AG 0; Pearson's r (CC, SCD) is 0 when either variance is 0; PSNR is +inf at MSE = 0; Qabf is 0 when no source pixel has a gradient
 (its Sobel responses see a zero border, so a flat non-black image has edges along its frame).
 
-The definitions are restated from the published ones and the common open evaluators; no MATLAB or VIFB toolkit is available to this
-build, so parity with any of them is unpinned.  VIF and Nabf are not provided.  SSIM is already available as
+VIF (multi-scale pixel-domain, per source and summed) and Nabf with its loss term Labf come from a second fused HIP call on the same
+levels, fp64 throughout (swf_fusion_fidelity: `fusion_fidelity`, or `FusionMetrics(fidelity=True)` for all fifteen values).  VIF of a
+source is 0 when its denominator is (an image under 17 pixels in an axis, a flat source).
+
+The definitions are restated from the published ones and the common open evaluators; no MATLAB, VIFB or sewar copy is available to
+this build, so parity with any of them is unpinned.  SSIM is already available as
 `MyLoss(choose_ms_ssim=False).calcu_ssim_loss`.
 """
 from __future__ import annotations
@@ -22,10 +26,13 @@ from torch import Tensor
 from . import _lib as L
 from .modules import _ptr, _stream, _workspace
 
-__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "fusion_metrics", "FusionMetrics"]
+__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "fusion_metrics", "fusion_fidelity", "FusionMetrics"]
 
 METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
 QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
+FIDELITY_NAMES = ("VIF", "VIF_IR", "VIF_VIS", "Nabf", "Labf")                        # the order of the header's SWF_FIDELITY_* enum
+FIDELITY_DEFAULTS = {"sigma_nsq": 2.0, "eps": 1e-10,                                # Sheikh & Bovik (vifp_mscale)
+                     "Td": 2.0, "wt_min": 0.001, "Nrg": 0.9999, "kg": 19.0, "sg": 0.5, "Nra": 0.9995, "ka": 22.0, "sa": 0.5}   # Kumar
 
 
 def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
@@ -69,14 +76,43 @@ def fusion_metrics(fusion: Tensor, ir: Tensor, vis: Tensor, **qabf_constants) ->
     return out
 
 
-class FusionMetrics:
-    """Running mean of the ten metrics over every image passed to update().  The sum lives on the device and update() does not
-    synchronise; compute() reads it back once.  The image count is a host int (`count`): the batch size is known on the host, so
-    counting there needs no synchronisation and no device scalar."""
+def _fidelity_desc(constants: dict) -> L.FidelityDesc:
+    unknown = set(constants) - set(FIDELITY_DEFAULTS)
+    if unknown:
+        raise TypeError(f"fusion_fidelity: unknown constant(s) {sorted(unknown)}; the constants are {list(FIDELITY_DEFAULTS)}")
+    c = {**FIDELITY_DEFAULTS, **constants}
+    return L.FidelityDesc(*(float(c[k]) for k in FIDELITY_DEFAULTS))
 
-    def __init__(self, **qabf_constants):
+
+def fusion_fidelity(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
+    """-> (B, 5) float64 tensor on the inputs' device, row b = the FIDELITY_NAMES values of image b: VIF = VIF_IR + VIF_VIS, Nabf and
+    Labf.  Inputs as for fusion_metrics.  Keyword arguments replace constants (FIDELITY_DEFAULTS).  One library call on the current
+    stream, no host synchronisation; bit-identical from call to call."""
+    desc = _fidelity_desc(constants)
+    _check_images(fusion, ir, vis)
+    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
+    b, _, h, w = f.shape
+    lib = L.lib()
+    need = lib.swf_fusion_fidelity_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
+    out = torch.empty((b, L.FIDELITY_COUNT), dtype=torch.float64, device=f.device)
+    ws, wsn = _workspace(need, f.device)
+    L.check(lib.swf_fusion_fidelity(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
+    return out
+
+
+class FusionMetrics:
+    """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` of fifteen, the FIDELITY_NAMES values
+    (constants: `fidelity_constants`) after the ten.  The sum lives on the device and update() does not synchronise; compute() reads
+    it back once.  The image count is a host int (`count`): the batch size is known on the host, so counting there needs no
+    synchronisation and no device scalar."""
+
+    def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, **qabf_constants):
         _desc(qabf_constants)   # refuse a misspelt constant here, not at the first batch
+        _fidelity_desc(fidelity_constants or {})
         self.qabf_constants = qabf_constants
+        self.fidelity = bool(fidelity)
+        self.fidelity_constants = dict(fidelity_constants or {})
+        self.names = METRIC_NAMES + FIDELITY_NAMES if self.fidelity else METRIC_NAMES
         self.reset()
 
     def reset(self) -> None:
@@ -84,8 +120,10 @@ class FusionMetrics:
         self.count = 0
 
     def update(self, fusion: Tensor, ir: Tensor, vis: Tensor) -> Tensor:
-        """Adds the batch's rows; -> the rows, (B, 10) float64 on the device."""
+        """Adds the batch's rows; -> the rows, (B, 10) float64 on the device, (B, 15) with fidelity."""
         rows = fusion_metrics(fusion, ir, vis, **self.qabf_constants)
+        if self.fidelity:
+            rows = torch.cat([rows, fusion_fidelity(fusion, ir, vis, **self.fidelity_constants)], dim=1)
         s = rows.sum(dim=0)
         self._sum = s if self._sum is None else self._sum + s
         self.count += rows.shape[0]
@@ -95,4 +133,4 @@ class FusionMetrics:
         """{name: mean over the images seen since reset()}, one device-to-host copy."""
         if self.count == 0:
             raise RuntimeError("FusionMetrics.compute(): no image since reset()")
-        return dict(zip(METRIC_NAMES, (self._sum / self.count).tolist()))
+        return dict(zip(self.names, (self._sum / self.count).tolist()))
