@@ -266,6 +266,52 @@ int swf_mlp_bwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* 
                      const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
                      const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- training side: kernel families of the exact-fp32 backward ---------------------------------------------------------------------
+ * The gradient GEMMs of every backward entry (dX = dY . W and dW = dY^T . X, the latter per 256-token chunk + a fixed reduction tree)
+ * exist in two families that return THE SAME BITS: both keep one accumulator per output element, start it at zero and take the
+ * reduction index in ascending order with one rounding per product.  SWF_BWD_GEMM_FMA: LDS-tiled scalar fmaf, 4 x 4 outputs per
+ * thread (what the entries above run).  SWF_BWD_GEMM_MFMA: the same chains on the matrix cores (v_mfma_f32_16x16x4_f32, an fmaf
+ * chain in hardware), 16-byte loads where the pointers and row lengths allow.  The attention core has one family, one thread per query /
+ * key (SWF_BWD_ATTN_THREAD); code 1 is kept for a matrix-core kernel and is refused until there is one.  Any other code:
+ * SWF_ERR_UNSUPPORTED.  All-zero options are the entries above. */
+typedef enum swf_bwd_gemm { SWF_BWD_GEMM_FMA = 0, SWF_BWD_GEMM_MFMA = 1 } swf_bwd_gemm;
+typedef enum swf_bwd_attn { SWF_BWD_ATTN_THREAD = 0 } swf_bwd_attn;
+typedef struct swf_bwd_options { int32_t gemm; int32_t attention; } swf_bwd_options;
+/* What a backward call launched, written by the branches that launch (host memory, zeroed by the call first; may be NULL): the number
+ * of dX and dW launches per family — a call never mixes them, so a caller can tell the family it asked for from a fallback — and the
+ * attention-core kernel. */
+typedef enum swf_bwd_attn_ran {
+    SWF_BWD_ATTN_RAN_NONE = 0,        /* the entry has no attention core */
+    SWF_BWD_ATTN_RAN_RESIDENT = 1,    /* thread family, probability tile of the (window, head) resident in LDS */
+    SWF_BWD_ATTN_RAN_RECOMPUTE = 2    /* thread family, every pass rebuilds its scores (windows whose tile does not fit: 16 x 16) */
+} swf_bwd_attn_ran;
+typedef struct swf_bwd_route { int32_t dx_fma, dx_mfma, dw_fma, dw_mfma; int32_t attention; } swf_bwd_route;
+/* The backward entries with the family as an argument: arguments, results and workspace as swf_basic_block_bwd /
+ * swf_window_attention_bwd / swf_mlp_bwd / swf_patch_layer_bwd, plus drop (NULL: no dropout, the workspace query of the plain entry;
+ * non-NULL: as the *_bwd_drop entry with its workspace query and, for the inner modules, its mask stream stream_id), the options
+ * (NULL = all zero) and the route (NULL = not wanted). */
+int swf_basic_block_bwd_opt(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                            const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
+                            const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
+                            const swf_dropout* drop, const swf_bwd_options* opt, swf_bwd_route* route,
+                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_window_attention_bwd_opt(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                 const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                                 int32_t W, const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route,
+                                 void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_mlp_bwd_opt(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                    const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                    const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route,
+                    void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* The per-layer seam of the two families: one linear layer y = x W^T + b on its own, x [M][K], W [N][K], gout = dL/dy [M][N], any
+ * M, N, K >= 1 and any 4-byte-aligned pointers.  gx [M][K] = gout . W (accumulate != 0: added to gx), gw [N][K] = gout^T . x,
+ * gb [N] = column sums of gout; each of the three may be NULL.  The workspace is the weight-gradient scratch, sized as the block
+ * entries size it for the same layer (not read when gw and gb are NULL). */
+size_t swf_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K);
+int swf_linear_bwd(const float* x, const float* weight, const float* gout, float* gx, float* gw, float* gb,
+                   int64_t M, int32_t N, int32_t K, int32_t accumulate, const swf_bwd_options* opt, swf_bwd_route* route,
+                   void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* SelfAndCrossBlockPair.forward (a012_SelfAndCrossBlockPair.py:70-78): four BasicBlocks in the
  * order self/normal, self/shifted, cross/normal, cross/shifted (a009:90-109).  `desc` gives the
  * shared dims; shift/cross flags inside it are ignored.  px[4], py[4]. */
@@ -395,6 +441,11 @@ size_t swf_patch_layer_bwd_workspace_bytes(int32_t B, int32_t H, int32_t W, int3
 int swf_patch_layer_bwd(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp,
                         int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t encoder,
                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* ... with the family of its gradient GEMMs as an argument (swf_bwd_options above; the layer has no dropout) */
+int swf_patch_layer_bwd_opt(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp,
+                            int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t encoder,
+                            const swf_bwd_options* opt, swf_bwd_route* route,
+                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
 /* Adjoint of swf_reflect_pad_fwd (MyPadding encoder side, a006:122-131): gout [B][H+pad_h][W+pad_w][C] -> gin [B][H][W][C]. */
 int swf_reflect_pad_bwd(const float* gout, float* gin, int32_t B, int32_t H, int32_t W, int32_t C, int32_t pad_h, int32_t pad_w,
                         swf_stream_t stream);

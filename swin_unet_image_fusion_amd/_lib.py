@@ -52,6 +52,19 @@ class Dropout(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("attn_p", C.c_float), ("proj_p", C.c_float), ("mlp_p", C.c_float)]
 
 
+class BwdOptions(C.Structure):   # swf_bwd_options: the kernel families of a backward call
+    _fields_ = [("gemm", C.c_int32), ("attention", C.c_int32)]
+
+
+class BwdRoute(C.Structure):     # swf_bwd_route: what the call launched
+    _fields_ = [("dx_fma", C.c_int32), ("dx_mfma", C.c_int32), ("dw_fma", C.c_int32), ("dw_mfma", C.c_int32), ("attention", C.c_int32)]
+
+
+BWD_GEMM_FMA, BWD_GEMM_MFMA = 0, 1                                   # swf_bwd_gemm
+BWD_ATTN_THREAD = 0                                                  # swf_bwd_attn
+BWD_ATTN_RAN_NONE, BWD_ATTN_RAN_RESIDENT, BWD_ATTN_RAN_RECOMPUTE = 0, 1, 2   # swf_bwd_attn_ran
+
+
 class PatchParams(C.Structure):
     _fields_ = [("conv", Linear), ("ln", Norm)]
 
@@ -168,10 +181,21 @@ SIGNATURES = {
     "swf_mlp_fwd_drop": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _i64, _i32, _i32, P(Dropout), _i32, _vp, _sz, _vp]),
     "swf_mlp_bwd_drop": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _vp, P(Linear), P(Linear), _i64, _i32, _i32, P(Dropout), _i32,
                                    _vp, _sz, _vp]),
+    "swf_basic_block_bwd_opt": (C.c_int, [P(BlockDesc), P(BlockStreamParams), P(BlockStreamParams), _vp, _vp, _vp, _vp, _vp, _vp,
+                                          P(BlockStreamParams), P(BlockStreamParams), _i32, _i32, _i32, P(Dropout), P(BwdOptions), P(BwdRoute),
+                                          _vp, _sz, _vp]),
+    "swf_window_attention_bwd_opt": (C.c_int, [P(AttnDesc), P(AttnParams), _vp, _vp, _vp, _vp, _vp, _vp, _vp, P(AttnParams), _i32, _i32,
+                                               _i32, P(Dropout), _i32, P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
+    "swf_mlp_bwd_opt": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _vp, P(Linear), P(Linear), _i64, _i32, _i32, P(Dropout), _i32,
+                                  P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
+    "swf_linear_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
+    "swf_linear_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
     "swf_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i32]),
     "swf_layernorm_bwd": (C.c_int, [P(Norm), _vp, _vp, _vp, P(Norm), _i64, _i32, _vp, _sz, _vp]),
     "swf_patch_layer_bwd_workspace_bytes": (_sz, [_i32] * 8),
     "swf_patch_layer_bwd": (C.c_int, [P(PatchParams), _vp, _vp, _vp, P(PatchParams), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_patch_layer_bwd_opt": (C.c_int, [P(PatchParams), _vp, _vp, _vp, P(PatchParams), _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32,
+                                          P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
     "swf_reflect_pad_bwd": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "swf_final_head_bwd_workspace_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "swf_final_head_bwd": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _vp, P(HeadGrads), _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),

@@ -4,19 +4,26 @@
 
 namespace swf {
 
+// The kernel family of a backward call (swf_bwd_options) and where it reports what it launched (may be NULL).  Every entry below that
+// runs gradient GEMMs takes one last; the default is the scalar-FMA family with no report.
+struct BwdTier {
+    int gemm = SWF_BWD_GEMM_FMA;
+    swf_bwd_route* route = nullptr;
+};
+
 size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, int W);
 int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                     const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
-                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t stream);
+                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t stream, const BwdTier& tier = {});
 
 // the inner modules on their own: WindowAttention (a001), one MLP stream (a003), one LayerNorm (a004)
 size_t window_attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W);
 int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, const float* gout,
                          float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream);
+                         hipStream_t stream, const BwdTier& tier = {});
 size_t mlp_bwd_ws(int64_t N, int C, int hid);
 int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
-            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t stream);
+            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t stream, const BwdTier& tier = {});
 size_t layernorm_bwd_ws(int64_t N, int C);
 int layernorm_bwd(const swf_norm& ln, const float* x, const float* gout, float* gx, const swf_norm_grad* gp, int64_t N, int C, void* workspace,
                   size_t workspace_bytes, hipStream_t stream);
@@ -30,25 +37,31 @@ int basic_block_fwd_drop(const swf_block_desc& d, const swf_block_stream_params*
 int basic_block_bwd_drop(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                          const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
                          const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout& drop, void* workspace, size_t workspace_bytes,
-                         hipStream_t stream);
+                         hipStream_t stream, const BwdTier& tier = {});
 size_t window_attention_drop_ws(const swf_attn_desc& d, int B, int H, int W);
 int window_attention_fwd_drop(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
                               const float* residual, float* out, int B, int H, int W, const swf_dropout& drop, int stream_id, void* workspace,
                               size_t workspace_bytes, hipStream_t stream);
 int window_attention_bwd_drop(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
                               const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W,
-                              const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t stream);
+                              const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t stream, const BwdTier& tier = {});
 size_t mlp_drop_ws(int64_t N, int C, int hid);
 int mlp_fwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, float* out, int64_t N, int C, int hid, const swf_dropout& drop,
                  int stream_id, void* workspace, size_t workspace_bytes, hipStream_t stream);
 int mlp_bwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
                  const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes,
-                 hipStream_t stream);
+                 hipStream_t stream, const BwdTier& tier = {});
+
+// one linear layer y = x W^T + b, x [M][K], W [N][K], gout [M][N]: gx (+)= gout . W, gw = gout^T . x, gb = column sums of gout (any of
+// the three may be NULL); the per-layer seam of the two gradient-GEMM families
+size_t linear_bwd_ws(int64_t M, int N, int K);
+int linear_bwd(const float* x, const float* w, const float* gout, float* gx, float* gw, float* gb, int64_t M, int N, int K, int accumulate,
+               void* workspace, size_t workspace_bytes, hipStream_t stream, const BwdTier& tier = {});
 
 // PatchMergingAndLinearLayer (one stream; H x W = the layer's input map), reflect pad, elementwise add
 size_t patch_bwd_ws(int B, int H, int W, int Cin, int Cout, int mh, int mw, int encoder);
 int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int B, int H, int W, int Cin,
-              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t stream);
+              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t stream, const BwdTier& tier = {});
 int reflect_pad_bwd(const float* g, float* dx, int B, int H, int W, int C, int ph, int pw, hipStream_t stream);
 int add_tensors(const float* a, const float* b, float* out, int64_t n, hipStream_t stream);
 

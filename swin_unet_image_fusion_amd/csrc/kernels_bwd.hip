@@ -8,6 +8,7 @@
 // and then walks the graph in reverse with the kernels of this file:
 //   bwd_dx_kernel        dX (+)= dY . W                      (the input gradient of a linear layer; LDS-tiled fp32 FMA)
 //   bwd_dw_kernel        dW  = dY^T . X, token chunks -> partial sums, reduced in fixed order (bit-reproducible, no atomics)
+//                        (both have a matrix-core twin that returns the same bits, kernels_bwdgemm.hip; dx() and dw() choose by BwdTier)
 //   bwd_colsum_kernel    db  = column sums of dY, same chunking
 //   ln_bwd_kernel        LayerNorm backward per token (+ the residual branch's gradient) and per-wave partial d gamma / d beta
 //   elu_bwd_kernel       du = dh . (h > 0 ? 1 : h + 1)     (ELU'(u) from the saved output: exp(u) = h + 1 for u <= 0)
@@ -16,18 +17,19 @@
 //                        relative-position bias gradient — every sum in a fixed order
 //   reduce_rows_kernel   out[i] = sum over partial rows in index order
 // Everything here is test-covered against torch.autograd of the CPU oracle (tests/test_gpu_backward.py).  It is the plain,
-// correct-first tier: no MFMA, no fusion.
+// correct-first tier: no fusion, and no MFMA in this file.
 #include "kernels_bwd.h"
 
 #include <algorithm>
 
+#include "kernels_bwdgemm.h"
 #include "kernels_dropout.h"
 #include "kernels_generic.h"
 
 namespace swf {
 namespace {
 
-constexpr int kChunk = 256;    // tokens per partial sum of bwd_dw / bwd_colsum (level 0 at B=16: 1 024 chunks fill the chip)
+constexpr int kChunk = kBwdChunk;   // tokens per partial sum of bwd_dw / bwd_colsum (level 0 at B=16: 1 024 chunks fill the chip)
 constexpr int kGroup = 32;     // partial rows summed per thread and tree level (reduce_rows)
 
 // out[M][K] (+)= dY[M][N] . W[N][K]
@@ -495,7 +497,8 @@ __global__ void attn_bwd_kernel(AttnBwdBatch batch, int ld, int B, int H, int W,
 }
 
 template <int DMAX>
-int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift, hipStream_t stream) {
+int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift,
+                      const BwdTier& tier, hipStream_t stream) {
     const int t = wh * ww, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int threads = cdiv(t, 64) * 64;
     if (threads > 1024) return fail(SWF_ERR_UNSUPPORTED, "attention backward: window of %d tokens > 1024", t);
@@ -507,6 +510,7 @@ int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<DMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res);
             if (e != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn_bwd): %s", hipGetErrorString(e));
         }
+        if (tier.route) tier.route->attention = SWF_BWD_ATTN_RAN_RESIDENT;
         hipLaunchKernelGGL(attn_bwd_kernel<DMAX>, grid, dim3(threads), lds_res, stream, batch, ld, B, H, W, wh, ww, heads, d, shift, scale);
         return check_launch("attn_bwd");
     }
@@ -516,12 +520,14 @@ int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_recompute_kernel<DMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn_bwd): %s", hipGetErrorString(e));
     }
+    if (tier.route) tier.route->attention = SWF_BWD_ATTN_RAN_RECOMPUTE;
     hipLaunchKernelGGL(attn_bwd_recompute_kernel<DMAX>, grid, dim3(threads), lds, stream, batch, ld, B, H, W, wh, ww, heads, d, shift, scale);
     return check_launch("attn_bwd (recompute)");
 }
 
-int launch_attn_bwd(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift, hipStream_t stream) {
-#define SWF_AB(D) return launch_attn_bwd_t<D>(batch, nprob, ld, B, H, W, wh, ww, heads, d, shift, stream)
+int launch_attn_bwd(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift,
+                    const BwdTier& tier, hipStream_t stream) {
+#define SWF_AB(D) return launch_attn_bwd_t<D>(batch, nprob, ld, B, H, W, wh, ww, heads, d, shift, tier, stream)
     if (d <= 4) SWF_AB(4);
     if (d <= 8) SWF_AB(8);
     if (d <= 16) SWF_AB(16);
@@ -580,7 +586,13 @@ __global__ __launch_bounds__(256) void add_kernel(const float* __restrict__ a, c
 }
 
 // ---- host helpers ----------------------------------------------------------------------------------------------------------------------
-int dx(const float* dY, const float* W, float* out, int64_t M, int N, int K, int accumulate, hipStream_t st) {
+// The family of a gradient GEMM is chosen HERE, in dx() and dw(), and the branch that launches counts itself in the route.
+int dx(const float* dY, const float* W, float* out, int64_t M, int N, int K, int accumulate, const BwdTier& t, hipStream_t st) {
+    if (t.gemm == SWF_BWD_GEMM_MFMA) {
+        if (t.route) ++t.route->dx_mfma;
+        return launch_bwd_dx_mfma(dY, W, out, M, N, K, accumulate, st);
+    }
+    if (t.route) ++t.route->dx_fma;
     dim3 grid(cdiv(K, 64), (unsigned)cdiv64(M, 64));
     hipLaunchKernelGGL(bwd_dx_kernel, grid, dim3(256), 0, st, dY, W, out, (int)M, N, K, accumulate);
     return check_launch("bwd_dx");
@@ -617,12 +629,18 @@ int colsum(const float* dY, float* partial, int64_t M, int N, hipStream_t st) {
     return check_launch("bwd_colsum");
 }
 // dW [N][K] (and db [N] when asked) of a linear layer y = x W^T + b from dY [M][N] and X [M][K]; scratch: tree_rows(chunks) * N * (K + 1) floats
-int dw(const float* dY, const float* X, float* dW, float* db, int64_t M, int N, int K, float* scratch, hipStream_t st) {
+int dw(const float* dY, const float* X, float* dW, float* db, int64_t M, int N, int K, float* scratch, const BwdTier& t, hipStream_t st) {
     if (!dW && !db) return SWF_OK;
     const int ch = chunks_of(M);
     // one pass over dY and X for both: the weight-gradient workgroups of k tile 0 also sum their dY columns (the bias gradient)
-    hipLaunchKernelGGL(bwd_dw_kernel, dim3(cdiv(K, 64), cdiv(N, 64), ch), dim3(256), 0, st, dY, X, scratch, (int)M, N, K);
-    SWF_TRY(check_launch("bwd_dw"));
+    if (t.gemm == SWF_BWD_GEMM_MFMA) {
+        if (t.route) ++t.route->dw_mfma;
+        SWF_TRY(launch_bwd_dw_mfma(dY, X, scratch, M, N, K, st));
+    } else {
+        if (t.route) ++t.route->dw_fma;
+        hipLaunchKernelGGL(bwd_dw_kernel, dim3(cdiv(K, 64), cdiv(N, 64), ch), dim3(256), 0, st, dY, X, scratch, (int)M, N, K);
+        SWF_TRY(check_launch("bwd_dw"));
+    }
     return reduce_rows(scratch, dW, (int64_t)N * (K + 1), ch, st, (int64_t)N * K, db);
 }
 int ln_blocks(int64_t M) { return (int)cdiv64(M, 4 * kLnRows); }
@@ -720,8 +738,8 @@ int block_forward(const swf_block_desc& d, int nstream, const swf_block_stream_p
 
 int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                          const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
-                         const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout* drop, void* workspace, size_t workspace_bytes,
-                         hipStream_t st) {
+                         const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout* drop, const BwdTier& tier, void* workspace,
+                         size_t workspace_bytes, hipStream_t st) {
     const int nstream = py ? 2 : 1;
     const int64_t N = (int64_t)B * H * W;
     const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
@@ -748,21 +766,21 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
     for (int s = 0; s < nstream; ++s) {
         const float* g2 = gout[s];
         if (pm > 0.f) { SWF_TRY(launch_dropout_mul(gout[s], b[s].dxn, N * C, drop_site(drop->seed, s, kDropMlpOut, pm), st)); g2 = b[s].dxn; }
-        SWF_TRY(dx(g2, pp[s]->fc2.weight, b[s].dh, N, C, hid, 0, st));                                       // dh = g2 . W2
-        SWF_TRY(dw(g2, b[s].hd, G(s).fc2.weight, G(s).fc2.bias, N, C, hid, scratch, st));                     // dW2, db2
+        SWF_TRY(dx(g2, pp[s]->fc2.weight, b[s].dh, N, C, hid, 0, tier, st));                                       // dh = g2 . W2
+        SWF_TRY(dw(g2, b[s].hd, G(s).fc2.weight, G(s).fc2.bias, N, C, hid, scratch, tier, st));                     // dW2, db2
         if (pm > 0.f) {
             SWF_TRY(launch_dropout_elu_bwd(b[s].dh, b[s].h, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
         } else {
             hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, b[s].dh, b[s].h, N * hid);
             SWF_TRY(check_launch("elu_bwd"));
         }
-        SWF_TRY(dx(b[s].dh, pp[s]->fc1.weight, b[s].dxn2, N, hid, C, 0, st));                                 // dxn2 = du . W1
-        SWF_TRY(dw(b[s].dh, b[s].xn2, G(s).fc1.weight, G(s).fc1.bias, N, hid, C, scratch, st));               // dW1, db1
+        SWF_TRY(dx(b[s].dh, pp[s]->fc1.weight, b[s].dxn2, N, hid, C, 0, tier, st));                                 // dxn2 = du . W1
+        SWF_TRY(dw(b[s].dh, b[s].xn2, G(s).fc1.weight, G(s).fc1.bias, N, hid, C, scratch, tier, st));               // dW1, db1
         SWF_TRY(ln_bwd(b[s].x1, pp[s]->ln2.gamma, b[s].dxn2, gout[s], b[s].gx1, G(s).ln2.gamma, G(s).ln2.beta, N, C, scratch, st));
         const float* g1 = b[s].gx1;
         if (pj > 0.f) { SWF_TRY(launch_dropout_mul(b[s].gx1, b[s].dxn, N * C, drop_site(drop->seed, s, kDropProj, pj), st)); g1 = b[s].dxn; }
-        SWF_TRY(dx(g1, pp[s]->attn.proj.weight, b[s].dO, N, C, HD, 0, st));                                  // dO = g1 . Wp
-        SWF_TRY(dw(g1, b[s].o, G(s).attn.proj.weight, G(s).attn.proj.bias, N, C, HD, scratch, st));           // (o: the dropped values)
+        SWF_TRY(dx(g1, pp[s]->attn.proj.weight, b[s].dO, N, C, HD, 0, tier, st));                                  // dO = g1 . Wp
+        SWF_TRY(dw(g1, b[s].o, G(s).attn.proj.weight, G(s).attn.proj.bias, N, C, HD, scratch, tier, st));           // (o: the dropped values)
         if (pa > 0.f) SWF_TRY(launch_dropout_mul(b[s].dO, b[s].dO, N * HD, drop_site(drop->seed, s, kDropAttn, pa), st));
     }
     // ---- attention core, reverse ----
@@ -770,21 +788,21 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
         AttnBwdBatch ab{};
         for (int s = 0; s < nstream; ++s)
             ab.p[s] = AttnBwdProb{b[s].q, b[s].k, b[s].v, b[s].dO, b[s].dq, b[s].dk, b[s].dv, pp[s]->attn.bias_table, b[s].dtab};
-        SWF_TRY(launch_attn_bwd(ab, nstream, HD, B, H, W, wh, ww, d.attn.heads, d.attn.head_dim, d.attn.shift, st));
+        SWF_TRY(launch_attn_bwd(ab, nstream, HD, B, H, W, wh, ww, d.attn.heads, d.attn.head_dim, d.attn.shift, tier, st));
         for (int s = 0; s < nstream; ++s)
             if (G(s).attn.bias_table) {
                 SWF_TRY(reduce_rows(b[s].dtab, G(s).attn.bias_table, (int64_t)tsz, nwin * d.attn.heads, st));
             }
     }
     // ---- Q / K / V projections, reverse: stream s's K and V read the normalised tokens of stream kvs (a002:67-82) ----
-    for (int s = 0; s < nstream; ++s) SWF_TRY(dx(b[s].dq, pp[s]->attn.q.weight, b[s].dxn, N, HD, C, 0, st));   // initialises dxn[s]
+    for (int s = 0; s < nstream; ++s) SWF_TRY(dx(b[s].dq, pp[s]->attn.q.weight, b[s].dxn, N, HD, C, 0, tier, st));   // initialises dxn[s]
     for (int s = 0; s < nstream; ++s) {
         const int kvs = cross ? 1 - s : s;
-        SWF_TRY(dx(b[s].dk, pp[s]->attn.k.weight, b[kvs].dxn, N, HD, C, 1, st));
-        SWF_TRY(dx(b[s].dv, pp[s]->attn.v.weight, b[kvs].dxn, N, HD, C, 1, st));
-        SWF_TRY(dw(b[s].dq, b[s].xn, G(s).attn.q.weight, G(s).attn.q.bias, N, HD, C, scratch, st));
-        SWF_TRY(dw(b[s].dk, b[kvs].xn, G(s).attn.k.weight, G(s).attn.k.bias, N, HD, C, scratch, st));
-        SWF_TRY(dw(b[s].dv, b[kvs].xn, G(s).attn.v.weight, G(s).attn.v.bias, N, HD, C, scratch, st));
+        SWF_TRY(dx(b[s].dk, pp[s]->attn.k.weight, b[kvs].dxn, N, HD, C, 1, tier, st));
+        SWF_TRY(dx(b[s].dv, pp[s]->attn.v.weight, b[kvs].dxn, N, HD, C, 1, tier, st));
+        SWF_TRY(dw(b[s].dq, b[s].xn, G(s).attn.q.weight, G(s).attn.q.bias, N, HD, C, scratch, tier, st));
+        SWF_TRY(dw(b[s].dk, b[kvs].xn, G(s).attn.k.weight, G(s).attn.k.bias, N, HD, C, scratch, tier, st));
+        SWF_TRY(dw(b[s].dv, b[kvs].xn, G(s).attn.v.weight, G(s).attn.v.bias, N, HD, C, scratch, tier, st));
     }
     // ---- LN1, reverse: the input gradient = gx1 (residual branch) + LayerNorm backward of dxn ----
     for (int s = 0; s < nstream; ++s)
@@ -799,15 +817,16 @@ size_t basic_block_drop_ws(const swf_block_desc& d, int nstream, int B, int H, i
 
 int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                     const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
-                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, nullptr, workspace, workspace_bytes, st);
+                    const swf_block_stream_grads* gy, int B, int H, int W, void* workspace, size_t workspace_bytes, hipStream_t st,
+                    const BwdTier& tier) {
+    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, nullptr, tier, workspace, workspace_bytes, st);
 }
 
 int basic_block_bwd_drop(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                          const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,
                          const swf_block_stream_grads* gy, int B, int H, int W, const swf_dropout& drop, void* workspace, size_t workspace_bytes,
-                         hipStream_t st) {
-    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, &drop, workspace, workspace_bytes, st);
+                         hipStream_t st, const BwdTier& tier) {
+    return basic_block_bwd_impl(d, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gx, gy, B, H, W, &drop, tier, workspace, workspace_bytes, st);
 }
 
 // BasicBlock.forward with dropout in the exact tier: block_forward, then out = x1 + dropout(fc2(hd)) (site 3); x_out may alias x_in
@@ -880,7 +899,8 @@ size_t attention_bwd_ws(const swf_attn_desc& d, int B, int H, int W, bool bwd, b
 // one tensor was passed more than once).  With dropout the output gradient goes through site 1 and dO through site 0.
 int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
                               const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W,
-                              const swf_dropout* drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                              const swf_dropout* drop, int stream_id, const BwdTier& tier, void* workspace, size_t workspace_bytes,
+                              hipStream_t st) {
     const int64_t N = (int64_t)B * H * W;
     const int C = d.channels, HD = d.heads * d.head_dim, wh = d.win_h, ww = d.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
@@ -894,19 +914,19 @@ int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, 
     SWF_TRY(window_attention_core(d, p, q_in, k_in, v_in, Q, K, V, O, B, H, W, drop, stream_id, st));
     if (drop && drop->proj_p > 0.f) SWF_TRY(launch_dropout_mul(gout, g1, N * C, drop_site(drop->seed, stream_id, kDropProj, drop->proj_p), st));
     else g1 = const_cast<float*>(gout);
-    SWF_TRY(dx(g1, p.proj.weight, dO, N, C, HD, 0, st));                                    // dO = gout . Wp
-    SWF_TRY(dw(g1, O, g.proj.weight, g.proj.bias, N, C, HD, scratch, st));
+    SWF_TRY(dx(g1, p.proj.weight, dO, N, C, HD, 0, tier, st));                                    // dO = gout . Wp
+    SWF_TRY(dw(g1, O, g.proj.weight, g.proj.bias, N, C, HD, scratch, tier, st));
     if (drop && drop->attn_p > 0.f) SWF_TRY(launch_dropout_mul(dO, dO, N * HD, drop_site(drop->seed, stream_id, kDropAttn, drop->attn_p), st));
     AttnBwdBatch ab{};
     ab.p[0] = AttnBwdProb{Q, K, V, dO, dQ, dK, dV, p.bias_table, dtab};
-    SWF_TRY(launch_attn_bwd(ab, 1, HD, B, H, W, wh, ww, d.heads, d.head_dim, d.shift, st));
+    SWF_TRY(launch_attn_bwd(ab, 1, HD, B, H, W, wh, ww, d.heads, d.head_dim, d.shift, tier, st));
     if (g.bias_table) SWF_TRY(reduce_rows(dtab, g.bias_table, (int64_t)tsz, nwin * d.heads, st));
-    SWF_TRY(dx(dQ, p.q.weight, gq, N, HD, C, 0, st));
-    SWF_TRY(dx(dK, p.k.weight, gk, N, HD, C, 0, st));
-    SWF_TRY(dx(dV, p.v.weight, gv, N, HD, C, 0, st));
-    SWF_TRY(dw(dQ, q_in, g.q.weight, g.q.bias, N, HD, C, scratch, st));
-    SWF_TRY(dw(dK, k_in, g.k.weight, g.k.bias, N, HD, C, scratch, st));
-    SWF_TRY(dw(dV, v_in, g.v.weight, g.v.bias, N, HD, C, scratch, st));
+    SWF_TRY(dx(dQ, p.q.weight, gq, N, HD, C, 0, tier, st));
+    SWF_TRY(dx(dK, p.k.weight, gk, N, HD, C, 0, tier, st));
+    SWF_TRY(dx(dV, p.v.weight, gv, N, HD, C, 0, tier, st));
+    SWF_TRY(dw(dQ, q_in, g.q.weight, g.q.bias, N, HD, C, scratch, tier, st));
+    SWF_TRY(dw(dK, k_in, g.k.weight, g.k.bias, N, HD, C, scratch, tier, st));
+    SWF_TRY(dw(dV, v_in, g.v.weight, g.v.bias, N, HD, C, scratch, tier, st));
     return SWF_OK;
 }
 
@@ -930,8 +950,8 @@ size_t mlp_ws(int64_t N, int C, int hid, bool bwd, bool masks) {
 
 // one stream of AutoPathMLP.forward (a003:46-50) under autograd: out = fc2(ELU(fc1(x))); with dropout out = d3(fc2(d2(ELU(fc1(x)))))
 int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
-                 const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout* drop, int stream_id, void* workspace, size_t workspace_bytes,
-                 hipStream_t st) {
+                 const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout* drop, int stream_id, const BwdTier& tier, void* workspace,
+                 size_t workspace_bytes, hipStream_t st) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_bwd: token count");
     Carver ws(workspace, workspace_bytes);
     const bool pm = drop && drop->mlp_p > 0.f;
@@ -948,16 +968,16 @@ int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, c
         SWF_TRY(launch_dropout_mul(gout, gf, N * C, drop_site(drop->seed, stream_id, kDropMlpOut, drop->mlp_p), st));
         g = gf;
     }
-    SWF_TRY(dx(g, fc2.weight, dh, N, C, hid, 0, st));
-    SWF_TRY(dw(g, hd, (g2 ? *g2 : none).weight, (g2 ? *g2 : none).bias, N, C, hid, scratch, st));
+    SWF_TRY(dx(g, fc2.weight, dh, N, C, hid, 0, tier, st));
+    SWF_TRY(dw(g, hd, (g2 ? *g2 : none).weight, (g2 ? *g2 : none).bias, N, C, hid, scratch, tier, st));
     if (pm) {
         SWF_TRY(launch_dropout_elu_bwd(dh, h, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
     } else {
         hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, dh, h, N * hid);
         SWF_TRY(check_launch("elu_bwd"));
     }
-    SWF_TRY(dx(dh, fc1.weight, gx, N, hid, C, 0, st));
-    SWF_TRY(dw(dh, x, (g1 ? *g1 : none).weight, (g1 ? *g1 : none).bias, N, hid, C, scratch, st));
+    SWF_TRY(dx(dh, fc1.weight, gx, N, hid, C, 0, tier, st));
+    SWF_TRY(dw(dh, x, (g1 ? *g1 : none).weight, (g1 ? *g1 : none).bias, N, hid, C, scratch, tier, st));
     return SWF_OK;
 }
 
@@ -971,13 +991,14 @@ size_t window_attention_drop_ws(const swf_attn_desc& d, int B, int H, int W) {
 
 int window_attention_bwd(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in, const float* gout,
                          float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W, void* workspace, size_t workspace_bytes,
-                         hipStream_t st) {
-    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, nullptr, 0, workspace, workspace_bytes, st);
+                         hipStream_t st, const BwdTier& tier) {
+    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, nullptr, 0, tier, workspace, workspace_bytes, st);
 }
 int window_attention_bwd_drop(const swf_attn_desc& d, const swf_attn_params& p, const float* q_in, const float* k_in, const float* v_in,
                               const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int B, int H, int W,
-                              const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, &drop, stream_id, workspace, workspace_bytes, st);
+                              const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st,
+                              const BwdTier& tier) {
+    return window_attention_bwd_impl(d, p, q_in, k_in, v_in, gout, gq, gk, gv, gp, B, H, W, &drop, stream_id, tier, workspace, workspace_bytes, st);
 }
 
 // WindowAttention.forward with dropout (exact fp32): out = [residual +] dropout1(proj(dropout0(attention values)))
@@ -1008,13 +1029,13 @@ size_t mlp_bwd_ws(int64_t N, int C, int hid) { return mlp_ws(N, C, hid, true, fa
 size_t mlp_drop_ws(int64_t N, int C, int hid) { return std::max(mlp_ws(N, C, hid, false, true), mlp_ws(N, C, hid, true, true)); }
 
 int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
-            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, nullptr, 0, workspace, workspace_bytes, st);
+            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, nullptr, 0, tier, workspace, workspace_bytes, st);
 }
 int mlp_bwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
                  const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes,
-                 hipStream_t st) {
-    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, &drop, stream_id, workspace, workspace_bytes, st);
+                 hipStream_t st, const BwdTier& tier) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, &drop, stream_id, tier, workspace, workspace_bytes, st);
 }
 
 // one stream of AutoPathMLP.forward with dropout (exact fp32): out = dropout3(fc2(dropout2(ELU(fc1(x)))))
@@ -1052,6 +1073,27 @@ int layernorm_bwd(const swf_norm& ln, const float* x, const float* gout, float* 
     return ln_bwd(x, ln.gamma, gout, nullptr, gx, gp ? gp->gamma : nullptr, gp ? gp->beta : nullptr, N, C, scratch, st);
 }
 
+// ---- one linear layer y = x W^T + b on its own: the per-layer seam of the two gradient-GEMM families -------------------------------
+static float* carve_linear_bwd(Carver& ws, int64_t M, int N, int K) { return ws.floats(bwd_scratch_floats(M, std::max(N, K), 0)); }
+size_t linear_bwd_ws(int64_t M, int N, int K) {
+    Carver m = Carver::measure();
+    carve_linear_bwd(m, M, N, K);
+    return m.bytes();
+}
+
+int linear_bwd(const float* x, const float* w, const float* gout, float* gx, float* gw, float* gb, int64_t M, int N, int K, int accumulate,
+               void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier) {
+    if (M > INT32_MAX / std::max(N, K)) return fail(SWF_ERR_UNSUPPORTED, "linear_bwd: token count");
+    float* scratch = nullptr;
+    if (gw || gb) {   // (the input gradient alone needs no workspace)
+        Carver ws(workspace, workspace_bytes);
+        scratch = carve_linear_bwd(ws, M, N, K);
+        if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "linear_bwd workspace too small (need %zu B)", ws.bytes());
+    }
+    if (gx) SWF_TRY(dx(gout, w, gx, M, N, K, accumulate, tier, st));
+    return dw(gout, x, gw, gb, M, N, K, scratch, tier, st);
+}
+
 // ---- PatchMergingAndLinearLayer backward (a011:244-264 under autograd), one stream, no window padding (the module-level layer) ----------
 struct PatchBwdBufs { float *Z, *U, *V, *A, *dV, *dZ, *scratch; };
 // n merged tokens, conv rows of K inputs and Nn outputs
@@ -1074,7 +1116,7 @@ size_t patch_bwd_ws(int B, int H, int W, int Cin, int Cout, int mh, int mw, int 
 }
 
 int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int B, int H, int W, int Cin,
-              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t st) {
+              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier) {
     // H x W: the layer's INPUT map (encoder: full map, divisible by the merging size; decoder: the merged map)
     if (encoder && (H % mh || W % mw)) return fail(SWF_ERR_BAD_SHAPE, "patch backward: map %dx%d not divisible by the merging size", H, W);
     const int Hm = encoder ? H / mh : H, Wm = encoder ? W / mw : W;
@@ -1113,13 +1155,13 @@ int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, flo
     SWF_TRY(check_launch("elu_bwd"));
     float* dU = V;            // (V is free again)
     SWF_TRY(ln_bwd(U, p.ln.gamma, dV, nullptr, dU, g.ln.gamma, g.ln.beta, n, Nn, scratch, st));
-    SWF_TRY(dw(dU, rows, g.conv.weight, g.conv.bias, n, Nn, K, scratch, st));
+    SWF_TRY(dw(dU, rows, g.conv.weight, g.conv.bias, n, Nn, K, scratch, tier, st));
     if (encoder) {
-        SWF_TRY(dx(dU, p.conv.weight, dZ, n, Nn, K, 0, st));
+        SWF_TRY(dx(dU, p.conv.weight, dZ, n, Nn, K, 0, tier, st));
         hipLaunchKernelGGL(patch_permute_kernel, dim3(blocks_img), dim3(256), 0, st, dZ, gin, B, Hm, Wm, Cin, mh, mw, 1);
         return check_launch("patch depth-to-space (gradient)");
     }
-    return dx(dU, p.conv.weight, gin, n, Nn, K, 0, st);
+    return dx(dU, p.conv.weight, gin, n, Nn, K, 0, tier, st);
 }
 
 int reflect_pad_bwd(const float* g, float* dxo, int B, int H, int W, int C, int ph, int pw, hipStream_t st) {

@@ -1328,44 +1328,14 @@ size_t swf_basic_block_bwd_workspace_bytes(const swf_block_desc* desc, int32_t B
     return basic_block_bwd_ws(*desc, 2, B, H, W);
 }
 
-int swf_basic_block_bwd(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
-                        const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gpx,
-                        const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes,
-                        swf_stream_t stream) {
-    SWF_TRY(check_block(desc, px, py, x_in, y_in, gx_in, gy_in, B, H, W, true, true));
-    if (!gx_out || (py && !gy_out)) return fail(SWF_ERR_NULL, "basic_block_bwd: NULL output gradient");
-    return basic_block_bwd(*desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
 size_t swf_window_attention_bwd_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0 || desc->win_h <= 0 || desc->win_w <= 0 || desc->channels <= 0 || desc->heads <= 0 || desc->head_dim <= 0) return 0;
     return window_attention_bwd_ws(*desc, B, H, W);
 }
 
-int swf_window_attention_bwd(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v, const float* gout,
-                             float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H, int32_t W, void* workspace,
-                             size_t workspace_bytes, swf_stream_t stream) {
-    if (!desc || !p || !q || !k || !v || !gout || !gq || !gk || !gv) return fail(SWF_ERR_NULL, "window_attention_bwd: NULL argument");
-    if (!p->q.weight || !p->k.weight || !p->v.weight || !p->proj.weight || !p->bias_table) return fail(SWF_ERR_NULL, "window_attention_bwd: NULL parameter");
-    if (B <= 0 || H <= 0 || W <= 0 || desc->channels <= 0 || desc->heads <= 0 || desc->head_dim <= 0 || desc->win_h <= 0 || desc->win_w <= 0)
-        return fail(SWF_ERR_BAD_SHAPE, "window_attention_bwd: bad sizes");
-    if (H % desc->win_h || W % desc->win_w)
-        return fail(SWF_ERR_BAD_SHAPE, "window_attention_bwd: map %dx%d is not a multiple of the window %dx%d", H, W, desc->win_h, desc->win_w);
-    if (gq == gk || gq == gv || gk == gv) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd: gq, gk, gv must be three buffers");
-    return window_attention_bwd(*desc, *p, q, k, v, gout, gq, gk, gv, gp, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
 size_t swf_mlp_bwd_workspace_bytes(int64_t tokens, int32_t channels, int32_t hidden) {
     if (tokens <= 0 || channels <= 0 || hidden <= 0) return 0;
     return mlp_bwd_ws(tokens, channels, hidden);
-}
-
-int swf_mlp_bwd(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* gfc1,
-                const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden, void* workspace, size_t workspace_bytes,
-                swf_stream_t stream) {
-    if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "mlp_bwd: NULL argument");
-    if (tokens <= 0 || channels <= 0 || hidden <= 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_bwd: bad sizes");
-    return mlp_bwd(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, workspace, workspace_bytes, as_stream(stream));
 }
 
 // ---- dropout (training side) --------------------------------------------------------------------------------------------------------
@@ -1397,17 +1367,6 @@ int swf_basic_block_fwd_drop(const swf_block_desc* desc, const swf_block_stream_
     return basic_block_fwd_drop(*desc, px, py, x_in, y_in, x_out, y_out, B, H, W, *drop, workspace, workspace_bytes, as_stream(stream));
 }
 
-int swf_basic_block_bwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
-                             const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
-                             const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
-                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    SWF_TRY(check_block(desc, px, py, x_in, y_in, gx_in, gy_in, B, H, W, true, true));
-    if (!gx_out || (py && !gy_out)) return fail(SWF_ERR_NULL, "basic_block_bwd_drop: NULL output gradient");
-    SWF_TRY(check_dropout(drop, "basic_block_bwd_drop"));
-    return basic_block_bwd_drop(*desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, *drop, workspace, workspace_bytes,
-                                as_stream(stream));
-}
-
 size_t swf_window_attention_drop_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W) {
     if (!desc || B <= 0 || H <= 0 || W <= 0 || desc->win_h <= 0 || desc->win_w <= 0 || desc->channels <= 0 || desc->heads <= 0 || desc->head_dim <= 0) return 0;
     return window_attention_drop_ws(*desc, B, H, W);
@@ -1430,17 +1389,6 @@ int swf_window_attention_fwd_drop(const swf_attn_desc* desc, const swf_attn_para
     return window_attention_fwd_drop(*desc, *p, q, k, v, residual, out, B, H, W, *drop, stream_id, workspace, workspace_bytes, as_stream(stream));
 }
 
-int swf_window_attention_bwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
-                                  const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
-                                  int32_t W, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes,
-                                  swf_stream_t stream) {
-    SWF_TRY(check_attn_drop_args(desc, p, q, k, v, drop, stream_id, B, H, W, "window_attention_bwd_drop"));
-    if (!gout || !gq || !gk || !gv) return fail(SWF_ERR_NULL, "window_attention_bwd_drop: NULL gradient");
-    if (gq == gk || gq == gv || gk == gv) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd_drop: gq, gk, gv must be three buffers");
-    return window_attention_bwd_drop(*desc, *p, q, k, v, gout, gq, gk, gv, gp, B, H, W, *drop, stream_id, workspace, workspace_bytes,
-                                     as_stream(stream));
-}
-
 size_t swf_mlp_drop_workspace_bytes(int64_t tokens, int32_t channels, int32_t hidden) {
     if (tokens <= 0 || channels <= 0 || hidden <= 0) return 0;
     return mlp_drop_ws(tokens, channels, hidden);
@@ -1454,14 +1402,143 @@ int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* 
     return mlp_fwd_drop(*fc1, *fc2, x, out, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes, as_stream(stream));
 }
 
+// ---- kernel families of the backward (swf_bwd_options / swf_bwd_route) -----------------------------------------------------------------
+// options -> the internal tier; the route is zeroed here and filled by the branches that launch
+static int bwd_tier(const swf_bwd_options* opt, swf_bwd_route* route, const char* what, BwdTier* tier) {
+    const int gemm = opt ? opt->gemm : SWF_BWD_GEMM_FMA, attn = opt ? opt->attention : SWF_BWD_ATTN_THREAD;
+    if (gemm != SWF_BWD_GEMM_FMA && gemm != SWF_BWD_GEMM_MFMA) return fail(SWF_ERR_UNSUPPORTED, "%s: unknown gradient-GEMM family %d", what, gemm);
+    if (attn != SWF_BWD_ATTN_THREAD) return fail(SWF_ERR_UNSUPPORTED, "%s: unknown attention-backward family %d", what, attn);
+    if (route) *route = swf_bwd_route{};
+    *tier = BwdTier{gemm, route};
+    return SWF_OK;
+}
+
+// One implementation behind the plain, the *_drop and the *_opt entry of each unit.  what: the entry's name in error texts;
+// need_drop: the *_drop entries require their masks (the others take NULL for none).
+static int block_bwd_entry(const char* what, bool need_drop, const swf_block_desc* desc, const swf_block_stream_params* px,
+                           const swf_block_stream_params* py, const float* x_in, const float* y_in, const float* gx_out, const float* gy_out,
+                           float* gx_in, float* gy_in, const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H,
+                           int32_t W, const swf_dropout* drop, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
+                           size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_block(desc, px, py, x_in, y_in, gx_in, gy_in, B, H, W, true, true));
+    if (!gx_out || (py && !gy_out)) return fail(SWF_ERR_NULL, "%s: NULL output gradient", what);
+    if (need_drop || drop) SWF_TRY(check_dropout(drop, what));
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, what, &tier));
+    if (drop)
+        return basic_block_bwd_drop(*desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, *drop, workspace, workspace_bytes,
+                                    as_stream(stream), tier);
+    return basic_block_bwd(*desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, workspace, workspace_bytes,
+                           as_stream(stream), tier);
+}
+int swf_basic_block_bwd(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
+                        const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gpx,
+                        const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes,
+                        swf_stream_t stream) {
+    return block_bwd_entry("basic_block_bwd", false, desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, nullptr, nullptr,
+                           nullptr, workspace, workspace_bytes, stream);
+}
+int swf_basic_block_bwd_drop(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                             const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
+                             const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
+                             const swf_dropout* drop, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return block_bwd_entry("basic_block_bwd_drop", true, desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, drop, nullptr,
+                           nullptr, workspace, workspace_bytes, stream);
+}
+int swf_basic_block_bwd_opt(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                            const float* x_in, const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in,
+                            const swf_block_stream_grads* gpx, const swf_block_stream_grads* gpy, int32_t B, int32_t H, int32_t W,
+                            const swf_dropout* drop, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
+                            size_t workspace_bytes, swf_stream_t stream) {
+    return block_bwd_entry("basic_block_bwd_opt", false, desc, px, py, x_in, y_in, gx_out, gy_out, gx_in, gy_in, gpx, gpy, B, H, W, drop, opt,
+                           route, workspace, workspace_bytes, stream);
+}
+
+static int attention_bwd_entry(const char* what, bool need_drop, const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k,
+                               const float* v, const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                               int32_t W, const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route,
+                               void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !p || !q || !k || !v) return fail(SWF_ERR_NULL, "%s: NULL argument", what);
+    if (!p->q.weight || !p->k.weight || !p->v.weight || !p->proj.weight || !p->bias_table) return fail(SWF_ERR_NULL, "%s: NULL parameter", what);
+    SWF_TRY(check_attn_desc(desc, B, H, W));
+    if (stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "%s: negative stream id", what);
+    if (need_drop || drop) SWF_TRY(check_dropout(drop, what));
+    if (!gout || !gq || !gk || !gv) return fail(SWF_ERR_NULL, "%s: NULL gradient", what);
+    if (gq == gk || gq == gv || gk == gv) return fail(SWF_ERR_UNSUPPORTED, "%s: gq, gk, gv must be three buffers", what);
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, what, &tier));
+    if (drop)
+        return window_attention_bwd_drop(*desc, *p, q, k, v, gout, gq, gk, gv, gp, B, H, W, *drop, stream_id, workspace, workspace_bytes,
+                                         as_stream(stream), tier);
+    return window_attention_bwd(*desc, *p, q, k, v, gout, gq, gk, gv, gp, B, H, W, workspace, workspace_bytes, as_stream(stream), tier);
+}
+int swf_window_attention_bwd(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v, const float* gout,
+                             float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H, int32_t W, void* workspace,
+                             size_t workspace_bytes, swf_stream_t stream) {
+    return attention_bwd_entry("window_attention_bwd", false, desc, p, q, k, v, gout, gq, gk, gv, gp, B, H, W, nullptr, 0, nullptr, nullptr,
+                               workspace, workspace_bytes, stream);
+}
+int swf_window_attention_bwd_drop(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                  const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                                  int32_t W, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes,
+                                  swf_stream_t stream) {
+    return attention_bwd_entry("window_attention_bwd_drop", true, desc, p, q, k, v, gout, gq, gk, gv, gp, B, H, W, drop, stream_id, nullptr,
+                               nullptr, workspace, workspace_bytes, stream);
+}
+int swf_window_attention_bwd_opt(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
+                                 const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp, int32_t B, int32_t H,
+                                 int32_t W, const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route,
+                                 void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return attention_bwd_entry("window_attention_bwd_opt", false, desc, p, q, k, v, gout, gq, gk, gv, gp, B, H, W, drop, stream_id, opt, route,
+                               workspace, workspace_bytes, stream);
+}
+
+static int mlp_bwd_entry(const char* what, bool need_drop, const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                         const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                         const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
+                         size_t workspace_bytes, swf_stream_t stream) {
+    if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "%s: NULL argument", what);
+    if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "%s: bad sizes", what);
+    if (need_drop || drop) SWF_TRY(check_dropout(drop, what));
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, what, &tier));
+    if (drop)
+        return mlp_bwd_drop(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes,
+                            as_stream(stream), tier);
+    return mlp_bwd(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, workspace, workspace_bytes, as_stream(stream), tier);
+}
+int swf_mlp_bwd(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* gfc1,
+                const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden, void* workspace, size_t workspace_bytes,
+                swf_stream_t stream) {
+    return mlp_bwd_entry("mlp_bwd", false, fc1, fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, nullptr, 0, nullptr, nullptr, workspace,
+                         workspace_bytes, stream);
+}
 int swf_mlp_bwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
                      const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
                      const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "mlp_bwd_drop: NULL argument");
-    if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_bwd_drop: bad sizes");
-    SWF_TRY(check_dropout(drop, "mlp_bwd_drop"));
-    return mlp_bwd_drop(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes,
-                        as_stream(stream));
+    return mlp_bwd_entry("mlp_bwd_drop", true, fc1, fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, drop, stream_id, nullptr, nullptr,
+                         workspace, workspace_bytes, stream);
+}
+int swf_mlp_bwd_opt(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* gfc1,
+                    const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden, const swf_dropout* drop, int32_t stream_id,
+                    const swf_bwd_options* opt, swf_bwd_route* route, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return mlp_bwd_entry("mlp_bwd_opt", false, fc1, fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, drop, stream_id, opt, route, workspace,
+                         workspace_bytes, stream);
+}
+
+size_t swf_linear_bwd_workspace_bytes(int64_t M, int32_t N, int32_t K) {
+    if (M <= 0 || N <= 0 || K <= 0) return 0;
+    return linear_bwd_ws(M, N, K);
+}
+
+int swf_linear_bwd(const float* x, const float* weight, const float* gout, float* gx, float* gw, float* gb, int64_t M, int32_t N, int32_t K,
+                   int32_t accumulate, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace, size_t workspace_bytes,
+                   swf_stream_t stream) {
+    if (!x || !weight || !gout) return fail(SWF_ERR_NULL, "linear_bwd: NULL tensor");
+    if (M <= 0 || N <= 0 || K <= 0) return fail(SWF_ERR_BAD_SHAPE, "linear_bwd: bad sizes");
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, "linear_bwd", &tier));
+    return linear_bwd(x, weight, gout, gx, gw, gb, M, N, K, accumulate, workspace, workspace_bytes, as_stream(stream), tier);
 }
 
 size_t swf_layernorm_bwd_workspace_bytes(int64_t tokens, int32_t C) {
@@ -1481,12 +1558,21 @@ size_t swf_patch_layer_bwd_workspace_bytes(int32_t B, int32_t H, int32_t W, int3
     return patch_bwd_ws(B, H, W, Cin, Cout, merge_h, merge_w, encoder);
 }
 
+int swf_patch_layer_bwd_opt(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int32_t B,
+                            int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t encoder,
+                            const swf_bwd_options* opt, swf_bwd_route* route, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!p || !p->conv.weight || !p->ln.gamma || !p->ln.beta || !in || !gout || !gin) return fail(SWF_ERR_NULL, "patch_layer_bwd: NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_layer_bwd: bad sizes");
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, "patch_layer_bwd", &tier));
+    return patch_bwd(*p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, workspace, workspace_bytes, as_stream(stream), tier);
+}
+
 int swf_patch_layer_bwd(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int32_t B, int32_t H,
                         int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t encoder, void* workspace,
                         size_t workspace_bytes, swf_stream_t stream) {
-    if (!p || !p->conv.weight || !p->ln.gamma || !p->ln.beta || !in || !gout || !gin) return fail(SWF_ERR_NULL, "patch_layer_bwd: NULL argument");
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_layer_bwd: bad sizes");
-    return patch_bwd(*p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, workspace, workspace_bytes, as_stream(stream));
+    return swf_patch_layer_bwd_opt(p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, nullptr, nullptr, workspace, workspace_bytes,
+                                   stream);
 }
 
 int swf_reflect_pad_bwd(const float* gout, float* gin, int32_t B, int32_t H, int32_t W, int32_t C, int32_t pad_h, int32_t pad_w, swf_stream_t stream) {

@@ -13,8 +13,9 @@ through exact-fp32 backward entries, and in train() the reference's three dropou
 > 0 runs the exact-fp32 *_drop entries of the library, with or without grad.
 
 Each entry family of the library is marshalled in one place: WindowAttention, AutoPathMLP and BasicBlock each have one `_fwd` and one
-`_bwd`, which pick the plain or the *_drop entry (with its workspace query and its mask arguments) from `drop is None`.  The no-grad
-forward, the dropout forward and the torch.autograd.Function of a module all go through those two.
+`_bwd`; `_fwd` picks the plain or the *_drop entry (with its workspace query and its mask arguments) from `drop is None`, `_bwd` calls
+the *_bwd_opt entry, which takes the masks (or NULL) and the kernel family of the module's `backward_tier` and reports what it launched.
+The no-grad forward, the dropout forward and the torch.autograd.Function of a module all go through those two.
 """
 from __future__ import annotations
 
@@ -213,6 +214,34 @@ def _precision_code(p) -> int:
     raise ValueError(f"precision must be 'fast' or 'fp32', got {p!r}")
 
 
+def _bwd_gemm_code(g) -> int:
+    if g not in ("fma", "mfma"):
+        raise ValueError(f"backward tier must be 'fma' or 'mfma', got {g!r}")
+    return L.BWD_GEMM_MFMA if g == "mfma" else L.BWD_GEMM_FMA
+
+
+class _BackwardTier:
+    """The kernel family of a module's own backward call (include/swinfuse.h swf_bwd_options).  `backward_tier` is 'fma' (the default:
+    LDS-tiled scalar-FMA gradient GEMMs) or 'mfma' (the same fmaf chains on the matrix cores: the same bits); it sets `backward_gemm`,
+    the one part that has two families today, which a test may also set on its own.  The family is read when the FORWARD of a
+    differentiable call runs and travels with it to the backward.  `last_backward_route` is the swf_bwd_route of the module's last backward
+    call (None before the first)."""
+    backward_gemm = "fma"
+    last_backward_route: Optional[L.BwdRoute] = None
+
+    @property
+    def backward_tier(self) -> str:
+        return self.backward_gemm
+
+    @backward_tier.setter
+    def backward_tier(self, tier) -> None:
+        _bwd_gemm_code(tier)
+        self.backward_gemm = tier
+
+    def _bwd_options(self) -> L.BwdOptions:
+        return L.BwdOptions(_bwd_gemm_code(self.backward_gemm), L.BWD_ATTN_THREAD)
+
+
 class StateRecorder:
     """LIFO used for pad sizes, shapes and U-Net skips (reference a010_StateRecorder.py:1-18)."""
 
@@ -240,7 +269,7 @@ class _FwdAlias:
 # ----------------------------------------------------------------------------------------------
 # a001 WindowAttention
 # ----------------------------------------------------------------------------------------------
-class WindowAttention(_FwdAlias, nn.Module):
+class WindowAttention(_FwdAlias, _BackwardTier, nn.Module):
     """Drop-in for a001_WindowAttention.WindowAttention (ctor a001:9-20, forward a001:448-474)."""
 
     def __init__(self, in_out_dims: int, num_heads: int, dims_per_head: int, window_size: tuple,
@@ -305,9 +334,9 @@ class WindowAttention(_FwdAlias, nn.Module):
                       ws, wsn, _stream(q.device)))
         return _to_nchw(out)
 
-    def _bwd(self, q: Tensor, k: Tensor, v: Tensor, g: Tensor, drop: Optional[L.Dropout]):
+    def _bwd(self, q: Tensor, k: Tensor, v: Tensor, g: Tensor, drop: Optional[L.Dropout], opt: L.BwdOptions):
         """dL/d(q, k, v) and the parameter gradients (bias table, then weight and bias of q, k, v, projection) through
-        swf_window_attention_bwd, with dropout swf_window_attention_bwd_drop and the forward's masks."""
+        swf_window_attention_bwd_opt in the kernel family `opt`, with dropout the forward's masks (mask stream 0)."""
         b, c, h, w = q.shape
         dev = q.device
         qn, kn, vn = _qkv_nhwc(q, k, v)
@@ -319,13 +348,13 @@ class WindowAttention(_FwdAlias, nn.Module):
         gt = _new_like(self.relative_position_bias_table)
         grads = L.AttnParams(*[L.Linear(_raw(wt), _raw(bs)) for wt, bs in zip(gw, gb)], _raw(gt))
         lib, desc, prm = L.lib(), self._desc(), self._params()
-        if drop is None:
-            size, entry, masks = lib.swf_window_attention_bwd_workspace_bytes, lib.swf_window_attention_bwd, ()
-        else:
-            size, entry, masks = lib.swf_window_attention_drop_workspace_bytes, lib.swf_window_attention_bwd_drop, (C.byref(drop), 0)
+        size = lib.swf_window_attention_bwd_workspace_bytes if drop is None else lib.swf_window_attention_drop_workspace_bytes
         ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
-        L.check(entry(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk), _ptr(gv), C.byref(grads),
-                      b, h, w, *masks, ws, wsn, _stream(dev)))
+        route = L.BwdRoute()
+        L.check(lib.swf_window_attention_bwd_opt(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
+                                                 _ptr(gv), C.byref(grads), b, h, w, _ref(drop), 0, C.byref(opt), C.byref(route),
+                                                 ws, wsn, _stream(dev)))
+        self.last_backward_route = route
         return (_to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *[t for pair in zip(gw, gb) for t in pair])
 
 
@@ -336,7 +365,7 @@ class _WindowAttentionFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, drop, q, k, v, table, *params):
-        ctx.module, ctx.drop = module, drop
+        ctx.module, ctx.drop, ctx.opt = module, drop, module._bwd_options()
         ctx.save_for_backward(q, k, v)
         with torch.no_grad():
             return module._fwd(q.detach(), k.detach(), v.detach(), drop)
@@ -344,7 +373,7 @@ class _WindowAttentionFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         with torch.no_grad():
-            return (None, None, *ctx.module._bwd(*ctx.saved_tensors, g, ctx.drop))
+            return (None, None, *ctx.module._bwd(*ctx.saved_tensors, g, ctx.drop, ctx.opt))
 
 
 class _MlpFunction(torch.autograd.Function):
@@ -353,7 +382,7 @@ class _MlpFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, module, s, drop, x, w1, b1, w2, b2):
-        ctx.module, ctx.s, ctx.drop = module, s, drop
+        ctx.module, ctx.s, ctx.drop, ctx.opt = module, s, drop, module._bwd_options()
         ctx.save_for_backward(x)
         with torch.no_grad():
             return module._fwd(drop, x.detach(), None, False, s)
@@ -361,7 +390,7 @@ class _MlpFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         with torch.no_grad():
-            return (None, None, None, *ctx.module._bwd(ctx.s, ctx.drop, ctx.saved_tensors[0], g))
+            return (None, None, None, *ctx.module._bwd(ctx.s, ctx.drop, ctx.saved_tensors[0], g, ctx.opt))
 
 
 class _LayerNormFunction(torch.autograd.Function):
@@ -427,7 +456,7 @@ class AutoPathWinAtt(_FwdAlias, nn.Module):
 _MASK_STREAM = {"x": 0, "y": 1}   # the stream id of the dropout masks (include/swinfuse.h swf_dropout)
 
 
-class AutoPathMLP(_FwdAlias, nn.Module):
+class AutoPathMLP(_FwdAlias, _BackwardTier, nn.Module):
     """a003_AutoPathMLP.AutoPathMLP: per-stream 1x1 conv -> activation -> 1x1 conv (a003:21-50)."""
 
     def __init__(self, in_out_dims: int, hidden_dims: int, activation_func: nn.Module, use_dual_path: bool,
@@ -478,9 +507,9 @@ class AutoPathMLP(_FwdAlias, nn.Module):
             outs.append(_to_nchw(out))
         return tuple(outs) if dual else outs[0]
 
-    def _bwd(self, s: str, drop: Optional[L.Dropout], x: Tensor, g: Tensor):
-        """dL/dx of stream `s` and the gradients of its fc1 / fc2 weight and bias through swf_mlp_bwd, with dropout swf_mlp_bwd_drop and
-        the forward's masks."""
+    def _bwd(self, s: str, drop: Optional[L.Dropout], x: Tensor, g: Tensor, opt: L.BwdOptions):
+        """dL/dx of stream `s` and the gradients of its fc1 / fc2 weight and bias through swf_mlp_bwd_opt in the kernel family `opt`, with
+        dropout the forward's masks."""
         b, c, h, w = x.shape
         dev = x.device
         c1, c2 = getattr(self, f"mlp_{s}_1"), getattr(self, f"mlp_{s}_2")
@@ -490,13 +519,12 @@ class AutoPathMLP(_FwdAlias, nn.Module):
         f1, f2 = self._fcs(s)
         gf1, gf2 = L.Linear(_raw(g1w), _raw(g1b)), L.Linear(_raw(g2w), _raw(g2b))
         lib, n, hid = L.lib(), b * h * w, self.hidden_dims
-        if drop is None:
-            size, entry, masks = lib.swf_mlp_bwd_workspace_bytes, lib.swf_mlp_bwd, ()
-        else:
-            size, entry, masks = lib.swf_mlp_drop_workspace_bytes, lib.swf_mlp_bwd_drop, (C.byref(drop), _MASK_STREAM[s])
+        size = lib.swf_mlp_bwd_workspace_bytes if drop is None else lib.swf_mlp_drop_workspace_bytes
         ws, wsn = _workspace(size(n, c, hid), dev)
-        L.check(entry(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, hid, *masks,
-                      ws, wsn, _stream(dev)))
+        route = L.BwdRoute()
+        L.check(lib.swf_mlp_bwd_opt(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, hid,
+                                    _ref(drop), _MASK_STREAM[s], C.byref(opt), C.byref(route), ws, wsn, _stream(dev)))
+        self.last_backward_route = route
         return _to_nchw(gx), g1w, g1b, g2w, g2b
 
     def _one_grad(self, x: Tensor, s: str, drop: Optional[L.Dropout]) -> Tensor:
@@ -590,7 +618,7 @@ class _BasicBlockFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, block, dual, drop, x, y, *params):
-        ctx.block, ctx.dual, ctx.drop = block, dual, drop
+        ctx.block, ctx.dual, ctx.drop, ctx.opt = block, dual, drop, block._bwd_options()
         ctx.save_for_backward(x, y) if dual else ctx.save_for_backward(x)
         ctx.nparams = len(params)
         with torch.no_grad():
@@ -603,13 +631,13 @@ class _BasicBlockFunction(torch.autograd.Function):
         saved = ctx.saved_tensors
         x, y = saved[0], (saved[1] if dual else None)
         with torch.no_grad():
-            gx, gy, bufs = block._bwd(x, y, gouts[0], gouts[1] if dual else None, dual, ctx.drop)
+            gx, gy, bufs = block._bwd(x, y, gouts[0], gouts[1] if dual else None, dual, ctx.drop, ctx.opt)
         streams = ("x", "y") if dual else ("x",)
         pg = [g for s in streams for g in bufs[s]]
         return (None, None, None, gx, gy, *pg)
 
 
-class BasicBlock(_FwdAlias, nn.Module):
+class BasicBlock(_FwdAlias, _BackwardTier, nn.Module):
     """a005_BasicBlock.BasicBlock (ctor a005:11-28, forward a005:127-145)."""
 
     def __init__(self, in_out_dims: int, num_heads: int, dims_per_head: int, window_size: tuple,
@@ -696,9 +724,9 @@ class BasicBlock(_FwdAlias, nn.Module):
                       ws, wsn, _stream(x.device)))
         return _nchw_out(ox, oy)
 
-    def _bwd(self, x, y, gox, goy, dual, drop: Optional[L.Dropout]):
-        """dL/d(x, y) and the parameter gradients of both streams through swf_basic_block_bwd (exact fp32, forward recomputed; with
-        dropout swf_basic_block_bwd_drop, the same masks as the forward)."""
+    def _bwd(self, x, y, gox, goy, dual, drop: Optional[L.Dropout], opt: L.BwdOptions):
+        """dL/d(x, y) and the parameter gradients of both streams through swf_basic_block_bwd_opt in the kernel family `opt` (exact fp32,
+        forward recomputed; with dropout the same masks as the forward)."""
         b, c, h, w = x.shape
         dev = x.device
         xn, yn = _to_nhwc(x), (_to_nhwc(y) if dual else None)
@@ -712,13 +740,12 @@ class BasicBlock(_FwdAlias, nn.Module):
         px = self._stream_params("x")
         py = self._stream_params("y") if dual else None
         lib = L.lib()
-        if drop is None:
-            size, entry, masks = lib.swf_basic_block_bwd_workspace_bytes, lib.swf_basic_block_bwd, ()
-        else:
-            size, entry, masks = lib.swf_basic_block_drop_workspace_bytes, lib.swf_basic_block_bwd_drop, (C.byref(drop),)
+        size = lib.swf_basic_block_bwd_workspace_bytes if drop is None else lib.swf_basic_block_drop_workspace_bytes
         ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
-        L.check(entry(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(gxo), _ptr(gyo), _ptr(gxi), _ptr(gyi), _ref(gsx), _ref(gsy),
-                      b, h, w, *masks, ws, wsn, _stream(dev)))
+        route = L.BwdRoute()
+        L.check(lib.swf_basic_block_bwd_opt(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(gxo), _ptr(gyo), _ptr(gxi), _ptr(gyi),
+                                            _ref(gsx), _ref(gsy), b, h, w, _ref(drop), C.byref(opt), C.byref(route), ws, wsn, _stream(dev)))
+        self.last_backward_route = route
         return _to_nchw(gxi), (_to_nchw(gyi) if dual else None), bufs
 
     def forward(self, x, y=None):
@@ -948,11 +975,12 @@ class MyPadding(_FwdAlias, nn.Module):
 
 
 class _PatchLayerFunction(torch.autograd.Function):
-    """One stream of PatchMergingAndLinearLayer under autograd: forward through the library, backward = swf_patch_layer_bwd."""
+    """One stream of PatchMergingAndLinearLayer under autograd: forward through the library, backward = swf_patch_layer_bwd_opt in the
+    layer's backward tier."""
 
     @staticmethod
     def forward(ctx, layer, s, t, cw, cb, lg, lb):
-        ctx.layer, ctx.s = layer, s
+        ctx.layer, ctx.s, ctx.opt = layer, s, layer._bwd_options()
         ctx.save_for_backward(t)
         with torch.no_grad():
             return layer._one(t.detach(), s)
@@ -973,12 +1001,14 @@ class _PatchLayerFunction(torch.autograd.Function):
             grads = L.PatchParams(L.Linear(_raw(gw), _raw(gb)), L.Norm(_raw(gg), _raw(gbe)))
             lib, enc = L.lib(), int(layer.belongs_to_encoder)
             ws, wsn = _workspace(lib.swf_patch_layer_bwd_workspace_bytes(b, h, w, layer.in_dims, layer.out_dims, mh, mw, enc), dev)
-            L.check(lib.swf_patch_layer_bwd(C.byref(prm), _ptr(tn), _ptr(gn), _ptr(gin), C.byref(grads), b, h, w, layer.in_dims, layer.out_dims,
-                                            mh, mw, enc, ws, wsn, _stream(dev)))
+            route = L.BwdRoute()
+            L.check(lib.swf_patch_layer_bwd_opt(C.byref(prm), _ptr(tn), _ptr(gn), _ptr(gin), C.byref(grads), b, h, w, layer.in_dims,
+                                                layer.out_dims, mh, mw, enc, C.byref(ctx.opt), C.byref(route), ws, wsn, _stream(dev)))
+            layer.last_backward_route = route
             return None, None, _to_nchw(gin), gw, gb, gg, gbe
 
 
-class PatchMergingAndLinearLayer(_FwdAlias, nn.Module):
+class PatchMergingAndLinearLayer(_FwdAlias, _BackwardTier, nn.Module):
     """a011_PatchOperation.PatchMergingAndLinearLayer (ctor a011:26-70, forward a011:244-264)."""
 
     def __init__(self, belongs_to_encoder: bool, use_dual_path: bool, in_dims: int, out_dims: int,
@@ -1117,7 +1147,7 @@ def get_encoder_or_decoder_block(mode: str, window_size: tuple, feature_shape_re
     return nn.ModuleList(mods if enc else mods[::-1])
 
 
-class MyModel(_FwdAlias, nn.Module):
+class MyModel(_FwdAlias, _BackwardTier, nn.Module):
     """Drop-in for a013_ModelDefinition.MyModel (ctor a013:18-38, forward a013:209-230).
 
     `forward(in_x, in_y)` is ONE call into the C-ABI (`swf_model_forward`): the parameters are
@@ -1125,7 +1155,9 @@ class MyModel(_FwdAlias, nn.Module):
     (`swf_model_param_info`), and the whole U-Net runs from that arena on the current stream.
     `precision` ('fast' | 'fp32') selects the arithmetic mode (include/swinfuse.h swf_precision); `schedule` ('latency' |
     'throughput', swf_schedule) the kernel shapes of the fast tier where it has a choice: 'latency' for one forward at a time,
-    'throughput' for several forwards in flight (shard.ShardedFusion sets it for its lanes).
+    'throughput' for several forwards in flight (shard.ShardedFusion sets it for its lanes).  `backward_tier` ('fma' | 'mfma', swf_bwd_options)
+    selects the kernel family of the gradient GEMMs of the differentiable forward's backward — the same bits either way — in every block
+    and patch layer; `backward_routes()` says what their last backward launched.
     """
 
     def __init__(self, window_size: tuple, merging_size: tuple, in_dims_list: list, out_dims_list: list,
@@ -1316,15 +1348,30 @@ class MyModel(_FwdAlias, nn.Module):
         y = in_y if in_y.requires_grad else in_y.detach().requires_grad_(True)
         # the blocks run in the MODEL's tier here (their own .precision is what they run at when called on their own); a block that
         # drops in train() ignores it and runs the exact tier (the fused fast kernels have no masks)
+        gemm = self.backward_gemm
+        _bwd_gemm_code(gemm)
         blocks = [m for m in self.modules() if isinstance(m, BasicBlock)]
         own = [blk.precision for blk in blocks]
         for blk in blocks:
             blk.precision = self.precision
+        # ... and every module with gradient GEMMs in the model's backward tier: read by their forward, so it holds for their backward
+        tiered = blocks + [m for m in self.modules() if isinstance(m, PatchMergingAndLinearLayer)]
+        own_gemm = [m.backward_gemm for m in tiered]
+        for m in tiered:
+            m.backward_gemm = gemm
         try:
             return self._forward_autograd_stages(x, y)
         finally:
             for blk, p in zip(blocks, own):
                 blk.precision = p
+            for m, g in zip(tiered, own_gemm):
+                m.backward_gemm = g
+
+    def backward_routes(self) -> dict:
+        """{module name: swf_bwd_route} of every sub-module whose backward has run (BasicBlock and PatchMergingAndLinearLayer under
+        the model's differentiable forward)."""
+        return {n: m.last_backward_route for n, m in self.named_modules()
+                if isinstance(m, _BackwardTier) and m is not self and m.last_backward_route is not None}
 
     def _forward_autograd_stages(self, x: Tensor, y: Tensor) -> Tensor:
         n = len(self.in_dims_list)

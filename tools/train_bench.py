@@ -5,8 +5,11 @@ reference's optimiser, a016:67, as one HIP launch).
 --loss standin (default) is a smooth stand-in, the mean squared distance to max(ir, vis); --loss fusion is the reference's step
 (a016:150-165): clamp_(0, 1), then MyLoss().calcu_total_loss on the fused HIP loss.
 
+--backward-tier fma (default) | mfma selects the kernel family of the gradient GEMMs (MyModel.backward_tier: the same bits either way);
+both times the two tiers in one process, each on a fresh model from the same weights, and reports them side by side.
+
     python tools/train_bench.py [--batch 4] [--size 128] [--config win8] [--iters 5] [--drop P] [--loss standin|fusion]
-                                [--opt sgd|adam|fused-adam]
+                                [--opt sgd|adam|fused-adam] [--backward-tier fma|mfma|both]
 
 --drop P sets the three dropout ratios (attention, projection, MLP) to P: every block then runs the exact-fp32 *_drop entries.
 """
@@ -23,17 +26,8 @@ from torch import nn
 import __graft_entry__ as entry
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--batch", type=int, default=4)
-    ap.add_argument("--size", type=int, default=128)
-    ap.add_argument("--config", default="win8")
-    ap.add_argument("--iters", type=int, default=5)
-    ap.add_argument("--drop", type=float, default=0.0, help="attention_drop_ratio = linear_after_att_drop_ratio = mlp_drop_ratio")
-    ap.add_argument("--loss", choices=["standin", "fusion"], default="standin")
-    ap.add_argument("--opt", choices=["sgd", "adam", "fused-adam"], default="sgd")
-    args = ap.parse_args()
-    entry.build()
+def time_steps(args, tier):
+    """args.iters timed steps (after one untimed) of a fresh model in backward tier `tier`: ({phase: ms per step}, losses)"""
     from swin_unet_image_fusion_amd import CONFIGS, FusedAdam, MyLoss, MyModel, load_recipe_into, synthetic_pair
     dev = torch.device("cuda:0")
     cfg = CONFIGS[args.config]
@@ -42,6 +36,7 @@ def main():
     model = MyModel(**kw)
     load_recipe_into(model, seed=0, flavor="kaiming")
     model.to(dev).train()
+    model.backward_tier = tier
     if args.opt == "sgd":
         opt = torch.optim.SGD(model.parameters(), lr=1e-3)
     else:
@@ -52,6 +47,7 @@ def main():
     fusion_loss = MyLoss() if args.loss == "fusion" else None
     times = {"forward": 0.0, "backward": 0.0, "update": 0.0}
     losses = []
+    torch.manual_seed(0)   # the dropout seeds of --drop: the same for every tier
     for it in range(args.iters + 1):
         torch.cuda.synchronize(); t0 = time.perf_counter()
         out = model(ir, vis)
@@ -70,12 +66,40 @@ def main():
         losses.append(float(loss))
         if it:
             times["forward"] += t1 - t0; times["backward"] += t2 - t1; times["update"] += t3 - t2
-    ms = {k: round(v / args.iters * 1e3, 2) for k, v in times.items()}
+    return {k: round(v / args.iters * 1e3, 2) for k, v in times.items()}, losses
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--size", type=int, default=128)
+    ap.add_argument("--config", default="win8")
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--drop", type=float, default=0.0, help="attention_drop_ratio = linear_after_att_drop_ratio = mlp_drop_ratio")
+    ap.add_argument("--loss", choices=["standin", "fusion"], default="standin")
+    ap.add_argument("--opt", choices=["sgd", "adam", "fused-adam"], default="sgd")
+    ap.add_argument("--backward-tier", choices=["fma", "mfma", "both"], default="fma", help="kernel family of the gradient GEMMs (MyModel.backward_tier)")
+    args = ap.parse_args()
+    entry.build()
     label = "SGD" if args.opt == "sgd" else args.opt
-    total = sum(ms.values())
-    print(json.dumps({"what": f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, {label}, dropout {args.drop}, loss {args.loss}",
-                      "ms": ms, "ms_per_step": round(total, 2), "pairs_per_s": round(args.batch / total * 1e3, 1),
-                      "loss_first_last": [losses[0], losses[-1]]}))
+    what = f"training step B={args.batch} {args.size}x{args.size} {args.config}, model.train(), autograd path, {label}, dropout {args.drop}, loss {args.loss}"
+    tiers = ["fma", "mfma"] if args.backward_tier == "both" else [args.backward_tier]
+    res = {}
+    for tier in tiers:
+        ms, losses = time_steps(args, tier)
+        total = sum(ms.values())
+        res[tier] = {"ms": ms, "ms_per_step": round(total, 2), "pairs_per_s": round(args.batch / total * 1e3, 1), "loss_first_last": [losses[0], losses[-1]],
+                     "losses": losses}
+    if len(tiers) == 1:
+        r = res[tiers[0]]
+        del r["losses"]
+        print(json.dumps({"what": what, "backward_tier": tiers[0], **r}))
+        return
+    # the two families return the same bits, so the two runs must have walked the same losses
+    same = res["fma"].pop("losses") == res["mfma"].pop("losses")
+    b0, b1 = res["fma"]["ms"]["backward"], res["mfma"]["ms"]["backward"]
+    print(json.dumps({"what": what, "tiers": res, "same_losses": same, "backward_ms_fma_over_mfma": round(b0 / b1, 3),
+                      "backward_gain_percent": round(100.0 * (b0 - b1) / b0, 1)}))
 
 
 if __name__ == "__main__":
