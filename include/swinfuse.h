@@ -201,7 +201,10 @@ int swf_basic_block_bwd(const swf_block_desc* desc, const swf_block_stream_param
 /* The inner modules on their own under autograd (a caller that keeps the reference's BasicBlock and swaps only a001 / a003 / a004):
  * exact fp32, forward intermediates recomputed, fixed-order sums.  Gradient pointers as above (NULL = not wanted).
  * WindowAttention.forward (a001:448-474): q / k / v [B][H][W][C]; gq / gk / gv are three separate buffers — where one tensor was passed
- * as more than one of q, k, v the caller adds them (torch.autograd does). */
+ * as more than one of q, k, v the caller adds them (torch.autograd does).
+ * A (window, head_dim) whose attention backward tile fits neither kernel's LDS (16 x 16 windows at head_dim > 32: 262.8 KB against
+ * 160 KB) is refused by the block and the attention entries with SWF_ERR_UNSUPPORTED before anything is launched, like a short
+ * workspace: no gradient buffer and no byte of the workspace is written.  The exact-tier forward accepts that shape. */
 size_t swf_window_attention_bwd_workspace_bytes(const swf_attn_desc* desc, int32_t B, int32_t H, int32_t W);
 int swf_window_attention_bwd(const swf_attn_desc* desc, const swf_attn_params* p, const float* q, const float* k, const float* v,
                              const float* gout, float* gq, float* gk, float* gv, const swf_attn_grads* gp,

@@ -496,16 +496,41 @@ __global__ void attn_bwd_kernel(AttnBwdBatch batch, int ld, int B, int H, int W,
     }
 }
 
+// LDS of one (window, head) of wh x ww tokens at DMAX padded channels: the resident form keeps the probability tile, the recompute form
+// three statistics per query.  The resident form runs up to kAttnBwdResidentMax, the recompute form up to kAttnBwdLdsMax.
+constexpr size_t kAttnBwdResidentMax = 96 * 1024, kAttnBwdLdsMax = 160 * 1024;
+size_t attn_bwd_lds_resident(int wh, int ww, int dmax) {
+    const size_t t = (size_t)wh * ww, tsz = (size_t)(2 * wh - 1) * (2 * ww - 1);
+    return (4 * t * dmax + tsz + t * (t + 1) + t) * sizeof(float);
+}
+size_t attn_bwd_lds_recompute(int wh, int ww, int dmax) {
+    const size_t t = (size_t)wh * ww, tsz = (size_t)(2 * wh - 1) * (2 * ww - 1);
+    return (4 * t * dmax + tsz + 3 * t) * sizeof(float);
+}
+int attn_bwd_dmax(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 0; }
+
+// What launch_attn_bwd would refuse, asked by every entry BEFORE its first launch (like the workspace check): a refused call has
+// enqueued nothing and written no gradient.
+int check_attn_bwd_shape(const char* what, int wh, int ww, int d) {
+    const int t = wh * ww, dmax = attn_bwd_dmax(d);
+    if (!dmax) return fail(SWF_ERR_UNSUPPORTED, "%s: attention backward: head_dim %d > 64", what, d);
+    if (cdiv(t, 64) * 64 > 1024) return fail(SWF_ERR_UNSUPPORTED, "%s: attention backward: window of %d tokens > 1024", what, t);
+    const size_t lds = attn_bwd_lds_recompute(wh, ww, dmax);
+    if (attn_bwd_lds_resident(wh, ww, dmax) > kAttnBwdResidentMax && lds > kAttnBwdLdsMax)
+        return fail(SWF_ERR_UNSUPPORTED, "%s: attention backward tile (t=%d, d=%d) needs %zu B of LDS (at most %zu B)", what, t, d, lds, kAttnBwdLdsMax);
+    return SWF_OK;
+}
+
 template <int DMAX>
 int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift,
                       const BwdTier& tier, hipStream_t stream) {
-    const int t = wh * ww, tsz = (2 * wh - 1) * (2 * ww - 1);
+    const int t = wh * ww;
     const int threads = cdiv(t, 64) * 64;
     if (threads > 1024) return fail(SWF_ERR_UNSUPPORTED, "attention backward: window of %d tokens > 1024", t);
     dim3 grid(B * (H / wh) * (W / ww), heads, nprob);
     const float scale = 1.0f / sqrtf((float)d);
-    const size_t lds_res = ((size_t)4 * t * DMAX + tsz + (size_t)t * (t + 1) + t) * sizeof(float);
-    if (lds_res <= 96 * 1024) {   // the probability tile stays in LDS (8 x 8 and 7 x 7 windows at every head width)
+    const size_t lds_res = attn_bwd_lds_resident(wh, ww, DMAX);
+    if (lds_res <= kAttnBwdResidentMax) {   // the probability tile stays in LDS (8 x 8 and 7 x 7 windows at every head width)
         if (lds_res > 64 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_kernel<DMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_res);
             if (e != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn_bwd): %s", hipGetErrorString(e));
@@ -514,8 +539,8 @@ int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H
         hipLaunchKernelGGL(attn_bwd_kernel<DMAX>, grid, dim3(threads), lds_res, stream, batch, ld, B, H, W, wh, ww, heads, d, shift, scale);
         return check_launch("attn_bwd");
     }
-    const size_t lds = ((size_t)4 * t * DMAX + tsz + 3 * t) * sizeof(float);
-    if (lds > 160 * 1024) return fail(SWF_ERR_UNSUPPORTED, "attention backward tile (t=%d, d=%d) needs %zu B of LDS", t, d, lds);
+    const size_t lds = attn_bwd_lds_recompute(wh, ww, DMAX);
+    if (lds > kAttnBwdLdsMax) return fail(SWF_ERR_UNSUPPORTED, "attention backward tile (t=%d, d=%d) needs %zu B of LDS", t, d, lds);
     if (lds > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_bwd_recompute_kernel<DMAX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return fail(SWF_ERR_HIP, "hipFuncSetAttribute(attn_bwd): %s", hipGetErrorString(e));
@@ -747,6 +772,7 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
     const int wh = d.attn.win_h, ww = d.attn.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_bwd: token count");
+    SWF_TRY(check_attn_bwd_shape("basic_block_bwd", wh, ww, d.attn.head_dim));
     Carver ws(workspace, workspace_bytes);
     BlockBufs b[2];
     float* scratch = carve_block(ws, b, d, nstream, B, H, W, drop != nullptr);
@@ -905,6 +931,7 @@ int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, 
     const int C = d.channels, HD = d.heads * d.head_dim, wh = d.win_h, ww = d.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(C, HD)) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd: token count");
+    SWF_TRY(check_attn_bwd_shape("window_attention_bwd", wh, ww, d.head_dim));
     Carver ws(workspace, workspace_bytes);
     const AttnBwdBufs b = carve_attention_bwd(ws, d, B, H, W, true, drop != nullptr);
     float *Q = b.Q, *K = b.K, *V = b.V, *O = b.O, *dO = b.dO, *dQ = b.dQ, *dK = b.dK, *dV = b.dV, *dtab = b.dtab, *scratch = b.scratch, *g1 = b.g1;

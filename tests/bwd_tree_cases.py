@@ -98,6 +98,7 @@ class Case:
     head_dim: int = 0
     hidden: int = 0           # block / mlp: hidden width; patch: output channels
     win: int = 0
+    win_w: int = 0            # window width where it differs from the height `win` (0: a square window)
     B: int = 1
     H: int = 0
     W: int = 0
@@ -107,6 +108,12 @@ class Case:
     train: bool = True        # head: batch statistics (train()) or running statistics (eval())
     cfg: str = "tiny"         # head / model
     seed: int = 0
+    shift: bool = True        # attention: cyclic shift
+    cross: bool = True        # attention: k = v = the other stream; False: q = k = v, one input
+
+    @property
+    def window(self) -> Tuple[int, int]:
+        return self.win, self.win_w or self.win
 
     @property
     def id(self) -> str:
@@ -190,7 +197,7 @@ def _model_maps(c: Case) -> List[Tuple[int, int]]:
 def rows(c: Case) -> Dict[str, Tuple[int, ...]]:
     """Partial rows of every sum the case exercises, tree by tree (the order Case.depth claims levels in)."""
     if c.kind in ("block", "attention"):
-        n, tab = c.B * c.H * c.W, c.B * (c.H // c.win) * (c.W // c.win) * c.heads
+        n, tab = c.B * c.H * c.W, c.B * (c.H // c.window[0]) * (c.W // c.window[1]) * c.heads
         return {"dw": (chunks(n),), "table": (tab,), **({"ln": (ln_rows(n),)} if c.kind == "block" else {})}
     if c.kind == "layernorm":
         return {"ln": (ln_rows(c.N),)}
@@ -241,9 +248,9 @@ def make_module(c: Case) -> nn.Module:
     """The package's module of the case with the stress recipe, on the CPU (direct entries have none)."""
     act = nn.ELU(inplace=True)
     if c.kind == "block":
-        m = BasicBlock(c.C, c.heads, c.head_dim, (c.win, c.win), True, True, True, True, c.drop, c.drop, c.hidden, act, c.drop)
+        m = BasicBlock(c.C, c.heads, c.head_dim, c.window, True, True, True, True, c.drop, c.drop, c.hidden, act, c.drop)
     elif c.kind == "attention":
-        m = WindowAttention(c.C, c.heads, c.head_dim, (c.win, c.win), True, True, True, 0.0, 0.0)
+        m = WindowAttention(c.C, c.heads, c.head_dim, c.window, c.shift, c.cross, True, 0.0, 0.0)
     elif c.kind == "patch":
         m = PatchMergingAndLinearLayer(belongs_to_encoder=c.encoder, use_dual_path=True, in_dims=c.C, out_dims=c.hidden,
                                        patch_merging_size_recorder=StateRecorder(), merging_or_unmerging_size=(2, 2), activation_func=act)
@@ -281,6 +288,8 @@ def inputs(c: Case) -> Tuple[torch.Tensor, ...]:
     if c.kind == "model":
         return tuple(torch.from_numpy(a) for a in synthetic_pair(c.B, c.H, c.W, seed_ir=c.seed + 1, seed_vis=c.seed + 2))
     ch = 1 if c.kind == "head" else c.C
+    if c.kind == "attention" and not c.cross:
+        return (G.randn((c.B, ch, c.H, c.W), c.seed + 1),)
     return G.randn((c.B, ch, c.H, c.W), c.seed + 1), G.randn((c.B, ch, c.H, c.W), c.seed + 2)
 
 
@@ -343,15 +352,15 @@ def drop_masks(c: Case):
 def _forward(c: Case, sd, ins):
     """outputs (a list) of the oracle on leaves `ins` with weights `sd`, in their dtype"""
     if c.kind == "block":
-        kw = dict(cross=True, shift=True, num_heads=c.heads, dims_per_head=c.head_dim, window_size=(c.win, c.win))
+        kw = dict(cross=True, shift=True, num_heads=c.heads, dims_per_head=c.head_dim, window_size=c.window)
         if c.drop:
             masks = drop_masks(c)
             return list(D.block_drop(sd, "", *ins, lambda s, site, wd: masks(s, site, wd).to(ins[0].dtype), **kw))
         return list(O.basic_block(sd, "", *ins, **kw))
     if c.kind == "attention":
-        q, kv = ins
-        return [O.window_attention(sd, "", q, kv, kv, num_heads=c.heads, dims_per_head=c.head_dim, window_size=(c.win, c.win),
-                                   use_cyclic_shift=True)]
+        q, kv = ins[0], ins[-1]
+        return [O.window_attention(sd, "", q, kv, kv, num_heads=c.heads, dims_per_head=c.head_dim, window_size=c.window,
+                                   use_cyclic_shift=c.shift)]
     if c.kind == "layernorm":
         return [F.layer_norm(ins[0], (c.C,), sd["norm_layer_1.weight"], sd["norm_layer_1.bias"], 1e-5)]
     if c.kind == "mlp":
