@@ -274,11 +274,20 @@ int swf_mlp_bwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* 
  * exist in two families that return THE SAME BITS: both keep one accumulator per output element, start it at zero and take the
  * reduction index in ascending order with one rounding per product.  SWF_BWD_GEMM_FMA: LDS-tiled scalar fmaf, 4 x 4 outputs per
  * thread (what the entries above run).  SWF_BWD_GEMM_MFMA: the same chains on the matrix cores (v_mfma_f32_16x16x4_f32, an fmaf
- * chain in hardware), 16-byte loads where the pointers and row lengths allow.  The attention core has one family, one thread per query /
- * key (SWF_BWD_ATTN_THREAD); code 1 is kept for a matrix-core kernel and is refused until there is one.  Any other code:
- * SWF_ERR_UNSUPPORTED.  All-zero options are the entries above. */
+ * chain in hardware), 16-byte loads where the pointers and row lengths allow.
+ * The attention core has two families, both exact fp32 with one thread per query / key, no atomics and fixed summation orders.
+ * SWF_BWD_ATTN_THREAD (the default): Q, K, V and dO of a (window, head) in LDS at once, the probability tile beside them where it
+ * fits (RAN_RESIDENT) or rebuilt by every pass (RAN_RECOMPUTE); it refuses a tile whose four operand tiles pass 160 KB — 256 tokens at
+ * head_dim 33 .. 64, level 4 of 16 x 16 windows.  SWF_BWD_ATTN_PHASED (opt-in): two operand tiles at a time — K and V while every query
+ * takes its softmax statistics and dQ, then Q and dO while every key takes dK and dV — and the table gradient through one private
+ * partial per wave; it runs at EVERY shape it can hold (RAN_PHASED) and refuses only head_dim > 64, more than 1024 tokens or an LDS
+ * need of its own past 160 KB (swf_attention_bwd_lds_bytes).  Its results agree with the thread family's to rounding, not bit for bit.
+ * Codes 1 and 2 are refused: 1 is kept for a matrix-core kernel, 2 so that the codes of swf_bwd_attn and swf_bwd_attn_ran that name
+ * the phased kernel are the same.  Any other code: SWF_ERR_UNSUPPORTED.  All-zero options are the entries above.
+ * swf_mlp_bwd_opt, swf_patch_layer_bwd_opt and swf_linear_bwd have no attention core: they validate `attention` like the others
+ * (0 or 3, anything else is refused), then ignore it and report SWF_BWD_ATTN_RAN_NONE, so one options struct serves a whole model. */
 typedef enum swf_bwd_gemm { SWF_BWD_GEMM_FMA = 0, SWF_BWD_GEMM_MFMA = 1 } swf_bwd_gemm;
-typedef enum swf_bwd_attn { SWF_BWD_ATTN_THREAD = 0 } swf_bwd_attn;
+typedef enum swf_bwd_attn { SWF_BWD_ATTN_THREAD = 0, SWF_BWD_ATTN_PHASED = 3 } swf_bwd_attn;
 typedef struct swf_bwd_options { int32_t gemm; int32_t attention; } swf_bwd_options;
 /* What a backward call launched, written by the branches that launch (host memory, zeroed by the call first; may be NULL): the number
  * of dX and dW launches per family — a call never mixes them, so a caller can tell the family it asked for from a fallback — and the
@@ -286,9 +295,13 @@ typedef struct swf_bwd_options { int32_t gemm; int32_t attention; } swf_bwd_opti
 typedef enum swf_bwd_attn_ran {
     SWF_BWD_ATTN_RAN_NONE = 0,        /* the entry has no attention core */
     SWF_BWD_ATTN_RAN_RESIDENT = 1,    /* thread family, probability tile of the (window, head) resident in LDS */
-    SWF_BWD_ATTN_RAN_RECOMPUTE = 2    /* thread family, every pass rebuilds its scores (windows whose tile does not fit: 16 x 16) */
+    SWF_BWD_ATTN_RAN_RECOMPUTE = 2,   /* thread family, every pass rebuilds its scores (windows whose tile does not fit: 16 x 16) */
+    SWF_BWD_ATTN_RAN_PHASED = 3       /* phased family: K and V in LDS for dQ, then Q and dO for dK and dV */
 } swf_bwd_attn_ran;
 typedef struct swf_bwd_route { int32_t dx_fma, dx_mfma, dw_fma, dw_mfma; int32_t attention; } swf_bwd_route;
+/* Dynamic LDS in bytes of the attention-backward kernel that `family` (swf_bwd_attn) launches for one (window, head) of
+ * win_h x win_w tokens at head_dim channels; 0 where the family refuses the tile or the code is unknown.  Host only, no GPU needed. */
+size_t swf_attention_bwd_lds_bytes(int32_t family, int32_t win_h, int32_t win_w, int32_t head_dim);
 /* The backward entries with the family as an argument: arguments, results and workspace as swf_basic_block_bwd /
  * swf_window_attention_bwd / swf_mlp_bwd / swf_patch_layer_bwd, plus drop (NULL: no dropout, the workspace query of the plain entry;
  * non-NULL: as the *_bwd_drop entry with its workspace query and, for the inner modules, its mask stream stream_id), the options

@@ -61,8 +61,8 @@ class BwdRoute(C.Structure):     # swf_bwd_route: what the call launched
 
 
 BWD_GEMM_FMA, BWD_GEMM_MFMA = 0, 1                                   # swf_bwd_gemm
-BWD_ATTN_THREAD = 0                                                  # swf_bwd_attn
-BWD_ATTN_RAN_NONE, BWD_ATTN_RAN_RESIDENT, BWD_ATTN_RAN_RECOMPUTE = 0, 1, 2   # swf_bwd_attn_ran
+BWD_ATTN_THREAD, BWD_ATTN_PHASED = 0, 3                              # swf_bwd_attn (1 and 2 are refused)
+BWD_ATTN_RAN_NONE, BWD_ATTN_RAN_RESIDENT, BWD_ATTN_RAN_RECOMPUTE, BWD_ATTN_RAN_PHASED = 0, 1, 2, 3   # swf_bwd_attn_ran
 
 
 class PatchParams(C.Structure):
@@ -188,6 +188,7 @@ SIGNATURES = {
                                                _i32, P(Dropout), _i32, P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
     "swf_mlp_bwd_opt": (C.c_int, [P(Linear), P(Linear), _vp, _vp, _vp, P(Linear), P(Linear), _i64, _i32, _i32, P(Dropout), _i32,
                                   P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
+    "swf_attention_bwd_lds_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "swf_linear_bwd_workspace_bytes": (_sz, [_i64, _i32, _i32]),
     "swf_linear_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, P(BwdOptions), P(BwdRoute), _vp, _sz, _vp]),
     "swf_layernorm_bwd_workspace_bytes": (_sz, [_i64, _i32]),

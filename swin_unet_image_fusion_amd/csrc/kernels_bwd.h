@@ -5,12 +5,15 @@
 namespace swf {
 
 // The kernel family of a backward call (swf_bwd_options) and where it reports what it launched (may be NULL).  Every entry below that
-// runs gradient GEMMs takes one last; the default is the scalar-FMA family with no report.
+// runs gradient GEMMs takes one last; the default is the scalar-FMA family with no report.  `attn` is read by the entries that reach the
+// attention core (basic_block_bwd*, window_attention_bwd*); the others ignore it.
 struct BwdTier {
     int gemm = SWF_BWD_GEMM_FMA;
     swf_bwd_route* route = nullptr;
+    int attn = SWF_BWD_ATTN_THREAD;
 };
 
+size_t attn_bwd_lds_bytes(int family, int wh, int ww, int d);
 size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, int W);
 int basic_block_bwd(const swf_block_desc& d, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in,
                     const float* y_in, const float* gx_out, const float* gy_out, float* gx_in, float* gy_in, const swf_block_stream_grads* gx,

@@ -15,6 +15,8 @@
 //   attn_bwd_kernel      per (window, head): recomputes the scores (bias, shift mask assigned as -1e10: a001:310), softmax statistics and
 //                        dS = P . (dP - rowsum(dP . P)); thread = query for dQ, thread = key for dK / dV, thread = table entry for the
 //                        relative-position bias gradient — every sum in a fixed order
+//                        (the thread family; the opt-in phased family, which holds two operand tiles in LDS instead of four, is
+//                        kernels_bwdattn.hip: launch_attn_bwd chooses by BwdTier)
 //   reduce_rows_kernel   out[i] = sum over partial rows in index order
 // Everything here is test-covered against torch.autograd of the CPU oracle (tests/test_gpu_backward.py).  It is the plain,
 // correct-first tier: no fusion, and no MFMA in this file.
@@ -22,6 +24,7 @@
 
 #include <algorithm>
 
+#include "kernels_bwdattn.h"
 #include "kernels_bwdgemm.h"
 #include "kernels_dropout.h"
 #include "kernels_generic.h"
@@ -220,13 +223,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
 
 // ---- attention backward ------------------------------------------------------------------------------------------------------------
 // One workgroup = one (window, head); Q, K, V, dO rows of the head in LDS (zero-padded to DMAX).  Scores exactly as attn_core_kernel.
-struct AttnBwdProb {
-    const float* Q; const float* K; const float* V; const float* dO;   // [tokens][heads*d], row stride ld
-    float* dQ; float* dK; float* dV;
-    const float* bias_table;
-    float* dtable_partial;   // [windows * heads][table entries]
-};
-struct AttnBwdBatch { AttnBwdProb p[2]; };
+// (AttnBwdProb / AttnBwdBatch: kernels_bwdattn.h)
 
 // (the recompute form: nothing of size t x t is kept, every pass rebuilds the scores it needs — the fallback for windows whose
 //  probability tile does not fit in LDS, e.g. 16 x 16)
@@ -498,7 +495,7 @@ __global__ void attn_bwd_kernel(AttnBwdBatch batch, int ld, int B, int H, int W,
 
 // LDS of one (window, head) of wh x ww tokens at DMAX padded channels: the resident form keeps the probability tile, the recompute form
 // three statistics per query.  The resident form runs up to kAttnBwdResidentMax, the recompute form up to kAttnBwdLdsMax.
-constexpr size_t kAttnBwdResidentMax = 96 * 1024, kAttnBwdLdsMax = 160 * 1024;
+constexpr size_t kAttnBwdResidentMax = 96 * 1024;   // (kAttnBwdLdsMax: kernels_bwdattn.h)
 size_t attn_bwd_lds_resident(int wh, int ww, int dmax) {
     const size_t t = (size_t)wh * ww, tsz = (size_t)(2 * wh - 1) * (2 * ww - 1);
     return (4 * t * dmax + tsz + t * (t + 1) + t) * sizeof(float);
@@ -510,8 +507,9 @@ size_t attn_bwd_lds_recompute(int wh, int ww, int dmax) {
 int attn_bwd_dmax(int d) { return d <= 4 ? 4 : d <= 8 ? 8 : d <= 16 ? 16 : d <= 32 ? 32 : d <= 64 ? 64 : 0; }
 
 // What launch_attn_bwd would refuse, asked by every entry BEFORE its first launch (like the workspace check): a refused call has
-// enqueued nothing and written no gradient.
-int check_attn_bwd_shape(const char* what, int wh, int ww, int d) {
+// enqueued nothing and written no gradient.  The phased family refuses only what IT cannot hold.
+int check_attn_bwd_shape(const char* what, int wh, int ww, int d, int family) {
+    if (family == SWF_BWD_ATTN_PHASED) return check_attn_bwd_phased_shape(what, wh, ww, d);
     const int t = wh * ww, dmax = attn_bwd_dmax(d);
     if (!dmax) return fail(SWF_ERR_UNSUPPORTED, "%s: attention backward: head_dim %d > 64", what, d);
     if (cdiv(t, 64) * 64 > 1024) return fail(SWF_ERR_UNSUPPORTED, "%s: attention backward: window of %d tokens > 1024", what, t);
@@ -552,6 +550,8 @@ int launch_attn_bwd_t(const AttnBwdBatch& batch, int nprob, int ld, int B, int H
 
 int launch_attn_bwd(const AttnBwdBatch& batch, int nprob, int ld, int B, int H, int W, int wh, int ww, int heads, int d, int shift,
                     const BwdTier& tier, hipStream_t stream) {
+    if (tier.attn == SWF_BWD_ATTN_PHASED)   // at every shape it can hold
+        return launch_attn_bwd_phased(batch, nprob, ld, B, H, W, wh, ww, heads, d, shift, tier.route, stream);
 #define SWF_AB(D) return launch_attn_bwd_t<D>(batch, nprob, ld, B, H, W, wh, ww, heads, d, shift, tier, stream)
     if (d <= 4) SWF_AB(4);
     if (d <= 8) SWF_AB(8);
@@ -772,7 +772,7 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
     const int wh = d.attn.win_h, ww = d.attn.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(std::max(C, HD), hid)) return fail(SWF_ERR_UNSUPPORTED, "basic_block_bwd: token count");
-    SWF_TRY(check_attn_bwd_shape("basic_block_bwd", wh, ww, d.attn.head_dim));
+    SWF_TRY(check_attn_bwd_shape("basic_block_bwd", wh, ww, d.attn.head_dim, tier.attn));
     Carver ws(workspace, workspace_bytes);
     BlockBufs b[2];
     float* scratch = carve_block(ws, b, d, nstream, B, H, W, drop != nullptr);
@@ -837,6 +837,20 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
 }
 
 }  // namespace
+
+// dynamic LDS of the attention-backward kernel that `family` runs for one (window, head); 0: the family refuses the tile (or is unknown)
+size_t attn_bwd_lds_bytes(int family, int wh, int ww, int d) {
+    if (wh <= 0 || ww <= 0 || d <= 0 || cdiv(wh * ww, 64) * 64 > 1024) return 0;
+    if (family == SWF_BWD_ATTN_PHASED) {
+        const int dp = attn_bwd_phased_width(d);
+        const size_t lds = dp ? attn_bwd_lds_phased(wh, ww, dp) : 0;
+        return lds <= kAttnBwdLdsMax ? lds : 0;
+    }
+    const int dmax = attn_bwd_dmax(d);
+    if (family != SWF_BWD_ATTN_THREAD || !dmax) return 0;
+    const size_t res = attn_bwd_lds_resident(wh, ww, dmax), rec = attn_bwd_lds_recompute(wh, ww, dmax);
+    return res <= kAttnBwdResidentMax ? res : rec <= kAttnBwdLdsMax ? rec : 0;
+}
 
 size_t basic_block_bwd_ws(const swf_block_desc& d, int nstream, int B, int H, int W) { return block_ws(d, nstream, B, H, W, false); }
 size_t basic_block_drop_ws(const swf_block_desc& d, int nstream, int B, int H, int W) { return block_ws(d, nstream, B, H, W, true); }
@@ -931,7 +945,7 @@ int window_attention_bwd_impl(const swf_attn_desc& d, const swf_attn_params& p, 
     const int C = d.channels, HD = d.heads * d.head_dim, wh = d.win_h, ww = d.win_w, tsz = (2 * wh - 1) * (2 * ww - 1);
     const int64_t nwin = (int64_t)B * (H / wh) * (W / ww);
     if (N > INT32_MAX / std::max(C, HD)) return fail(SWF_ERR_UNSUPPORTED, "window_attention_bwd: token count");
-    SWF_TRY(check_attn_bwd_shape("window_attention_bwd", wh, ww, d.head_dim));
+    SWF_TRY(check_attn_bwd_shape("window_attention_bwd", wh, ww, d.head_dim, tier.attn));
     Carver ws(workspace, workspace_bytes);
     const AttnBwdBufs b = carve_attention_bwd(ws, d, B, H, W, true, drop != nullptr);
     float *Q = b.Q, *K = b.K, *V = b.V, *O = b.O, *dO = b.dO, *dQ = b.dQ, *dK = b.dK, *dV = b.dV, *dtab = b.dtab, *scratch = b.scratch, *g1 = b.g1;

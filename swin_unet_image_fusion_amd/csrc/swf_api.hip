@@ -1407,10 +1407,14 @@ int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* 
 static int bwd_tier(const swf_bwd_options* opt, swf_bwd_route* route, const char* what, BwdTier* tier) {
     const int gemm = opt ? opt->gemm : SWF_BWD_GEMM_FMA, attn = opt ? opt->attention : SWF_BWD_ATTN_THREAD;
     if (gemm != SWF_BWD_GEMM_FMA && gemm != SWF_BWD_GEMM_MFMA) return fail(SWF_ERR_UNSUPPORTED, "%s: unknown gradient-GEMM family %d", what, gemm);
-    if (attn != SWF_BWD_ATTN_THREAD) return fail(SWF_ERR_UNSUPPORTED, "%s: unknown attention-backward family %d", what, attn);
+    if (attn != SWF_BWD_ATTN_THREAD && attn != SWF_BWD_ATTN_PHASED) return fail(SWF_ERR_UNSUPPORTED, "%s: unknown attention-backward family %d", what, attn);
     if (route) *route = swf_bwd_route{};
-    *tier = BwdTier{gemm, route};
+    *tier = BwdTier{gemm, route, attn};
     return SWF_OK;
+}
+
+size_t swf_attention_bwd_lds_bytes(int32_t family, int32_t win_h, int32_t win_w, int32_t head_dim) {
+    return attn_bwd_lds_bytes(family, win_h, win_w, head_dim);
 }
 
 // One implementation behind the plain, the *_drop and the *_opt entry of each unit.  what: the entry's name in error texts;

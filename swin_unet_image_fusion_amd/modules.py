@@ -220,14 +220,45 @@ def _bwd_gemm_code(g) -> int:
     return L.BWD_GEMM_MFMA if g == "mfma" else L.BWD_GEMM_FMA
 
 
+def _bwd_attn_code(a) -> int:
+    if a not in ("thread", "phased"):
+        raise ValueError(f"backward attention family must be 'thread' or 'phased', got {a!r}")
+    return L.BWD_ATTN_PHASED if a == "phased" else L.BWD_ATTN_THREAD
+
+
+def _check_attn_bwd(status: int, opt: L.BwdOptions, desc: L.AttnDesc) -> None:
+    """L.check of an attention-bearing backward entry; where the default family refused a tile that the phased family holds, the
+    error text (the library's, unchanged) ends with how to select that family."""
+    try:
+        L.check(status)
+    except NotImplementedError as e:
+        if (opt.attention == L.BWD_ATTN_THREAD and "LDS" in str(e)
+                and L.lib().swf_attention_bwd_lds_bytes(L.BWD_ATTN_PHASED, desc.win_h, desc.win_w, desc.head_dim) > 0):
+            raise NotImplementedError(f'{e}; the phased family holds this tile: set backward_attention = "phased"') from None
+        raise
+
+
 class _BackwardTier:
     """The kernel family of a module's own backward call (include/swinfuse.h swf_bwd_options).  `backward_tier` is 'fma' (the default:
     LDS-tiled scalar-FMA gradient GEMMs) or 'mfma' (the same fmaf chains on the matrix cores: the same bits); it sets `backward_gemm`,
-    the one part that has two families today, which a test may also set on its own.  The family is read when the FORWARD of a
-    differentiable call runs and travels with it to the backward.  `last_backward_route` is the swf_bwd_route of the module's last backward
-    call (None before the first)."""
+    the gradient-GEMM family, which a test may also set on its own.  `backward_attention` is the family of the attention core:
+    'thread' (the default: Q, K, V and dO of a (window, head) in LDS at once; it refuses the 256-token, head_dim 48 tile of level 4 of
+    `win16`) or 'phased' (two operand tiles at a time: every shape up to 160 KB of its own LDS need, that tile included); modules
+    without an attention core carry it and ignore it.  Both are read when the FORWARD of a differentiable call runs and travel with it
+    to the backward; neither is part of the state dict.  `last_backward_route` is the swf_bwd_route of the module's last backward call
+    (None before the first)."""
     backward_gemm = "fma"
+    _backward_attention = "thread"
     last_backward_route: Optional[L.BwdRoute] = None
+
+    @property
+    def backward_attention(self) -> str:
+        return self._backward_attention
+
+    @backward_attention.setter
+    def backward_attention(self, family) -> None:
+        _bwd_attn_code(family)
+        self._backward_attention = family
 
     @property
     def backward_tier(self) -> str:
@@ -239,7 +270,7 @@ class _BackwardTier:
         self.backward_gemm = tier
 
     def _bwd_options(self) -> L.BwdOptions:
-        return L.BwdOptions(_bwd_gemm_code(self.backward_gemm), L.BWD_ATTN_THREAD)
+        return L.BwdOptions(_bwd_gemm_code(self.backward_gemm), _bwd_attn_code(self._backward_attention))
 
 
 class StateRecorder:
@@ -351,9 +382,9 @@ class WindowAttention(_FwdAlias, _BackwardTier, nn.Module):
         size = lib.swf_window_attention_bwd_workspace_bytes if drop is None else lib.swf_window_attention_drop_workspace_bytes
         ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
         route = L.BwdRoute()
-        L.check(lib.swf_window_attention_bwd_opt(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq), _ptr(gk),
-                                                 _ptr(gv), C.byref(grads), b, h, w, _ref(drop), 0, C.byref(opt), C.byref(route),
-                                                 ws, wsn, _stream(dev)))
+        _check_attn_bwd(lib.swf_window_attention_bwd_opt(C.byref(desc), C.byref(prm), _ptr(qn), _ptr(kn), _ptr(vn), _ptr(gn), _ptr(gq),
+                                                         _ptr(gk), _ptr(gv), C.byref(grads), b, h, w, _ref(drop), 0, C.byref(opt),
+                                                         C.byref(route), ws, wsn, _stream(dev)), opt, desc)
         self.last_backward_route = route
         return (_to_nchw(gq), _to_nchw(gk), _to_nchw(gv), gt, *[t for pair in zip(gw, gb) for t in pair])
 
@@ -743,8 +774,9 @@ class BasicBlock(_FwdAlias, _BackwardTier, nn.Module):
         size = lib.swf_basic_block_bwd_workspace_bytes if drop is None else lib.swf_basic_block_drop_workspace_bytes
         ws, wsn = _workspace(size(C.byref(desc), b, h, w), dev)
         route = L.BwdRoute()
-        L.check(lib.swf_basic_block_bwd_opt(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(gxo), _ptr(gyo), _ptr(gxi), _ptr(gyi),
-                                            _ref(gsx), _ref(gsy), b, h, w, _ref(drop), C.byref(opt), C.byref(route), ws, wsn, _stream(dev)))
+        _check_attn_bwd(lib.swf_basic_block_bwd_opt(C.byref(desc), _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(gxo), _ptr(gyo), _ptr(gxi),
+                                                    _ptr(gyi), _ref(gsx), _ref(gsy), b, h, w, _ref(drop), C.byref(opt), C.byref(route), ws,
+                                                    wsn, _stream(dev)), opt, desc.attn)
         self.last_backward_route = route
         return _to_nchw(gxi), (_to_nchw(gyi) if dual else None), bufs
 
@@ -1157,7 +1189,8 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
     'throughput', swf_schedule) the kernel shapes of the fast tier where it has a choice: 'latency' for one forward at a time,
     'throughput' for several forwards in flight (shard.ShardedFusion sets it for its lanes).  `backward_tier` ('fma' | 'mfma', swf_bwd_options)
     selects the kernel family of the gradient GEMMs of the differentiable forward's backward — the same bits either way — in every block
-    and patch layer; `backward_routes()` says what their last backward launched.
+    and patch layer, `backward_attention` ('thread' | 'phased') the family of the attention core in every block ('phased' is what
+    `win16` at five stages needs: the default refuses its level-4 tile); `backward_routes()` says what their last backward launched.
     """
 
     def __init__(self, window_size: tuple, merging_size: tuple, in_dims_list: list, out_dims_list: list,
@@ -1348,24 +1381,26 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
         y = in_y if in_y.requires_grad else in_y.detach().requires_grad_(True)
         # the blocks run in the MODEL's tier here (their own .precision is what they run at when called on their own); a block that
         # drops in train() ignores it and runs the exact tier (the fused fast kernels have no masks)
-        gemm = self.backward_gemm
+        gemm, attn = self.backward_gemm, self._backward_attention
         _bwd_gemm_code(gemm)
+        _bwd_attn_code(attn)
         blocks = [m for m in self.modules() if isinstance(m, BasicBlock)]
         own = [blk.precision for blk in blocks]
         for blk in blocks:
             blk.precision = self.precision
-        # ... and every module with gradient GEMMs in the model's backward tier: read by their forward, so it holds for their backward
+        # ... and every module with gradient GEMMs in the model's backward tier and attention family: read by their forward, so they hold
+        # for their backward
         tiered = blocks + [m for m in self.modules() if isinstance(m, PatchMergingAndLinearLayer)]
-        own_gemm = [m.backward_gemm for m in tiered]
+        own_gemm = [(m.backward_gemm, m._backward_attention) for m in tiered]
         for m in tiered:
-            m.backward_gemm = gemm
+            m.backward_gemm, m._backward_attention = gemm, attn
         try:
             return self._forward_autograd_stages(x, y)
         finally:
             for blk, p in zip(blocks, own):
                 blk.precision = p
-            for m, g in zip(tiered, own_gemm):
-                m.backward_gemm = g
+            for m, (g, a) in zip(tiered, own_gemm):
+                m.backward_gemm, m._backward_attention = g, a
 
     def backward_routes(self) -> dict:
         """{module name: swf_bwd_route} of every sub-module whose backward has run (BasicBlock and PatchMergingAndLinearLayer under

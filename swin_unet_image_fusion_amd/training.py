@@ -13,7 +13,9 @@ STATE_KEYS = ("model_state", "optimizer_state", "scheduler_state", "current_epoc
 
 def train_step(model, loss_fn, optimizer, ir: Tensor, vis: Tensor):
     """One iteration of a016:150-165, in its order: forward, clamp_(0, 1), calcu_total_loss, zero_grad, backward, step.
-    -> (loss, the loss's detail dict).  The caller steps the scheduler (a016:167, `scheduler.step(fractional_epoch(...))`)."""
+    -> (loss, the loss's detail dict).  The caller steps the scheduler (a016:167, `scheduler.step(fractional_epoch(...))`).
+    The model comes configured: its `backward_tier` and `backward_attention` are read by its own forward and nothing here touches
+    them (a `win16` model at five stages needs backward_attention = "phased": its level-4 tile does not fit the default family)."""
     fusion = model(ir, vis)
     fusion = torch.clamp_(fusion, min=0, max=1)
     loss, detail = loss_fn.calcu_total_loss(fusion_images=fusion, ir_images=ir, vis_images=vis)
