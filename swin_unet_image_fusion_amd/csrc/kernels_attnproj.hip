@@ -12,8 +12,9 @@
 //  * O (normalised, split to bf16 hi / lo) is exchanged through a row-major LDS image laid over the V images; each wave produces
 //    a 32-column x 64-token tile of O . Wp^T over half of k on the bf16x3 MFMA path (Wp's rows as A fragments from L2, all
 //    requested before the exchange), and the k halves are added through LDS in fixed order.
-//  * The three column thirds recompute the window's attention (6 + 8 MFMAs per head and query tile): cheaper than a second launch
-//    and the O planes' round trip (attention core 8.2 us + projection GEMM 12.5 us -> one launch).
+//  * Latency schedule: the three column thirds recompute the window's attention (6 + 8 MFMAs per head and query tile): cheaper
+//    than a second launch and the O planes' round trip (attention core 8.2 us + projection GEMM 12.5 us -> one launch).
+//    Throughput schedule: one workgroup per (window, stream) runs the attention once and walks the three thirds itself.
 #include "kernels_attnproj.h"
 
 #include <cstdlib>
@@ -47,9 +48,13 @@ __device__ unsigned long long ap_probe[16];
 #define AP_STAMP(i) do { } while (0)
 #endif
 
-template <int WS>
+// NSW: column thirds one workgroup projects.  1 (latency schedule): grid (window, third, stream), the thirds of a window run side
+// by side and each repeats the attention.  kNS (throughput schedule): grid (window, 1, stream), one attention, then the thirds one
+// after the other — a third of the CU-time for a longer launch.  Every output element is the same sum in the same order.
+template <int WS, int NSW>
 __global__ __launch_bounds__(512) void attn_proj_kernel(ApDev a) {
     static_assert(WS == 7 || WS == 8, "window side");
+    static_assert(NSW == 1 || NSW == kNS, "thirds per workgroup");
     constexpr int C = kC, D = kD, VRS = kVRS, LDO = kLDO, TW = 2 * WS - 1;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f16* vt = reinterpret_cast<f16*>(smem);                            // [head][channel 48][VRS]
@@ -60,7 +65,7 @@ __global__ __launch_bounds__(512) void attn_proj_kernel(ApDev a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 31, hf = lane >> 5;
     const int H = a.H, W = a.W, nwx = W / WS, nwy = H / WS, npi = nwx * nwy;
-    const int win = blockIdx.x, ns = blockIdx.y, st = blockIdx.z;
+    const int win = blockIdx.x, ns0 = NSW == 1 ? (int)blockIdx.y : 0, st = blockIdx.z;
     const int b = win / npi, wrem = win - b * npi, wy = wrem / nwx, wx = wrem - wy * nwx;
     const int sh = a.shift ? WS / 2 : 0;
     auto padding = [](int t) { return WS != 8 && ((t >> 3) >= WS || (t & 7) >= WS); };
@@ -178,29 +183,30 @@ __global__ __launch_bounds__(512) void attn_proj_kernel(ApDev a) {
     // ---- projection operands go out now and fly under the O exchange: wave (ct, kh) owns column tile ct for BOTH token halves over
     //      k half kh (each Wp fragment crosses the memory pipe once per workgroup; all 24 of a wave are requested at once — with a
     //      4-deep ring the 24-step k loop waited six L2 round trips, 5.2 us), and finishes token half kh in the epilogue ----
-    const int ct = wave & 3, kh = wave >> 2, col0 = ns * (C / kNS) + 32 * ct;
+    const int ct = wave & 3, kh = wave >> 2;
     constexpr int KSH = C / 32;   // k-steps of one k half
     u32x4 wfh[KSH], wfl[KSH];
-    {
-        // fragment-major image: block (32-row tile, k16 step) = one contiguous 1-KB load, lane l at bytes [16 l, 16 l + 16)
-        // (row-strided 16-byte loads from the nn.Linear layout ran at 32 GB/s per CU here: 6 us for the 24 fragments of a wave)
-        const size_t blk0 = (size_t)(col0 / 32) * (C / 16) + KSH * kh;
-        const bf16* wh = a.wp_hi[st] + blk0 * 512 + lane * 8;
-        const bf16* wl = a.wp_lo[st] + blk0 * 512 + lane * 8;
+    // fragment-major image: block (32-row tile, k16 step) = one contiguous 1-KB load, lane l at bytes [16 l, 16 l + 16)
+    // (row-strided 16-byte loads from the nn.Linear layout ran at 32 GB/s per CU here: 6 us for the 24 fragments of a wave)
+    auto wp_frag = [&](int third, int ks) {
+        const size_t blk = (size_t)(third * (C / kNS) / 32 + ct) * (C / 16) + KSH * kh + ks;
+        wfh[ks] = *reinterpret_cast<const u32x4*>(a.wp_hi[st] + blk * 512 + lane * 8);
+        wfl[ks] = *reinterpret_cast<const u32x4*>(a.wp_lo[st] + blk * 512 + lane * 8);
+    };
 #pragma unroll
-        for (int ks = 0; ks < KSH; ++ks) {
-            wfh[ks] = *reinterpret_cast<const u32x4*>(wh + 512 * ks);
-            wfl[ks] = *reinterpret_cast<const u32x4*>(wl + 512 * ks);
-        }
-    }
+    for (int ks = 0; ks < KSH; ++ks) wp_frag(ns0, ks);
     const int t = 32 * kh + r;   // the token this lane finishes
-    const size_t orow = tok_index(t) * C + col0 + 4 * hf;
+    const size_t trow = tok_index(t) * C + 4 * hf;
     f32x4 rv[4], bv[4];
+    auto row_operands = [&](int third) {   // residual and bias of the third's columns
+        const int col0 = third * (C / kNS) + 32 * ct;
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        rv[g] = *reinterpret_cast<const f32x4*>(a.res[st] + orow + 8 * g);
-        bv[g] = a.pbias[st] ? *reinterpret_cast<const f32x4*>(a.pbias[st] + col0 + 8 * g + 4 * hf) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+        for (int g = 0; g < 4; ++g) {
+            rv[g] = *reinterpret_cast<const f32x4*>(a.res[st] + trow + col0 + 8 * g);
+            bv[g] = a.pbias[st] ? *reinterpret_cast<const f32x4*>(a.pbias[st] + col0 + 8 * g + 4 * hf) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    row_operands(ns0);
     __syncthreads();   // every wave has left the V images and the bias tile
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb)
@@ -224,40 +230,72 @@ __global__ __launch_bounds__(512) void attn_proj_kernel(ApDev a) {
     __syncthreads();
     AP_STAMP(5);
 
-    // ---- out^T[column][token] tiles (ct, both halves), partial over k half kh = Wp[col0.., k half] . O^T ----
-    f32x16 acc[2] = {zero16, zero16};
-    {
-        const bf16* oh = o_hi + r * LDO + (C / 2) * kh + 8 * hf;
-        const bf16* ol = o_lo + r * LDO + (C / 2) * kh + 8 * hf;
-#pragma unroll
-        for (int ks = 0; ks < KSH; ++ks) {
-            const u32x4 bh0 = *reinterpret_cast<const u32x4*>(oh + 16 * ks), bl0 = *reinterpret_cast<const u32x4*>(ol + 16 * ks);
-            const u32x4 bh1 = *reinterpret_cast<const u32x4*>(oh + 32 * LDO + 16 * ks), bl1 = *reinterpret_cast<const u32x4*>(ol + 32 * LDO + 16 * ks);
-            acc[0] = mma3(wfh[ks], wfl[ks], bh0, bl0, acc[0]);
-            acc[1] = mma3(wfh[ks], wfl[ks], bh1, bl1, acc[1]);
-        }
-    }
-    // ---- the two k halves meet through LDS: each wave hands over the token half it does not finish.  k half 0 + k half 1 in both
-    //      finishing waves (a + b == b + a bit for bit) ----
     float* xch = reinterpret_cast<float*>(smem + kOBytes);   // [wave][register][lane]
+    const bf16* oh = o_hi + r * LDO + (C / 2) * kh + 8 * hf;
+    const bf16* ol = o_lo + r * LDO + (C / 2) * kh + 8 * hf;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) xch[(wave * 16 + i) * 64 + lane] = kh ? acc[0][i] : acc[1][i];
-    __syncthreads();
-    AP_STAMP(6);
-    f32x16 mine = kh ? acc[1] : acc[0];
+    for (int i3 = 0; i3 < NSW; ++i3) {
+        const int ns = ns0 + i3;
+        if (i3 > 0) {
+            __syncthreads();        // every wave has read the previous third's partials: the exchange buffer is free again
+            row_operands(ns);       // fly under the k loop
+        }
+        // ---- out^T[column][token] tiles (ct, both halves), partial over k half kh = Wp[col0.., k half] . O^T.  A fragment's
+        //      registers are refilled with the next third's fragment as soon as its MFMAs are issued: a whole k loop ahead ----
+        f32x16 acc[2] = {zero16, zero16};
+        if constexpr (NSW > 1) {   // fenced k-steps: the O fragments are read a step ahead by hand
+            u32x4 nb[4] = {*reinterpret_cast<const u32x4*>(oh), *reinterpret_cast<const u32x4*>(ol),
+                           *reinterpret_cast<const u32x4*>(oh + 32 * LDO), *reinterpret_cast<const u32x4*>(ol + 32 * LDO)};
 #pragma unroll
-    for (int i = 0; i < 16; ++i) mine[i] += xch[((wave ^ 4) * 16 + i) * 64 + lane];
-    // ---- + bias + residual; registers 4g..4g+3 = 4 consecutive columns of token t ----
-    if (padding(t)) return;
-    float* out = a.out[st] + orow;
+            for (int ks = 0; ks < KSH; ++ks) {
+                const u32x4 bh0 = nb[0], bl0 = nb[1], bh1 = nb[2], bl1 = nb[3];
+                if (ks + 1 < KSH) {
+                    nb[0] = *reinterpret_cast<const u32x4*>(oh + 16 * (ks + 1)); nb[1] = *reinterpret_cast<const u32x4*>(ol + 16 * (ks + 1));
+                    nb[2] = *reinterpret_cast<const u32x4*>(oh + 32 * LDO + 16 * (ks + 1)); nb[3] = *reinterpret_cast<const u32x4*>(ol + 32 * LDO + 16 * (ks + 1));
+                }
+                acc[0] = mma3(wfh[ks], wfl[ks], bh0, bl0, acc[0]);
+                acc[1] = mma3(wfh[ks], wfl[ks], bh1, bl1, acc[1]);
+                if (i3 + 1 < NSW) wp_frag(ns + 1, ks);
+                __builtin_amdgcn_sched_barrier(0);   // hipcc otherwise sinks the refills behind the loop: an L2 round trip per third
+            }
+        } else {
 #pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        f32x4 v = {mine[4 * g], mine[4 * g + 1], mine[4 * g + 2], mine[4 * g + 3]};
-        v += bv[g];
-        v += rv[g];
-        *reinterpret_cast<f32x4*>(out + 8 * g) = v;
+            for (int ks = 0; ks < KSH; ++ks) {
+                const u32x4 bh0 = *reinterpret_cast<const u32x4*>(oh + 16 * ks), bl0 = *reinterpret_cast<const u32x4*>(ol + 16 * ks);
+                const u32x4 bh1 = *reinterpret_cast<const u32x4*>(oh + 32 * LDO + 16 * ks), bl1 = *reinterpret_cast<const u32x4*>(ol + 32 * LDO + 16 * ks);
+                acc[0] = mma3(wfh[ks], wfl[ks], bh0, bl0, acc[0]);
+                acc[1] = mma3(wfh[ks], wfl[ks], bh1, bl1, acc[1]);
+            }
+        }
+        // ---- the two k halves meet through LDS: each wave hands over the token half it does not finish.  k half 0 + k half 1 in
+        //      both finishing waves (a + b == b + a bit for bit) ----
+#pragma unroll
+        for (int i = 0; i < 16; ++i) xch[(wave * 16 + i) * 64 + lane] = kh ? acc[0][i] : acc[1][i];
+        __syncthreads();
+        AP_STAMP(6 + 2 * i3);
+        f32x16 mine = kh ? acc[1] : acc[0];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) mine[i] += xch[((wave ^ 4) * 16 + i) * 64 + lane];
+        // ---- + bias + residual; registers 4g..4g+3 = 4 consecutive columns of token t ----
+        if (!padding(t)) {
+            float* out = a.out[st] + trow + ns * (C / kNS) + 32 * ct;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 v = {mine[4 * g], mine[4 * g + 1], mine[4 * g + 2], mine[4 * g + 3]};
+                v += bv[g];
+                v += rv[g];
+                *reinterpret_cast<f32x4*>(out + 8 * g) = v;
+            }
+        }
+        AP_STAMP(7 + 2 * i3);
     }
-    AP_STAMP(7);
+}
+
+template <int WS, int NSW>
+int launch_t(const ApDev& dv, int nwin, int nstream, hipStream_t stream) {
+    SWF_TRY((raise_lds_limit<&attn_proj_kernel<WS, NSW>>((int)kLds, "attn_proj")));
+    hipLaunchKernelGGL((attn_proj_kernel<WS, NSW>), dim3(nwin, kNS / NSW, nstream), dim3(512), kLds, stream, dv);
+    return check_launch("attn_proj");
 }
 
 }  // namespace
@@ -282,14 +320,10 @@ int launch_attnproj(const swf_block_desc& d, const AttnProjArgs& a, int nstream,
     }
     dv.B = a.B; dv.H = a.H; dv.W = a.W; dv.shift = a.shift;
     const int nwin = a.B * (a.H / ws) * (a.W / ws);
-    if (ws == 8) {
-        SWF_TRY(raise_lds_limit<&attn_proj_kernel<8>>((int)kLds, "attn_proj"));
-        hipLaunchKernelGGL((attn_proj_kernel<8>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
-    } else {
-        SWF_TRY(raise_lds_limit<&attn_proj_kernel<7>>((int)kLds, "attn_proj"));
-        hipLaunchKernelGGL((attn_proj_kernel<7>), dim3(nwin, kNS, nstream), dim3(512), kLds, stream, dv);
-    }
-    return check_launch("attn_proj");
+    // with several graph lanes in flight a launch costs workgroups x duration: the throughput schedule does not repeat the attention
+    const bool all_thirds = d.schedule == SWF_SCHED_THROUGHPUT;
+    if (ws == 8) return all_thirds ? launch_t<8, kNS>(dv, nwin, nstream, stream) : launch_t<8, 1>(dv, nwin, nstream, stream);
+    return all_thirds ? launch_t<7, kNS>(dv, nwin, nstream, stream) : launch_t<7, 1>(dv, nwin, nstream, stream);
 }
 
 }  // namespace swf

@@ -39,6 +39,7 @@ struct DeepQkvArgs {
     unsigned short* out[2][3];                                        // fp16 [M][C] each
     float qscale; int cross, M;                                       // cross: K and V of stream s read stream 1 - s
     int C;                                                            // 384, or 192 (16x16-window levels: the fused Q/K/V + attention kernel covers the rest)
+    int schedule;                                                     // swf_schedule: THROUGHPUT takes 384-column slices on eight waves where LATENCY takes 192 on four (C = 384)
 };
 bool deep_qkv_supported(const swf_block_desc& d);
 int launch_deep_qkv(const DeepQkvArgs& q, int nstream, hipStream_t stream);

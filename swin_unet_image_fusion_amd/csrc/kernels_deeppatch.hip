@@ -614,6 +614,10 @@ int launch_deep_qkv(const DeepQkvArgs& q, int nstream, hipStream_t stream) {
     a.M = q.M; a.qscale = q.qscale; a.cross = q.cross && nstream == 2;
     if (q.C == 192) return launch_t<192, 192, 2, 4, 2, 576>(a, nstream, stream);
     if (q.C != 384) return fail(SWF_ERR_UNSUPPORTED, "deep_qkv: C=%d", q.C);
+    // Throughput schedule: three 384-column slices on eight waves instead of six 192-column slices on four — half the workgroups,
+    // so half the copies of the 64-token LayerNorm image, and two waves per SIMD share one image.  A wave owns one whole tile and
+    // half of another (the half-tile dealing of the template); every output column keeps its k order.
+    if (q.schedule == SWF_SCHED_THROUGHPUT) return launch_t<384, 384, 2, 8, 2, 1152>(a, nstream, stream);
     return launch_t<384, 192, 2, 4, 2, 1152>(a, nstream, stream);
 }
 

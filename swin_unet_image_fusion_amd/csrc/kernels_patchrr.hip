@@ -36,11 +36,16 @@ struct PRR {
 };
 
 // KS: 16-deep k-steps covering K; NT: 32-row tiles covering N; DEC: 0 merge, 1 unmerge; CIN1: encoder with one input channel
-// (K = 4 scalar gathers); TPW: 32-token tiles a wave carries through one pass over the weight fragments
-template <int KS, int NT, int DEC, int CIN1, int TPW>
+// (K = 4 scalar gathers); TPW: 32-token tiles a wave carries through one pass over the weight fragments; RD: k-steps of weight
+// fragments the register ring holds (KS: all of them, requested at once; chosen per instantiation by the registers its grid leaves
+// a wave: launch_patch_rr)
+template <int KS, int NT, int DEC, int CIN1, int TPW, int RD>
 __global__ __launch_bounds__(256) void patch_rr_kernel(PrrArgs a) {
     using P = PRR<KS, NT>;
     constexpr int NV = P::NV;
+    static_assert(RD >= 1 && RD <= KS && (RD >= 2 || KS == 1), "ring depth");
+    constexpr int PRE = RD == KS ? KS : RD - 1;   // k-steps requested ahead of the k loop; step ks + PRE is requested before the MFMAs of step ks
+    constexpr bool PIN = PRE > 1;                 // one step ahead: hipcc's own placement of the loads is the faster one (<3,3,1,0,1>: 32.6 vs 34.7 us)
     __shared__ float lvec[3 * 2 * NV];
     const int s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hf = lane >> 5;
@@ -169,26 +174,31 @@ __global__ __launch_bounds__(256) void patch_rr_kernel(PrrArgs a) {
                 }
             }
         }
-        // weight fragments: a two-deep register ring, k-step ks + 1 requested before the MFMAs of k-step ks (the loads are
-        // loop-invariant: the fences keep hipcc from hoisting them out of the token loop, or sinking them next to their use)
-        u32x4 wr[2][NT][2];
+        // weight fragments: a register ring RD k-steps deep, the first PRE steps requested here and k-step ks + PRE before the MFMAs
+        // of k-step ks (the loads are loop-invariant: the fences keep hipcc from hoisting them out of the token loop; the scheduling
+        // barriers (PIN) keep it from sinking each next to its use, which it does past the fences alone: one L2 round trip per k-step)
+        u32x4 wr[RD][NT][2];
         SWF_WF_FENCE();
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) { wr[0][nt][0] = WA(nt, 0, 0); wr[0][nt][1] = WA(nt, 0, 1); }
+        for (int ks = 0; ks < PRE; ++ks)
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) { wr[ks % RD][nt][0] = WA(nt, ks, 0); wr[ks % RD][nt][1] = WA(nt, ks, 1); }
+        if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-            if (ks + 1 < KS) {
+            if (ks + PRE < KS) {
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) { wr[(ks + 1) & 1][nt][0] = WA(nt, ks + 1, 0); wr[(ks + 1) & 1][nt][1] = WA(nt, ks + 1, 1); }
+                for (int nt = 0; nt < NT; ++nt) { wr[(ks + PRE) % RD][nt][0] = WA(nt, ks + PRE, 0); wr[(ks + PRE) % RD][nt][1] = WA(nt, ks + PRE, 1); }
             }
             SWF_WF_FENCE();
+            if constexpr (PIN) __builtin_amdgcn_sched_barrier(0);
             u32x4 bh[TPW], bl[TPW];
 #pragma unroll
             for (int u = 0; u < TPW; ++u) split8(xin[u][ks], bh[u], bl[u]);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
 #pragma unroll
-                for (int u = 0; u < TPW; ++u) acc[u][nt] = mma3(wr[ks & 1][nt][0], wr[ks & 1][nt][1], bh[u], bl[u], acc[u][nt]);
+                for (int u = 0; u < TPW; ++u) acc[u][nt] = mma3(wr[ks % RD][nt][0], wr[ks % RD][nt][1], bh[u], bl[u], acc[u][nt]);
         }
         // ---- per token: conv bias, LayerNorm over the N channels (registers x the two lanes of the token), ELU, store ----
 #pragma unroll
@@ -299,11 +309,11 @@ bool shape_class(int decoder, int Cin, int Cout, int mh, int mw, int* ks, int* n
     return (k == 1 && n == 1 && Cin == 1) || (k == 6 && n == 2) || (k == 12 && n == 3);
 }
 
-template <int KS, int NT, int DEC, int CIN1, int TPW>
+template <int KS, int NT, int DEC, int CIN1, int TPW, int RD>
 int launch_t(const PrrArgs& a, int nstream, hipStream_t stream) {
     const int ngroup = (a.M + 32 * TPW - 1) / (32 * TPW);
     const int gx = std::max(1, std::min((ngroup + 3) / 4, 8 * num_cus() / nstream));
-    hipLaunchKernelGGL((patch_rr_kernel<KS, NT, DEC, CIN1, TPW>), dim3(gx, nstream), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL((patch_rr_kernel<KS, NT, DEC, CIN1, TPW, RD>), dim3(gx, nstream), dim3(256), 0, stream, a);
     return check_launch("patch_rr");
 }
 
@@ -351,13 +361,13 @@ int launch_patch_rr(const PatchFusedDesc& d, const void* const* packed, int nstr
     a.B = d.B; a.H = d.H; a.W = d.W; a.Cin = d.Cin; a.mh = d.mh; a.mw = d.mw; a.Hm = d.Hm; a.Wm = d.Wm; a.Ho = d.Ho; a.Wo = d.Wo;
     a.K = d.K; a.N = d.N; a.Cout = d.Cout; a.M = (int)d.M;
     if (!d.decoder) {
-        if (ks == 1 && nt == 1 && d.Cin == 1) return launch_t<1, 1, 0, 1, 2>(a, nstream, stream);   // (4 tiles per wave: no faster; the decoder twin 20.6 -> 31.8 us)
-        if (ks == 6 && nt == 2) return launch_t<6, 2, 0, 0, 2>(a, nstream, stream);
-        if (ks == 12 && nt == 3) return launch_t<12, 3, 0, 0, 1>(a, nstream, stream);
+        if (ks == 1 && nt == 1 && d.Cin == 1) return launch_t<1, 1, 0, 1, 2, 1>(a, nstream, stream);   // (4 tiles per wave: no faster; the decoder twin 20.6 -> 31.8 us)
+        if (ks == 6 && nt == 2) return launch_t<6, 2, 0, 0, 2, 3>(a, nstream, stream);
+        if (ks == 12 && nt == 3) return launch_t<12, 3, 0, 0, 1, 3>(a, nstream, stream);
     } else {
-        if (ks == 2 && nt == 1) return launch_t<2, 1, 1, 0, 2>(a, nstream, stream);
-        if (ks == 3 && nt == 3) return launch_t<3, 3, 1, 0, 1>(a, nstream, stream);
-        if (ks == 6 && nt == 6) return launch_t<6, 6, 1, 0, 1>(a, nstream, stream);
+        if (ks == 2 && nt == 1) return launch_t<2, 1, 1, 0, 2, 2>(a, nstream, stream);
+        if (ks == 3 && nt == 3) return launch_t<3, 3, 1, 0, 1, 2>(a, nstream, stream);
+        if (ks == 6 && nt == 6) return launch_t<6, 6, 1, 0, 1, 3>(a, nstream, stream);
     }
     return fail(SWF_ERR_UNSUPPORTED, "patch_rr: no instantiation for k-steps %d, tiles %d (decoder %d)", ks, nt, d.decoder);
 }

@@ -371,7 +371,7 @@ static int deep_block_impl(const swf_block_desc* desc, const swf_block_stream_pa
             dq.bias[s][0] = pp[s]->attn.q.bias; dq.bias[s][1] = pp[s]->attn.k.bias; dq.bias[s][2] = pp[s]->attn.v.bias;
             for (int i = 0; i < 3; ++i) dq.out[s][i] = b.qkv[s][i];
         }
-        dq.qscale = gq.qscale; dq.cross = cross; dq.M = (int)N; dq.C = C;
+        dq.qscale = gq.qscale; dq.cross = cross; dq.M = (int)N; dq.C = C; dq.schedule = desc->schedule;
         SWF_TRY(launch_deep_qkv(dq, nstream, stream));
         trace_block(route, SWF_BLOCK_DEEP_QKV);
     }
