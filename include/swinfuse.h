@@ -630,8 +630,8 @@ int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float*
 /* ---- fusion-quality metrics of fused images against their two sources, ten values per image in one call ------------
  * The numbers the field reports for a fusion method (the reference's README claims them; neither it nor a016 / a017 computes one).
  * Restated from the published definitions and the common open evaluators; no MATLAB or VIFB toolkit is available to this build:
- * PARITY WITH ANY OF THEM IS UNPINNED.  VIF and Nabf are swf_fusion_fidelity's (below); SSIM is the loss's (swf_fusion_loss,
- * ssim_mode 1).
+ * PARITY WITH ANY OF THEM IS UNPINNED.  VIF and Nabf are swf_fusion_fidelity's, SSIM, MS-SSIM and the Piella / Cvejic / Yang indices
+ * swf_fusion_structure's (both below); the SSIM of swf_fusion_loss is the training loss's, on unit-range floats, not a metric on levels.
  * Levels.  Every metric is a function of 8-bit levels, quantised as torchvision save_image does, in fp32 with two roundings:
  * q = (int) min(max(fadd(fmul(x, 255), 0.5), 0), 255) (never one fused multiply-add; NaN -> 0), so a stored uint8 image passed as
  * u8 / 255.0f evaluates exactly.  F, A, B = the level images of fusion, ir, vis as reals 0..255, N = H W.
@@ -706,6 +706,52 @@ size_t swf_fusion_fidelity_workspace_bytes(int32_t B, int32_t H, int32_t W);
 int swf_fusion_fidelity(const swf_fidelity_desc* desc, const float* fusion, const float* ir, const float* vis,
                         double* out /* device [B][SWF_FIDELITY_COUNT] */, int32_t B, int32_t H, int32_t W,
                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
+/* ---- the structural-similarity group: SSIM, MS-SSIM and the Piella / Cvejic / Yang indices, nine values per image in one call ------
+ * Restated from the published definitions (Wang et al.'s SSIM and MS-SSIM; Piella and Heijmans' Q_S, Q_W, Q_E; Cvejic et al.'s Q_C;
+ * Yang et al.'s Q_Y, as Liu et al.'s assessment of fusion metrics gives them); no MATLAB or toolbox copy is available to this build:
+ * PARITY WITH ANY OF THEM IS UNPINNED.
+ * Levels.  F, A, B = the level images of fusion, ir, vis of the metrics above (the same quantiser: fp32, two roundings, never one
+ * fused multiply-add, NaN -> 0).  C1 = (255 K1)^2, C2 = (255 K2)^2; K1, K2 > 0 is required, so no denominator below is 0.
+ * Gaussian group.  Window of 11 taps, sigma 1.5, g[i] = exp(-(i - 5)^2 / (2 1.5^2)) normalised to sum 1 (the 1-D factor; the window is
+ * separable); * is the "valid" filtering.  Biased moments, not clamped: mu_X = g*X, var_X = g*(X X) - mu_X^2, cov_XY = g*(X Y) - mu_X mu_Y;
+ * l = (2 mu_X mu_Y + C1) / (mu_X^2 + mu_Y^2 + C1), cs = (2 cov_XY + C2) / (var_X + var_Y + C2), ssim(X, Y) = mean(l cs).
+ *   SSIM      SSIM_IR + SSIM_VIS, SSIM_IR = ssim(A, F), SSIM_VIS = ssim(B, F) (the sum follows the VIF convention above).  All three
+ *             are exactly 0 when min(H, W) < 11.
+ *   MS_SSIM   msssim(A, F) + msssim(B, F) over five scales with weights w = 0.0448, 0.2856, 0.3001, 0.2363, 0.1333.  Plane j + 1 is the
+ *             mean of the non-overlapping 2x2 blocks of plane j, floor(h / 2) x floor(w / 2) (an odd last row or column is dropped),
+ *             kept in fp64 and not re-quantised.  msssim = prod_{j <= 4} max(mean cs_j, 0)^w_j  max(mean (l cs)_5, 0)^w_5.  Exactly 0
+ *             when the scale-5 plane is under 11 in an axis, that is when min(H, W) < 176.
+ * Box group.  w x w windows at valid positions only, n = w^2; a group's values are exactly 0 when the image is smaller than its
+ * window.  Per window the INTEGER sums S_X, S_XX, S_XY; V_X = n S_XX - S_X^2, C_XY = n S_XY - S_X S_Y; mu_X = S_X / n, var_X = V_X / n^2,
+ * cov_XY = C_XY / n^2; s(X, Y) = (2 mu_X mu_Y + C1)(2 cov_XY + C2) / ((mu_X^2 + mu_Y^2 + C1)(var_X + var_Y + C2)).
+ *   QS        Piella, w = 8: mean t, t = lambda s(A, F) + (1 - lambda) s(B, F), lambda = V_A / (V_A + V_B), 1/2 when V_A + V_B = 0
+ *   QW        sum(m t) / sum(m), m = max(V_A, V_B); QS when sum(m) = 0
+ *   QE        QW max(QW', 0)^alpha, QW' the same formula on the edge images E_X = |sx| + |sy|, sx and sy the Sobel responses of the
+ *             QABF section (its masks, its zero border).  The L1 magnitude is chosen on purpose: an integer of at most 2040, so the
+ *             moments of the edge images stay exact.
+ *   QC        Cvejic, w = 8: mean [sim s(A, F) + (1 - sim) s(B, F)], sim = clip(C_AF / (C_AF + C_BF), 0, 1), 1/2 when C_AF + C_BF = 0
+ *   QY        Yang, w = 7: mean over the windows of lambda s(A, F) + (1 - lambda) s(B, F) where s(A, B) >= Ty, of
+ *             max(s(A, F), s(B, F)) elsewhere
+ * Usual constants: K1 0.01, K2 0.03, alpha 1, Ty 0.75.
+ * Arithmetic.  Box group: the window sums are exact (int32 sums, int64 V and C), EVERY ZERO TEST IS MADE ON THE INTEGERS (V_A + V_B,
+ * C_AF + C_BF, sum(m)), and the per-window value is then one fp64 expression.  Gaussian group: fp64 throughout after the quantiser;
+ * window weights are computed on the host in fp64.  Sums over windows go through per-tile partials added in a fixed order; no float
+ * atomics; one finishing workgroup per image: results are bit-identical from call to call, and an image's row does not depend on the
+ * rest of its batch. */
+typedef struct swf_structure_desc { double K1, K2, alpha, Ty; } swf_structure_desc;   /* defaults 0.01, 0.03, 1.0, 0.75 */
+enum { SWF_STRUCTURE_SSIM, SWF_STRUCTURE_SSIM_IR, SWF_STRUCTURE_SSIM_VIS, SWF_STRUCTURE_MS_SSIM, SWF_STRUCTURE_QS,
+       SWF_STRUCTURE_QW, SWF_STRUCTURE_QE, SWF_STRUCTURE_QC, SWF_STRUCTURE_QY, SWF_STRUCTURE_COUNT };
+/* 0 for a shape swf_fusion_structure would refuse, and for an image under 7 pixels in an axis, which has no window of any kind and
+ * needs no workspace (the call then takes a NULL one and writes nine zeros) */
+size_t swf_fusion_structure_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_STRUCTURE_COUNT], one row per image.  The call writes every workspace
+ * element it reads, allocates nothing and does not synchronise the host, so it can be captured into a hipGraph on one stream.
+ * SWF_ERR_BAD_SHAPE for H W > 2^30 or B > 65535 (the limits of swf_fusion_metrics), and for a non-finite constant, K1 <= 0, K2 <= 0
+ * or alpha < 0, before anything is launched. */
+int swf_fusion_structure(const swf_structure_desc* desc, const float* fusion, const float* ir, const float* vis,
+                         double* out /* device [B][SWF_STRUCTURE_COUNT] */, int32_t B, int32_t H, int32_t W,
+                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);

@@ -124,6 +124,13 @@ class FidelityDesc(C.Structure):   # swf_fidelity_desc: the constants of VIF (si
 FIDELITY_COUNT = 5   # SWF_FIDELITY_COUNT
 
 
+class StructureDesc(C.Structure):   # swf_structure_desc: the SSIM constants K1, K2, Piella's edge exponent alpha, Yang's threshold Ty
+    _fields_ = [(n, C.c_double) for n in ("K1", "K2", "alpha", "Ty")]
+
+
+STRUCTURE_COUNT = 9   # SWF_STRUCTURE_COUNT
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -250,6 +257,8 @@ SIGNATURES = {
     "swf_fusion_metrics": (C.c_int, [P(MetricsDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_fusion_fidelity_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "swf_fusion_fidelity": (C.c_int, [P(FidelityDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_structure_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_structure": (C.c_int, [P(StructureDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

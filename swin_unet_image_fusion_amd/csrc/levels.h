@@ -1,5 +1,5 @@
 // The 8-bit level of a unit-range fp32 pixel, shared by every kernel file that evaluates images on levels (kernels_metrics.hip,
-// kernels_fidelity.hip): torchvision save_image's quantiser, (int) min(max(x * 255 + 0.5, 0), 255) in fp32 with two roundings.
+// kernels_fidelity.hip, kernels_structure.hip): torchvision save_image's quantiser, (int) min(max(x * 255 + 0.5, 0), 255) in fp32 with two roundings.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,6 +14,7 @@
 #include "kernels_dropout.h"
 #include "kernels_loss.h"
 #include "kernels_fidelity.h"
+#include "kernels_structure.h"
 #include "kernels_metrics.h"
 #include "kernels_optim.h"
 #include "kernels_deep.h"
@@ -2311,6 +2312,33 @@ int swf_fusion_fidelity(const swf_fidelity_desc* desc, const float* fusion, cons
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "fusion_fidelity: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return fusion_fidelity(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// SSIM, MS-SSIM and the Piella / Cvejic / Yang indices.  Every argument check comes before the first HIP call.
+static int check_fusion_structure(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!fusion_structure_shape_ok(B, H, W))
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: B=%d H=%d W=%d exceeds the kernels' grids (H W <= 2^30, B <= 65535)", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_structure_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    if (check_fusion_structure(B, H, W) != SWF_OK) return 0;
+    return fusion_structure_workspace_bytes(B, H, W);
+}
+
+int swf_fusion_structure(const swf_structure_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
+                         int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_structure: NULL descriptor, image or output");
+    SWF_TRY(check_fusion_structure(B, H, W));
+    if (!std::isfinite(desc->K1) || !std::isfinite(desc->K2) || !std::isfinite(desc->alpha) || !std::isfinite(desc->Ty) ||
+        desc->K1 <= 0.0 || desc->K2 <= 0.0 || desc->alpha < 0.0)
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: constants K1=%g K2=%g alpha=%g Ty=%g (finite, K1 > 0, K2 > 0, alpha >= 0)",
+                    desc->K1, desc->K2, desc->alpha, desc->Ty);
+    const size_t need = fusion_structure_workspace_bytes(B, H, W);   // 0 under 7 pixels in an axis: no window, nothing to carve
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(SWF_ERR_WORKSPACE, "fusion_structure: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return fusion_structure(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

@@ -11,9 +11,14 @@ VIF (multi-scale pixel-domain, per source and summed) and Nabf with its loss ter
 levels, fp64 throughout (swf_fusion_fidelity: `fusion_fidelity`, or `FusionMetrics(fidelity=True)` for all fifteen values).  VIF of a
 source is 0 when its denominator is (an image under 17 pixels in an axis, a flat source).
 
+The structural-similarity group comes from a third fused HIP call on the same levels (swf_fusion_structure: `fusion_structure`, or
+`FusionMetrics(structure=True)`): Wang's SSIM (per source and summed) and MS-SSIM with the 11-tap Gaussian in fp64, Piella's Q_S, Q_W
+and Q_E, Cvejic's Q_C and Yang's Q_Y on exact integer window sums.  SSIM is 0 for an image under 11 pixels in an axis, MS-SSIM under
+176, the Piella / Cvejic values under 8 and Yang's under 7.
+
 The definitions are restated from the published ones and the common open evaluators; no MATLAB, VIFB or sewar copy is available to
-this build, so parity with any of them is unpinned.  SSIM is already available as
-`MyLoss(choose_ms_ssim=False).calcu_ssim_loss`.
+this build, so parity with any of them is unpinned.  `MyLoss(choose_ms_ssim=False).calcu_ssim_loss` is a different
+thing: the training loss's kornia-style SSIM on unit-range floats, returned as a loss; SSIM as a metric on levels is `fusion_structure`'s.
 """
 from __future__ import annotations
 
@@ -26,13 +31,16 @@ from torch import Tensor
 from . import _lib as L
 from .modules import _ptr, _stream, _workspace
 
-__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "fusion_metrics", "fusion_fidelity", "FusionMetrics"]
+__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "STRUCTURE_NAMES", "STRUCTURE_DEFAULTS", "fusion_metrics",
+           "fusion_fidelity", "fusion_structure", "FusionMetrics"]
 
 METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
 QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
 FIDELITY_NAMES = ("VIF", "VIF_IR", "VIF_VIS", "Nabf", "Labf")                        # the order of the header's SWF_FIDELITY_* enum
 FIDELITY_DEFAULTS = {"sigma_nsq": 2.0, "eps": 1e-10,                                # Sheikh & Bovik (vifp_mscale)
                      "Td": 2.0, "wt_min": 0.001, "Nrg": 0.9999, "kg": 19.0, "sg": 0.5, "Nra": 0.9995, "ka": 22.0, "sa": 0.5}   # Kumar
+STRUCTURE_NAMES = ("SSIM", "SSIM_IR", "SSIM_VIS", "MS_SSIM", "Qs", "Qw", "Qe", "Qc", "Qy")   # the order of the header's SWF_STRUCTURE_* enum
+STRUCTURE_DEFAULTS = {"K1": 0.01, "K2": 0.03, "alpha": 1.0, "Ty": 0.75}   # Wang's SSIM constants, Piella's edge exponent, Yang's threshold
 
 
 def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
@@ -100,19 +108,49 @@ def fusion_fidelity(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Ten
     return out
 
 
-class FusionMetrics:
-    """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` of fifteen, the FIDELITY_NAMES values
-    (constants: `fidelity_constants`) after the ten.  The sum lives on the device and update() does not synchronise; compute() reads
-    it back once.  The image count is a host int (`count`): the batch size is known on the host, so counting there needs no
-    synchronisation and no device scalar."""
+def _structure_desc(constants: dict) -> L.StructureDesc:
+    unknown = set(constants) - set(STRUCTURE_DEFAULTS)
+    if unknown:
+        raise TypeError(f"fusion_structure: unknown constant(s) {sorted(unknown)}; the constants are {list(STRUCTURE_DEFAULTS)}")
+    c = {**STRUCTURE_DEFAULTS, **constants}
+    return L.StructureDesc(*(float(c[k]) for k in STRUCTURE_DEFAULTS))
 
-    def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, **qabf_constants):
+
+def fusion_structure(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
+    """-> (B, 9) float64 tensor on the inputs' device, row b = the STRUCTURE_NAMES values of image b: SSIM = SSIM_IR + SSIM_VIS,
+    MS_SSIM, Piella's Qs, Qw, Qe, Cvejic's Qc and Yang's Qy.  Inputs as for fusion_metrics.  Keyword arguments replace constants
+    (STRUCTURE_DEFAULTS); a non-finite one, K1 <= 0, K2 <= 0 or alpha < 0 raises ValueError.  One library call on the current stream,
+    no host synchronisation; bit-identical from call to call."""
+    desc = _structure_desc(constants)
+    _check_images(fusion, ir, vis)
+    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
+    b, _, h, w = f.shape
+    lib = L.lib()
+    need = lib.swf_fusion_structure_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
+    out = torch.empty((b, L.STRUCTURE_COUNT), dtype=torch.float64, device=f.device)
+    ws, wsn = _workspace(need, f.device)
+    L.check(lib.swf_fusion_structure(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
+    return out
+
+
+class FusionMetrics:
+    """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` the FIDELITY_NAMES values (constants:
+    `fidelity_constants`) follow the ten, with `structure=True` the STRUCTURE_NAMES values (constants: `structure_constants`) follow
+    those: 10, 15, 19 or 24 values.  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
+    image count is a host int (`count`): the batch size is known on the host, so counting there needs no synchronisation and no
+    device scalar."""
+
+    def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, structure: bool = False,
+                 structure_constants: Optional[dict] = None, **qabf_constants):
         _desc(qabf_constants)   # refuse a misspelt constant here, not at the first batch
         _fidelity_desc(fidelity_constants or {})
+        _structure_desc(structure_constants or {})
         self.qabf_constants = qabf_constants
         self.fidelity = bool(fidelity)
         self.fidelity_constants = dict(fidelity_constants or {})
-        self.names = METRIC_NAMES + FIDELITY_NAMES if self.fidelity else METRIC_NAMES
+        self.structure = bool(structure)
+        self.structure_constants = dict(structure_constants or {})
+        self.names = METRIC_NAMES + (FIDELITY_NAMES if self.fidelity else ()) + (STRUCTURE_NAMES if self.structure else ())
         self.reset()
 
     def reset(self) -> None:
@@ -120,10 +158,12 @@ class FusionMetrics:
         self.count = 0
 
     def update(self, fusion: Tensor, ir: Tensor, vis: Tensor) -> Tensor:
-        """Adds the batch's rows; -> the rows, (B, 10) float64 on the device, (B, 15) with fidelity."""
+        """Adds the batch's rows; -> the rows, (B, len(names)) float64 on the device."""
         rows = fusion_metrics(fusion, ir, vis, **self.qabf_constants)
         if self.fidelity:
             rows = torch.cat([rows, fusion_fidelity(fusion, ir, vis, **self.fidelity_constants)], dim=1)
+        if self.structure:
+            rows = torch.cat([rows, fusion_structure(fusion, ir, vis, **self.structure_constants)], dim=1)
         s = rows.sum(dim=0)
         self._sum = s if self._sum is None else self._sum + s
         self.count += rows.shape[0]
