@@ -6,9 +6,6 @@
 
 namespace swf {
 
-// The limits of the other metrics: H * W <= 2^30 pixels per image, B <= 65535 images per call.
-bool fusion_fidelity_shape_ok(int B, int H, int W);
-
 // Bytes of workspace swf_fusion_fidelity needs: per image the fp64 planes of pyramid scales 2-4 (three per scale) and the per-tile
 // fp64 partial sums (four per VIF tile, three per Sobel tile).
 size_t fusion_fidelity_workspace_bytes(int B, int H, int W);

@@ -5,9 +5,6 @@
 
 namespace swf {
 
-// What the kernels' counters and grids hold: H * W <= 2^30 pixels per image, B <= 65535 images per call.
-bool fusion_metrics_shape_ok(int B, int H, int W);
-
 // Bytes of workspace swf_fusion_metrics needs: per image two 256x256 u32 joint histograms and three u64 sums (zeroed by the call),
 // and three fp64 partial sums per 32x32 tile.
 size_t fusion_metrics_workspace_bytes(int B, int H, int W);

@@ -22,7 +22,7 @@
 //
 // gfx950 cross-compile (hipcc -O3): no scratch in any kernel; VGPRs hist<true> / hist<false> / grad / finish as reported in DESIGN.md 6c.
 #include "kernels_metrics.h"
-#include "levels.h"
+#include "metric_frag.h"
 
 #include <algorithm>
 #include <cmath>
@@ -34,19 +34,13 @@ constexpr int kCells = 256 * 256;
 constexpr int kHistTile = 8192;        // pixels per workgroup of the histogram pass
 constexpr int kHistThreads = 1024;
 constexpr int kHistLdsBytes = kCells * 2;
-constexpr int kMaxPixels = 1 << 30;    // int pixel indices with room for the loop strides; u32 counters hold 2^32 - 1
-constexpr int kMaxBatch = 65535;       // grid.z / grid.y
 static_assert(kHistTile <= 65535, "a packed 16-bit counter must hold a whole tile");
 static_assert((int64_t)(kHistTile / kHistThreads) * 255 * 255 * 64 < (int64_t(1) << 32), "a wave's u32 partial sum must not wrap");
 constexpr int kSumsPerImage = 4;       // sum ir*vis, sum row diff^2, sum col diff^2, (pad)
-constexpr int kGT = 32, kGP = kGT + 2; // gradient tile and its padded pitch
-constexpr int kGradThreads = 256;
 constexpr int kFinThreads = 1024;
 constexpr double kHalfPi = 1.57079632679489661923;
 
 typedef unsigned long long u64;
-
-// level(): the two-rounding quantiser of levels.h, shared with kernels_fidelity.hip.
 
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
@@ -120,14 +114,6 @@ __global__ __launch_bounds__(kHistThreads) void metrics_hist_kernel(const float*
 // ------------------------------------------------------------------------------------------------------------------------------
 // Sobel (zero border), Qabf numerator / denominator, AG
 // ------------------------------------------------------------------------------------------------------------------------------
-// p = top-left of the 3x3 patch.  sx = [-1 0 1; -2 0 2; -1 0 1], sy = [1 2 1; 0 0 0; -1 -2 -1] applied as written; conv2's flip negates
-// both, which changes neither g nor sy / sx.
-__device__ __forceinline__ void sobel(const int* p, int& sx, int& sy) {
-    const int a = p[0], b = p[1], c = p[2], d = p[kGP], e = p[kGP + 2], f = p[2 * kGP], g = p[2 * kGP + 1], h = p[2 * kGP + 2];
-    sx = (c - a) + 2 * (e - d) + (h - f);
-    sy = (a + 2 * b + c) - (f + 2 * g + h);
-}
-
 __device__ __forceinline__ double edge_angle(int sx, int sy) { return sx == 0 ? kHalfPi : atan((double)sy / (double)sx); }
 
 // Q_X g_X of one source at one pixel; n = sx^2 + sy^2 as integers, g = sqrt(n), a = edge_angle
@@ -139,61 +125,37 @@ __device__ __forceinline__ double qabf_term(const swf_metrics_desc& d, int nF, d
     return Qg * Qa * gX;
 }
 
-__global__ __launch_bounds__(kGradThreads) void metrics_grad_kernel(const float* __restrict__ fusion, const float* __restrict__ ir,
-                                                                    const float* __restrict__ vis, double* __restrict__ part,
-                                                                    int H, int W, int tiles_x, swf_metrics_desc d) {
-    __shared__ int sL[3][kGP * kGP];
-    __shared__ double red[3][kGradThreads];
+__global__ __launch_bounds__(kThreads) void metrics_grad_kernel(const float* __restrict__ fusion, const float* __restrict__ ir,
+                                                                const float* __restrict__ vis, double* __restrict__ part,
+                                                                int H, int W, int tiles_x, swf_metrics_desc d) {
+    __shared__ int sL[3][kLP * kLP];
+    __shared__ double red[3][kThreads];
     const int tid = threadIdx.x, b = blockIdx.y;
-    const int ty0 = (blockIdx.x / tiles_x) * kGT, tx0 = (blockIdx.x % tiles_x) * kGT;
-    const int64_t img = (int64_t)b * H * W;
-    for (int i = tid; i < kGP * kGP; i += kGradThreads) {
-        const int hh = ty0 + i / kGP - 1, w = tx0 + i % kGP - 1;
-        const bool in = hh >= 0 && hh < H && w >= 0 && w < W;
-        const int64_t o = img + (int64_t)hh * W + w;
-        sL[0][i] = in ? level(fusion[o]) : 0;
-        sL[1][i] = in ? level(ir[o]) : 0;
-        sL[2][i] = in ? level(vis[o]) : 0;
-    }
-    __syncthreads();
+    const int ty0 = (blockIdx.x / tiles_x) * kLT, tx0 = (blockIdx.x % tiles_x) * kLT;
+    load_level_tile<false>(sL, fusion, ir, vis, (int64_t)b * H * W, ty0, tx0, H, W);   // zero border
     double num = 0.0, den = 0.0, ag = 0.0;
-    const int lx = tid & 31;
-#pragma unroll 1
-    for (int k = 0; k < kGT / 8; ++k) {
-        const int ly = (tid >> 5) + 8 * k;
-        const int hh = ty0 + ly, w = tx0 + lx;
-        if (hh < H && w < W) {
-            const int o = ly * kGP + lx;   // top-left of the patch centred on (ly + 1, lx + 1)
-            int sx, sy;
-            sobel(&sL[0][o], sx, sy);
-            const int nF = sx * sx + sy * sy;
-            const double gF = sqrt((double)nF), aF = edge_angle(sx, sy);
-            sobel(&sL[1][o], sx, sy);
-            const int nA = sx * sx + sy * sy;
-            const double gA = sqrt((double)nA), aA = edge_angle(sx, sy);
-            sobel(&sL[2][o], sx, sy);
-            const int nB = sx * sx + sy * sy;
-            const double gB = sqrt((double)nB), aB = edge_angle(sx, sy);
-            num += qabf_term(d, nF, gF, aF, nA, gA, aA) + qabf_term(d, nF, gF, aF, nB, gB, aB);
-            den += gA + gB;
-            if (hh < H - 1 && w < W - 1) {
-                const int c = sL[0][o + kGP + 1], gx = sL[0][o + kGP + 2] - c, gy = sL[0][o + 2 * kGP + 1] - c;
-                ag += sqrt((double)(gx * gx + gy * gy) / 2.0);
-            }
+    walk_level_tile(ty0, tx0, H, W, [&](int o, int hh, int w) {
+        int sx, sy;
+        sobel3x3(&sL[0][o], kLP, sx, sy);
+        const int nF = sx * sx + sy * sy;
+        const double gF = sqrt((double)nF), aF = edge_angle(sx, sy);
+        sobel3x3(&sL[1][o], kLP, sx, sy);
+        const int nA = sx * sx + sy * sy;
+        const double gA = sqrt((double)nA), aA = edge_angle(sx, sy);
+        sobel3x3(&sL[2][o], kLP, sx, sy);
+        const int nB = sx * sx + sy * sy;
+        const double gB = sqrt((double)nB), aB = edge_angle(sx, sy);
+        num += qabf_term(d, nF, gF, aF, nA, gA, aA) + qabf_term(d, nF, gF, aF, nB, gB, aB);
+        den += gA + gB;
+        if (hh < H - 1 && w < W - 1) {
+            const int c = sL[0][o + kLP + 1], gx = sL[0][o + kLP + 2] - c, gy = sL[0][o + 2 * kLP + 1] - c;
+            ag += sqrt((double)(gx * gx + gy * gy) / 2.0);
         }
-    }
+    });
     red[0][tid] = num;
     red[1][tid] = den;
     red[2][tid] = ag;
-    __syncthreads();
-    for (int s = kGradThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red[0][tid] += red[0][tid + s];
-            red[1][tid] += red[1][tid + s];
-            red[2][tid] += red[2][tid + s];
-        }
-        __syncthreads();
-    }
+    SWF_TILE_TREE(3, red);
     if (tid < 3) part[((int64_t)b * gridDim.x + blockIdx.x) * 3 + tid] = red[tid][0];
 }
 
@@ -329,8 +291,8 @@ struct MetricsBufs {
 };
 MetricsBufs carve_metrics(Carver& ws, int B, int H, int W) {
     MetricsBufs m{};
-    m.tiles_x = cdiv(W, kGT);
-    m.ntiles = m.tiles_x * cdiv(H, kGT);
+    m.tiles_x = cdiv(W, kLT);
+    m.ntiles = m.tiles_x * cdiv(H, kLT);
     const int64_t words = (int64_t)B * (2 * kCells + kSumsPerImage * 2);
     float* z = ws.floats(words);
     m.hist = reinterpret_cast<uint32_t*>(z);
@@ -340,23 +302,14 @@ MetricsBufs carve_metrics(Carver& ws, int B, int H, int W) {
     return m;
 }
 
-// Tools only (SWF_DEBUG_SWITCHES=1), read at every call so that tools/metrics_bench.py can time the parts in one process:
-// SWF_METRICS_STAGES = bit mask of what to enqueue (1 zeroing, 2 histograms, 4 gradients, 8 finish), SWF_METRICS_HIST=global sends
-// the histogram atomics straight to global memory.
-int stage_mask() {
-    const char* e = debug_env("SWF_METRICS_STAGES");
-    return e ? atoi(e) : 15;
-}
+// Tools only (SWF_DEBUG_SWITCHES=1), read at every call so that tools/metrics_bench.py can time both in one process:
+// SWF_METRICS_HIST=global sends the histogram atomics straight to global memory.
 bool hist_private() {
     const char* e = debug_env("SWF_METRICS_HIST");
     return !(e && e[0] == 'g');
 }
 
 }  // namespace
-
-bool fusion_metrics_shape_ok(int B, int H, int W) {
-    return B > 0 && H > 0 && W > 0 && B <= kMaxBatch && (int64_t)H * W <= kMaxPixels;
-}
 
 size_t fusion_metrics_workspace_bytes(int B, int H, int W) {
     Carver ws = Carver::measure();
@@ -369,7 +322,7 @@ int fusion_metrics(const swf_metrics_desc& d, const float* fusion, const float* 
     Carver ws(workspace, workspace_bytes);
     const MetricsBufs m = carve_metrics(ws, B, H, W);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "fusion_metrics: workspace of %zu bytes, %zu needed", workspace_bytes, ws.bytes());
-    const int stages = stage_mask();
+    const int stages = stage_mask("SWF_METRICS_STAGES");   // 1 zeroing, 2 histograms, 4 gradients, 8 finish
     if (stages & 1) {
         const int64_t n16 = (int64_t)(m.zero_bytes / 16);   // B * (2 * kCells + 8) words: a multiple of 16 bytes
         metrics_zero_kernel<<<(unsigned)std::min<int64_t>(cdiv64(n16, 256), 2048), 256, 0, stream>>>(reinterpret_cast<uint4*>(m.hist), n16);
@@ -386,7 +339,7 @@ int fusion_metrics(const swf_metrics_desc& d, const float* fusion, const float* 
         SWF_TRY(check_launch("metrics_hist_kernel"));
     }
     if (stages & 4) {
-        metrics_grad_kernel<<<dim3(m.ntiles, B), kGradThreads, 0, stream>>>(fusion, ir, vis, m.part, H, W, m.tiles_x, d);
+        metrics_grad_kernel<<<dim3(m.ntiles, B), kThreads, 0, stream>>>(fusion, ir, vis, m.part, H, W, m.tiles_x, d);
         SWF_TRY(check_launch("metrics_grad_kernel"));
     }
     if (stages & 8) {

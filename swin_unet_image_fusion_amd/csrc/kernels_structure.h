@@ -6,9 +6,6 @@
 
 namespace swf {
 
-// The limits of the other metrics: H * W <= 2^30 pixels per image, B <= 65535 images per call.
-bool fusion_structure_shape_ok(int B, int H, int W);
-
 // Bytes of workspace swf_fusion_structure needs: per image the per-tile partial sums (four per Gaussian tile and scale, four per box
 // tile and launch) and, for images of 176 pixels or more in both axes, the fp64 planes of pyramid scales 2-5 (three per scale).
 size_t fusion_structure_workspace_bytes(int B, int H, int W);

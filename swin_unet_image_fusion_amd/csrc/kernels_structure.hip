@@ -16,13 +16,13 @@
 //                          moments A, B, F, AA, BB, FF, AF, BF, AB are summed along rows into LDS and down columns into registers,
 //                          two windows per thread; four sums per tile: t, m t, m (an integer) and Q_C's (WN = 8) or Q_Y's (WN = 7)
 //                          term.  Launched three times: <8, levels>, <8, edges>, <7, levels>.
-//   ssim_moments_kernel<QUANT>    one per scale, both pairs sharing F: vif_moments_kernel's scheme with the 11-tap window; four sums
-//                          per tile: l cs and cs of (A, F) and of (B, F).
+//   gauss_moments_kernel<11, QUANT, SsimRule> (metric_frag.h)  one per scale, both pairs sharing F; four sums per tile: l cs and cs
+//                          of (A, F) and of (B, F).
 //   mean2x2_kernel<QUANT>  the three planes of scale j + 1 from those of scale j (QUANT: from the fp32 images, quantised here).
 //   structure_finish_kernel  one workgroup per image adds the per-tile sums in a fixed order and writes the row.
 // The window weights are computed on the host in fp64 and passed by value.
 #include "kernels_structure.h"
-#include "levels.h"
+#include "metric_frag.h"
 
 #include <algorithm>
 #include <cmath>
@@ -30,45 +30,11 @@
 namespace swf {
 namespace {
 
-constexpr int kMaxPixels = 1 << 30;    // as the other metrics: int pixel indices with room for the tile strides
-constexpr int kMaxBatch = 65535;       // grid.y
 constexpr int kScales = 5;
-constexpr int kTaps = 11;              // the Gaussian window
+constexpr int kTaps = 11;              // the Gaussian window: g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), normalised to sum 1
+constexpr double kSigma = 1.5;
 constexpr int kMinMs = kTaps << (kScales - 1);   // 176: the smallest axis whose scale-5 plane still holds one window
-constexpr int kThreads = 256;
-constexpr int kTX = 32, kTY = 16;      // tile of the moment kernels (outputs): two outputs per thread
 constexpr int kBoxLaunches = 3;        // <8, levels>, <8, edges>, <7, levels>
-static_assert(kTX * kTY == 2 * kThreads && kTX == 32, "the thread -> output maps below");
-
-struct Window {
-    double g[kTaps];
-};
-
-// g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)), normalised to sum 1: the 1-D factor of the separable window.
-Window make_window() {
-    Window w;
-    double sum = 0.0;
-    for (int i = 0; i < kTaps; ++i) {
-        const double d = i - (kTaps - 1) / 2;
-        w.g[i] = std::exp(-(d * d) / (2.0 * 1.5 * 1.5));
-        sum += w.g[i];
-    }
-    for (int i = 0; i < kTaps; ++i) w.g[i] /= sum;
-    return w;
-}
-
-// The three input planes of a scale, in the order A, B, F: image 0's planes and the distance between images, in elements.
-struct Source {
-    const void* p[3];
-    int64_t stride;
-};
-
-// QUANT: an fp32 image, quantised here; else an fp64 plane of the workspace.
-template <bool QUANT>
-__device__ __forceinline__ double load_px(const void* p, int64_t o) {
-    if (QUANT) return (double)level(static_cast<const float*>(p)[o]);
-    return static_cast<const double*>(p)[o];
-}
 
 // ------------------------------------------------------------------------------------------------------------------------------
 // Box group
@@ -82,11 +48,10 @@ __device__ __forceinline__ double s_index(int SX, int SY, int64_t VX, int64_t VY
     return ((2.0 * mx * my + C1) * (2.0 * cxy + C2)) / ((mx * mx + my * my + C1) * (vx + vy + C2));
 }
 
-// p = top-left of the 3x3 patch of levels, pitch in elements.  sx with [-1 0 1; -2 0 2; -1 0 1], sy with [1 2 1; 0 0 0; -1 -2 -1].
+// The Sobel-L1 edge strength |sx| + |sy| of the 3x3 patch of levels whose top-left is p, pitch in elements.
 __device__ __forceinline__ int sobel_l1(const unsigned short* p, int pitch) {
-    const int a = p[0], b = p[1], c = p[2], d = p[pitch], e = p[pitch + 2], f = p[2 * pitch], g = p[2 * pitch + 1], h = p[2 * pitch + 2];
-    const int sx = (c - a) + 2 * (e - d) + (h - f);
-    const int sy = (a + 2 * b + c) - (f + 2 * g + h);
+    int sx, sy;
+    sobel3x3(p, pitch, sx, sy);
     return abs(sx) + abs(sy);
 }
 
@@ -103,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void box_moments_kernel(const float* __re
     __shared__ unsigned short in[3][PH * PW];
     __shared__ int tmp[9][PH * kTX];
     __shared__ double red[3][kThreads];
-    __shared__ long long redm[kThreads];
+    __shared__ unsigned long long redm[kThreads];
     const int tid = threadIdx.x, b = blockIdx.y;
     const int ty0 = (blockIdx.x / tiles_x) * kTY, tx0 = (blockIdx.x % tiles_x) * kTX;
     const int64_t img = (int64_t)b * H * W;
@@ -194,109 +159,33 @@ __global__ __launch_bounds__(kThreads) void box_moments_kernel(const float* __re
     red[0][tid] = st;
     red[1][tid] = smt;
     red[2][tid] = sx;
-    redm[tid] = sm;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) red[k][tid] += red[k][tid + s];
-            redm[tid] += redm[tid + s];
-        }
-        __syncthreads();
-    }
+    redm[tid] = (unsigned long long)sm;
+    SWF_TILE_TREE_INT(3, red, true, redm);
     if (tid == 0) {
         double* p = part + (int64_t)b * part_stride + part_off + (int64_t)blockIdx.x * 4;
         p[0] = red[0][0];
         p[1] = red[1][0];
-        p[2] = __longlong_as_double(redm[0]);
+        p[2] = __longlong_as_double((long long)redm[0]);
         p[3] = red[2][0];
     }
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
-// Gaussian group: moments and evaluation of one scale
+// Gaussian group: evaluation of one scale's moments
 // ------------------------------------------------------------------------------------------------------------------------------
-// One output pixel of ssim(X, Y): biased moments, not clamped.  No contraction: the variances are the differences the restatement
-// forms, product rounded first.
-__device__ __forceinline__ void ssim_pixel(double muX, double muY, double XX, double YY, double XY, double C1, double C2, double& lcs,
-                                           double& cs) {
+// gauss_moments_kernel's rule for one output pixel of ssim(X, Y), adding to sum l cs and sum cs: biased moments, not clamped.  No
+// contraction: the variances are the differences the restatement forms, product rounded first.
+struct SsimRule {
+    static __device__ __forceinline__ void pixel(double muX, double muY, double XX, double YY, double XY, double C1, double C2, double& lcs,
+                                                 double& cs) {
 #pragma clang fp contract(off)
-    const double vx = XX - muX * muX, vy = YY - muY * muY, cxy = XY - muX * muY;
-    const double l = (2.0 * muX * muY + C1) / (muX * muX + muY * muY + C1);
-    const double c = (2.0 * cxy + C2) / (vx + vy + C2);
-    lcs += l * c;
-    cs += c;
-}
-
-// h, w: the scale's input; oh = h - 10, ow = w - 10 >= 1: its "valid" output.  part: [B][part_stride] doubles, this scale's tiles from
-// part_off on, four per tile: sum l cs and sum cs of (A, F), then of (B, F).
-template <bool QUANT>
-__global__ __launch_bounds__(kThreads) void ssim_moments_kernel(Source src, int h, int w, int oh, int ow, int tiles_x,
-                                                                double* __restrict__ part, int64_t part_stride, int64_t part_off,
-                                                                Window win, double C1, double C2) {
-    constexpr int N = kTaps, PW = kTX + N - 1, PH = kTY + N - 1;
-    __shared__ double in[3][PH * PW];
-    __shared__ double tmp[PH * kTX];
-    __shared__ double red[4][kThreads];
-    const int tid = threadIdx.x, b = blockIdx.y;
-    const int ty0 = (blockIdx.x / tiles_x) * kTY, tx0 = (blockIdx.x % tiles_x) * kTX;
-    const int64_t img = (int64_t)b * src.stride;
-    for (int i = tid; i < PH * PW; i += kThreads) {
-        const int y = ty0 + i / PW, x = tx0 + i % PW;
-        const bool ok = y < h && x < w;
-        const int64_t o = img + (int64_t)y * w + x;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) in[k][i] = ok ? load_px<QUANT>(src.p[k], o) : 0.0;
+        const double vx = XX - muX * muX, vy = YY - muY * muY, cxy = XY - muX * muY;
+        const double l = (2.0 * muX * muY + C1) / (muX * muX + muY * muY + C1);
+        const double c = (2.0 * cxy + C2) / (vx + vy + C2);
+        lcs += l * c;
+        cs += c;
     }
-    __syncthreads();
-    const int lx = tid & 31, ly0 = tid >> 5;
-    double m[8][2];   // A, B, F, AA, BB, FF, AF, BF at output pixels (ly0, lx) and (ly0 + 8, lx)
-#pragma unroll
-    for (int p = 0; p < 8; ++p) {
-        const int pa = p < 3 ? p : (p < 6 ? p - 3 : p - 6);   // first factor
-        const int pb = p < 6 ? p - 3 : 2;                     // second factor of a product plane
-        for (int i = tid; i < PH * kTX; i += kThreads) {      // rows
-            const int r = i >> 5, c = i & 31;
-            const double* ra = &in[pa][r * PW + c];
-            const double* rb = &in[p < 3 ? 0 : pb][r * PW + c];
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) acc += win.g[k] * (p < 3 ? ra[k] : ra[k] * rb[k]);
-            tmp[i] = acc;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {                          // columns
-            const double* col = &tmp[(ly0 + 8 * j) * kTX + lx];
-            double acc = 0.0;
-#pragma unroll
-            for (int k = 0; k < N; ++k) acc += win.g[k] * col[k * kTX];
-            m[p][j] = acc;
-        }
-        __syncthreads();
-    }
-    double lcsA = 0.0, csA = 0.0, lcsB = 0.0, csB = 0.0;
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        if (ty0 + ly0 + 8 * j < oh && tx0 + lx < ow) {
-            ssim_pixel(m[0][j], m[2][j], m[3][j], m[5][j], m[6][j], C1, C2, lcsA, csA);
-            ssim_pixel(m[1][j], m[2][j], m[4][j], m[5][j], m[7][j], C1, C2, lcsB, csB);
-        }
-    }
-    red[0][tid] = lcsA;
-    red[1][tid] = csA;
-    red[2][tid] = lcsB;
-    red[3][tid] = csB;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + s];
-        }
-        __syncthreads();
-    }
-    if (tid < 4) part[(int64_t)b * part_stride + part_off + (int64_t)blockIdx.x * 4 + tid] = red[tid][0];
-}
+};
 
 // dst[B][dst_stride]: planes A, B, F of dh x dw, dh = floor(h / 2), dw = floor(w / 2): output (y, x) is the mean of the 2x2 block at
 // (2 y, 2 x), whose last row 2 y + 1 <= h - 1.  Exact: the planes hold multiples of 4^-j below 256.
@@ -326,38 +215,6 @@ struct FinishArgs {
     double alpha;
 };
 
-// r[k] <- the sum of p[t * 4 + k] over t < n, k < 4, in a fixed order (per-thread strided sequences, then one tree for the four),
-// returned to every thread.  WITH_INT: *isum <- the sum of the int64 values kept in the bits of slot 2, exact, so its order is immaterial.
-template <bool WITH_INT>
-__device__ __forceinline__ void tile_sums(const double* p, int64_t n, double (*red)[kThreads], unsigned long long* ired, double r[4],
-                                          long long* isum) {
-    const int tid = threadIdx.x;
-    double v[4] = {0.0, 0.0, 0.0, 0.0};
-    unsigned long long iv = 0;
-    for (int64_t t = tid; t < n; t += kThreads) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (!(WITH_INT && k == 2)) v[k] += p[t * 4 + k];   // slot 2 of a box tile is no double: r[2] stays 0
-        if (WITH_INT) iv += (unsigned long long)__double_as_longlong(p[t * 4 + 2]);
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) red[k][tid] = v[k];
-    if (WITH_INT) ired[tid] = iv;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) red[k][tid] += red[k][tid + s];
-            if (WITH_INT) ired[tid] += ired[tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r[k] = red[k][0];
-    if (WITH_INT) *isum = (long long)ired[0];
-    __syncthreads();
-}
-
 __global__ __launch_bounds__(kThreads) void structure_finish_kernel(const double* __restrict__ part, int64_t part_stride, FinishArgs a,
                                                                     double* __restrict__ out) {
     __shared__ double red[4][kThreads];
@@ -368,7 +225,7 @@ __global__ __launch_bounds__(kThreads) void structure_finish_kernel(const double
     const double* pg = p;
     for (int s = 0; s < a.nscales; ++s) {
         double r[4];   // sum l cs and sum cs of (A, F), then of (B, F)
-        tile_sums<false>(pg, a.g_tiles[s], red, ired, r, nullptr);
+        tile_sums<4>(pg, a.g_tiles[s], red, r);
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const double lcs = r[2 * k] / a.g_count[s], cs = r[2 * k + 1] / a.g_count[s];
@@ -384,7 +241,7 @@ __global__ __launch_bounds__(kThreads) void structure_finish_kernel(const double
         if (a.box_tiles[i] == 0) continue;
         double r[4];   // sum t, sum m t, (slot 2: see sm), sum of the launch's own term
         long long sm;  // sum m
-        tile_sums<true>(p + a.box_off[i], a.box_tiles[i], red, ired, r, &sm);
+        tile_sums<4, true>(p + a.box_off[i], a.box_tiles[i], red, r, ired, &sm);
         q[i][0] = r[0] / a.box_count[i];
         q[i][1] = sm == 0 ? q[i][0] : r[1] / (double)sm;
         q[i][2] = r[3] / a.box_count[i];
@@ -406,14 +263,6 @@ __global__ __launch_bounds__(kThreads) void structure_finish_kernel(const double
 // ------------------------------------------------------------------------------------------------------------------------------
 // Host
 // ------------------------------------------------------------------------------------------------------------------------------
-struct Scale {
-    int h, w;               // input of the scale
-    int oh, ow;             // "valid" output of its moments
-    int tiles_x, ntiles;    // moment tiles
-    int64_t plane_off;      // scales 2-5: offset of the scale's three planes within an image's planes, in doubles
-    int64_t part_off;       // offset of the scale's partial sums within an image's, in doubles
-};
-
 struct Box {
     int oh, ow;             // window positions
     int tiles_x, ntiles;    // 0 tiles: the image is smaller than the window
@@ -444,12 +293,7 @@ StructurePlan carve_structure(Carver& ws, int B, int H, int W) {
             s.plane_off = f.planes_per_image;
             f.planes_per_image += (int64_t)3 * h * w;
         }
-        s.h = h;
-        s.w = w;
-        s.oh = h - kTaps + 1;
-        s.ow = w - kTaps + 1;
-        s.tiles_x = cdiv(s.ow, kTX);
-        s.ntiles = s.tiles_x * cdiv(s.oh, kTY);
+        s.size(h, w, kTaps);
         s.part_off = f.part_stride;
         f.part_stride += (int64_t)s.ntiles * 4;
     }
@@ -468,14 +312,6 @@ StructurePlan carve_structure(Carver& ws, int B, int H, int W) {
     return f;
 }
 
-// The three planes of scale i (>= 1) in the workspace.
-Source plane_source(const StructurePlan& f, int i) {
-    const Scale& s = f.s[i];
-    const double* base = f.planes + s.plane_off;
-    const int64_t n = (int64_t)s.h * s.w;
-    return Source{{base, base + n, base + 2 * n}, f.planes_per_image};
-}
-
 template <int WN, bool EDGE>
 int launch_box(const StructurePlan& f, int i, const swf_structure_desc& d, double C1, double C2, const float* fusion, const float* ir,
                const float* vis, int B, int H, int W, hipStream_t stream) {
@@ -486,18 +322,7 @@ int launch_box(const StructurePlan& f, int i, const swf_structure_desc& d, doubl
     return check_launch("box_moments_kernel");
 }
 
-// Tools only (SWF_DEBUG_SWITCHES=1), read at every call so that tools/structure_bench.py can time the parts in one process:
-// SWF_STRUCTURE_STAGES = bit mask of what to enqueue (1 Gaussian moments, 2 2x2 means, 4 box moments, 8 finish).
-int stage_mask() {
-    const char* e = debug_env("SWF_STRUCTURE_STAGES");
-    return e ? atoi(e) : 15;
-}
-
 }  // namespace
-
-bool fusion_structure_shape_ok(int B, int H, int W) {
-    return B > 0 && H > 0 && W > 0 && B <= kMaxBatch && (int64_t)H * W <= kMaxPixels;
-}
 
 size_t fusion_structure_workspace_bytes(int B, int H, int W) {
     Carver ws = Carver::measure();
@@ -510,10 +335,10 @@ int fusion_structure(const swf_structure_desc& d, const float* fusion, const flo
     Carver ws(workspace, workspace_bytes);
     const StructurePlan f = carve_structure(ws, B, H, W);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "fusion_structure: workspace of %zu bytes, %zu needed", workspace_bytes, ws.bytes());
-    const int stages = stage_mask();
+    const int stages = stage_mask("SWF_STRUCTURE_STAGES");   // 1 Gaussian moments, 2 2x2 means, 4 box moments, 8 finish
     const double c1 = 255.0 * d.K1, c2 = 255.0 * d.K2;
     const double C1 = c1 * c1, C2 = c2 * c2;
-    const Window win = make_window();
+    const Window<kTaps> win = make_window<kTaps>(kSigma);
     const Source images{{ir, vis, fusion}, (int64_t)H * W};
     for (int i = 0; i < f.nscales; ++i) {
         const Scale& s = f.s[i];
@@ -529,12 +354,12 @@ int fusion_structure(const swf_structure_desc& d, const float* fusion, const flo
         if (stages & 1) {
             const dim3 grid(s.ntiles, B);
             if (i == 0)
-                ssim_moments_kernel<true><<<grid, kThreads, 0, stream>>>(images, s.h, s.w, s.oh, s.ow, s.tiles_x, f.part, f.part_stride,
-                                                                         s.part_off, win, C1, C2);
+                gauss_moments_kernel<kTaps, true, SsimRule><<<grid, kThreads, 0, stream>>>(images, s.h, s.w, s.oh, s.ow, s.tiles_x, f.part,
+                                                                                           f.part_stride, s.part_off, win, C1, C2);
             else
-                ssim_moments_kernel<false><<<grid, kThreads, 0, stream>>>(plane_source(f, i), s.h, s.w, s.oh, s.ow, s.tiles_x, f.part,
-                                                                          f.part_stride, s.part_off, win, C1, C2);
-            SWF_TRY(check_launch("ssim_moments_kernel"));
+                gauss_moments_kernel<kTaps, false, SsimRule><<<grid, kThreads, 0, stream>>>(plane_source(f, i), s.h, s.w, s.oh, s.ow, s.tiles_x,
+                                                                                            f.part, f.part_stride, s.part_off, win, C1, C2);
+            SWF_TRY(check_launch("gauss_moments_kernel"));
         }
     }
     if (stages & 4) {

@@ -16,6 +16,7 @@
 #include "kernels_fidelity.h"
 #include "kernels_structure.h"
 #include "kernels_metrics.h"
+#include "metric_frag.h"
 #include "kernels_optim.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
@@ -2268,77 +2269,67 @@ int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float*
     return fusion_loss(*desc, fusion, ir, vis, terms, grad_fusion, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
-// Fusion-quality metrics.  Every argument check comes before the first HIP call.
-static int check_fusion_metrics(int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_metrics: empty tensor (B=%d H=%d W=%d)", B, H, W);
-    if (!fusion_metrics_shape_ok(B, H, W))
-        return fail(SWF_ERR_BAD_SHAPE, "fusion_metrics: B=%d H=%d W=%d exceeds the kernels' counters (H W <= 2^30, B <= 65535)", B, H, W);
+// The three evaluation calls: fusion-quality metrics; VIF and Nabf; SSIM, MS-SSIM and the Piella / Cvejic / Yang indices.  Every
+// argument check comes before the first HIP call.  `holds` is what of the kernels the shape message says the shape exceeds.
+static int check_metric_shape(const char* name, const char* holds, int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "%s: empty tensor (B=%d H=%d W=%d)", name, B, H, W);
+    if (!metric_shape_ok(B, H, W))
+        return fail(SWF_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d exceeds the kernels' %s (H W <= 2^30, B <= 65535)", name, B, H, W, holds);
     return SWF_OK;
 }
 
+// NULL check -> shape -> the descriptor's own check, if it has one -> workspace -> call.  A call that carves nothing needs no workspace
+// (fusion_structure under 7 pixels in an axis: no window).
+extern "C++" template <class DESC>
+static int metric_call(const char* name, const char* holds, int (*check_desc)(const DESC&), size_t (*bytes)(int, int, int),
+                       int (*run)(const DESC&, const float*, const float*, const float*, double*, int, int, int, void*, size_t, hipStream_t),
+                       const DESC* desc, const float* fusion, const float* ir, const float* vis, double* out, int32_t B, int32_t H,
+                       int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "%s: NULL descriptor, image or output", name);
+    SWF_TRY(check_metric_shape(name, holds, B, H, W));
+    if (check_desc) SWF_TRY(check_desc(*desc));
+    const size_t need = bytes(B, H, W);
+    if (need > 0 && (!workspace || workspace_bytes < need))
+        return fail(SWF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", name, workspace ? workspace_bytes : (size_t)0, need);
+    return run(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
 size_t swf_fusion_metrics_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (check_fusion_metrics(B, H, W) != SWF_OK) return 0;
-    return fusion_metrics_workspace_bytes(B, H, W);
+    return check_metric_shape("fusion_metrics", "counters", B, H, W) == SWF_OK ? fusion_metrics_workspace_bytes(B, H, W) : 0;
 }
 
 int swf_fusion_metrics(const swf_metrics_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
                        int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_metrics: NULL descriptor, image or output");
-    SWF_TRY(check_fusion_metrics(B, H, W));
-    const size_t need = fusion_metrics_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "fusion_metrics: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return fusion_metrics(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
-// VIF and Nabf.  Every argument check comes before the first HIP call.
-static int check_fusion_fidelity(int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_fidelity: empty tensor (B=%d H=%d W=%d)", B, H, W);
-    if (!fusion_fidelity_shape_ok(B, H, W))
-        return fail(SWF_ERR_BAD_SHAPE, "fusion_fidelity: B=%d H=%d W=%d exceeds the kernels' grids (H W <= 2^30, B <= 65535)", B, H, W);
-    return SWF_OK;
+    return metric_call<swf_metrics_desc>("fusion_metrics", "counters", nullptr, fusion_metrics_workspace_bytes, fusion_metrics, desc, fusion,
+                                         ir, vis, out, B, H, W, workspace, workspace_bytes, stream);
 }
 
 size_t swf_fusion_fidelity_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (check_fusion_fidelity(B, H, W) != SWF_OK) return 0;
-    return fusion_fidelity_workspace_bytes(B, H, W);
+    return check_metric_shape("fusion_fidelity", "grids", B, H, W) == SWF_OK ? fusion_fidelity_workspace_bytes(B, H, W) : 0;
 }
 
 int swf_fusion_fidelity(const swf_fidelity_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
                         int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_fidelity: NULL descriptor, image or output");
-    SWF_TRY(check_fusion_fidelity(B, H, W));
-    const size_t need = fusion_fidelity_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "fusion_fidelity: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return fusion_fidelity(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
-// SSIM, MS-SSIM and the Piella / Cvejic / Yang indices.  Every argument check comes before the first HIP call.
-static int check_fusion_structure(int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: empty tensor (B=%d H=%d W=%d)", B, H, W);
-    if (!fusion_structure_shape_ok(B, H, W))
-        return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: B=%d H=%d W=%d exceeds the kernels' grids (H W <= 2^30, B <= 65535)", B, H, W);
-    return SWF_OK;
+    return metric_call<swf_fidelity_desc>("fusion_fidelity", "grids", nullptr, fusion_fidelity_workspace_bytes, fusion_fidelity, desc, fusion,
+                                          ir, vis, out, B, H, W, workspace, workspace_bytes, stream);
 }
 
 size_t swf_fusion_structure_workspace_bytes(int32_t B, int32_t H, int32_t W) {
-    if (check_fusion_structure(B, H, W) != SWF_OK) return 0;
-    return fusion_structure_workspace_bytes(B, H, W);
+    return check_metric_shape("fusion_structure", "grids", B, H, W) == SWF_OK ? fusion_structure_workspace_bytes(B, H, W) : 0;
+}
+
+static int check_structure_desc(const swf_structure_desc& d) {
+    if (!std::isfinite(d.K1) || !std::isfinite(d.K2) || !std::isfinite(d.alpha) || !std::isfinite(d.Ty) || d.K1 <= 0.0 || d.K2 <= 0.0 ||
+        d.alpha < 0.0)
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: constants K1=%g K2=%g alpha=%g Ty=%g (finite, K1 > 0, K2 > 0, alpha >= 0)", d.K1,
+                    d.K2, d.alpha, d.Ty);
+    return SWF_OK;
 }
 
 int swf_fusion_structure(const swf_structure_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
                          int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_structure: NULL descriptor, image or output");
-    SWF_TRY(check_fusion_structure(B, H, W));
-    if (!std::isfinite(desc->K1) || !std::isfinite(desc->K2) || !std::isfinite(desc->alpha) || !std::isfinite(desc->Ty) ||
-        desc->K1 <= 0.0 || desc->K2 <= 0.0 || desc->alpha < 0.0)
-        return fail(SWF_ERR_BAD_SHAPE, "fusion_structure: constants K1=%g K2=%g alpha=%g Ty=%g (finite, K1 > 0, K2 > 0, alpha >= 0)",
-                    desc->K1, desc->K2, desc->alpha, desc->Ty);
-    const size_t need = fusion_structure_workspace_bytes(B, H, W);   // 0 under 7 pixels in an axis: no window, nothing to carve
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(SWF_ERR_WORKSPACE, "fusion_structure: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return fusion_structure(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+    return metric_call<swf_structure_desc>("fusion_structure", "grids", check_structure_desc, fusion_structure_workspace_bytes,
+                                           fusion_structure, desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, stream);
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

@@ -23,7 +23,7 @@ thing: the training loss's kornia-style SSIM on unit-range floats, returned as a
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 from torch import Tensor
@@ -60,60 +60,57 @@ def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
                            "detached tensors")
 
 
-def _desc(qabf_constants: dict) -> L.MetricsDesc:
-    unknown = set(qabf_constants) - set(QABF_DEFAULTS)
+class _Family(NamedTuple):
+    names: Tuple[str, ...]
+    defaults: dict
+    desc: type      # the ctypes descriptor; its fields are the defaults, in their order
+    count: int
+    call: str       # the library entry; its size query is `call + "_workspace_bytes"`
+    constant: str   # what the unknown-constant message calls a constant
+
+
+_FAMILIES = {
+    "metrics": _Family(METRIC_NAMES, QABF_DEFAULTS, L.MetricsDesc, L.METRIC_COUNT, "swf_fusion_metrics", "Qabf constant(s)"),
+    "fidelity": _Family(FIDELITY_NAMES, FIDELITY_DEFAULTS, L.FidelityDesc, L.FIDELITY_COUNT, "swf_fusion_fidelity", "constant(s)"),
+    "structure": _Family(STRUCTURE_NAMES, STRUCTURE_DEFAULTS, L.StructureDesc, L.STRUCTURE_COUNT, "swf_fusion_structure", "constant(s)"),
+}
+
+
+def _desc(kind: str, constants: dict):
+    fam = _FAMILIES[kind]
+    unknown = set(constants) - set(fam.defaults)
     if unknown:
-        raise TypeError(f"fusion_metrics: unknown Qabf constant(s) {sorted(unknown)}; the constants are {list(QABF_DEFAULTS)}")
-    c = {**QABF_DEFAULTS, **qabf_constants}
-    return L.MetricsDesc(*(float(c[k]) for k in QABF_DEFAULTS))
+        raise TypeError(f"fusion_{kind}: unknown {fam.constant} {sorted(unknown)}; the constants are {list(fam.defaults)}")
+    c = {**fam.defaults, **constants}
+    return fam.desc(*(float(c[k]) for k in fam.defaults))
+
+
+def _call(kind: str, fusion: Tensor, ir: Tensor, vis: Tensor, constants: dict) -> Tensor:
+    fam = _FAMILIES[kind]
+    desc = _desc(kind, constants)
+    _check_images(fusion, ir, vis)
+    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
+    b, _, h, w = f.shape
+    lib = L.lib()
+    need = getattr(lib, fam.call + "_workspace_bytes")(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
+    out = torch.empty((b, fam.count), dtype=torch.float64, device=f.device)
+    ws, wsn = _workspace(need, f.device)
+    L.check(getattr(lib, fam.call)(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
+    return out
 
 
 def fusion_metrics(fusion: Tensor, ir: Tensor, vis: Tensor, **qabf_constants) -> Tensor:
     """-> (B, 10) float64 tensor on the inputs' device, row b = the METRIC_NAMES values of image b.  Inputs: (B, 1, H, W) fp32 CUDA
     tensors of one shape.  Keyword arguments replace Qabf constants (Tg, kg, Dg, Ta, ka, Da).  One library call on the current stream,
     no host synchronisation; bit-identical from call to call."""
-    desc = _desc(qabf_constants)
-    _check_images(fusion, ir, vis)
-    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
-    b, _, h, w = f.shape
-    lib = L.lib()
-    need = lib.swf_fusion_metrics_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
-    out = torch.empty((b, L.METRIC_COUNT), dtype=torch.float64, device=f.device)
-    ws, wsn = _workspace(need, f.device)
-    L.check(lib.swf_fusion_metrics(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
-    return out
-
-
-def _fidelity_desc(constants: dict) -> L.FidelityDesc:
-    unknown = set(constants) - set(FIDELITY_DEFAULTS)
-    if unknown:
-        raise TypeError(f"fusion_fidelity: unknown constant(s) {sorted(unknown)}; the constants are {list(FIDELITY_DEFAULTS)}")
-    c = {**FIDELITY_DEFAULTS, **constants}
-    return L.FidelityDesc(*(float(c[k]) for k in FIDELITY_DEFAULTS))
+    return _call("metrics", fusion, ir, vis, qabf_constants)
 
 
 def fusion_fidelity(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
     """-> (B, 5) float64 tensor on the inputs' device, row b = the FIDELITY_NAMES values of image b: VIF = VIF_IR + VIF_VIS, Nabf and
     Labf.  Inputs as for fusion_metrics.  Keyword arguments replace constants (FIDELITY_DEFAULTS).  One library call on the current
     stream, no host synchronisation; bit-identical from call to call."""
-    desc = _fidelity_desc(constants)
-    _check_images(fusion, ir, vis)
-    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
-    b, _, h, w = f.shape
-    lib = L.lib()
-    need = lib.swf_fusion_fidelity_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
-    out = torch.empty((b, L.FIDELITY_COUNT), dtype=torch.float64, device=f.device)
-    ws, wsn = _workspace(need, f.device)
-    L.check(lib.swf_fusion_fidelity(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
-    return out
-
-
-def _structure_desc(constants: dict) -> L.StructureDesc:
-    unknown = set(constants) - set(STRUCTURE_DEFAULTS)
-    if unknown:
-        raise TypeError(f"fusion_structure: unknown constant(s) {sorted(unknown)}; the constants are {list(STRUCTURE_DEFAULTS)}")
-    c = {**STRUCTURE_DEFAULTS, **constants}
-    return L.StructureDesc(*(float(c[k]) for k in STRUCTURE_DEFAULTS))
+    return _call("fidelity", fusion, ir, vis, constants)
 
 
 def fusion_structure(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
@@ -121,16 +118,7 @@ def fusion_structure(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Te
     MS_SSIM, Piella's Qs, Qw, Qe, Cvejic's Qc and Yang's Qy.  Inputs as for fusion_metrics.  Keyword arguments replace constants
     (STRUCTURE_DEFAULTS); a non-finite one, K1 <= 0, K2 <= 0 or alpha < 0 raises ValueError.  One library call on the current stream,
     no host synchronisation; bit-identical from call to call."""
-    desc = _structure_desc(constants)
-    _check_images(fusion, ir, vis)
-    f, i, v = fusion.detach().contiguous(), ir.detach().contiguous(), vis.detach().contiguous()
-    b, _, h, w = f.shape
-    lib = L.lib()
-    need = lib.swf_fusion_structure_workspace_bytes(b, h, w)   # 0 for a shape the call refuses: it then raises with the library's text
-    out = torch.empty((b, L.STRUCTURE_COUNT), dtype=torch.float64, device=f.device)
-    ws, wsn = _workspace(need, f.device)
-    L.check(lib.swf_fusion_structure(C.byref(desc), _ptr(f), _ptr(i), _ptr(v), out.data_ptr(), b, h, w, ws, wsn, _stream(f.device)))
-    return out
+    return _call("structure", fusion, ir, vis, constants)
 
 
 class FusionMetrics:
@@ -142,15 +130,17 @@ class FusionMetrics:
 
     def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, structure: bool = False,
                  structure_constants: Optional[dict] = None, **qabf_constants):
-        _desc(qabf_constants)   # refuse a misspelt constant here, not at the first batch
-        _fidelity_desc(fidelity_constants or {})
-        _structure_desc(structure_constants or {})
         self.qabf_constants = qabf_constants
         self.fidelity = bool(fidelity)
         self.fidelity_constants = dict(fidelity_constants or {})
         self.structure = bool(structure)
         self.structure_constants = dict(structure_constants or {})
-        self.names = METRIC_NAMES + (FIDELITY_NAMES if self.fidelity else ()) + (STRUCTURE_NAMES if self.structure else ())
+        families = (("metrics", True, self.qabf_constants), ("fidelity", self.fidelity, self.fidelity_constants),
+                    ("structure", self.structure, self.structure_constants))
+        for kind, _, constants in families:
+            _desc(kind, constants)   # refuse a misspelt constant here, not at the first batch, of a family that is off too
+        self._families = [(kind, constants) for kind, on, constants in families if on]
+        self.names = sum((_FAMILIES[kind].names for kind, _ in self._families), ())
         self.reset()
 
     def reset(self) -> None:
@@ -159,11 +149,8 @@ class FusionMetrics:
 
     def update(self, fusion: Tensor, ir: Tensor, vis: Tensor) -> Tensor:
         """Adds the batch's rows; -> the rows, (B, len(names)) float64 on the device."""
-        rows = fusion_metrics(fusion, ir, vis, **self.qabf_constants)
-        if self.fidelity:
-            rows = torch.cat([rows, fusion_fidelity(fusion, ir, vis, **self.fidelity_constants)], dim=1)
-        if self.structure:
-            rows = torch.cat([rows, fusion_structure(fusion, ir, vis, **self.structure_constants)], dim=1)
+        parts = [globals()["fusion_" + kind](fusion, ir, vis, **c) for kind, c in self._families]   # the public functions, as bound now
+        rows = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
         s = rows.sum(dim=0)
         self._sum = s if self._sum is None else self._sum + s
         self.count += rows.shape[0]
