@@ -753,6 +753,49 @@ int swf_fusion_structure(const swf_structure_desc* desc, const float* fusion, co
                          double* out /* device [B][SWF_STRUCTURE_COUNT] */, int32_t B, int32_t H, int32_t W,
                          void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- the human-perception group: Q_CB, Q_CV, and CE, EI, RMSE, five values per image in one call ----------------------------------
+ * With the calls above this covers VIFB's thirteen as well (AG, CE, EI, EN, MI, PSNR, Qabf, Q_CB, Q_CV, RMSE, SF, SSIM, SD).  Restated
+ * from the published definitions (Chen and Blum 2009; Chen and Varshney 2007; Liu et al.'s assessment of fusion metrics) and the open
+ * MATLAB evaluators; none of them is available to this build: PARITY WITH ANY OF THEM IS UNPINNED.  These definitions are this project's.
+ * Levels.  F, A, B = the level images of fusion, ir, vis of the metrics above (the same quantiser: fp32, two roundings, never one
+ * fused multiply-add, NaN -> 0), N = H W.
+ *   stretch(X)   rint((255 (X - min X)) / (max X - min X)); a flat image becomes all zeros
+ *   s(j, n)      j if j < ceil(n / 2), else j - n: freqspace with fftshift, written without the shift
+ *   spec(X, G)   Re(IDFT2(DFT2(X) o G)), G evaluated at bin (u, v) from rho = sqrt(s(u, H)^2 + s(v, W)^2)
+ *   QCB    Chen and Blum.  r = rho / 15, S = exp(-(r / f0)^2) - a exp(-(r / f1)^2).  For each X of A, B, F: X' = spec(stretch(X), S);
+ *          b1, b2 = X' filtered with zero padding and 'same' size by the 31x31 kernels exp(-(x^2 + y^2) / (2 sd^2)) / (2 pi sd^2),
+ *          x, y = -15 .. 15, sd = 2 for b1 and 4 for b2 (separable; not normalised to sum 1); C = |b1 / b2 - 1|, 0 where b2 = 0;
+ *          C' = C^p / (C^q + Z).  Q_XF = min(C'_X, C'_F) / max(C'_X, C'_F), 1 where both are 0; lambda_A = C'_A^2 / (C'_A^2 + C'_B^2),
+ *          1/2 where the denominator is 0; QCB = mean(lambda_A Q_AF + (1 - lambda_A) Q_BF).
+ *   QCV    Chen and Varshney; LOWER IS BETTER.  On sA, sB, sF = stretch(A), stretch(B), stretch(F): G_X = sqrt(sx^2 + sy^2), the Sobel
+ *          responses of the QABF section (its masks, its zero border) of sA and sB; 16x16 blocks tiling from the top-left, partial
+ *          blocks kept; lambda_X(block) = sum of G_X^alpha over the block's pixels inside the image;
+ *          theta = 2.6 (0.0192 + 0.144 r) exp(-(0.144 r)^1.1), r = rho / 4 (Mannos and Sakrison); D_X(block) = the sum of
+ *          spec(sX - sF, theta)^2 over those pixels, divided by 256 always (a partial block is zero-padded);
+ *          QCV = sum(lambda_A D_A + lambda_B D_B) / sum(lambda_A + lambda_B) over the blocks, 0 when that denominator is 0.
+ *   CE     (ce(A, F) + ce(B, F)) / 2, ce(X, F) = sum_k p_X(k) log2(p_X(k) / p_F(k)) over the bins of the 256-bin histograms where both
+ *          are non-zero
+ *   EI     mean over the N pixels of sqrt(gv^2 + gh^2), the unnormalised Sobel sums of F of the NABF section (its replicated border)
+ *   RMSE   (sqrt(sum (A - F)^2 / N) + sqrt(sum (B - F)^2 / N)) / (2 255): on levels / 255
+ * Usual constants: f0 15.3870, f1 1.3456, a 0.7622, p 3, q 2, Z 1e-4, alpha 1.
+ * Arithmetic.  fp64 throughout after the quantiser.  spec runs as dense fp64 products on the matrix cores against twiddle matrices
+ * exp(-+2 pi i ((j k) mod n) / n) that the call itself builds in its workspace (arguments reduced in integers), over the half
+ * spectrum a real image and a real, even filter need.  Histograms are counted without atomics; sums go through per-tile partials added
+ * in a fixed order; one finishing workgroup per image: results are bit-identical from call to call, and an image's row does not
+ * depend on the rest of its batch.  f0, f1, a, p, q, Z reach QCB only and alpha QCV only. */
+typedef struct swf_perception_desc { double f0, f1, a, p, q, Z, alpha; } swf_perception_desc;   /* defaults 15.3870, 1.3456, 0.7622, 3, 2, 1e-4, 1 */
+enum { SWF_PERCEPTION_QCB, SWF_PERCEPTION_QCV, SWF_PERCEPTION_CE, SWF_PERCEPTION_EI, SWF_PERCEPTION_RMSE, SWF_PERCEPTION_COUNT };
+/* 0 for a shape swf_fusion_perception would refuse */
+size_t swf_fusion_perception_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_PERCEPTION_COUNT], one row per image.  The call writes every workspace
+ * element it reads, allocates nothing and does not synchronise the host, so it can be captured into a hipGraph on one stream.
+ * SWF_ERR_BAD_SHAPE for B, H or W <= 0, and for a non-finite constant, f0 <= 0, f1 <= 0, Z <= 0, p < 0, q < 0 or alpha < 0;
+ * SWF_ERR_UNSUPPORTED for H or W > 16384 or B > 13107 (the int32 indices of the dense transforms; the work grows as H W (H + W));
+ * all before anything is launched. */
+int swf_fusion_perception(const swf_perception_desc* desc, const float* fusion, const float* ir, const float* vis,
+                          double* out /* device [B][SWF_PERCEPTION_COUNT] */, int32_t B, int32_t H, int32_t W,
+                          void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);
  * v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps), IEEE sqrt and division, no atomics.

@@ -131,6 +131,13 @@ class StructureDesc(C.Structure):   # swf_structure_desc: the SSIM constants K1,
 STRUCTURE_COUNT = 9   # SWF_STRUCTURE_COUNT
 
 
+class PerceptionDesc(C.Structure):   # swf_perception_desc: Q_CB's filter (f0, f1, a) and contrast map (p, q, Z), Q_CV's saliency exponent alpha
+    _fields_ = [(n, C.c_double) for n in ("f0", "f1", "a", "p", "q", "Z", "alpha")]
+
+
+PERCEPTION_COUNT = 5   # SWF_PERCEPTION_COUNT
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -259,6 +266,8 @@ SIGNATURES = {
     "swf_fusion_fidelity": (C.c_int, [P(FidelityDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_fusion_structure_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "swf_fusion_structure": (C.c_int, [P(StructureDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_perception_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_perception": (C.c_int, [P(PerceptionDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

@@ -15,6 +15,7 @@
 #include "kernels_loss.h"
 #include "kernels_fidelity.h"
 #include "kernels_structure.h"
+#include "kernels_perception.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2330,6 +2331,40 @@ int swf_fusion_structure(const swf_structure_desc* desc, const float* fusion, co
                          int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     return metric_call<swf_structure_desc>("fusion_structure", "grids", check_structure_desc, fusion_structure_workspace_bytes,
                                            fusion_structure, desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, stream);
+}
+
+// The perception call's shape check: its transforms are dense, so what it holds is narrower than the other calls' and is its own status.
+static int check_perception_shape(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_perception: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!perception_shape_ok(B, H, W))
+        return fail(SWF_ERR_UNSUPPORTED, "fusion_perception: B=%d H=%d W=%d exceeds the int32 indices of the dense transforms "
+                    "(H, W <= 16384, B <= 13107)", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_perception_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    return check_perception_shape(B, H, W) == SWF_OK ? fusion_perception_workspace_bytes(B, H, W) : 0;
+}
+
+static int check_perception_desc(const swf_perception_desc& d) {
+    const double v[7] = {d.f0, d.f1, d.a, d.p, d.q, d.Z, d.alpha};
+    bool ok = d.f0 > 0.0 && d.f1 > 0.0 && d.Z > 0.0 && d.p >= 0.0 && d.q >= 0.0 && d.alpha >= 0.0;
+    for (double x : v) ok = ok && std::isfinite(x);
+    if (!ok)
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_perception: constants f0=%g f1=%g a=%g p=%g q=%g Z=%g alpha=%g (finite, f0 > 0, f1 > 0, "
+                    "Z > 0, p >= 0, q >= 0, alpha >= 0)", d.f0, d.f1, d.a, d.p, d.q, d.Z, d.alpha);
+    return SWF_OK;
+}
+
+int swf_fusion_perception(const swf_perception_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
+                          int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_perception: NULL descriptor, image or output");
+    SWF_TRY(check_perception_shape(B, H, W));
+    SWF_TRY(check_perception_desc(*desc));
+    const size_t need = fusion_perception_workspace_bytes(B, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "fusion_perception: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return fusion_perception(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

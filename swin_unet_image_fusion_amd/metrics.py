@@ -16,6 +16,26 @@ The structural-similarity group comes from a third fused HIP call on the same le
 and Q_E, Cvejic's Q_C and Yang's Q_Y on exact integer window sums.  SSIM is 0 for an image under 11 pixels in an axis, MS-SSIM under
 176, the Piella / Cvejic values under 8 and Yang's under 7.
 
+The human-perception group comes from a fourth fused HIP call on the same levels, fp64 throughout (swf_fusion_perception:
+`fusion_perception`, or `FusionMetrics(perception=True)`; with the three switches on, all 29 values, which cover VIFB's thirteen as well).
+With A = ir, B = vis, F = fusion; stretch(X) = rint((255 (X - min X)) / (max X - min X)), a flat image becoming all zeros; s(j, n) = j if
+j < ceil(n / 2) else j - n; spec(X, G) = Re(IDFT2(DFT2(X) o G)), G evaluated at bin (u, v) from rho = sqrt(s(u, H)^2 + s(v, W)^2):
+  Qcb   Chen & Blum.  S = exp(-(r / f0)^2) - a exp(-(r / f1)^2), r = rho / 15.  For each X of A, B, F: X' = spec(stretch(X), S); b1, b2 =
+        X' filtered with zero padding and 'same' size by the 31x31 kernels exp(-(x^2 + y^2) / (2 sd^2)) / (2 pi sd^2), x, y = -15 .. 15,
+        sd = 2 and 4; C = |b1 / b2 - 1|, 0 where b2 = 0; C' = C^p / (C^q + Z).  Q_XF = min(C'_X, C'_F) / max(C'_X, C'_F), 1 where both
+        are 0; lambda_A = C'_A^2 / (C'_A^2 + C'_B^2), 1/2 where the denominator is 0; Qcb = mean(lambda_A Q_AF + (1 - lambda_A) Q_BF).
+  Qcv   Chen & Varshney, LOWER IS BETTER.  On stretch(A), stretch(B), stretch(F): G_X = the Sobel magnitude sqrt(gx^2 + gy^2) of the
+        stretched A and B under a zero border; 16x16 blocks tiling from the top-left, partial blocks kept and zero-padded;
+        lambda_X(block) = sum of G_X^alpha over the block's pixels inside the image; theta = 2.6 (0.0192 + 0.144 r) exp(-(0.144 r)^1.1),
+        r = rho / 4 (Mannos-Sakrison); D_X(block) = sum of spec(X - F, theta)^2 over the block / 256;
+        Qcv = sum(lambda_A D_A + lambda_B D_B) / sum(lambda_A + lambda_B), 0 where that sum is 0.
+  CE    (ce(A, F) + ce(B, F)) / 2, ce(X, F) = sum_k p_X(k) log2(p_X(k) / p_F(k)) over the bins of the 256-bin histograms where both
+        are non-zero.
+  EI    the mean over pixels of the Sobel magnitude of F's levels with replicated borders.
+  RMSE  (sqrt(mean((A - F)^2)) + sqrt(mean((B - F)^2))) / 2 on levels / 255.
+So F = A = B gives Qcb = 1, Qcv = 0, CE = 0, RMSE = 0; three flat images 1, 0, 0, 0; a flat vis with F = ir gives Qcb = 1.  The filtering
+is dense (fp64 DFT products on the matrix cores against twiddle matrices the call builds), for any H and W up to 16384.
+
 The definitions are restated from the published ones and the common open evaluators; no MATLAB, VIFB or sewar copy is available to
 this build, so parity with any of them is unpinned.  `MyLoss(choose_ms_ssim=False).calcu_ssim_loss` is a different
 thing: the training loss's kornia-style SSIM on unit-range floats, returned as a loss; SSIM as a metric on levels is `fusion_structure`'s.
@@ -31,8 +51,8 @@ from torch import Tensor
 from . import _lib as L
 from .modules import _ptr, _stream, _workspace
 
-__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "STRUCTURE_NAMES", "STRUCTURE_DEFAULTS", "fusion_metrics",
-           "fusion_fidelity", "fusion_structure", "FusionMetrics"]
+__all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "STRUCTURE_NAMES", "STRUCTURE_DEFAULTS", "PERCEPTION_NAMES",
+           "PERCEPTION_DEFAULTS", "fusion_metrics", "fusion_fidelity", "fusion_structure", "fusion_perception", "FusionMetrics"]
 
 METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
 QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
@@ -41,6 +61,9 @@ FIDELITY_DEFAULTS = {"sigma_nsq": 2.0, "eps": 1e-10,                            
                      "Td": 2.0, "wt_min": 0.001, "Nrg": 0.9999, "kg": 19.0, "sg": 0.5, "Nra": 0.9995, "ka": 22.0, "sa": 0.5}   # Kumar
 STRUCTURE_NAMES = ("SSIM", "SSIM_IR", "SSIM_VIS", "MS_SSIM", "Qs", "Qw", "Qe", "Qc", "Qy")   # the order of the header's SWF_STRUCTURE_* enum
 STRUCTURE_DEFAULTS = {"K1": 0.01, "K2": 0.03, "alpha": 1.0, "Ty": 0.75}   # Wang's SSIM constants, Piella's edge exponent, Yang's threshold
+PERCEPTION_NAMES = ("Qcb", "Qcv", "CE", "EI", "RMSE")                                # the order of the header's SWF_PERCEPTION_* enum
+PERCEPTION_DEFAULTS = {"f0": 15.3870, "f1": 1.3456, "a": 0.7622, "p": 3.0, "q": 2.0, "Z": 1e-4,   # Chen & Blum's filter and contrast map
+                       "alpha": 1.0}                                                              # Chen & Varshney's saliency exponent
 
 
 def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
@@ -73,6 +96,7 @@ _FAMILIES = {
     "metrics": _Family(METRIC_NAMES, QABF_DEFAULTS, L.MetricsDesc, L.METRIC_COUNT, "swf_fusion_metrics", "Qabf constant(s)"),
     "fidelity": _Family(FIDELITY_NAMES, FIDELITY_DEFAULTS, L.FidelityDesc, L.FIDELITY_COUNT, "swf_fusion_fidelity", "constant(s)"),
     "structure": _Family(STRUCTURE_NAMES, STRUCTURE_DEFAULTS, L.StructureDesc, L.STRUCTURE_COUNT, "swf_fusion_structure", "constant(s)"),
+    "perception": _Family(PERCEPTION_NAMES, PERCEPTION_DEFAULTS, L.PerceptionDesc, L.PERCEPTION_COUNT, "swf_fusion_perception", "constant(s)"),
 }
 
 
@@ -121,22 +145,35 @@ def fusion_structure(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Te
     return _call("structure", fusion, ir, vis, constants)
 
 
+def fusion_perception(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
+    """-> (B, 5) float64 tensor on the inputs' device, row b = the PERCEPTION_NAMES values of image b: Chen & Blum's Qcb, Chen &
+    Varshney's Qcv (lower is better), CE, EI and RMSE.  Inputs as for fusion_metrics, at most 16384 pixels in an axis
+    (NotImplementedError beyond: the transforms are dense).  Keyword arguments replace constants (PERCEPTION_DEFAULTS); a non-finite
+    one, f0 <= 0, f1 <= 0, Z <= 0, p < 0, q < 0 or alpha < 0 raises ValueError.  One library call on the current stream, no host
+    synchronisation; bit-identical from call to call."""
+    return _call("perception", fusion, ir, vis, constants)
+
+
 class FusionMetrics:
     """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` the FIDELITY_NAMES values (constants:
     `fidelity_constants`) follow the ten, with `structure=True` the STRUCTURE_NAMES values (constants: `structure_constants`) follow
-    those: 10, 15, 19 or 24 values.  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
+    those, with `perception=True` the PERCEPTION_NAMES values (constants: `perception_constants`) follow those: 10, 15, 19 or 24
+    values without the last group, five more with it (up to 29).  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
     image count is a host int (`count`): the batch size is known on the host, so counting there needs no synchronisation and no
     device scalar."""
 
     def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, structure: bool = False,
-                 structure_constants: Optional[dict] = None, **qabf_constants):
+                 structure_constants: Optional[dict] = None, perception: bool = False, perception_constants: Optional[dict] = None,
+                 **qabf_constants):
         self.qabf_constants = qabf_constants
         self.fidelity = bool(fidelity)
         self.fidelity_constants = dict(fidelity_constants or {})
         self.structure = bool(structure)
         self.structure_constants = dict(structure_constants or {})
+        self.perception = bool(perception)
+        self.perception_constants = dict(perception_constants or {})
         families = (("metrics", True, self.qabf_constants), ("fidelity", self.fidelity, self.fidelity_constants),
-                    ("structure", self.structure, self.structure_constants))
+                    ("structure", self.structure, self.structure_constants), ("perception", self.perception, self.perception_constants))
         for kind, _, constants in families:
             _desc(kind, constants)   # refuse a misspelt constant here, not at the first batch, of a family that is off too
         self._families = [(kind, constants) for kind, on, constants in families if on]
