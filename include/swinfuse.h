@@ -446,6 +446,31 @@ int swf_final_head_batch_stats(const swf_head_params* p, const float* x, const f
                                float* running_mean, float* running_var, float momentum,
                                int32_t B, int32_t H, int32_t W, int32_t ksize,
                                void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* The same BatchNorm over a batch that is SPREAD over several calls or ranks (data-parallel training): the two entries above split at
+ * the per-channel sums, which the caller adds up (an all-reduce SUM) between the calls.  All sums live in device memory; nothing is
+ * kept in the workspace from one call to the next.  Workspace of the three entries that take one: swf_final_head_bwd's.
+ *   forward:   stats_pass(0) -> add -> stats_finish(0) writes mean;  stats_pass(1, mean) -> add -> stats_finish(1) writes var and running
+ *   backward:  bwd_sums -> add -> bwd_synced
+ * swf_final_head_stats_pass: ONE pass over this call's batch; sums_out[2] <- sum of t (pass 0) or of (t - mean)^2 (pass 1, mean[2] from
+ * the caller), t = conv1(cat(x, y)). */
+int swf_final_head_stats_pass(const swf_head_params* p, const float* x, const float* y, int32_t pass, const float* mean, float* sums_out,
+                              int32_t B, int32_t H, int32_t W, int32_t ksize,
+                              void* workspace, size_t workspace_bytes, swf_stream_t stream);
+/* sums[2] over a batch of `count` elements per channel in all (sums_bytes: the size of that buffer, at least 8; SWF_ERR_WORKSPACE
+ * otherwise): pass 0 writes mean = sums / count; pass 1 writes the biased var = sums / count and, where non-NULL, moves the running
+ * statistics by `momentum` towards mean[2] and the unbiased variance sums / (count - 1), as swf_final_head_batch_stats does. */
+int swf_final_head_stats_finish(const float* sums, size_t sums_bytes, int64_t count, int32_t pass, float* mean, float* var,
+                                float* running_mean, float* running_var, float momentum, swf_stream_t stream);
+/* The two halves of swf_final_head_bwd with batch_stats != 0.  bwd_sums: sums_out[4] <- sum of dt2 xhat [2], sum of dt2 [2] over this
+ * call's batch (p->bn_mean / bn_var: the statistics of the WHOLE batch).  bwd_synced: the backward with the normalisation's gradient
+ * formed from sums[4] (device) of the whole batch and its `count` elements per channel; gx, gy and the parameter gradients are this
+ * call's batch's. */
+int swf_final_head_bwd_sums(const swf_head_params* p, const float* x, const float* y, const float* gout, float* sums_out,
+                            int32_t B, int32_t H, int32_t W, int32_t ksize,
+                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_final_head_bwd_synced(const swf_head_params* p, const float* x, const float* y, const float* gout, const float* sums, int64_t count,
+                              float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize,
+                              void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- training side, second stage: patch layers, padding, skip add ------------------------------------------------------------ */
 /* Backward of one stream of PatchMergingAndLinearLayer (a011:244-264) as the module runs it (no padding inside: MyPadding is its own
@@ -834,6 +859,20 @@ int swf_adam_grad_norm(double max_grad_norm, const void* table_pinned_host, void
  * by the update; may be NULL when clipping is off.  The gradients themselves are never written. */
 int swf_adam_step(const swf_adam_desc* desc, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
                   float* norm_out_device, swf_stream_t stream);
+
+/* ---- gather / scatter of a tensor list in one launch (the gradient all-reduce of data-parallel training) ---------------------------
+ * n_tensors contiguous fp32 tensors <-> consecutive, UNPADDED segments of one flat fp32 buffer, in the table's order.  The table is the
+ * optimiser's (swf_adam_table_bytes / swf_adam_table_fill, uploaded the same way): a row's `grad` is the SOURCE of its elements and its
+ * `param` their DESTINATION; exp_avg / exp_avg_sq are not read.  One workgroup per 4096-element chunk, 16-byte stores between the
+ * destination's 16-byte boundaries (segment offsets are not aligned), no atomics, no synchronisation, no read-back: capturable.
+ * swf_tensors_gather: row i has param = flat + (numel of the rows before it); flat segment <- grad[i] * scale, each product rounded once,
+ * so flat is bit for bit scale * cat(tensors).  A row whose grad is NULL (set it after swf_adam_table_fill) fills its segment with zeros.
+ * swf_tensors_scatter: row i has grad = flat + (numel of the rows before it); param[i] <- that segment, unscaled.
+ * Both check, before the upload, that the rows address exactly those segments and that they end within flat_elems. */
+int swf_tensors_gather(const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors, float* flat,
+                       int64_t flat_elems, float scale, swf_stream_t stream);
+int swf_tensors_scatter(const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors, const float* flat,
+                        int64_t flat_elems, swf_stream_t stream);
 
 /* ---- misc ------------------------------------------------------------------------------------ */
 int swf_version(void);                     /* major*1000 + minor */

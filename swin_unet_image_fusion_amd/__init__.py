@@ -14,6 +14,7 @@ from .modules import (AddAndLayerNormWithOtherModule, AutoPathMLP, AutoPathWinAt
                       StateRecorder, WindowAttention, get_encoder_or_decoder_block)
 
 from .optim import FusedAdam  # noqa: F401
+from .parallel import DataParallelStep, TorchCollective  # noqa: F401
 from .training import fractional_epoch, load_training_state, save_training_state, train_step, validate  # noqa: F401
 
 __version__ = "0.1.0"

@@ -272,6 +272,12 @@ SIGNATURES = {
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),
     "swf_adam_step": (C.c_int, [P(AdamDesc), _vp, _vp, _sz, _i32, _vp, _vp]),
+    "swf_tensors_gather": (C.c_int, [_vp, _vp, _sz, _i32, _vp, _i64, C.c_float, _vp]),
+    "swf_tensors_scatter": (C.c_int, [_vp, _vp, _sz, _i32, _vp, _i64, _vp]),
+    "swf_final_head_stats_pass": (C.c_int, [P(HeadParams), _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_final_head_stats_finish": (C.c_int, [_vp, _sz, _i64, _i32, _vp, _vp, _vp, _vp, C.c_float, _vp]),
+    "swf_final_head_bwd_sums": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_final_head_bwd_synced": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _i64, _vp, _vp, P(HeadGrads), _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

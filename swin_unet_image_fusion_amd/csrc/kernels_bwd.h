@@ -75,5 +75,17 @@ int head_bwd(const swf_head_params& p, const float* x, const float* y, const flo
 // batch mean / biased variance of conv1's two output channels (BatchNorm2d in training mode, a013:133) + the running-statistics update
 int head_batch_stats(const swf_head_params& p, const float* x, const float* y, float* mean, float* var, float* running_mean, float* running_var,
                      float momentum, int B, int H, int W, int ks, void* workspace, size_t workspace_bytes, hipStream_t stream);
+// The same over a batch that is spread over several calls (or ranks): one pass stopped at its two per-channel sums (device), and the
+// finish over sums the caller has added up, with the element count of the whole batch.
+int head_stats_pass(const swf_head_params& p, const float* x, const float* y, int pass, const float* mean, float* sums_out, int B, int H, int W,
+                    int ks, void* workspace, size_t workspace_bytes, hipStream_t stream);
+int head_stats_finish(const float* sums, int64_t count, int pass, float* mean, float* var, float* running_mean, float* running_var,
+                      float momentum, hipStream_t stream);
+// head_bwd with batch statistics in two phases: the four sums (dt2 xhat [2], dt2 [2]) of this call's batch -> sums_out (device); then the
+// backward proper with k1, k2 from the sums of the whole batch (device) over n_global elements per channel.  No state is kept between them.
+int head_bwd_sums(const swf_head_params& p, const float* x, const float* y, const float* gout, float* sums_out, int B, int H, int W, int ks,
+                  void* workspace, size_t workspace_bytes, hipStream_t stream);
+int head_bwd_apply(const swf_head_params& p, const float* x, const float* y, const float* gout, const float* sums, int64_t n_global, float* gx,
+                   float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 }  // namespace swf

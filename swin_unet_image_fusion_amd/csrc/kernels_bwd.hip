@@ -1413,8 +1413,59 @@ int head_batch_stats(const swf_head_params& p, const float* x, const float* y, f
     return SWF_OK;
 }
 
+// One pass of the statistics over THIS call's batch, stopped where the sums exist: sums[2] <- sum of t1 (pass 0) or of (t1 - mean)^2
+// (pass 1) per channel.  The caller adds the sums of every part of the batch and finishes with head_stats_finish.
+int head_stats_pass(const swf_head_params& p, const float* x, const float* y, int pass, const float* mean, float* sums_out, int B, int H, int W,
+                    int ks, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    if (ks < 1 || ks % 2 == 0 || ks / 2 >= H || ks / 2 >= W) return fail(SWF_ERR_PAD, "head statistics: kernel %d on a %dx%d map", ks, H, W);
+    const int64_t n = (int64_t)B * H * W;
+    Carver ws(workspace, workspace_bytes);
+    const HeadBufs bufs = carve_head(ws, n, ks, false);
+    if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "head statistics workspace too small (need %zu B)", ws.bytes());
+    const unsigned blocks = (unsigned)cdiv64(n, 256);
+    const int ch = chunks_of(n);
+    float* sums = bufs.part + tree_rows(ch) * 2;
+    hipLaunchKernelGGL(head_t1_kernel, dim3(blocks), dim3(256), 0, st, x, y, bufs.t1, p, B, H, W, ks);
+    SWF_TRY(check_launch("head_t1"));
+    hipLaunchKernelGGL(head_stat_rows_kernel, dim3(blocks), dim3(256), 0, st, bufs.t1, mean, bufs.rows, pass, n);
+    SWF_TRY(check_launch("head stat rows"));
+    SWF_TRY(colsum(bufs.rows, bufs.part, n, 2, st));
+    SWF_TRY(reduce_rows(bufs.part, sums, 2, ch, st));
+    if (hipMemcpyAsync(sums_out, sums, 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(SWF_ERR_HIP, "head statistics: copy failed");
+    return SWF_OK;
+}
+
+// head_stat_finish_kernel over sums of a batch of `count` elements per channel in all
+int head_stats_finish(const float* sums, int64_t count, int pass, float* mean, float* var, float* running_mean, float* running_var,
+                      float momentum, hipStream_t st) {
+    hipLaunchKernelGGL(head_stat_finish_kernel, dim3(1), dim3(64), 0, st, sums, mean, var, running_mean, running_var, momentum, pass, (float)count);
+    return check_launch("head stat finish");
+}
+
+// phase 0: the whole backward over this call's batch (swf_final_head_bwd).
+// phase 1: stop at the four sums of the training-mode BatchNorm backward and leave them in sums_io (device) for the caller to add up.
+// phase 2: the whole backward with k1, k2 formed from sums_io (device, the sums of the WHOLE batch) and n_global elements per channel;
+//          t1 and dt2 are computed again, nothing is kept from phase 1.
+static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf_head_params& p, const float* x, const float* y,
+                          const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, int batch_stats,
+                          void* workspace, size_t workspace_bytes, hipStream_t st);
+
 int head_bwd(const swf_head_params& p, const float* x, const float* y, const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B,
              int H, int W, int ks, int batch_stats, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return head_bwd_phase(0, nullptr, 0, p, x, y, gout, gx, gy, gp, B, H, W, ks, batch_stats, workspace, workspace_bytes, st);
+}
+int head_bwd_sums(const swf_head_params& p, const float* x, const float* y, const float* gout, float* sums_out, int B, int H, int W, int ks,
+                  void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return head_bwd_phase(1, sums_out, 0, p, x, y, gout, nullptr, nullptr, nullptr, B, H, W, ks, 1, workspace, workspace_bytes, st);
+}
+int head_bwd_apply(const swf_head_params& p, const float* x, const float* y, const float* gout, const float* sums, int64_t n_global, float* gx,
+                   float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, void* workspace, size_t workspace_bytes, hipStream_t st) {
+    return head_bwd_phase(2, const_cast<float*>(sums), n_global, p, x, y, gout, gx, gy, gp, B, H, W, ks, 1, workspace, workspace_bytes, st);
+}
+
+static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf_head_params& p, const float* x, const float* y,
+                          const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, int batch_stats,
+                          void* workspace, size_t workspace_bytes, hipStream_t st) {
     if (ks < 1 || ks % 2 == 0 || ks / 2 >= H || ks / 2 >= W) return fail(SWF_ERR_PAD, "head backward: kernel %d on a %dx%d map", ks, H, W);
     const int64_t n = (int64_t)B * H * W;
     const int nc1 = 4 * ks * ks + 6, nc2 = 2 * ks * ks + 1;
@@ -1447,7 +1498,7 @@ int head_bwd(const swf_head_params& p, const float* x, const float* y, const flo
         if (!dst) return SWF_OK;
         return hipMemcpyAsync(dst, src, (size_t)count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess ? SWF_OK : fail(SWF_ERR_HIP, "head backward: copy failed");
     };
-    if (g.conv2_w || g.conv2_b) {
+    if (phase != 1 && (g.conv2_w || g.conv2_b)) {
         hipLaunchKernelGGL(head_rows2_kernel, dim3(blocks), dim3(256), 0, st, gout, t1, rows, a[0], c[0], a[1], c[1], B, H, W, ks);
         SWF_TRY(check_launch("head rows2"));
         SWF_TRY(colsums(nc2, sums));
@@ -1456,13 +1507,17 @@ int head_bwd(const swf_head_params& p, const float* x, const float* y, const flo
     }
     float k1[2] = {0.f, 0.f}, k2[2] = {0.f, 0.f};
     if (batch_stats) {   // p.bn_mean / p.bn_var hold the BATCH statistics of this forward: the normalisation itself has a gradient
-        hipLaunchKernelGGL(head_rowsk_kernel, dim3(blocks), dim3(256), 0, st, dt2, t1, rows, hm[0], hm[1], is[0], is[1], n);
-        SWF_TRY(check_launch("head rows k"));
-        SWF_TRY(colsums(4, sums));
+        if (phase != 2) {
+            hipLaunchKernelGGL(head_rowsk_kernel, dim3(blocks), dim3(256), 0, st, dt2, t1, rows, hm[0], hm[1], is[0], is[1], n);
+            SWF_TRY(check_launch("head rows k"));
+            SWF_TRY(colsums(4, sums));
+        }
+        if (phase == 1) return copy(sums_io, sums, 4);
+        const float nk = (float)(phase == 2 ? n_global : n);   // the batch the statistics were taken over
         float hs[4];
-        if (hipMemcpyAsync(hs, sums, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        if (hipMemcpyAsync(hs, phase == 2 ? sums_io : sums, 16, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
             return fail(SWF_ERR_HIP, "head backward: reading the batch sums failed");
-        for (int i = 0; i < 2; ++i) { k2[i] = hs[i] / (float)n; k1[i] = hs[2 + i] / (float)n; }
+        for (int i = 0; i < 2; ++i) { k2[i] = hs[i] / nk; k1[i] = hs[2 + i] / nk; }
     }
     hipLaunchKernelGGL(head_rows1_kernel, dim3(blocks), dim3(256), 0, st, dt2, t1, x, y, rows, a[0], a[1], hm[0], hm[1], is[0], is[1], k1[0], k1[1],
                        k2[0], k2[1], B, H, W, ks);

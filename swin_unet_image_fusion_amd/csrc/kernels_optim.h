@@ -22,6 +22,18 @@ inline AdamLayout adam_layout(int64_t n_tensors, int64_t n_chunks) {
     return l;
 }
 
+// The device image of a table after its upload.
+struct AdamTable {
+    const swf_adam_tensor* rows;
+    const int32_t* map;
+    double* partials;
+    int n_chunks;
+};
+// ONE asynchronous copy of rows and chunk map to table_device on `stream`; shared by every entry that takes a table (the optimiser's
+// and kernels_flat's).  The host table must stay untouched until the copy has run.
+int upload_adam_table(const char* who, const void* table_host, void* table_device, int32_t n_tensors, int64_t n_chunks, hipStream_t stream,
+                      AdamTable* t);
+
 // norm_out[0] <- || all gradients ||_2, norm_out[1] <- min(1, max_norm / (norm + 1e-6)) (torch.nn.utils.clip_grad_norm_).
 int launch_gradnorm(const swf_adam_tensor* rows, const int32_t* chunk_row, int n_chunks, double* partials, float max_norm,
                     float* norm_out, hipStream_t stream);

@@ -1,7 +1,8 @@
 // Multi-tensor Adam step and global gradient norm for gfx950.
 //
 // adam_multi_kernel     one persistent grid over the chunks of every tensor of a parameter group: reads p, g, m, v and writes p, m, v
-//                       once (28 bytes per element), 16-byte accesses where the four pointers of a tensor allow them.
+//                       once (28 bytes per element), 16-byte accesses where p, m and v of a tensor allow them (the gradient may be a
+//                       4-byte-aligned view: only its loads differ, the update's bits do not).
 // gradnorm_partials_kernel / gradnorm_finish_kernel
 //                       sum of squares per chunk in fp64 (fixed chunking, fixed tree), then one block adds the partials in a fixed
 //                       order: the norm does not depend on the grid size and is bit-reproducible.  No atomics anywhere.
@@ -63,15 +64,23 @@ __global__ __launch_bounds__(kThreads) void adam_multi_kernel(const swf_adam_ten
         float* __restrict__ m = row.exp_avg + off;
         float* __restrict__ v = row.exp_avg_sq + off;
         int done = 0;   // elements handled by the 16-byte path (chunk offsets are multiples of 16 bytes: alignment is the tensor's)
-        if (aligned16(p, g, m, v)) {
+        // The gradient alone may sit at any 4-byte address (a view into a flat buffer of reduced gradients): its group of four is then
+        // four 4-byte loads, and everything after the loads is the same code, so the update does not depend on the gradient's alignment.
+        if (aligned16(p, p, m, v)) {
             const int nv = n >> 2;
+            const bool gvec = ((uintptr_t)g & 15) == 0;
             f32x4 P[kVecPerThread], G[kVecPerThread], M[kVecPerThread], V[kVecPerThread];
 #pragma unroll
             for (int j = 0; j < kVecPerThread; ++j) {
                 const int i = tid + j * kThreads;
                 if (i < nv) {
                     P[j] = ld4(p, i);
-                    G[j] = ld4(g, i);
+                    if (gvec) {
+                        G[j] = ld4(g, i);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) G[j][e] = ld1(g, 4 * i + e);
+                    }
                     M[j] = ld4(m, i);
                     V[j] = ld4(v, i);
                 }
@@ -171,6 +180,19 @@ __global__ __launch_bounds__(kThreads) void gradnorm_finish_kernel(const double*
 int stream_grid(int n_chunks) { return std::max(1, std::min(n_chunks, num_cus() * 8)); }
 
 }  // namespace
+
+int upload_adam_table(const char* who, const void* table_host, void* table_device, int32_t n_tensors, int64_t n_chunks, hipStream_t stream,
+                      AdamTable* t) {
+    const AdamLayout lay = adam_layout(n_tensors, n_chunks);
+    hipError_t e = hipMemcpyAsync(table_device, table_host, lay.copy_bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) return fail(SWF_ERR_HIP, "%s: table copy: %s", who, hipGetErrorString(e));
+    char* base = static_cast<char*>(table_device);
+    t->rows = reinterpret_cast<const swf_adam_tensor*>(base);
+    t->map = reinterpret_cast<const int32_t*>(base + lay.map_off);
+    t->partials = reinterpret_cast<double*>(base + lay.partial_off);
+    t->n_chunks = (int)n_chunks;
+    return SWF_OK;
+}
 
 int launch_gradnorm(const swf_adam_tensor* rows, const int32_t* chunk_row, int n_chunks, double* partials, float max_norm,
                     float* norm_out, hipStream_t stream) {

@@ -19,6 +19,7 @@
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
+#include "kernels_flat.h"
 #include "kernels_deep.h"
 #include "kernels_patch.h"
 #include "kernels_patchrr.h"
@@ -1610,6 +1611,46 @@ int swf_final_head_bwd(const swf_head_params* p, const float* x, const float* y,
     return head_bwd(*p, x, y, gout, gx, gy, gp, B, H, W, ksize, batch_stats, workspace, workspace_bytes, as_stream(stream));
 }
 
+// The head's BatchNorm over a batch that spans several calls or ranks: the entries above, split where the per-channel sums exist.
+int swf_final_head_stats_pass(const swf_head_params* p, const float* x, const float* y, int32_t pass, const float* mean, float* sums_out,
+                              int32_t B, int32_t H, int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!p || !p->conv1_w || !x || !y || !sums_out) return fail(SWF_ERR_NULL, "final_head_stats_pass: NULL argument");
+    if (pass != 0 && pass != 1) return fail(SWF_ERR_BAD_SHAPE, "final_head_stats_pass: pass %d is neither 0 nor 1", pass);
+    if (pass == 1 && !mean) return fail(SWF_ERR_NULL, "final_head_stats_pass: pass 1 needs the mean");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_stats_pass: empty tensor");
+    return head_stats_pass(*p, x, y, pass, mean, sums_out, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
+}
+
+int swf_final_head_stats_finish(const float* sums, size_t sums_bytes, int64_t count, int32_t pass, float* mean, float* var, float* running_mean,
+                                float* running_var, float momentum, swf_stream_t stream) {
+    if (!sums || !mean || (pass == 1 && !var)) return fail(SWF_ERR_NULL, "final_head_stats_finish: NULL argument");
+    if (pass != 0 && pass != 1) return fail(SWF_ERR_BAD_SHAPE, "final_head_stats_finish: pass %d is neither 0 nor 1", pass);
+    if (count <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_stats_finish: a batch of %lld elements", (long long)count);
+    if (sums_bytes < 2 * sizeof(float))
+        return fail(SWF_ERR_WORKSPACE, "final_head_stats_finish: sums buffer of %zu bytes, %zu needed", sums_bytes, 2 * sizeof(float));
+    return head_stats_finish(sums, count, pass, mean, var, running_mean, running_var, momentum, as_stream(stream));
+}
+
+int swf_final_head_bwd_sums(const swf_head_params* p, const float* x, const float* y, const float* gout, float* sums_out, int32_t B, int32_t H,
+                            int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!p || !p->conv1_w || !p->conv2_w || !p->bn_gamma || !p->bn_beta || !p->bn_mean || !p->bn_var || !x || !y || !gout || !sums_out)
+        return fail(SWF_ERR_NULL, "final_head_bwd_sums: NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_sums: empty tensor");
+    return head_bwd_sums(*p, x, y, gout, sums_out, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
+}
+
+int swf_final_head_bwd_synced(const swf_head_params* p, const float* x, const float* y, const float* gout, const float* sums, int64_t count,
+                              float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize, void* workspace,
+                              size_t workspace_bytes, swf_stream_t stream) {
+    if (!p || !p->conv1_w || !p->conv2_w || !p->bn_gamma || !p->bn_beta || !p->bn_mean || !p->bn_var || !x || !y || !gout || !sums || !gx || !gy)
+        return fail(SWF_ERR_NULL, "final_head_bwd_synced: NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_synced: empty tensor");
+    if (count < (int64_t)B * H * W)
+        return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_synced: a whole batch of %lld elements is smaller than this call's %lld", (long long)count,
+                    (long long)B * H * W);
+    return head_bwd_apply(*p, x, y, gout, sums, count, gx, gy, gp, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
+}
+
 int swf_add_fwd(const float* a, const float* b, float* out, int64_t count, swf_stream_t stream) {
     if (!a || !b || !out) return fail(SWF_ERR_NULL, "add: NULL tensor");
     if (count <= 0) return fail(SWF_ERR_BAD_SHAPE, "add: empty tensor");
@@ -2412,8 +2453,9 @@ int swf_adam_table_fill(void* table_host, size_t table_bytes, int32_t n_tensors,
 }
 
 // Validate a filled host table against the buffer size, -> the number of chunks.  Reads host memory only.
+// `flat` (swf_tensors_gather / _scatter): only `param`, the destination, must be set in every row; the moments are not read.
 static int check_adam_table(const char* who, const void* table_host, void* table_device, size_t table_bytes, int32_t n_tensors,
-                            int64_t* n_chunks_out) {
+                            int64_t* n_chunks_out, bool flat = false) {
     if (!table_host || !table_device) return fail(SWF_ERR_NULL, "%s: NULL table", who);
     if (n_tensors <= 0) return fail(SWF_ERR_BAD_SHAPE, "%s: %d tensors", who, n_tensors);
     if (table_bytes < (size_t)n_tensors * sizeof(swf_adam_tensor))
@@ -2422,7 +2464,7 @@ static int check_adam_table(const char* who, const void* table_host, void* table
     int64_t c = 0;
     for (int32_t i = 0; i < n_tensors; ++i) {
         const swf_adam_tensor& r = rows[i];
-        if (!r.param || !r.grad || !r.exp_avg || !r.exp_avg_sq) return fail(SWF_ERR_NULL, "%s: row %d has a NULL pointer", who, i);
+        if (!r.param || (!flat && (!r.grad || !r.exp_avg || !r.exp_avg_sq))) return fail(SWF_ERR_NULL, "%s: row %d has a NULL pointer", who, i);
         if (r.numel <= 0 || r.first_chunk != c)
             return fail(SWF_ERR_BAD_SHAPE, "%s: row %d is not what swf_adam_table_fill writes (numel %lld, first chunk %d, expected %lld)", who, i,
                         (long long)r.numel, r.first_chunk, (long long)c);
@@ -2437,25 +2479,6 @@ static int check_adam_table(const char* who, const void* table_host, void* table
             k >= rows[map[k]].first_chunk + cdiv64(rows[map[k]].numel, kAdamChunk))
             return fail(SWF_ERR_BAD_SHAPE, "%s: chunk %lld maps to row %d, which does not cover it", who, (long long)k, map[k]);
     *n_chunks_out = c;
-    return SWF_OK;
-}
-
-struct AdamTable {
-    const swf_adam_tensor* rows;
-    const int32_t* map;
-    double* partials;
-    int n_chunks;
-};
-static int upload_adam_table(const char* who, const void* table_host, void* table_device, int32_t n_tensors, int64_t n_chunks,
-                             hipStream_t stream, AdamTable* t) {
-    const AdamLayout lay = adam_layout(n_tensors, n_chunks);
-    hipError_t e = hipMemcpyAsync(table_device, table_host, lay.copy_bytes, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return fail(SWF_ERR_HIP, "%s: table copy: %s", who, hipGetErrorString(e));
-    char* base = static_cast<char*>(table_device);
-    t->rows = reinterpret_cast<const swf_adam_tensor*>(base);
-    t->map = reinterpret_cast<const int32_t*>(base + lay.map_off);
-    t->partials = reinterpret_cast<double*>(base + lay.partial_off);
-    t->n_chunks = (int)n_chunks;
     return SWF_OK;
 }
 
@@ -2485,6 +2508,40 @@ int swf_adam_step(const swf_adam_desc* desc, const void* table_pinned_host, void
     if (clip && !desc->norm_ready)
         SWF_TRY(launch_gradnorm(t.rows, t.map, t.n_chunks, t.partials, (float)desc->max_grad_norm, norm_out_device, as_stream(stream)));
     return launch_adam_multi(t.rows, t.map, t.n_chunks, *desc, clip ? norm_out_device : nullptr, as_stream(stream));
+}
+
+// Gather / scatter of a tensor list (kernels_flat.hip) over the optimiser's table.  The flat side of every row must be the unpadded
+// running-sum segment of `flat`, so nothing outside flat[0, flat_elems) is touched; all of it is checked on the host before the upload.
+static int tensors_flat(const char* who, bool gather, const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors,
+                        float* flat, int64_t flat_elems, float scale, hipStream_t stream) {
+    if (!flat) return fail(SWF_ERR_NULL, "%s: NULL flat buffer", who);
+    int64_t n_chunks = 0;
+    SWF_TRY(check_adam_table(who, table_pinned_host, table_device, table_bytes, n_tensors, &n_chunks, true));
+    const swf_adam_tensor* rows = static_cast<const swf_adam_tensor*>(table_pinned_host);
+    int64_t off = 0;
+    for (int32_t i = 0; i < n_tensors; ++i) {
+        const float* seg = gather ? rows[i].param : rows[i].grad;
+        if (!gather && !seg) return fail(SWF_ERR_NULL, "%s: row %d has no source segment", who, i);
+        if (seg != flat + off)
+            return fail(SWF_ERR_BAD_SHAPE, "%s: row %d does not address element %lld of the flat buffer (segments are consecutive and unpadded)", who, i,
+                        (long long)off);
+        off += rows[i].numel;
+    }
+    if (off > flat_elems) return fail(SWF_ERR_BAD_SHAPE, "%s: %lld elements in a flat buffer of %lld", who, (long long)off, (long long)flat_elems);
+    AdamTable t;
+    SWF_TRY(upload_adam_table(who, table_pinned_host, table_device, n_tensors, n_chunks, stream, &t));
+    return launch_tensors_copy(t.rows, t.map, t.n_chunks, scale, gather ? 1 : 0, stream);
+}
+
+int swf_tensors_gather(const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors, float* flat, int64_t flat_elems,
+                       float scale, swf_stream_t stream) {
+    return tensors_flat("tensors_gather", true, table_pinned_host, table_device, table_bytes, n_tensors, flat, flat_elems, scale, as_stream(stream));
+}
+
+int swf_tensors_scatter(const void* table_pinned_host, void* table_device, size_t table_bytes, int32_t n_tensors, const float* flat,
+                        int64_t flat_elems, swf_stream_t stream) {
+    return tensors_flat("tensors_scatter", false, table_pinned_host, table_device, table_bytes, n_tensors, const_cast<float*>(flat), flat_elems, 1.f,
+                        as_stream(stream));
 }
 
 }  // extern "C"

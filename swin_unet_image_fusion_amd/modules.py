@@ -1112,6 +1112,7 @@ class _HeadFunction(torch.autograd.Function):
         # batch statistics exactly when torch's BatchNorm2d would use them: from the BatchNorm's own mode (a frozen BatchNorm inside a
         # model in train() normalises with, and keeps, its running statistics), or always when it tracks none
         ctx.model, ctx.train = model, bool(bn.training or (bn.running_mean is None and bn.running_var is None))
+        ctx.collective, ctx.count = None, 0
         b, _, h, w = x.shape
         x, y = x.detach().contiguous(), y.detach().contiguous()
         out = torch.empty((b, 1, h, w), dtype=torch.float32, device=x.device)
@@ -1128,9 +1129,23 @@ class _HeadFunction(torch.autograd.Function):
                 bn.num_batches_tracked += 1
                 if bn.momentum is None:
                     mom = 1.0 / float(bn.num_batches_tracked)
-            L.check(lib.swf_final_head_batch_stats(C.byref(hp), _ptr(x), _ptr(y), stats.data_ptr(), stats.data_ptr() + 8,
-                                                   _ptr(bn.running_mean) if track else None,
-                                                   _ptr(bn.running_var) if track else None, mom, b, h, w, ks, ws, wsn, _stream(x.device)))
+            rm, rv = (_ptr(bn.running_mean) if track else None), (_ptr(bn.running_var) if track else None)
+            # data-parallel training (parallel.DataParallelStep, sync_head_bn): the batch spans the ranks, so each pass stops at its
+            # per-channel sums, which are added over the ranks before the finish divides by the element count of the whole batch
+            coll = getattr(model, "_head_collective", None)
+            ctx.collective = coll if coll is not None and coll.world_size > 1 else None
+            if ctx.collective is not None:
+                from .parallel import synced_batch_stats
+                st = _stream(x.device)
+                ctx.count = synced_batch_stats(
+                    ctx.collective, b * h * w, x.device,
+                    lambda k, sums: L.check(lib.swf_final_head_stats_pass(C.byref(hp), _ptr(x), _ptr(y), k, stats.data_ptr(), sums.data_ptr(),
+                                                                          b, h, w, ks, ws, wsn, st)),
+                    lambda k, sums, count: L.check(lib.swf_final_head_stats_finish(sums.data_ptr(), sums.numel() * 4, count, k, stats.data_ptr(),
+                                                                                   stats.data_ptr() + 8, rm, rv, mom, st)))
+            else:
+                L.check(lib.swf_final_head_batch_stats(C.byref(hp), _ptr(x), _ptr(y), stats.data_ptr(), stats.data_ptr() + 8, rm, rv, mom,
+                                                       b, h, w, ks, ws, wsn, _stream(x.device)))
             hp.bn_mean, hp.bn_var = stats.data_ptr(), stats.data_ptr() + 8
         ctx.save_for_backward(x, y, stats)
         L.check(lib.swf_final_head_fwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(out), b, h, w, ks, ws, wsn, _stream(x.device)))
@@ -1152,6 +1167,15 @@ class _HeadFunction(torch.autograd.Function):
             if ctx.train:
                 hp.bn_mean, hp.bn_var = stats.data_ptr(), stats.data_ptr() + 8
             ws, wsn = _workspace(lib.swf_final_head_bwd_workspace_bytes(b, h, w, ks), dev)
+            if ctx.train and ctx.collective is not None:
+                # the normalisation's own gradient needs two per-channel means over the WHOLE batch: local sums, one all-reduce, then
+                # the backward proper (which recomputes what the first call computed: nothing waits in the workspace for the collective)
+                sums = torch.empty(4, dtype=torch.float32, device=dev)
+                L.check(lib.swf_final_head_bwd_sums(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), b, h, w, ks, ws, wsn, _stream(dev)))
+                ctx.collective.all_reduce_(sums)
+                L.check(lib.swf_final_head_bwd_synced(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), ctx.count, _ptr(gx), _ptr(gy),
+                                                      C.byref(grads), b, h, w, ks, ws, wsn, _stream(dev)))
+                return (None, gx, gy, *bufs)
             L.check(lib.swf_final_head_bwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), _ptr(gx), _ptr(gy), C.byref(grads), b, h, w, ks,
                                            int(ctx.train), ws, wsn, _stream(dev)))
         return (None, gx, gy, *bufs)
