@@ -821,6 +821,83 @@ int swf_fusion_perception(const swf_perception_desc* desc, const float* fusion, 
                           double* out /* device [B][SWF_PERCEPTION_COUNT] */, int32_t B, int32_t H, int32_t W,
                           void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- the comparative-study group: Q_MI, Q_TE, Q_NCIE, Q_M, Q_SF, Q_P, six values per image in one call ---------------------------
+ * The six of the twelve measures of Liu et al.'s comparative study (TPAMI 2012) that the calls above lack (they have Q_G = QABF, Q_S,
+ * Q_C, Q_Y, Q_CV, Q_CB).  Restated from memory of the published definitions (Hossny et al.; Cvejic et al. / Nava et al.; Wang et al.;
+ * Wang and Liu; Zheng et al.; Zhao et al. with Kovesi's phase congruency); no copy of a paper or of an evaluator is available to this
+ * build: PARITY WITH ANY OF THEM IS UNPINNED.  These definitions are this project's, and where a paper differs the text here holds.
+ * Known differences from the papers as recalled: Wang and Liu's Q_M uses a wavelet with more scales and a normalised edge-preservation
+ * map, here it is two scales of the Haar transform with exp(-|difference|); Kovesi's noise estimate may use the Rayleigh mean or the
+ * median and compensates frequency spread, here it is the median and no more; Zhao's Q_P is restated with plain correlation
+ * coefficients of whole maps, where the paper may take them over blocks.
+ * Levels.  A, B, F = the level images of ir, vis, fusion of the metrics above (the same quantiser), N = H W.  p_X, p_XY = the 256-bin
+ * and 256 x 256-bin relative frequencies; H(X) = the entropy with log2, H_b = the entropy with base-256 logarithms (log2 / 8); sums
+ * over non-zero bins only; MI(X, Y) = sum p_XY log2(p_XY / (p_X p_Y)).
+ *   QMI    2 [MI(A, F) / (H(A) + H(F)) + MI(B, F) / (H(B) + H(F))]; a term whose denominator is 0 contributes 0
+ *   QTE    I(X, Y) = (1 - sum p_XY^q / (p_X p_Y)^(q - 1)) / (1 - q), Hq(X) = (1 - sum p_X^q) / (q - 1);
+ *          QTE = (I(A, F) + I(B, F)) / (Hq(A) + Hq(B) - I(A, B)), 0 where that denominator is 0
+ *   QNCIE  NCC(X, Y) = H_b(X) + H_b(Y) - H_b(X, Y); R = the symmetric 3 x 3 matrix with unit diagonal and the three NCCs in the order
+ *          (A, B, F); lambda_i = its eigenvalues by cyclic Jacobi sweeps (pairs (0,1), (0,2), (1,2); t = sign(theta) / (|theta| +
+ *          sqrt(theta^2 + 1)), theta = (r_qq - r_pp) / (2 r_pq); until the off-diagonal squares sum to <= 1e-60, 64 sweeps at most);
+ *          QNCIE = 1 + sum_i (lambda_i / 3) log_256(lambda_i / 3), a term with lambda_i <= 0 being 0
+ *   QSF    D_h = I(i, j) - I(i, j-1), D_v = I(i, j) - I(i-1, j), D_md = I(i, j) - I(i-1, j-1), D_sd = I(i, j) - I(i-1, j+1), each
+ *          where both pixels exist; SF = sqrt((sum D_h^2 + sum D_v^2 + w_d sum D_md^2 + w_d sum D_sd^2) / N), w_d = 1 / sqrt 2.  SF_F
+ *          from F's differences, SF_R from max(|D(A)|, |D(B)|) per pixel and direction; QSF = (SF_F - SF_R) / SF_R, 0 where SF_R = 0.
+ *          The sums are exact integers; the weight is applied once to each exact sum.
+ *   QM     on levels / 255: two scales of the decimated orthonormal Haar transform, per 2 x 2 block [a b; c d] of the previous
+ *          approximation LL = (a + b + c + d) / 2, LH = (a + b - c - d) / 2, HL = (a - b + c - d) / 2, HH = (a - b - c + d) / 2, an odd
+ *          trailing row or column dropped.  At scale s, for X of A, B: EP_X = (exp(-|LH_X - LH_F|) + exp(-|HL_X - HL_F|) +
+ *          exp(-|HH_X - HH_F|)) / 3, w_X = LH_X^2 + HL_X^2 + HH_X^2, Q_s = sum(EP_A w_A + EP_B w_B) / sum(w_A + w_B); Q_s = 1 for a
+ *          scale without coefficients (an axis under 2, under 4 for the second), 0 when its weights sum to 0;
+ *          QM = Q_1^alpha1 Q_2^alpha2
+ *   QP     phase congruency of the levels (as doubles), 4 scales s = 1..4 and 6 orientations o = 1..6.  fx = s(v, W) / W,
+ *          fy = s(u, H) / H at bin (u, v), s(j, n) of the perception group; rho = sqrt(fx^2 + fy^2), rho(0, 0) = 1;
+ *          theta = atan2(-fy, fx); lp = 1 / (1 + (rho / 0.45)^30); G_s = exp(-ln(rho / f_s)^2 / (2 ln(sigma_onf)^2)) lp,
+ *          f_s = 1 / (min_wavelength mult^(s-1)), G_s(0, 0) = 0; a = (o - 1) pi / 6, dtheta = min(3 |atan2(sin theta cos a -
+ *          cos theta sin a, cos theta cos a + sin theta sin a)|, pi), spread = (cos dtheta + 1) / 2;
+ *          EO_so = IDFT2(DFT2(X) G_s spread), E = Re, O = Im, An = |EO|.
+ *          Per orientation: sumE, sumO, sumAn = sums over s, maxAn the maximum; XE = sqrt(sumE^2 + sumO^2) + eps, mE = sumE / XE,
+ *          mO = sumO / XE; Energy = sum_s (E mE + O mO - |E mO - O mE|); tau = the median over the N pixels of An at s = 1 (the mean
+ *          of the two middle values for even N) / sqrt(ln 4); tt = tau (1 - (1 / mult)^4) / (1 - 1 / mult);
+ *          T = tt sqrt(pi / 2) + k tt sqrt((4 - pi) / 2); Energy <- max(Energy - T, 0); width = (sumAn / (maxAn + eps) - 1) / 3;
+ *          weight = 1 / (1 + exp((cutoff - width) g)); PC_o = weight Energy / (sumAn + eps).
+ *          Over orientations: cx2 = sum (PC_o cos a)^2 / 3, cy2 = sum (PC_o sin a)^2 / 3, cxy = sum PC_o^2 cos a sin a / 3;
+ *          den = sqrt(cxy^2 + (cx2 - cy2)^2) + eps; M = (cy2 + cx2 + den) / 2, m = (cy2 + cx2 - den) / 2, p = sum_o PC_o.
+ *          For each map kind X of p, M, m: S_X = max(X_A, X_B) per pixel; c(U, V) = (cov(U, V) + C) / (sd(U) sd(V) + C), population
+ *          moments over the whole image; P_X = max(c(X_A, X_F), c(X_B, X_F), c(S_X, X_F), 0); QP = P_p^ep P_M^eM P_m^em.
+ * So F = A = B gives QMI = 2 (not flat), QSF = 0, QM = 1 (not flat), QP = 1; three flat images give QMI = 0, QTE = 0,
+ * QNCIE = 1 - log_256 3, QSF = 0, QM = 0 (1 under 2 pixels in an axis), QP = 1.  An axis of one pixel leaves only the differences
+ * along the other in QSF.
+ * Usual constants: q 1.85, alpha1 1, alpha2 1, min_wavelength 3, mult 2.1, sigma_onf 0.55, k 2, cutoff 0.5, g 10, eps 1e-4, C 1e-4,
+ * ep 1, eM 1, em 1.
+ * Arithmetic.  fp64 throughout after the quantiser.  The three joint histograms are u32 counts (integer atomics: exact, so their
+ * order is immaterial), the marginals their column sums.  QP's transforms are the dense fp64 products of the perception group on the
+ * half spectrum: one forward transform per image plane; a filter G_s spread_o splits into its even and odd parts under (u, v) ->
+ * (-u, -v), whose filtered spectra invert to E and to i O, so each of the 24 takes two real inverse transforms, the filter applied
+ * as the spectrum is loaded.  The median is a radix select over the bit patterns of the non-negative doubles.  Floating-point sums
+ * go through per-tile partials added in a fixed order; no floating-point atomics: results are bit-identical from call to call, and
+ * an image's row does not depend on the rest of its batch.
+ * Workspace (every carve rounded up to 256 bytes), Wh = floor(W / 2) + 1, P = 2 H Wh, t1 = ceil(H / 32) ceil(W / 32),
+ * t2 = ceil(N / 1024): doubles 8 H^2 + 4 W Wh (twiddles) + 48 H Wh (filters) + B (3 N + 3 P + 24 P + 24 N + 12 N + 3 + 288 + 12 t1 +
+ * 12 t2 + 21 t2), and B 3 65536 u32 counters. */
+typedef struct swf_comparative_desc {
+    double q, alpha1, alpha2, min_wavelength, mult, sigma_onf, k, cutoff, g, eps, C, ep, eM, em;
+} swf_comparative_desc;   /* defaults 1.85, 1, 1, 3, 2.1, 0.55, 2, 0.5, 10, 1e-4, 1e-4, 1, 1, 1 */
+enum { SWF_COMPARATIVE_QMI, SWF_COMPARATIVE_QTE, SWF_COMPARATIVE_QNCIE, SWF_COMPARATIVE_QM, SWF_COMPARATIVE_QSF, SWF_COMPARATIVE_QP,
+       SWF_COMPARATIVE_COUNT };
+/* 0 for a shape swf_fusion_comparative would refuse */
+size_t swf_fusion_comparative_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_COMPARATIVE_COUNT], one row per image.  The call zeroes what it
+ * accumulates into and writes every other workspace element it reads, allocates nothing and does not synchronise the host, so it
+ * can be captured into a hipGraph on one stream.
+ * SWF_ERR_BAD_SHAPE for B, H or W <= 0, and for a non-finite constant, q <= 0, q = 1, mult <= 1, sigma_onf outside (0, 1),
+ * min_wavelength < 2, eps <= 0, C <= 0 or a negative exponent (alpha1, alpha2, ep, eM, em);
+ * SWF_ERR_UNSUPPORTED for H or W > 16384 or B > 2730 (the int32 indices of the dense transforms, 24 transform planes per image);
+ * all before anything is launched. */
+int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion, const float* ir, const float* vis,
+                           double* out /* device [B][SWF_COMPARATIVE_COUNT] */, int32_t B, int32_t H, int32_t W,
+                           void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);
  * v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps), IEEE sqrt and division, no atomics.

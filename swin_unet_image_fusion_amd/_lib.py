@@ -138,6 +138,14 @@ class PerceptionDesc(C.Structure):   # swf_perception_desc: Q_CB's filter (f0, f
 PERCEPTION_COUNT = 5   # SWF_PERCEPTION_COUNT
 
 
+class ComparativeDesc(C.Structure):   # swf_comparative_desc: Q_TE's order q, Q_M's exponents, Q_P's log-Gabor bank, noise, weighting and exponents
+    _fields_ = [(n, C.c_double) for n in ("q", "alpha1", "alpha2", "min_wavelength", "mult", "sigma_onf", "k", "cutoff", "g", "eps", "C",
+                                          "ep", "eM", "em")]
+
+
+COMPARATIVE_COUNT = 6   # SWF_COMPARATIVE_COUNT
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -268,6 +276,8 @@ SIGNATURES = {
     "swf_fusion_structure": (C.c_int, [P(StructureDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_fusion_perception_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "swf_fusion_perception": (C.c_int, [P(PerceptionDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_comparative_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_comparative": (C.c_int, [P(ComparativeDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

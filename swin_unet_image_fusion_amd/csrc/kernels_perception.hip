@@ -15,6 +15,7 @@
 //   3  [Ur; Ui]  = [C_H -S_H; S_H C_H] [Zr; Zi]      2H x 2H by 2H x Wh     stored as [Ur | Ui]
 //   4  Y         = [Ur | Ui] [C_W; -S_W]             H x 2Wh by 2Wh x W
 // The other half of the spectrum is the conjugate of this one (X real, G even), which is what c_v stands for.
+// The twiddle matrices, the GEMM kernel and its launch are dft_frag.h's, shared with kernels_comparative.hip.
 //
 // Kernels, all on one stream (A, B, F = levels of ir, vis, fusion; five planes per image: stretch(A), stretch(B), stretch(F) for Q_CB,
 // stretch(A) - stretch(F) and stretch(B) - stretch(F) for Q_CV):
@@ -34,6 +35,7 @@
 //   perception_finish_kernel  one workgroup per image adds the per-tile sums in a fixed order and writes the row.
 #include "kernels_perception.h"
 #include "metric_frag.h"
+#include "dft_frag.h"
 
 #include <cmath>
 
@@ -51,39 +53,15 @@ constexpr int kMaxImages = 65535 / kPlanes;
 // Tables
 // ------------------------------------------------------------------------------------------------------------------------------
 struct Tables {
-    double *a2, *a3;    // [2H][2H]: [C S; -S C] and [C -S; S C]
-    double *bw1;        // [W][2Wh]: [C | -S]
-    double *bw4;        // [2Wh][W]: [C; -S]
-    double *g;          // [2][H][Wh]: G' of Q_CB, then of Q_CV
+    Twiddles w;         // the four twiddle matrices (dft_frag.h)
+    double* g;          // [2][H][Wh]: G' of Q_CB, then of Q_CV
 };
 
 __global__ __launch_bounds__(kThreads) void tables_kernel(Tables t, int H, int W, int Wh, double f0, double f1, double a) {
-    const int64_t nH = (int64_t)4 * H * H, nW = (int64_t)W * Wh, nG = (int64_t)H * Wh;
+    const int64_t nG = (int64_t)H * Wh;
     int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i < nH) {
-        const int r = (int)(i / (2 * H)), c = (int)(i % (2 * H));
-        const int64_t m = ((int64_t)(r % H) * (c % H)) % H;
-        double sn, cs;
-        sincospi(2.0 * (double)m / (double)H, &sn, &cs);
-        const bool lower = r >= H, right = c >= H;
-        const double v2 = lower == right ? cs : (right ? sn : -sn);
-        t.a2[i] = v2;
-        t.a3[i] = lower == right ? cs : -v2;
-        return;
-    }
-    i -= nH;
-    if (i < nW) {
-        const int k = (int)(i / Wh), v = (int)(i % Wh);
-        const int64_t m = ((int64_t)k * v) % W;
-        double sn, cs;
-        sincospi(2.0 * (double)m / (double)W, &sn, &cs);
-        t.bw1[(int64_t)k * 2 * Wh + v] = cs;
-        t.bw1[(int64_t)k * 2 * Wh + Wh + v] = -sn;
-        t.bw4[(int64_t)v * W + k] = cs;
-        t.bw4[(int64_t)(Wh + v) * W + k] = -sn;
-        return;
-    }
-    i -= nW;
+    if (fill_twiddle(t.w, i, H, W, Wh)) return;
+    i -= twiddle_count(H, W, Wh);
     if (i < nG) {
         const int u = (int)(i / Wh), v = (int)(i % Wh);
         const int64_t su = u < (H + 1) / 2 ? u : u - H;   // s(v, W)^2 = v^2 for every v <= W / 2
@@ -152,90 +130,6 @@ __global__ __launch_bounds__(kThreads) void stretch_kernel(const float* __restri
 // ------------------------------------------------------------------------------------------------------------------------------
 // The DFT products
 // ------------------------------------------------------------------------------------------------------------------------------
-constexpr int kBM = 64, kBK = 16;      // a tile of C is 64 rows by 48 or 64 columns (NF = 3 or 4 MFMA tiles of 16)
-constexpr int kLdsPitch = kBM + 16;    // 160 dwords = 32 mod 64 banks: the k rows a half-wave reads fall on disjoint banks
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-enum { kStorePlain, kStoreFoldCols, kStoreScale, kStoreFoldRows };
-
-struct Gemm {
-    const double* A;    // [M][K], pitch lda; a_batch elements between planes (0: shared)
-    const double* B;    // [K][N], pitch ldb
-    double* C;
-    int64_t a_batch, b_batch, c_batch;
-    int lda, ldb, M, N, K;
-    int half;           // FoldCols: N / 2; Scale and FoldRows: M / 2
-    const double* g;    // Scale: [2][half][N]
-};
-
-// C = A B in fp64 on the matrix cores.  A workgroup owns a 64 x 16 NF tile of C, wave w its rows 16 w .. 16 w + 15 as NF MFMA tiles
-// side by side; operands go through LDS k-major, 16 of K at a time, the next step's global loads in flight under this step's MFMAs.
-// NF = 3 or 4, whichever pads N less: the half spectrum of a power-of-two width is 2^k + 1 columns, which 64-wide tiles would
-// compute half as many again of.
-// v_mfma_f64_16x16x4_f64: lane l holds A[row l & 15][k = l >> 4] and B[k = l >> 4][col l & 15]; result register r is
-// C[row (l >> 4) + 4 r][col l & 15] (not the row map of the other MFMAs).
-// Stores: Plain C[m][n]; FoldCols [Cl | Cr] -> [Cl; Cr]; Scale C[m][n] g[plane >= 3][m mod half][n]; FoldRows [Ct; Cb] -> [Ct | Cb].
-template <int STORE, int NF>
-__global__ __launch_bounds__(kThreads) void dft_gemm_kernel(Gemm g) {
-    constexpr int BN = 16 * NF;
-    __shared__ double sA[kBK * kLdsPitch], sB[kBK * kLdsPitch];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * kBM, n0 = blockIdx.x * BN;
-    const int64_t plane = blockIdx.z;
-    const double* __restrict__ A = g.A + plane * g.a_batch;
-    const double* __restrict__ B = g.B + plane * g.b_batch;
-    double* __restrict__ C = g.C + plane * g.c_batch;
-    const int am = tid >> 2, ak = (tid & 3) * 4;   // A: row m0 + am, k = ak .. ak + 3
-    const bool a_in = m0 + am < g.M;
-    const double* pa = A + (int64_t)(m0 + am) * g.lda + ak;
-    double ra[4], rb[NF];                          // B: element tid + 256 i of the 16 x BN tile, row-major
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) ra[i] = (a_in && k0 + ak + i < g.K) ? pa[k0 + i] : 0.0;
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int e = tid + kThreads * i, k = k0 + e / BN, n = n0 + e % BN;
-            rb[i] = (k < g.K && n < g.N) ? B[(int64_t)k * g.ldb + n] : 0.0;
-        }
-    };
-    v4d acc[NF] = {};
-    fetch(0);
-    const int fr = lane & 15, fk = lane >> 4;
-    for (int k0 = 0; k0 < g.K; k0 += kBK) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sA[(ak + i) * kLdsPitch + am] = ra[i];
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int e = tid + kThreads * i;
-            sB[(e / BN) * kLdsPitch + e % BN] = rb[i];
-        }
-        __syncthreads();
-        if (k0 + kBK < g.K) fetch(k0 + kBK);
-#pragma unroll
-        for (int kk = 0; kk < kBK; kk += 4) {
-            const double a = sA[(kk + fk) * kLdsPitch + wave * 16 + fr];
-            const double* qb = &sB[(kk + fk) * kLdsPitch + fr];
-#pragma unroll
-            for (int j = 0; j < NF; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, qb[16 * j], acc[j], 0, 0, 0);
-        }
-    }
-    const double* gt = STORE == kStoreScale ? g.g + ((int)(plane % kPlanes) >= kCbPlanes ? (int64_t)g.half * g.N : 0) : nullptr;
-#pragma unroll
-    for (int j = 0; j < NF; ++j)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int m = m0 + wave * 16 + fk + 4 * r, n = n0 + j * 16 + fr;
-            if (m >= g.M || n >= g.N) continue;
-            const double v = acc[j][r];
-            if (STORE == kStorePlain) C[(int64_t)m * g.N + n] = v;
-            if (STORE == kStoreFoldCols) C[((int64_t)m + (int64_t)(n / g.half) * g.M) * g.half + n % g.half] = v;
-            if (STORE == kStoreScale) C[(int64_t)m * g.N + n] = v * gt[(int64_t)(m % g.half) * g.N + n];
-            if (STORE == kStoreFoldRows) C[(int64_t)(m % g.half) * 2 * g.N + (int64_t)(m / g.half) * g.N + n] = v;
-        }
-}
-
 // ------------------------------------------------------------------------------------------------------------------------------
 // Q_CB: local contrast of the three filtered planes and the pointwise quality map
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -430,8 +324,6 @@ struct PerceptionPlan {
     unsigned* hist;
 };
 
-inline double* carve_doubles(Carver& ws, int64_t n) { return reinterpret_cast<double*>(ws.floats(2 * n)); }
-
 PerceptionPlan carve_perception(Carver& ws, int B, int H, int W) {
     PerceptionPlan f{};
     f.Wh = W / 2 + 1;
@@ -443,10 +335,10 @@ PerceptionPlan carve_perception(Carver& ws, int B, int H, int W) {
     f.lev_tiles = f.lev_tiles_x * cdiv(H, kLT);
     f.n = (int64_t)H * W;
     f.plane = (int64_t)2 * H * f.Wh;
-    f.t.a2 = carve_doubles(ws, (int64_t)4 * H * H);
-    f.t.a3 = carve_doubles(ws, (int64_t)4 * H * H);
-    f.t.bw1 = carve_doubles(ws, (int64_t)2 * W * f.Wh);
-    f.t.bw4 = carve_doubles(ws, (int64_t)2 * W * f.Wh);
+    f.t.w.a2 = carve_doubles(ws, (int64_t)4 * H * H);
+    f.t.w.a3 = carve_doubles(ws, (int64_t)4 * H * H);
+    f.t.w.bw1 = carve_doubles(ws, (int64_t)2 * W * f.Wh);
+    f.t.w.bw4 = carve_doubles(ws, (int64_t)2 * W * f.Wh);
     f.t.g = carve_doubles(ws, (int64_t)2 * H * f.Wh);
     f.mm = reinterpret_cast<int*>(ws.floats((int64_t)B * 6));
     f.X = carve_doubles(ws, (int64_t)B * kPlanes * f.n);
@@ -457,16 +349,6 @@ PerceptionPlan carve_perception(Carver& ws, int B, int H, int W) {
     f.lev_part = carve_doubles(ws, (int64_t)B * f.lev_tiles * 4);
     f.hist = reinterpret_cast<unsigned*>(ws.floats((int64_t)B * f.lev_tiles * 768));
     return f;
-}
-
-template <int STORE>
-int launch_gemm(const Gemm& g, int planes, hipStream_t stream) {
-    const dim3 grid48(cdiv(g.N, 48), cdiv(g.M, kBM), planes), grid64(cdiv(g.N, 64), cdiv(g.M, kBM), planes);
-    if (grid48.x * 48 < grid64.x * 64)   // the narrower tile pads N less
-        dft_gemm_kernel<STORE, 3><<<grid48, kThreads, 0, stream>>>(g);
-    else
-        dft_gemm_kernel<STORE, 4><<<grid64, kThreads, 0, stream>>>(g);
-    return check_launch("dft_gemm_kernel");
 }
 
 // The 1-D factor of exp(-(x^2 + y^2) / (2 sd^2)) / (2 pi sd^2) over x = -15 .. 0 (even in x; not normalised to sum 1).
@@ -507,13 +389,13 @@ int fusion_perception(const swf_perception_desc& d, const float* fusion, const f
     }
     if (stages & 2) {
         Gemm g{};
-        g = Gemm{f.X, f.t.bw1, f.T, f.n, 0, f.plane, W, 2 * Wh, H, 2 * Wh, W, Wh, nullptr};
+        g = Gemm{f.X, f.t.w.bw1, f.T, f.n, 0, f.plane, W, 2 * Wh, H, 2 * Wh, W, Wh, nullptr};
         SWF_TRY(launch_gemm<kStoreFoldCols>(g, planes, stream));
-        g = Gemm{f.t.a2, f.T, f.Z, 0, f.plane, f.plane, 2 * H, Wh, 2 * H, Wh, 2 * H, H, f.t.g};
+        g = Gemm{f.t.w.a2, f.T, f.Z, 0, f.plane, f.plane, 2 * H, Wh, 2 * H, Wh, 2 * H, H, f.t.g, kPlanes, kCbPlanes};
         SWF_TRY(launch_gemm<kStoreScale>(g, planes, stream));
-        g = Gemm{f.t.a3, f.Z, f.T, 0, f.plane, f.plane, 2 * H, Wh, 2 * H, Wh, 2 * H, H, nullptr};
+        g = Gemm{f.t.w.a3, f.Z, f.T, 0, f.plane, f.plane, 2 * H, Wh, 2 * H, Wh, 2 * H, H, nullptr};
         SWF_TRY(launch_gemm<kStoreFoldRows>(g, planes, stream));
-        g = Gemm{f.T, f.t.bw4, f.Z, f.plane, 0, f.plane, 2 * Wh, W, H, W, 2 * Wh, 0, nullptr};
+        g = Gemm{f.T, f.t.w.bw4, f.Z, f.plane, 0, f.plane, 2 * Wh, W, H, W, 2 * Wh, 0, nullptr};
         SWF_TRY(launch_gemm<kStorePlain>(g, planes, stream));
     }
     if (stages & 4) {

@@ -16,6 +16,7 @@
 #include "kernels_fidelity.h"
 #include "kernels_structure.h"
 #include "kernels_perception.h"
+#include "kernels_comparative.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2406,6 +2407,43 @@ int swf_fusion_perception(const swf_perception_desc* desc, const float* fusion, 
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "fusion_perception: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return fusion_perception(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// The comparative-study call: dense transforms too, 24 planes per image.
+static int check_comparative_shape(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_comparative: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!comparative_shape_ok(B, H, W))
+        return fail(SWF_ERR_UNSUPPORTED, "fusion_comparative: B=%d H=%d W=%d exceeds the int32 indices of the dense transforms "
+                    "(H, W <= 16384, B <= 2730)", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_comparative_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    return check_comparative_shape(B, H, W) == SWF_OK ? fusion_comparative_workspace_bytes(B, H, W) : 0;
+}
+
+static int check_comparative_desc(const swf_comparative_desc& d) {
+    const double v[14] = {d.q, d.alpha1, d.alpha2, d.min_wavelength, d.mult, d.sigma_onf, d.k, d.cutoff, d.g, d.eps, d.C, d.ep, d.eM, d.em};
+    bool ok = d.q > 0.0 && d.q != 1.0 && d.mult > 1.0 && d.sigma_onf > 0.0 && d.sigma_onf < 1.0 && d.min_wavelength >= 2.0 && d.eps > 0.0 &&
+              d.C > 0.0 && d.alpha1 >= 0.0 && d.alpha2 >= 0.0 && d.ep >= 0.0 && d.eM >= 0.0 && d.em >= 0.0;
+    for (double x : v) ok = ok && std::isfinite(x);
+    if (!ok)
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_comparative: constants q=%g alpha1=%g alpha2=%g min_wavelength=%g mult=%g sigma_onf=%g k=%g "
+                    "cutoff=%g g=%g eps=%g C=%g ep=%g eM=%g em=%g (finite, q > 0, q != 1, mult > 1, 0 < sigma_onf < 1, min_wavelength >= 2, "
+                    "eps > 0, C > 0, exponents >= 0)", d.q, d.alpha1, d.alpha2, d.min_wavelength, d.mult, d.sigma_onf, d.k, d.cutoff, d.g,
+                    d.eps, d.C, d.ep, d.eM, d.em);
+    return SWF_OK;
+}
+
+int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion, const float* ir, const float* vis, double* out,
+                           int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_comparative: NULL descriptor, image or output");
+    SWF_TRY(check_comparative_shape(B, H, W));
+    SWF_TRY(check_comparative_desc(*desc));
+    const size_t need = fusion_comparative_workspace_bytes(B, H, W);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "fusion_comparative: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return fusion_comparative(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

@@ -36,6 +36,35 @@ j < ceil(n / 2) else j - n; spec(X, G) = Re(IDFT2(DFT2(X) o G)), G evaluated at 
 So F = A = B gives Qcb = 1, Qcv = 0, CE = 0, RMSE = 0; three flat images 1, 0, 0, 0; a flat vis with F = ir gives Qcb = 1.  The filtering
 is dense (fp64 DFT products on the matrix cores against twiddle matrices the call builds), for any H and W up to 16384.
 
+The comparative-study group comes from a fifth fused HIP call on the same levels, fp64 throughout (swf_fusion_comparative:
+`fusion_comparative`, or `FusionMetrics(comparative=True)`; with the four switches on, all 35 values): the six of Liu et al.'s twelve
+(TPAMI 2012) that the other calls lack (they have Q_G = Qabf, Q_S, Q_C, Q_Y, Q_CV, Q_CB).  Restated from memory of the papers: PARITY
+WITH ANY OF THEM IS UNPINNED, and where a paper differs, this text holds.  p_X, p_XY = the 256-bin and 256 x 256-bin relative
+frequencies, H = entropy with log2, H_b = H / 8 (base 256), sums over non-zero bins, MI(X, Y) = sum p_XY log2(p_XY / (p_X p_Y)):
+  Qmi   2 [MI(A, F) / (H(A) + H(F)) + MI(B, F) / (H(B) + H(F))]; a term whose denominator is 0 contributes 0.
+  Qte   I(X, Y) = (1 - sum p_XY^q / (p_X p_Y)^(q - 1)) / (1 - q), Hq(X) = (1 - sum p_X^q) / (q - 1);
+        Qte = (I(A, F) + I(B, F)) / (Hq(A) + Hq(B) - I(A, B)), 0 where that denominator is 0.
+  Qncie NCC(X, Y) = H_b(X) + H_b(Y) - H_b(X, Y); R = the symmetric 3 x 3 matrix with unit diagonal and the NCCs in the order (A, B, F);
+        lambda_i its eigenvalues (cyclic Jacobi sweeps); Qncie = 1 + sum (lambda_i / 3) log_256(lambda_i / 3), terms with lambda_i <= 0 being 0.
+  Qsf   D_h, D_v, D_md, D_sd = I(i, j) minus I(i, j-1), I(i-1, j), I(i-1, j-1), I(i-1, j+1) where both pixels exist;
+        SF = sqrt((sum D_h^2 + sum D_v^2 + w_d sum D_md^2 + w_d sum D_sd^2) / (H W)), w_d = 1 / sqrt 2; SF_F from F, SF_R from
+        max(|D(A)|, |D(B)|) per pixel and direction; Qsf = (SF_F - SF_R) / SF_R, 0 where SF_R = 0.  An axis of one pixel leaves only the
+        differences along the other.
+  Qm    on levels / 255, two scales of the decimated orthonormal Haar transform (per 2 x 2 block [a b; c d]: LL = (a + b + c + d) / 2,
+        LH = (a + b - c - d) / 2, HL = (a - b + c - d) / 2, HH = (a - b - c + d) / 2; an odd trailing row or column dropped).  Per scale,
+        for X of A, B: EP_X = (exp(-|LH_X - LH_F|) + exp(-|HL_X - HL_F|) + exp(-|HH_X - HH_F|)) / 3, w_X = LH_X^2 + HL_X^2 + HH_X^2,
+        Q_s = sum(EP_A w_A + EP_B w_B) / sum(w_A + w_B), 1 for a scale without coefficients (an axis under 2 pixels; under 4 for the
+        second), 0 when the weights sum to 0; Qm = Q_1^alpha1 Q_2^alpha2.
+  Qp    Zhao's, on Kovesi-style phase congruency of the levels with 4 scales and 6 orientations: log-Gabor filters
+        G_s = exp(-ln(rho / f_s)^2 / (2 ln(sigma_onf)^2)) / (1 + (rho / 0.45)^30), f_s = 1 / (min_wavelength mult^(s-1)), angular spread
+        (cos(min(3 dtheta, pi)) + 1) / 2 about a = (o - 1) pi / 6; per orientation the energy sum_s (E mE + O mO - |E mO - O mE|) less
+        T = tt sqrt(pi / 2) + k tt sqrt((4 - pi) / 2), tt = tau (1 - mult^-4) / (1 - 1 / mult), tau = median(An at s = 1) / sqrt(ln 4),
+        weighted by 1 / (1 + exp((cutoff - width) g)), width = (sumAn / (maxAn + eps) - 1) / 3, over sumAn + eps; the maps p = sum_o PC_o
+        and the maximum and minimum moments M, m; for each map kind S = max(X_A, X_B), c(U, V) = (cov + C) / (sd_U sd_V + C) over the
+        whole image, P = max(c(X_A, X_F), c(X_B, X_F), c(S, X_F), 0); Qp = P_p^ep P_M^eM P_m^em.  include/swinfuse.h has every step.
+So F = A = B gives Qmi = 2 (not flat), Qsf = 0, Qm = 1 (not flat), Qp = 1; three flat images give Qmi = 0, Qte = 0, Qncie = 1 - log_256 3,
+Qsf = 0, Qm = 0 (1 under 2 pixels in an axis: no coefficients), Qp = 1.
+
 The definitions are restated from the published ones and the common open evaluators; no MATLAB, VIFB or sewar copy is available to
 this build, so parity with any of them is unpinned.  `MyLoss(choose_ms_ssim=False).calcu_ssim_loss` is a different
 thing: the training loss's kornia-style SSIM on unit-range floats, returned as a loss; SSIM as a metric on levels is `fusion_structure`'s.
@@ -52,7 +81,8 @@ from . import _lib as L
 from .modules import _ptr, _stream, _workspace
 
 __all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "STRUCTURE_NAMES", "STRUCTURE_DEFAULTS", "PERCEPTION_NAMES",
-           "PERCEPTION_DEFAULTS", "fusion_metrics", "fusion_fidelity", "fusion_structure", "fusion_perception", "FusionMetrics"]
+           "PERCEPTION_DEFAULTS", "COMPARATIVE_NAMES", "COMPARATIVE_DEFAULTS", "fusion_metrics", "fusion_fidelity", "fusion_structure",
+           "fusion_perception", "fusion_comparative", "FusionMetrics"]
 
 METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
 QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
@@ -64,6 +94,10 @@ STRUCTURE_DEFAULTS = {"K1": 0.01, "K2": 0.03, "alpha": 1.0, "Ty": 0.75}   # Wang
 PERCEPTION_NAMES = ("Qcb", "Qcv", "CE", "EI", "RMSE")                                # the order of the header's SWF_PERCEPTION_* enum
 PERCEPTION_DEFAULTS = {"f0": 15.3870, "f1": 1.3456, "a": 0.7622, "p": 3.0, "q": 2.0, "Z": 1e-4,   # Chen & Blum's filter and contrast map
                        "alpha": 1.0}                                                              # Chen & Varshney's saliency exponent
+COMPARATIVE_NAMES = ("Qmi", "Qte", "Qncie", "Qm", "Qsf", "Qp")                       # the order of the header's SWF_COMPARATIVE_* enum
+COMPARATIVE_DEFAULTS = {"q": 1.85, "alpha1": 1.0, "alpha2": 1.0,                                  # Tsallis order, Q_M's scale exponents
+                        "min_wavelength": 3.0, "mult": 2.1, "sigma_onf": 0.55, "k": 2.0, "cutoff": 0.5, "g": 10.0, "eps": 1e-4,   # Kovesi
+                        "C": 1e-4, "ep": 1.0, "eM": 1.0, "em": 1.0}                                # Zhao's stabiliser and exponents
 
 
 def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
@@ -97,6 +131,8 @@ _FAMILIES = {
     "fidelity": _Family(FIDELITY_NAMES, FIDELITY_DEFAULTS, L.FidelityDesc, L.FIDELITY_COUNT, "swf_fusion_fidelity", "constant(s)"),
     "structure": _Family(STRUCTURE_NAMES, STRUCTURE_DEFAULTS, L.StructureDesc, L.STRUCTURE_COUNT, "swf_fusion_structure", "constant(s)"),
     "perception": _Family(PERCEPTION_NAMES, PERCEPTION_DEFAULTS, L.PerceptionDesc, L.PERCEPTION_COUNT, "swf_fusion_perception", "constant(s)"),
+    "comparative": _Family(COMPARATIVE_NAMES, COMPARATIVE_DEFAULTS, L.ComparativeDesc, L.COMPARATIVE_COUNT, "swf_fusion_comparative",
+                           "constant(s)"),
 }
 
 
@@ -154,17 +190,28 @@ def fusion_perception(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> T
     return _call("perception", fusion, ir, vis, constants)
 
 
+def fusion_comparative(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
+    """-> (B, 6) float64 tensor on the inputs' device, row b = the COMPARATIVE_NAMES values of image b: Hossny's Qmi, the Tsallis-entropy
+    Qte, Qncie, Wang & Liu's Qm, Zheng's Qsf and Zhao's Qp.  Inputs as for fusion_metrics, at most 16384 pixels in an axis and 2730
+    images (NotImplementedError beyond: the transforms are dense).  Keyword arguments replace constants (COMPARATIVE_DEFAULTS); a
+    non-finite one, q <= 0, q = 1, mult <= 1, sigma_onf outside (0, 1), min_wavelength < 2, eps <= 0, C <= 0 or a negative exponent
+    (alpha1, alpha2, ep, eM, em) raises ValueError.  One library call on the current stream, no host synchronisation; bit-identical
+    from call to call."""
+    return _call("comparative", fusion, ir, vis, constants)
+
+
 class FusionMetrics:
     """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` the FIDELITY_NAMES values (constants:
     `fidelity_constants`) follow the ten, with `structure=True` the STRUCTURE_NAMES values (constants: `structure_constants`) follow
-    those, with `perception=True` the PERCEPTION_NAMES values (constants: `perception_constants`) follow those: 10, 15, 19 or 24
-    values without the last group, five more with it (up to 29).  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
+    those, with `perception=True` the PERCEPTION_NAMES values (constants: `perception_constants`) follow those, with `comparative=True` the
+    COMPARATIVE_NAMES values (constants: `comparative_constants`) follow those: 10, 15, 19 or 24 values without the last two groups, five
+    more with the perception group, six more with the comparative group (up to 35).  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
     image count is a host int (`count`): the batch size is known on the host, so counting there needs no synchronisation and no
     device scalar."""
 
     def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, structure: bool = False,
                  structure_constants: Optional[dict] = None, perception: bool = False, perception_constants: Optional[dict] = None,
-                 **qabf_constants):
+                 comparative: bool = False, comparative_constants: Optional[dict] = None, **qabf_constants):
         self.qabf_constants = qabf_constants
         self.fidelity = bool(fidelity)
         self.fidelity_constants = dict(fidelity_constants or {})
@@ -172,8 +219,11 @@ class FusionMetrics:
         self.structure_constants = dict(structure_constants or {})
         self.perception = bool(perception)
         self.perception_constants = dict(perception_constants or {})
+        self.comparative = bool(comparative)
+        self.comparative_constants = dict(comparative_constants or {})
         families = (("metrics", True, self.qabf_constants), ("fidelity", self.fidelity, self.fidelity_constants),
-                    ("structure", self.structure, self.structure_constants), ("perception", self.perception, self.perception_constants))
+                    ("structure", self.structure, self.structure_constants), ("perception", self.perception, self.perception_constants),
+                    ("comparative", self.comparative, self.comparative_constants))
         for kind, _, constants in families:
             _desc(kind, constants)   # refuse a misspelt constant here, not at the first batch, of a family that is off too
         self._families = [(kind, constants) for kind, on, constants in families if on]
