@@ -601,6 +601,57 @@ int swf_gray8_to_unit_fwd(const uint8_t* gray, float* out, int64_t count, swf_st
 int swf_ycrcb_to_rgb_fwd(const float* fused_y, const float* crcb, float* rgb_f, uint8_t* rgb8,
                          int32_t B, int32_t H, int32_t W, swf_stream_t stream);
 
+/* ---- baseline JPEG encoder: the last line of the reference's test loop, save_image(fus, "..._MKX_SELF.jpg") (a017:112-114) ---------
+ * Baseline sequential DCT (SOF0), 8 bits, from RGB [B][H][W][3] (three components in JFIF YCbCr, chroma 4:2:0 or 4:4:4) or gray
+ * [B][H][W] (one component).  The files are decoded by Pillow; the bytes are this format's, not libjpeg's: PARITY WITH libjpeg's
+ * STREAM IS NOT CLAIMED.  The format, all integer arithmetic:
+ *   tables   Annex K luminance / chrominance quantisation tables scaled as libjpeg scales them: s = 5000 / q (integer) for q < 50,
+ *            else 200 - 2 q; t = clamp((base s + 50) / 100, 1, 255).  The four Annex K.3 Huffman tables.
+ *   colour   Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + (128 << 16) + 32767) >> 16,
+ *            Cr = (32768 R - 27439 G - 5329 B + (128 << 16) + 32767) >> 16; 4:2:0 chroma (a + b + c + d + 2) >> 2 over each 2 x 2.
+ *            Partial MCUs at the right and bottom edges replicate the edge pixels of the input before the colour transform.
+ *   DCT      level shift -128; C13[u][x] = round(8192 alpha(u) cos((2x + 1) u pi / 16)), alpha(0) = sqrt(1/8), else sqrt(2/8);
+ *            rows t = (sum_x C13[u][x] s[x] + 1024) >> 11, then columns c = (sum_y C13[v][y] t[y] + 16384) >> 15;
+ *            quantised sign(c) ((|c| + (Q >> 1)) / Q).
+ *   entropy  zig-zag scan, DC differences, (run, size) codes with ZRL and EOB, 0xFF -> 0xFF00, as the standard prescribes.
+ *   stream   the MCU is 16 x 16 in 4:2:0 (Y00 Y01 Y10 Y11 Cb Cr) and 8 x 8 otherwise.  The restart interval is one MCU row (DRI's Ri =
+ *            the MCUs per row): every MCU row starts from zero DC predictors, is padded to a byte with 1-bits and is followed by
+ *            RSTm, m = row index mod 8, the last one by EOI instead.
+ *   header   SOI, APP0 JFIF 1.01 (no units, density 1:1), DQT (luminance; then chrominance, each its own segment), SOF0, DHT (DC0,
+ *            AC0; then DC1, AC1, each its own segment), DRI, SOS; gray carries the luminance tables only.  629 bytes with three
+ *            components, 334 with one.
+ * swf_jpeg_header_bytes / swf_jpeg_header / swf_jpeg_capacity_bytes / swf_jpeg_workspace_bytes are host-only. */
+enum { SWF_JPEG_444 = 0, SWF_JPEG_420 = 1 };
+typedef struct swf_jpeg_desc {
+    int32_t channels;      /* 1 (gray) or 3 (RGB) */
+    int32_t subsampling;   /* SWF_JPEG_444 or SWF_JPEG_420; one channel takes SWF_JPEG_444 only */
+    int32_t quality;       /* 1..100 */
+} swf_jpeg_desc;
+/* Bytes of the header; 0 for a descriptor the encoder would refuse. */
+size_t swf_jpeg_header_bytes(const swf_jpeg_desc* desc);
+/* host_out[0 .. swf_jpeg_header_bytes) <- the header of an H x W image.  SWF_ERR_BAD_SHAPE for a bad descriptor or H, W < 1,
+ * SWF_ERR_UNSUPPORTED for H or W > 65535, SWF_ERR_WORKSPACE for n below the header's size. */
+int swf_jpeg_header(const swf_jpeg_desc* desc, int32_t H, int32_t W, uint8_t* host_out, size_t n);
+/* The most bytes one image's stream can take: the header, and per MCU row 2 marker bytes and twice its worst bytes before stuffing,
+ * ceil(blocks per row (20 + 63 * 26) / 8) (a block is at most a 20-bit DC symbol and 63 AC symbols of 16 + 10 bits, and stuffing at
+ * most doubles a byte).  0 for what the encoder would refuse. */
+size_t swf_jpeg_capacity_bytes(const swf_jpeg_desc* desc, int32_t H, int32_t W);
+/* Bytes of workspace swf_jpeg_encode needs (the carve of kernels_jpeg.hip run without memory): per image the zig-zagged int16
+ * coefficients and one int32 bit count per block, one int32 byte count per MCU row, and the rows' staged streams.  0 for what the
+ * encoder would refuse. */
+size_t swf_jpeg_workspace_bytes(const swf_jpeg_desc* desc, int32_t B, int32_t H, int32_t W);
+/* pixels: device [B][H][W][channels] uint8.  header_dev: the bytes of swf_jpeg_header on the device (a caller encodes many batches
+ * of one shape with one upload), or NULL: the kernels then write the header from their constant tables.  out: device
+ * [B][capacity], capacity >= swf_jpeg_capacity_bytes; out[b][0 .. lengths[b]) <- the file of image b, and no byte of out[b] at or
+ * after lengths[b] is written.  lengths: device int32 [B].  Three launches (coefficients, entropy coding per MCU row, packing); no
+ * allocation, no copy to the host and no synchronisation, so the call can be captured into a hipGraph on one stream.  The bytes of
+ * an image depend on that image alone: not on B, the rest of the batch, an earlier use of the workspace, or timing.
+ * SWF_ERR_BAD_SHAPE for B, H or W < 1, quality outside 1..100, channels not 1 or 3, 4:2:0 with one channel or an unknown
+ * subsampling; SWF_ERR_UNSUPPORTED for H or W > 65535, B H W > 2^31 - 1 or swf_jpeg_capacity_bytes > 2^31 - 1 (lengths is int32);
+ * SWF_ERR_WORKSPACE for a workspace or a capacity below the queries; all before anything is launched. */
+int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint8_t* header_dev, uint8_t* out, size_t capacity,
+                    int32_t* lengths, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- resident paired dataset: the reference's training-time input transform (a015_dataset.py:57-66, :89-103) in one launch --------
  * The decoded uint8 images of a training set lie in two device arenas (gray [H][W], BGR [H][W][3], cv2.imread layouts).  A batch is
  * described by B rows; the launch writes ir = u8/255 and vis_y = cv2's uint8 luma/255 (the BGR->YCrCb restatement above) of the crop

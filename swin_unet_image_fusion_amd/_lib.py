@@ -146,6 +146,13 @@ class ComparativeDesc(C.Structure):   # swf_comparative_desc: Q_TE's order q, Q_
 COMPARATIVE_COUNT = 6   # SWF_COMPARATIVE_COUNT
 
 
+class JpegDesc(C.Structure):   # swf_jpeg_desc
+    _fields_ = [("channels", C.c_int32), ("subsampling", C.c_int32), ("quality", C.c_int32)]
+
+
+JPEG_444, JPEG_420 = 0, 1   # SWF_JPEG_444, SWF_JPEG_420
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -252,6 +259,11 @@ SIGNATURES = {
     "swf_bgr8_to_ycrcb_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "swf_gray8_to_unit_fwd": (C.c_int, [_vp, _vp, _i64, _vp]),
     "swf_ycrcb_to_rgb_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "swf_jpeg_header_bytes": (_sz, [P(JpegDesc)]),
+    "swf_jpeg_header": (C.c_int, [P(JpegDesc), _i32, _i32, _vp, _sz]),
+    "swf_jpeg_capacity_bytes": (_sz, [P(JpegDesc), _i32, _i32]),
+    "swf_jpeg_workspace_bytes": (_sz, [P(JpegDesc), _i32, _i32, _i32]),
+    "swf_jpeg_encode": (C.c_int, [P(JpegDesc), _vp, _vp, _vp, _sz, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_paired_crop_rows_bytes": (_sz, [_i32]),
     "swf_paired_crop_rows_check": (C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64]),
     "swf_paired_crop_resize_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

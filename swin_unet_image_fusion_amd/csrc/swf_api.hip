@@ -17,6 +17,7 @@
 #include "kernels_structure.h"
 #include "kernels_perception.h"
 #include "kernels_comparative.h"
+#include "kernels_jpeg.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2444,6 +2445,55 @@ int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "fusion_comparative: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return fusion_comparative(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// Baseline JPEG encoder.  One check of the descriptor and one of the shape serve the four queries and the call.
+static int check_jpeg_desc(const swf_jpeg_desc* d) {
+    if (!d) return fail(SWF_ERR_NULL, "jpeg: NULL descriptor");
+    if (!jpeg_desc_ok(*d))
+        return fail(SWF_ERR_BAD_SHAPE, "jpeg: channels=%d subsampling=%d quality=%d (channels 1 or 3, subsampling 0 (4:4:4) or, with three "
+                    "channels, 1 (4:2:0), quality 1..100)", d->channels, d->subsampling, d->quality);
+    return SWF_OK;
+}
+
+static int check_jpeg_shape(const swf_jpeg_desc& d, int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "jpeg: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!jpeg_shape_ok(d, B, H, W))
+        return fail(SWF_ERR_UNSUPPORTED, "jpeg: B=%d H=%d W=%d: H, W <= 65535 (the frame header's 16 bits), B H W and one image's capacity "
+                    "within int32", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_jpeg_header_bytes(const swf_jpeg_desc* desc) { return check_jpeg_desc(desc) == SWF_OK ? jpeg_header_bytes(*desc) : 0; }
+
+int swf_jpeg_header(const swf_jpeg_desc* desc, int32_t H, int32_t W, uint8_t* host_out, size_t n) {
+    SWF_TRY(check_jpeg_desc(desc));
+    if (!host_out) return fail(SWF_ERR_NULL, "jpeg_header: NULL output");
+    if (H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "jpeg_header: empty image (H=%d W=%d)", H, W);
+    if (H > 65535 || W > 65535) return fail(SWF_ERR_UNSUPPORTED, "jpeg_header: H=%d W=%d beyond the frame header's 16 bits", H, W);
+    if (n < jpeg_header_bytes(*desc)) return fail(SWF_ERR_WORKSPACE, "jpeg_header: room for %zu bytes, %zu needed", n, jpeg_header_bytes(*desc));
+    jpeg_header(*desc, H, W, host_out);
+    return SWF_OK;
+}
+
+size_t swf_jpeg_capacity_bytes(const swf_jpeg_desc* desc, int32_t H, int32_t W) {
+    return check_jpeg_desc(desc) == SWF_OK && check_jpeg_shape(*desc, 1, H, W) == SWF_OK ? jpeg_capacity_bytes(*desc, H, W) : 0;
+}
+
+size_t swf_jpeg_workspace_bytes(const swf_jpeg_desc* desc, int32_t B, int32_t H, int32_t W) {
+    return check_jpeg_desc(desc) == SWF_OK && check_jpeg_shape(*desc, B, H, W) == SWF_OK ? jpeg_workspace_bytes(*desc, B, H, W) : 0;
+}
+
+int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint8_t* header_dev, uint8_t* out, size_t capacity,
+                    int32_t* lengths, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_jpeg_desc(desc));
+    if (!pixels || !out || !lengths) return fail(SWF_ERR_NULL, "jpeg_encode: NULL pixels, output or lengths");
+    SWF_TRY(check_jpeg_shape(*desc, B, H, W));
+    const size_t cap = jpeg_capacity_bytes(*desc, H, W), need = jpeg_workspace_bytes(*desc, B, H, W);
+    if (capacity < cap) return fail(SWF_ERR_WORKSPACE, "jpeg_encode: capacity of %zu bytes per image, %zu needed", capacity, cap);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "jpeg_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return jpeg_encode(*desc, pixels, header_dev, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.
