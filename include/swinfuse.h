@@ -652,6 +652,89 @@ size_t swf_jpeg_workspace_bytes(const swf_jpeg_desc* desc, int32_t B, int32_t H,
 int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint8_t* header_dev, uint8_t* out, size_t capacity,
                     int32_t* lengths, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- baseline JPEG decoder: the input end of the same loop, many files per call ----------------------------------------------------
+ * Pixels equal to Pillow's on libjpeg-turbo (Image.open(...).convert(mode)), bit for bit: libjpeg's default decode path is three
+ * integer-only pieces, restated here from the published format and the published libjpeg sources.
+ *   scope    baseline sequential DCT (SOF0), 8-bit samples, ONE interleaved scan holding all components; one component (its sampling
+ *            factors are read as 1 x 1) or three with chroma 1 x 1 and luma 1 x 1, 2 x 1 or 2 x 2 (4:4:4, 4:2:2, 4:2:0); up to four
+ *            8-bit quantisation tables and four DC and four AC Huffman tables, arbitrary; any DRI; any APPn / COM; JFIF YCbCr assumed.
+ *   parse    host only.  SWF_ERR_UNSUPPORTED (a caller falls back to another decoder): any other SOFn, DAC, precision not 8, 16-bit DQT,
+ *            2 or 4 or more components, other sampling, a scan that does not hold every component in frame order or is not Ss 0 Se 63
+ *            Ah Al 0, a marker other than EOI behind the scan (several scans), an Adobe APP14 segment with transform 0, components
+ *            named 'R' 'G' 'B' without a JFIF segment, H or W of 0, a file of 2^32 bytes or more.  SWF_ERR_BAD_SHAPE (broken): no SOI, a
+ *            segment running past the file, SOS before SOF, two SOFs, a table the scan or frame names but no segment defined, a DHT
+ *            with more than 256 values, over-subscribed code lengths or a DC symbol above 15, restart markers out of the order RST0 ..
+ *            RST7, RST0 .., or a number of restart intervals other than ceil(MCUs / Ri) (1 for Ri = 0).
+ *   entropy  one lane per restart interval: bytes [begin, end) of the file, 0xFF00 -> 0xFF, the data ending at the first 0xFF that
+ *            is followed by anything else or by nothing; DC predictors from zero; canonical codes (mincode / maxcode / valptr); a
+ *            size-0 AC symbol is ZRL for run 15 and EOB for every other run, as libjpeg reads it.  The interval ENDS with a status
+ *            kind at: a code that needs more bits than the interval has (SWF_JPEG_STREAM_TRUNCATED); a ZRL or a run that puts the next
+ *            coefficient past 63 (SWF_JPEG_STREAM_RUN); 16 bits that start no code, a DC category above 11 or a DC value outside int16
+ *            (SWF_JPEG_STREAM_CODE).  Blocks the interval did not reach are zero, the block it ended in keeps what was decoded.
+ *            status[file] = the largest kind over the file's intervals (0: none), so it does not depend on timing.
+ *   IDCT     dequantised in int32, libjpeg's "islow" 8 x 8 inverse DCT (13-bit constants 2446 3196 4433 6270 7373 9633 12299 15137
+ *            16069 16819 20995 25172, columns rounded at 11 bits, rows at 18), + 128, CLAMPED to 0..255 (libjpeg wraps out-of-range
+ *            results of crafted coefficients instead; a stream an encoder wrote never reaches that).
+ *   finish   libjpeg's "fancy" chroma upsampling: h2v1 (3 this + previous + 1) >> 2 for the even output sample, (3 this + next + 2) >>
+ *            2 for the odd one; h2v2 column sums 3 near + far over the two nearest rows, then (3 this + previous + 8) >> 4 and (3 this +
+ *            next + 7) >> 4; at the edges the outermost real row / column of the down-sampled component (ceil(H / 2), ceil(W / 2))
+ *            repeats.  R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16), G = Y + ((-22554
+ *            (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16), clamped.  Gray from three components is Pillow's convert("L") of that RGB,
+ *            (19595 R + 38470 G + 7471 B + 32768) >> 16; colour from one component is R = G = B = Y.
+ * swf_jpeg_parse and swf_jpeg_decode_workspace_bytes are host-only and touch no GPU. */
+enum { SWF_JPEG_OUT_BGR = 0, SWF_JPEG_OUT_RGB = 1, SWF_JPEG_OUT_GRAY = 2 };   /* [H][W][3], [H][W][3], [H][W] */
+enum { SWF_JPEG_STREAM_OK = 0, SWF_JPEG_STREAM_TRUNCATED = 1, SWF_JPEG_STREAM_RUN = 2, SWF_JPEG_STREAM_CODE = 3 };
+typedef struct swf_jpeg_huff {     /* one Huffman table, Annex F.2.2.3: a code c of length l is a symbol iff c <= maxcode[l] */
+    int32_t mincode[17];           /* [l], l = 1..16: the first code of length l */
+    int32_t maxcode[17];           /* the last one, -1 when the table has none of that length */
+    int32_t valptr[17];            /* index in vals of the symbol of mincode[l] */
+    uint8_t vals[256];
+    uint16_t look[256];            /* by the next 8 bits: (l << 8) | symbol of the code of length l <= 8 they start with, 0 when they start none */
+    int32_t defined;               /* a DHT segment defined it */
+} swf_jpeg_huff;
+typedef struct swf_jpeg_file {
+    uint64_t data_off;             /* SET BY THE CALLER: where the file's bytes start in swf_jpeg_decode's data buffer */
+    uint64_t out_off;              /* SET BY THE CALLER: where its pixels go in swf_jpeg_decode's output buffer */
+    uint32_t data_bytes;           /* the file's size */
+    uint32_t scan_off, scan_end;   /* the entropy-coded data: bytes [scan_off, scan_end) of the file */
+    int32_t H, W, components;      /* components 1 or 3 */
+    int32_t hs, vs;                /* luma sampling: 1 x 1, 2 x 1 or 2 x 2 (hs x vs); 1 x 1 with one component */
+    int32_t mcus_x, mcus_y;        /* ceil(W / (8 hs)), ceil(H / (8 vs)) */
+    int32_t blocks;                /* mcus_x mcus_y (hs vs + components - 1): 8 x 8 blocks of all components */
+    int32_t restart_interval;      /* DRI's Ri in MCUs; 0: the scan is one interval */
+    int32_t intervals;             /* ceil(mcus_x mcus_y / Ri), 1 for Ri = 0 */
+    int32_t comp_quant[3], comp_dc[3], comp_ac[3];   /* table index of each component */
+    uint16_t quant[4][64];         /* natural (row-major) order; tables no segment defined are zero */
+    swf_jpeg_huff dc[4], ac[4];
+} swf_jpeg_file;
+/* Host only.  data[0 .. n): one file.  *file <- its descriptor (data_off = out_off = 0), *intervals_needed <- file->intervals.
+ * intervals: NULL (a size query), or room for intervals_cap pairs of uint32: pair i <- (begin, end) of restart interval i, byte
+ * offsets in the file, the marker behind it excluded; SWF_ERR_WORKSPACE when intervals_cap < file->intervals.  The refusals are
+ * listed above; SWF_ERR_NULL for a NULL data, file or intervals_needed. */
+int swf_jpeg_parse(const uint8_t* data, size_t n, swf_jpeg_file* file, uint32_t* intervals, size_t intervals_cap, size_t* intervals_needed);
+/* Bytes of workspace swf_jpeg_decode needs for these files (the carve of kernels_jpegdec.hip run without memory): two uint32 per file
+ * and one (first interval, first block; a prefix sum the first launch computes), per 8 x 8 block 64 int16 quantised coefficients and 64
+ * uint8 samples.  0 for what the call would refuse.  Host only. */
+size_t swf_jpeg_decode_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files);
+/* data: device buffer of data_bytes bytes holding every file at its data_off.  files_host / files_dev: the n_files descriptors in host
+ * memory, where they are checked, and the same bytes in device memory, where the kernels read them.  intervals_dev: device, the pairs
+ * swf_jpeg_parse wrote, all files' one after another in file order.  out: device buffer of out_bytes bytes; file i's pixels <- out +
+ * out_off in `layout`, H W 3 or H W bytes.  status: device int32 [n_files] <- the stream status of each file.  The workspace holds,
+ * after the call, per file and component the quantised coefficients, [block row][block column][64] int16 in natural order over the
+ * component's grid of whole MCUs (tests read them).  Four launches (prefix sums and status reset; entropy decode, one lane per
+ * interval of any file; dequantise + IDCT, one thread per block; upsample + colour, one thread per pixel); no allocation, no copy to
+ * the host and no synchronisation, so the call can be captured into a hipGraph on one stream.  A file's pixels depend on that file
+ * alone: not on the other files, their order, an earlier use of the workspace, or timing.  Whatever the FILE BYTES are, nothing
+ * outside the file's own coefficients, samples, pixels and status word is written, and nothing outside its bytes is read; the
+ * descriptors and intervals are trusted to be what swf_jpeg_parse wrote (the host copy is checked).
+ * SWF_ERR_NULL for a NULL pointer; SWF_ERR_BAD_SHAPE for n_files < 1, an unknown layout, a descriptor swf_jpeg_parse could not have
+ * written, a file that leaves the data buffer, or pixels that leave the output buffer or overlap another file's; SWF_ERR_UNSUPPORTED
+ * for more than 65535 files or 2^31 - 1 blocks or intervals in one call; SWF_ERR_WORKSPACE for a workspace below the query; all before
+ * anything is launched. */
+int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
+                    const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
+                    size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- resident paired dataset: the reference's training-time input transform (a015_dataset.py:57-66, :89-103) in one launch --------
  * The decoded uint8 images of a training set lie in two device arenas (gray [H][W], BGR [H][W][3], cv2.imread layouts).  A batch is
  * described by B rows; the launch writes ir = u8/255 and vis_y = cv2's uint8 luma/255 (the BGR->YCrCb restatement above) of the crop

@@ -153,6 +153,23 @@ class JpegDesc(C.Structure):   # swf_jpeg_desc
 JPEG_444, JPEG_420 = 0, 1   # SWF_JPEG_444, SWF_JPEG_420
 
 
+class JpegHuff(C.Structure):   # swf_jpeg_huff
+    _fields_ = [("mincode", C.c_int32 * 17), ("maxcode", C.c_int32 * 17), ("valptr", C.c_int32 * 17), ("vals", C.c_uint8 * 256),
+                ("look", C.c_uint16 * 256), ("defined", C.c_int32)]
+
+
+class JpegFile(C.Structure):   # swf_jpeg_file: written by swf_jpeg_parse; data_off and out_off are the caller's
+    _fields_ = [("data_off", C.c_uint64), ("out_off", C.c_uint64), ("data_bytes", C.c_uint32), ("scan_off", C.c_uint32),
+                ("scan_end", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("components", C.c_int32), ("hs", C.c_int32), ("vs", C.c_int32),
+                ("mcus_x", C.c_int32), ("mcus_y", C.c_int32), ("blocks", C.c_int32), ("restart_interval", C.c_int32),
+                ("intervals", C.c_int32), ("comp_quant", C.c_int32 * 3), ("comp_dc", C.c_int32 * 3), ("comp_ac", C.c_int32 * 3),
+                ("quant", (C.c_uint16 * 64) * 4), ("dc", JpegHuff * 4), ("ac", JpegHuff * 4)]
+
+
+JPEG_OUT_BGR, JPEG_OUT_RGB, JPEG_OUT_GRAY = 0, 1, 2                              # SWF_JPEG_OUT_*
+JPEG_STREAM_OK, JPEG_STREAM_TRUNCATED, JPEG_STREAM_RUN, JPEG_STREAM_CODE = 0, 1, 2, 3   # SWF_JPEG_STREAM_*
+
+
 class AdamDesc(C.Structure):
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
                 ("max_grad_norm", C.c_double), ("norm_ready", C.c_int32)]
@@ -264,6 +281,9 @@ SIGNATURES = {
     "swf_jpeg_capacity_bytes": (_sz, [P(JpegDesc), _i32, _i32]),
     "swf_jpeg_workspace_bytes": (_sz, [P(JpegDesc), _i32, _i32, _i32]),
     "swf_jpeg_encode": (C.c_int, [P(JpegDesc), _vp, _vp, _vp, _sz, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_jpeg_parse": (C.c_int, [_vp, _sz, P(JpegFile), _vp, _sz, P(_sz)]),
+    "swf_jpeg_decode_workspace_bytes": (_sz, [_vp, _i32]),
+    "swf_jpeg_decode": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
     "swf_paired_crop_rows_bytes": (_sz, [_i32]),
     "swf_paired_crop_rows_check": (C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64]),
     "swf_paired_crop_resize_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -18,6 +18,7 @@
 #include "kernels_perception.h"
 #include "kernels_comparative.h"
 #include "kernels_jpeg.h"
+#include "kernels_jpegdec.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2494,6 +2495,57 @@ int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "jpeg_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return jpeg_encode(*desc, pixels, header_dev, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// Baseline JPEG decoder.  The parse and the workspace query are host-only; the call checks the host copy of the descriptors, every
+// file's place in the data buffer and every file's pixels in the output buffer before the first launch.
+int swf_jpeg_parse(const uint8_t* data, size_t n, swf_jpeg_file* file, uint32_t* intervals, size_t intervals_cap, size_t* intervals_needed) {
+    if (!data || !file || !intervals_needed) return fail(SWF_ERR_NULL, "jpeg_parse: NULL data, descriptor or count");
+    return jpegdec_parse(data, n, file, intervals, intervals ? intervals_cap : 0, intervals_needed);
+}
+
+static int check_jpeg_files(const swf_jpeg_file* files, int32_t n_files) {
+    if (!files) return fail(SWF_ERR_NULL, "jpeg_decode: NULL descriptors");
+    if (n_files < 1) return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: %d files", n_files);
+    if (n_files > kJpegDecMaxFiles) return fail(SWF_ERR_UNSUPPORTED, "jpeg_decode: %d files in one call (%d at most)", n_files, kJpegDecMaxFiles);
+    for (int32_t i = 0; i < n_files; ++i) SWF_TRY(jpegdec_file_ok(files[i], i));
+    if (jpegdec_workspace_bytes(files, n_files) == 0) return fail(SWF_ERR_UNSUPPORTED, "jpeg_decode: more than 2^31 - 1 blocks or intervals in one call");
+    return SWF_OK;
+}
+
+size_t swf_jpeg_decode_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files) {
+    return check_jpeg_files(files_host, n_files) == SWF_OK ? jpegdec_workspace_bytes(files_host, n_files) : 0;
+}
+
+int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
+                    const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
+                    size_t workspace_bytes, swf_stream_t stream) {
+    if (!data || !files_host || !files_dev || !intervals_dev || !out || !status)
+        return fail(SWF_ERR_NULL, "jpeg_decode: NULL data, descriptors, intervals, output or status");
+    if (layout != SWF_JPEG_OUT_BGR && layout != SWF_JPEG_OUT_RGB && layout != SWF_JPEG_OUT_GRAY)
+        return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: layout %d (0 BGR, 1 RGB, 2 gray)", layout);
+    SWF_TRY(check_jpeg_files(files_host, n_files));
+    const uint64_t px = layout == SWF_JPEG_OUT_GRAY ? 1 : 3;
+    std::vector<std::pair<uint64_t, uint64_t>> ranges((size_t)n_files);
+    for (int32_t i = 0; i < n_files; ++i) {
+        const swf_jpeg_file& f = files_host[i];
+        if (f.data_off > data_bytes || f.data_bytes > data_bytes - f.data_off)
+            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: file %d: bytes [%llu, + %u) leave the data buffer of %zu bytes", i,
+                        (unsigned long long)f.data_off, f.data_bytes, data_bytes);
+        const uint64_t n = (uint64_t)f.H * f.W * px;
+        if (f.out_off > out_bytes || n > out_bytes - f.out_off)
+            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: file %d: pixels [%llu, + %llu) leave the output buffer of %zu bytes", i,
+                        (unsigned long long)f.out_off, (unsigned long long)n, out_bytes);
+        ranges[(size_t)i] = {f.out_off, f.out_off + n};
+    }
+    std::sort(ranges.begin(), ranges.end());
+    for (size_t i = 1; i < ranges.size(); ++i)
+        if (ranges[i].first < ranges[i - 1].second)
+            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: the pixels of two files overlap at byte %llu of the output", (unsigned long long)ranges[i].first);
+    const size_t need = jpegdec_workspace_bytes(files_host, n_files);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return jpegdec_decode(data, files_host, files_dev, n_files, intervals_dev, out, status, layout, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

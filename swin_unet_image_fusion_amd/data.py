@@ -30,6 +30,8 @@ __all__ = ["sample_crop_params", "ResidentPairs", "PairLoader"]
 
 _ROW = np.dtype(L.CropRow)
 _ALIGN = 16
+_DECODE_BUDGET = 256 << 20     # bytes of coefficient workspace one swf_jpeg_decode call of from_folder(decode="device") may take
+_DECODE_GROUP_FILES = 4096     # and files per call
 
 
 def sample_crop_params(H: int, W: int, size=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip: float = 0.5,
@@ -84,6 +86,19 @@ class ResidentPairs:
     def __len__(self) -> int:
         return len(self.items)
 
+    @staticmethod
+    def _place(shapes: Sequence[Tuple[int, int]], paths: Optional[Sequence] = None) -> Tuple[List[tuple], int, int]:
+        """(H, W) per pair -> (items, bytes of ir_arena, bytes of vis_arena): every image at the next 16-byte boundary of its arena."""
+        items, ir_end, vis_end = [], 0, 0
+        for i, (h, w) in enumerate(shapes):
+            ir_off, vis_off = -(-ir_end // _ALIGN) * _ALIGN, -(-vis_end // _ALIGN) * _ALIGN
+            ir_end, vis_end = ir_off + h * w, vis_off + h * w * 3
+            ip, vp = paths[i] if paths is not None else (f"ir/{i}", f"vis/{i}")
+            items.append((ir_off, vis_off, int(h), int(w), ip, vp))
+        if not items:
+            raise ValueError("no image pairs")
+        return items, ir_end, vis_end
+
     @classmethod
     def from_arrays(cls, pairs: Sequence, paths: Optional[Sequence] = None, device="cuda") -> "ResidentPairs":
         """pairs: (ir_u8 of shape (H, W), vis_bgr_u8 of shape (H, W, 3)) numpy arrays or CPU tensors; paths: (ir_path, vis_path) per
@@ -92,20 +107,15 @@ class ResidentPairs:
         and indexed; loading batches from it raises, since the transform runs on the GPU only.)"""
         if paths is not None and len(paths) != len(pairs):
             raise ValueError(f"{len(pairs)} pairs but {len(paths)} paths")
-        arrays, items, ir_end, vis_end = [], [], 0, 0
+        arrays = []
         for i, (ir, vis) in enumerate(pairs):
             ir, vis = (a.numpy() if isinstance(a, torch.Tensor) else np.asarray(a) for a in (ir, vis))
             if ir.dtype != np.uint8 or vis.dtype != np.uint8:
                 raise TypeError(f"pair {i}: expected uint8 images, got {ir.dtype} and {vis.dtype}")
             if ir.ndim != 2 or vis.ndim != 3 or vis.shape[2] != 3 or vis.shape[:2] != ir.shape or ir.size == 0:
                 raise ValueError(f"pair {i}: expected ir (H, W) and vis (H, W, 3) of one size, got {ir.shape} and {vis.shape}")
-            ir_off, vis_off = -(-ir_end // _ALIGN) * _ALIGN, -(-vis_end // _ALIGN) * _ALIGN
-            ir_end, vis_end = ir_off + ir.size, vis_off + vis.size
-            ip, vp = paths[i] if paths is not None else (f"ir/{i}", f"vis/{i}")
-            items.append((ir_off, vis_off, int(ir.shape[0]), int(ir.shape[1]), ip, vp))
             arrays.append((ir, vis))
-        if not items:
-            raise ValueError("no image pairs")
+        items, ir_end, vis_end = cls._place([ir.shape for ir, _ in arrays], paths)
         ir_host, vis_host = np.zeros(ir_end, dtype=np.uint8), np.zeros(vis_end, dtype=np.uint8)
         for (ir_off, vis_off, *_), (ir, vis) in zip(items, arrays):
             ir_host[ir_off:ir_off + ir.size] = ir.reshape(-1)
@@ -113,11 +123,20 @@ class ResidentPairs:
         return cls(torch.from_numpy(ir_host).to(device), torch.from_numpy(vis_host).to(device), items)
 
     @classmethod
-    def from_folder(cls, path, device="cuda") -> "ResidentPairs":
+    def from_folder(cls, path, device="cuda", decode="pil") -> "ResidentPairs":
         """Every file below a directory named `ir` and below one named `vis` under `path`, each list sorted, paired by position
         (a015:38-50).  Decoded with PIL: ir as mode "L" (the gray image), vis as RGB reversed to cv2's BGR.  The reference decodes with
         cv2.imread, which is not available here: DECODE PARITY WITH cv2.imread IS UNPINNED (JPEG decoding and colour-to-gray conversion
-        may differ in the last bits; lossless gray/RGB files decode alike)."""
+        may differ in the last bits; lossless gray/RGB files decode alike).
+
+        decode="device": the files that begin with FF D8 and that swf_jpeg_parse accepts (baseline JPEG, include/swinfuse.h) are decoded
+        by swf_jpeg_decode straight into the arenas, ir as gray and vis as BGR, in groups whose coefficient workspace (192 bytes per
+        8 x 8 block) stays under 256 MiB; every other file goes through PIL as above.  The store is byte-equal to decode="pil"'s with
+        Pillow on libjpeg-turbo.  GPU only."""
+        if decode not in ("pil", "device"):
+            raise ValueError(f"decode {decode!r}: expected 'pil' or 'device'")
+        if decode == "device" and torch.device(device).type != "cuda":
+            raise RuntimeError(f"ResidentPairs.from_folder(decode='device'): the store would live on {device}; the decoder runs on the GPU only")
         from PIL import Image
         ir_paths, vis_paths = [], []
         for root, _, files in os.walk(str(path)):
@@ -129,6 +148,8 @@ class ResidentPairs:
         ir_paths, vis_paths = sorted(ir_paths), sorted(vis_paths)
         if len(ir_paths) != len(vis_paths):
             raise ValueError(f"{path}: {len(ir_paths)} ir files but {len(vis_paths)} vis files")
+        if decode == "device":
+            return cls._from_files_device(ir_paths, vis_paths, torch.device(device))
         pairs = []
         for ip, vp in zip(ir_paths, vis_paths):
             with Image.open(ip) as im:
@@ -137,6 +158,58 @@ class ResidentPairs:
                 vis = np.ascontiguousarray(np.asarray(im.convert("RGB"), dtype=np.uint8)[..., ::-1])
             pairs.append((ir, vis))
         return cls.from_arrays(pairs, list(zip(ir_paths, vis_paths)), device=device)
+
+    @classmethod
+    def _from_files_device(cls, ir_paths: List[str], vis_paths: List[str], device: torch.device) -> "ResidentPairs":
+        """from_folder(decode="device") behind the pairing.  Per file: its bytes and the parser's descriptor, or PIL's array."""
+        from PIL import Image
+
+        from . import imaging
+
+        def read(p, mode):   # -> (bytes, parsed) for the decoder, or (None, array) from PIL
+            with open(p, "rb") as f:
+                data = f.read()
+            if data[:2] == b"\xff\xd8":
+                try:
+                    return data, imaging.parse_jpeg(data)
+                except (NotImplementedError, ValueError):
+                    pass
+            with Image.open(p) as im:
+                a = np.array(im.convert(mode), dtype=np.uint8)
+            return None, (a if mode == "L" else np.ascontiguousarray(a[..., ::-1]))
+
+        def shape(entry):
+            data, x = entry
+            return (x[0].H, x[0].W) if data is not None else tuple(x.shape[:2])
+
+        irs, viss = [read(p, "L") for p in ir_paths], [read(p, "RGB") for p in vis_paths]
+        for i, (a, b) in enumerate(zip(irs, viss)):
+            if shape(a) != shape(b):
+                raise ValueError(f"pair {i}: expected ir (H, W) and vis (H, W, 3) of one size, got {shape(a)} and {shape(b) + (3,)}")
+        items, ir_end, vis_end = cls._place([shape(a) for a in irs], list(zip(ir_paths, vis_paths)))
+        ir_arena, vis_arena = torch.zeros(ir_end, dtype=torch.uint8, device=device), torch.zeros(vis_end, dtype=torch.uint8, device=device)
+        for arena, entries, paths, col, layout in ((ir_arena, irs, ir_paths, 0, "gray"), (vis_arena, viss, vis_paths, 1, "bgr")):
+            group, blocks, pending = [], 0, []
+
+            def flush():
+                if group:
+                    st = imaging.decode_jpeg_into(arena, [items[i][col] for i in group], [entries[i][0] for i in group],
+                                                  [entries[i][1] for i in group], layout)
+                    pending.append((st, [paths[i] for i in group]))
+
+            for i, (data, x) in enumerate(entries):
+                if data is None:
+                    arena[items[i][col]:items[i][col] + x.size].copy_(torch.from_numpy(x.reshape(-1)))
+                    continue
+                if group and ((blocks + x[0].blocks) * 192 > _DECODE_BUDGET or len(group) >= _DECODE_GROUP_FILES):
+                    flush()
+                    group, blocks = [], 0
+                group.append(i)
+                blocks += x[0].blocks
+            flush()
+            for st, names in pending:
+                imaging.check_stream_status(st.cpu().tolist(), names)
+        return cls(ir_arena, vis_arena, items)
 
     def split(self, ratio: float, generator: Optional[torch.Generator] = None) -> Tuple[List[int], List[int]]:
         """Two index lists as `random_split(dataset, [ratio, 1 - ratio])` divides the dataset (a016:46-49): torch's own function on

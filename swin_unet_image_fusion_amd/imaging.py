@@ -7,12 +7,16 @@ libswinfuse on the current stream, no host round trip.
 `encode_jpeg(images_u8)` = the reference's last line, `save_image(fus, "..._MKX_SELF.jpg")` (a017:112-114), up to the write: a baseline JPEG
 encoder as three HIP launches (swf_jpeg_encode), the files of a batch left in device memory until `JpegBatch.to_bytes()` copies what
 they hold.  Decoded by Pillow; the bytes are not libjpeg's: parity with libjpeg's stream is not claimed.
+
+`decode_jpeg(files)` = the input end: baseline JPEG files parsed on the host (swf_jpeg_parse) and decoded in four HIP launches over all
+files of the call (swf_jpeg_decode), pixels equal to Pillow's on libjpeg-turbo bit for bit; `jpeg_info(data)` exposes the parse.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 from torch import Tensor
 
@@ -122,3 +126,95 @@ def encode_jpeg(images_u8: Tensor, quality: int = 75, subsampling: str = "4:2:0"
     L.check(lib.swf_jpeg_encode(C.byref(desc), images_u8.data_ptr(), header.data_ptr(), data.data_ptr(), capacity, lengths.data_ptr(),
                                 b, h, w, workspace.data_ptr(), need, _stream(dev)))
     return JpegBatch(data, lengths)
+
+
+# ---- the decoder ---------------------------------------------------------------------------------------------------------------------
+_LAYOUTS = {"bgr": (L.JPEG_OUT_BGR, 3), "rgb": (L.JPEG_OUT_RGB, 3), "gray": (L.JPEG_OUT_GRAY, 1)}
+_STREAM_KINDS = {L.JPEG_STREAM_TRUNCATED: "the data ends inside a code", L.JPEG_STREAM_RUN: "a run past coefficient 63",
+                 L.JPEG_STREAM_CODE: "an undefined code or a DC value out of range"}
+_INTERVALS_GUESS = 256   # pairs the first parse of a file has room for; a file with more is parsed a second time
+_OUT_ALIGN = 16
+
+
+def parse_jpeg(data: bytes, index: int = 0) -> Tuple["L.JpegFile", np.ndarray]:
+    """swf_jpeg_parse on the host: -> (descriptor, (intervals, 2) uint32 array of (begin, end) byte offsets).  NotImplementedError for a
+    file outside the decoder's scope, ValueError for a broken one, both naming `index`."""
+    lib, desc, need = L.lib(), L.JpegFile(), C.c_size_t(0)
+    src = C.cast(C.c_char_p(data), C.c_void_p)
+    iv = np.empty((_INTERVALS_GUESS, 2), dtype=np.uint32)
+    st = lib.swf_jpeg_parse(src, len(data), C.byref(desc), iv.ctypes.data, len(iv), C.byref(need))
+    if st == L.ERR_WORKSPACE:
+        iv = np.empty((need.value, 2), dtype=np.uint32)
+        st = lib.swf_jpeg_parse(src, len(data), C.byref(desc), iv.ctypes.data, len(iv), C.byref(need))
+    try:
+        L.check(st)
+    except (NotImplementedError, ValueError) as e:
+        raise type(e)(f"file {index}: {e}") from None
+    return desc, iv[:need.value].copy()
+
+
+def jpeg_info(data: bytes) -> dict:
+    """What the parser reads from a file's header and restart markers."""
+    d, iv = parse_jpeg(data)
+    return {"height": d.H, "width": d.W, "components": d.components, "sampling": (d.hs, d.vs), "restart_interval": d.restart_interval,
+            "intervals": len(iv)}
+
+
+def decode_jpeg_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes], parsed: Sequence[tuple], layout: str) -> Tensor:
+    """One swf_jpeg_decode call: file i's pixels to out[offsets[i]:] (flat uint8 on the GPU) in `layout`.  One upload of the files' bytes
+    and one of the descriptors and interval tables; four launches on the current stream.  -> the device int32 stream status per file."""
+    code, _ = _LAYOUTS[layout]
+    out = _u8(out, "out")
+    lib, dev, n = L.lib(), out.device, len(files)
+    descs = (L.JpegFile * n)()
+    pos = 0
+    for i, ((d, _), data) in enumerate(zip(parsed, files)):
+        d.data_off, d.out_off = pos, int(offsets[i])
+        descs[i] = d
+        pos += len(data)
+    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8)] + [iv.reshape(-1).view(np.uint8) for _, iv in parsed])
+    tables_dev = torch.from_numpy(tables).to(dev)
+    data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
+    need = lib.swf_jpeg_decode_workspace_bytes(descs, n)
+    workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    L.check(lib.swf_jpeg_decode(data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n,
+                                tables_dev.data_ptr() + n * C.sizeof(L.JpegFile), out.data_ptr(), out.numel(), status.data_ptr(), code,
+                                workspace.data_ptr(), need, _stream(dev)))
+    return status
+
+
+def check_stream_status(statuses: Sequence[int], names: Optional[Sequence] = None) -> None:
+    """ValueError for the first file whose entropy-coded data ended early, naming it and the kind."""
+    for i, s in enumerate(statuses):
+        if s:
+            raise ValueError(f"file {names[i] if names is not None else i}: corrupt JPEG data: {_STREAM_KINDS.get(s, s)} (status {s})")
+
+
+def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True):
+    """Baseline JPEG files (the scope of swf_jpeg_decode in include/swinfuse.h) -> one uint8 tensor per file, (H, W, 3) for "rgb" and
+    "bgr", (H, W) for "gray": views into one flat device tensor, equal to np.asarray(PIL.Image.open(f).convert(mode)) with Pillow on
+    libjpeg-turbo.  A file the parser refuses raises NotImplementedError (out of scope) or ValueError (broken) naming its index.  The
+    stream statuses are read once after the call; a file whose data ended early raises ValueError, unless strict=False: then
+    (images, statuses) is returned and such a file's image is partly zero coefficients."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("no files")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"decode_jpeg: the decoder runs on the GPU only, got {dev}")
+    parsed = [parse_jpeg(f, i) for i, f in enumerate(files)]
+    px = _LAYOUTS[layout][1]
+    offsets, end = [], 0
+    for d, _ in parsed:
+        offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
+        end = offsets[-1] + d.H * d.W * px
+    out = torch.empty(end, dtype=torch.uint8, device=dev)
+    statuses = decode_jpeg_into(out, offsets, files, parsed, layout).cpu().tolist()
+    images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
+    if strict:
+        check_stream_status(statuses)
+        return images
+    return images, statuses
