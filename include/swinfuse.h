@@ -91,7 +91,8 @@ size_t swf_window_attention_workspace_bytes(const swf_attn_desc* desc, int32_t B
 /* Which kernel shapes the fast tier picks where it has a choice (same arithmetic, results differ in the last bits):
  * LATENCY (default): shortest single forward — eight waves per window at level 2, 32-token MLP tiles at level 3;
  * THROUGHPUT: least CU-time per forward, for callers that keep several forwards in flight on separate streams
- * (ShardedFusion lanes) — four waves per window (two windows per CU), 64-token MLP tiles. */
+ * (ShardedFusion lanes) — four waves per window at level 2, two windows per CU: two resident workgroups on maps of more windows
+ * than CUs, one 512-thread workgroup of two windows (same bits) on maps of up to 2 x CUs windows; 64-token MLP tiles. */
 typedef enum swf_schedule { SWF_SCHED_LATENCY = 0, SWF_SCHED_THROUGHPUT = 1 } swf_schedule;
 
 typedef struct swf_block_desc {

@@ -2,7 +2,8 @@
 // design of kernels_win24.hip / kernels_win48.hip one size up.  A 256-thread workgroup walks windows; wave (stream w >> 1, 32-token
 // half w & 1) owns its tokens through every phase, the MFMA accumulator layout of one linear is the operand layout of the next
 // (weights packed with their k columns in accumulator order), and only the K / V^T images of the attention cross waves (64 KB
-// of LDS for both streams, two workgroups per CU).
+// of LDS for both streams, two workgroups per CU; launches of up to 2 x CUs windows in the throughput schedule: two such groups in
+// one 512-thread workgroup, window96_kernel<.., PAIR>).
 //
 // Layouts.  Channels: three 32-channel tiles; register i of tile T in lane (token r, half hf) is channel 32T + rho(i, hf).
 // Attention: a head owns 16 virtual channels (12 real + 4 spare) = ONE 16-deep k-step: virtual-channel tile T holds heads 2T and
@@ -36,6 +37,9 @@ struct G96 {
     static constexpr size_t p_total = p_bias + size_t(2) * 2 * 16 * 64 * 4;
     // LDS: K images [stream 2][key tile 2][vch tile 4][k-step 2] x 1 KB, V^T images [stream 2][vch tile 4][pv-step 4] x 1 KB, vectors
     static constexpr size_t l_k = 0, l_v = 32 * 1024, l_vec = 64 * 1024, l_total = l_vec + size_t(2) * VSTREAM * 4;
+    // window96_kernel<.., PAIR>: the images of half 0, the images of half 1, one copy of the vectors behind them
+    static constexpr size_t l_vecp = 128 * 1024, l_totalp = l_vecp + size_t(2) * VSTREAM * 4;
+    static_assert(l_totalp <= 160 * 1024, "LDS");
     // window96x8_kernel: the same images, the split-K exchange buffers [wave 8][12][lane 64] x 16 B laid over them, vectors behind
     static constexpr size_t l_vec8 = 96 * 1024, l_total8 = l_vec8 + size_t(2) * VSTREAM * 4;
     // 16x16 windows (window96w16_kernel): bias tiles by key-tile / query-tile distance, fp32 [distance 15][reg/4 4][lane 64][4];
@@ -154,18 +158,35 @@ __device__ __forceinline__ void attention96(const u32x4* ksrc, const u32x4* vsrc
 
 // WS = window side, 8 or 7 (the reference's default): 7x7 windows run on the 8x8 token grid, padding tokens beyond the buffer
 // range (reads 0, stores dropped) and -inf in the packed bias matrix as keys (kernels_win24.hip).
-template <int HID, int WS, int MODE = WIN_BLOCK, bool RAW = false>
-__global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
+//
+// PAIR (whole block only; L96::launch takes it in the throughput schedule when the launch would otherwise put at most one
+// workgroup on most CUs): a 512-thread workgroup of two halves, threads 0-255 and 256-511, each half exactly the four-wave
+// window group above with its own K / V^T images (2 x 64 KB) and its own bias tiles; the fp32 vectors behind them are one
+// copy filled by all 512 threads.  Workgroup g runs window 2g in half 0 and 2g + 1 in half 1, ONE pass (grid = ceil(nwin / 2)), so
+// that the two waves a SIMD then holds cover each other's round trips.  Every row's arithmetic and its order are those of the
+// unpaired form: the outputs are bit-identical.  Barriers are workgroup-wide, so both halves run the same sequence; with one pass
+// that sequence is
+//   1. behind fill_vectors (the "first window" branch, compiled unconditional here),
+//   2. "K / V^T images of both streams complete", ahead of the attention,
+// and nothing else: the overwrite barrier of the first K tile belongs to later passes, the other two to the RAW and MLP-half
+// instantiations.  A half without a window (nwin odd: half 1 of the last workgroup) runs the WHOLE body on the clamped window
+// nwin - 1, with a store descriptor of zero records (the hardware drops its stores) and without the warm-up tail; it branches
+// around nothing and no thread returns before the tail.
+template <int HID, int WS, int MODE = WIN_BLOCK, bool RAW = false, bool PAIR = false>
+__global__ __launch_bounds__(PAIR ? 512 : 256, PAIR ? 1 : 2) void window96_kernel(WinArgs args) {
     using G = G96<HID>;
     static_assert(WS == 7 || WS == 8, "window side");
     static_assert(!RAW || MODE != WIN_BLOCK, "RAW belongs to the half-block modes");
+    static_assert(!PAIR || MODE == WIN_BLOCK, "the paired form runs whole blocks");
     constexpr bool ATT = MODE != WIN_MLP, MLP = MODE != WIN_ATTN;
     extern __shared__ __attribute__((aligned(16))) char smem96[];
-    u32x4* kimg = reinterpret_cast<u32x4*>(smem96 + G::l_k);   // [stream][key tile][vch tile][k-step][lane]
-    u32x4* vimg = reinterpret_cast<u32x4*>(smem96 + G::l_v);   // [stream][vch tile][pv-step][lane]
-    float* lvec = reinterpret_cast<float*>(smem96 + G::l_vec);
+    const int half = PAIR ? __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8) : 0;   // which window group of a paired workgroup
+    char* simg = smem96 + (PAIR ? half * (int)G::l_vec : 0);
+    u32x4* kimg = reinterpret_cast<u32x4*>(simg + G::l_k);   // [stream][key tile][vch tile][k-step][lane]
+    u32x4* vimg = reinterpret_cast<u32x4*>(simg + G::l_v);   // [stream][vch tile][pv-step][lane]
+    float* lvec = reinterpret_cast<float*>(smem96 + (PAIR ? G::l_vecp : G::l_vec));
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = PAIR ? (int)threadIdx.x & 255 : (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ws = wave >> 1, qb = wave & 1, r = lane & 31, hf = lane >> 5;
     const int H = args.H, W = args.W, nwx = ATT ? W / WS : 1, nwy = ATT ? H / WS : 1, npi = nwx * nwy;
     const int nwin = ATT ? args.B * npi : (max(args.ntok[0], args.ntok[1]) + 63) / 64;   // MLP half: 64 tokens of the flat list per step
@@ -176,7 +197,9 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
     const __amdgpu_buffer_rsrc_t krs = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(uniform_ptr(args.packed[kvs])), 0, (int)G::p_total, 0x00020000);
     const int act_bytes = ATT ? args.B * H * W * 96 * 4 : args.ntok[ws] * 96 * 4;   // < 2^31 (launch_win96)
     const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(uniform_ptr(args.in[ws])), 0, act_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, (MODE == WIN_BLOCK || args.out[ws]) ? act_bytes : 0, 0x00020000);
+    // paired form: this half's window, clamped for the half that has none (its stores meet a descriptor of zero records)
+    const bool live = !PAIR || 2 * (int)blockIdx.x + half < nwin;
+    const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(uniform_ptr(args.out[ws]), 0, ((MODE == WIN_BLOCK || args.out[ws]) && live) ? act_bytes : 0, 0x00020000);
     const unsigned loff = (unsigned)lane * 16u;
     auto WF = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(wrs, loff, f * 1024, 0)); };   // own stream: Q, proj, MLP
     auto WK = [&](int f) { return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(krs, loff, f * 1024, 0)); };   // K / V weights
@@ -187,7 +210,8 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
     const bool col_masked = half1 != (((r >> 2) & 1) != 0);
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 
-    for (int win = blockIdx.x; win < nwin; win += gridDim.x) {
+    for (int win = PAIR ? min(2 * (int)blockIdx.x + half, nwin - 1) : (int)blockIdx.x; PAIR || win < nwin; win += gridDim.x) {
+        auto first = [&] { return PAIR || win == (int)blockIdx.x; };   // the workgroup's first pass (the paired form has one)
         SWF_WF_FENCE();
         const int b = win / npi, wrem = win - b * npi;
         const int wy = wrem / nwx, wx = wrem - wy * nwx;
@@ -231,13 +255,13 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
             {
                 f32x16 x[3];
                 load_rows(x);
-                if (win == (int)blockIdx.x) {
+                if (first()) {
                     // the fp32 vectors of both streams -> LDS, once per launch: requested BEHIND the first window's rows and first
                     // weight fragments so that the three round trips overlap (a launch of 256 windows is one window per workgroup:
                     // its prologue is on the critical path)
                     static_assert(G::VSTREAM % 4 == 0 && G::p_vec % 16 == 0, "vector sections move as 16-byte groups");
-                    fill_vectors<G::VSTREAM / 4, 256>(lvec, args.packed[0] + G::p_vec, args.packed[1] + G::p_vec, tid);
-                    __syncthreads();
+                    fill_vectors<G::VSTREAM / 4, PAIR ? 512 : 256>(lvec, args.packed[0] + G::p_vec, args.packed[1] + G::p_vec, (int)threadIdx.x);
+                    __syncthreads();   // paired form: barrier 1 of 2
                 }
                 if constexpr (RAW) raw96(x, xh, xl);
                 else layernorm96(x, vec, G::V_LN1G, G::V_LN1B, xh, xl);
@@ -253,7 +277,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
                 // (wave-uniform) RAW attention: the key / value stream has no queries, the query stream's tokens are nobody's keys; the
                 // barrier of the first K tile is every wave's
                 const bool skip = RAW && (m == 0 ? ws == 1 : ws == 0);
-                if (skip && hp == 9 && win != (int)blockIdx.x) __syncthreads();
+                if (skip && hp == 9 && !first()) __syncthreads();
                 if (half == 0) acc = zero16;
                 if (!skip) {
 #pragma unroll
@@ -276,7 +300,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
                             qf[T][0] = pack8_f16(t);
                             qf[T][1] = pack8_f16(t + 8);
                         } else {
-                            if (T == 0 && win != (int)blockIdx.x) __syncthreads();   // the attention phase of the window before has read the images
+                            if (T == 0 && !first()) __syncthreads();   // the attention phase of the window before has read the images
                             u32x4* kdst = kimg + (((kvs * 2 + qb) * 4 + T) * 2) * 64 + lane;
                             kdst[0] = pack8_f16(t);
                             kdst[64] = pack8_f16(t + 8);
@@ -295,7 +319,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
         // the bias tile of (stream, query block) is requested ahead of the barrier: its L2 round trip runs under the wait
         f32x16 bias[2];
         load_bias_tiles(wrs, loff, (int)G::p_bias, __builtin_amdgcn_readfirstlane(qb) * 2, bias);
-        __syncthreads();   // K / V^T images of both streams complete
+        __syncthreads();   // K / V^T images of both streams complete (paired form: barrier 2 of 2)
         if (RAW && ws == 1) continue;   // RAW: the key / value stream is done with this window
 
         // ---- attention of the wave's 32 queries, 8 heads (shift mask: kernels_win24.hip) ----
@@ -351,7 +375,7 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
 
         } else {   // MLP half: the rows as they are; the fp32 vectors once per launch
             load_rows(res);
-            if (win == (int)blockIdx.x) {
+            if (first()) {
                 fill_vectors<G::VSTREAM / 4, 256>(lvec, args.packed[0] + G::p_vec, args.packed[1] + G::p_vec, tid);
                 __syncthreads();
             }
@@ -410,10 +434,21 @@ __global__ __launch_bounds__(256, 2) void window96_kernel(WinArgs args) {
             const f32x4 v = {res[a >> 2][4 * (a & 3)], res[a >> 2][4 * (a & 3) + 1], res[a >> 2][4 * (a & 3) + 2], res[a >> 2][4 * (a & 3) + 3]};
             __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), ors, tokoff, 32 * a, 0);
         }
+        if constexpr (PAIR) break;   // one pass
     }
 
     // ---- L2 warm-up of the next block's packed weights (see kernels_window.hip) ----
-    if (args.warm[0]) warm_next_block<256>(args, tid);
+    // (paired form: half the workgroups of twice the threads.  warm_next_block slices the image over the gridDim.x / 8 workgroups
+    // that share an XCD, so the slices are twice as long and 512 threads walk each; a workgroup whose half 1 has no window walks
+    // its slice with half 0 alone.)
+    if (args.warm[0]) {
+        if constexpr (PAIR) {
+            if (2 * (int)blockIdx.x + 1 < nwin) warm_next_block<512>(args, (int)threadIdx.x);
+            else if (live) warm_next_block<256>(args, tid);
+        } else {
+            warm_next_block<256>(args, tid);
+        }
+    }
 }
 
 
@@ -1110,7 +1145,19 @@ struct L96 {
             static const bool no_x8 = [] { const char* e = debug_env("SWF_WIN96X8"); return e && e[0] == '0'; }();   // A/B switch (tools)
             // Maps of up to 16 windows (32 x 32 tokens: B=16 256x256 has 256 windows for 256 CUs) take eight waves per window
             // (window96x8_kernel), one workgroup per CU.  The rule looks at the map, never at the batch: batch shards stay bit-identical.
-            // (THROUGHPUT schedule: four waves per window, two windows per CU hide each other's phase latencies)
+            // THROUGHPUT schedule: four waves per window, and two windows per CU so that they hide each other's phase latencies.
+            // `grid` fills every CU with two resident workgroups only from 2 x num_cus() windows on; a launch of num_cus() or fewer
+            // deals them one per CU, a lone wave on every SIMD.  Launches of up to 2 x num_cus() windows take the paired form: two
+            // windows in one 512-thread workgroup on half as many CUs, the others left free for the launches of other lanes.  The
+            // paired form is bit-identical to the unpaired one, so this rule may look at the batch; the route code is the same.
+            static const bool no_pair = [] { const char* e = debug_env("SWF_WIN96_PAIR"); return e && e[0] == '0'; }();   // A/B switch (tools, tests)
+            const int nwin = a.B * (a.H / WS) * (a.W / WS), pairs = (nwin + 1) / 2;
+            if (!no_pair && d.schedule == SWF_SCHED_THROUGHPUT && pairs <= num_cus()) {
+                constexpr int ldsp = (int)G96<HID>::l_totalp;
+                SWF_TRY((raise_lds_limit<&window96_kernel<HID, WS, WIN_BLOCK, false, true>>(ldsp, "window96 paired")));
+                hipLaunchKernelGGL((window96_kernel<HID, WS, WIN_BLOCK, false, true>), dim3(pairs), dim3(512), ldsp, stream, a);
+                return check_launch("window96 paired");
+            }
             if (!no_x8 && d.schedule != SWF_SCHED_THROUGHPUT && (a.H / WS) * (a.W / WS) <= 16) {
                 constexpr int lds8 = (int)G96<HID>::l_total8;
                 SWF_TRY((raise_lds_limit<&window96x8_kernel<HID, WS>>(lds8, "window96x8")));
