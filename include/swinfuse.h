@@ -682,7 +682,23 @@ int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint
  *            repeats.  R = Y + ((91881 (Cr - 128) + 32768) >> 16), B = Y + ((116130 (Cb - 128) + 32768) >> 16), G = Y + ((-22554
  *            (Cb - 128) - 46802 (Cr - 128) + 32768) >> 16), clamped.  Gray from three components is Pillow's convert("L") of that RGB,
  *            (19595 R + 38470 G + 7471 B + 32768) >> 16; colour from one component is R = G = B = Y.
- * swf_jpeg_parse and swf_jpeg_decode_workspace_bytes are host-only and touch no GPU. */
+ *   split    swf_jpeg_decode_split: the same result by another entropy pass, for files whose restart intervals are long (no restart
+ *            markers: one interval, one lane above).  The self-synchronising decode of Klein & Wiseman and Weissenberger & Schmidt:
+ *            each interval's bytes are unstuffed (0xFF00 -> 0xFF, ending as above) into words of the workspace and cut into SEGMENTS of
+ *            segment_bytes unstuffed bytes, max(1, ceil(raw length / segment_bytes)) of them, the raw length being what the host knows
+ *            (trailing segments may be empty).  A decode state is (bit position, block slot in the MCU, zig-zag index).  Every segment is
+ *            decoded speculatively from (its first bit, slot 0, a DC symbol due), one lane per segment, storing nothing; a decode that
+ *            meets what the interval path ends at notes the first such failure and goes on by a fixed rule, since from a wrong state
+ *            failures are the rule and stopping would keep it from ever falling into step.  Then one workgroup per interval hands end
+ *            states from left to right: in round r every segment whose predecessor's end state is not the state it was decoded from
+ *            decodes again; after round r segments 0 .. r are final, so at most segments - 1 rounds, fewer when a round changes
+ *            nothing.  A prefix sum of completed blocks gives each segment its first block; the first noted failure of the final chain,
+ *            if it lies below the interval's block count, is the interval path's.  One more decode per segment stores the coefficients
+ *            (DC differences) into the zero-filled area, up to the failure; a last pass per interval sums the differences per
+ *            component, finds the first predictor outside int16 (the interval path ends there before writing that block), zeroes from
+ *            there on and settles status[file].  IDCT and finish are the launches above.  Coefficients, status and pixels are those of
+ *            swf_jpeg_decode whatever the file bytes are.
+ * swf_jpeg_parse and the two workspace queries are host-only and touch no GPU. */
 enum { SWF_JPEG_OUT_BGR = 0, SWF_JPEG_OUT_RGB = 1, SWF_JPEG_OUT_GRAY = 2 };   /* [H][W][3], [H][W][3], [H][W] */
 enum { SWF_JPEG_STREAM_OK = 0, SWF_JPEG_STREAM_TRUNCATED = 1, SWF_JPEG_STREAM_RUN = 2, SWF_JPEG_STREAM_CODE = 3 };
 typedef struct swf_jpeg_huff {     /* one Huffman table, Annex F.2.2.3: a code c of length l is a symbol iff c <= maxcode[l] */
@@ -735,6 +751,28 @@ size_t swf_jpeg_decode_workspace_bytes(const swf_jpeg_file* files_host, int32_t 
 int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
                     const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
                     size_t workspace_bytes, swf_stream_t stream);
+/* The split path (see "split" above).  intervals_host: the pairs of intervals_dev in host memory; segment counts, grid sizes and the
+ * carve depend on the interval lengths.  segment_bytes: a multiple of 4 in 32 .. 4096.  The workspace starts with the areas of
+ * swf_jpeg_decode at their offsets there (tests read the coefficients the same way); at offset swf_jpeg_decode_workspace_bytes(files_host,
+ * n_files) follows one swf_jpeg_split_diag per interval of the call, in file order; behind them the split pass's own tables (first
+ * segment and first word per interval, unstuffed lengths and words, four records per segment, one per interval).  Ten launches
+ * on the stream (two prefix sums, zero fill, unstuff, speculate, synchronise, write, DC, IDCT, finish); no lane waits
+ * for another workgroup of its launch; otherwise every guarantee and every refusal of swf_jpeg_decode, plus SWF_ERR_NULL for a NULL
+ * intervals_host, SWF_ERR_BAD_SHAPE for another segment_bytes and SWF_ERR_UNSUPPORTED for more than 2^31 - 1 segments or unstuffed
+ * words in one call; all before anything is launched.  The query returns 0 for what the call would refuse.  With SWF_DEBUG_SWITCHES=1,
+ * SWF_JPEG_DECODE_STAGES selects this call's launches by its own bits: 1 prefix sums and zero fill, 2 unstuff, 4 speculate,
+ * 8 synchronise, 16 write, 32 DC, 64 IDCT, 128 finish. */
+typedef struct swf_jpeg_split_diag {
+    uint32_t segments;             /* of the interval */
+    uint32_t rounds;               /* synchronisation rounds run, the one that changed nothing included; 0 for one segment */
+    uint32_t wrong;                /* segments whose speculative end state was not their final one */
+    uint32_t pad_;
+} swf_jpeg_split_diag;
+size_t swf_jpeg_decode_split_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files, const uint32_t* intervals_host,
+                                             int32_t segment_bytes);
+int swf_jpeg_decode_split(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev,
+                          int32_t n_files, const uint32_t* intervals_dev, const uint32_t* intervals_host, int32_t segment_bytes, uint8_t* out,
+                          size_t out_bytes, int32_t* status, int32_t layout, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- resident paired dataset: the reference's training-time input transform (a015_dataset.py:57-66, :89-103) in one launch --------
  * The decoded uint8 images of a training set lie in two device arenas (gray [H][W], BGR [H][W][3], cv2.imread layouts).  A batch is

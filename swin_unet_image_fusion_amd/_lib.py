@@ -284,6 +284,8 @@ SIGNATURES = {
     "swf_jpeg_parse": (C.c_int, [_vp, _sz, P(JpegFile), _vp, _sz, P(_sz)]),
     "swf_jpeg_decode_workspace_bytes": (_sz, [_vp, _i32]),
     "swf_jpeg_decode": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
+    "swf_jpeg_decode_split_workspace_bytes": (_sz, [_vp, _i32, _vp, _i32]),
+    "swf_jpeg_decode_split": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
     "swf_paired_crop_rows_bytes": (_sz, [_i32]),
     "swf_paired_crop_rows_check": (C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64]),
     "swf_paired_crop_resize_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

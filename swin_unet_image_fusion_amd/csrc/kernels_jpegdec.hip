@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "jpegdec_core.h"
+#include "jpegdec_split_core.h"
 
 namespace swf {
 namespace {
@@ -494,6 +495,333 @@ int jpegdec_decode(const uint8_t* data, const swf_jpeg_file* files_host, const s
     const unsigned gx = (unsigned)std::min<int64_t>(cdiv64(t.max_pixels, kJpegDecThreads), 4096);
     hipLaunchKernelGGL(jpegdec_finish_kernel, dim3(gx, (unsigned)n_files), dim3(kJpegDecThreads), 0, stream, files_dev,
                        (const uint32_t*)k.block_first, (const uint8_t*)k.planes, out, layout);
+    return check_launch("jpegdec_finish_kernel");
+}
+
+// ---- split: the entropy decode in parallel inside a restart interval (swf_jpeg_decode_split) -----------------------------------------------
+// jpegdec_split_core.h holds the method and every loop; the kernels here give its lane functions their lanes, barriers and shared arrays:
+//   jpegdec_place_kernel         as above.
+//   jpegsplit_place_kernel       one workgroup: per interval the index of its first segment and of its first unstuffed word among the
+//                                call's (two exclusive prefix sums over the interval lengths).
+//   jpegsplit_zero_kernel        the coefficient area <- 0.
+//   jpegsplit_unstuff_kernel     one workgroup per interval: 0xFF00 -> 0xFF into the interval's words, its length.
+//   jpegsplit_segment_kernel<0>  one lane per segment of any interval: the speculative decode, nothing stored.
+//   jpegsplit_sync_kernel        one workgroup per interval: rounds until every segment was decoded from its true state (at most
+//                                segments - 1 of them), then each segment's first block and the interval's record and diagnostics.
+//   jpegsplit_segment_kernel<1>  one lane per segment: the decode from the true state into the zero-filled coefficient area.
+//   jpegsplit_dc_kernel          one workgroup per interval: DC differences -> predictors, the int16 check, status[file].
+//   jpegdec_idct_kernel, jpegdec_finish_kernel   as above.
+// Launch order on the stream is the only ordering between them; inside a workgroup, __syncthreads.
+namespace {
+
+constexpr int kJpegSplitThreads = 256;   // of a per-interval workgroup
+
+struct JpegSplitCarve {
+    JpegDecCarve base;        // the interval path's areas first, so the coefficients lie where that path leaves them
+    JpegSplitDiag* diag;      // [intervals]: at the offset swf_jpeg_decode_workspace_bytes gives
+    uint32_t* seg_first;      // [intervals + 1]
+    uint32_t* word_first;     // [intervals + 1]
+    uint32_t* ulen;           // [intervals]: unstuffed bytes
+    uint32_t* words;          // [words]: unstuffed data, every interval's at a word boundary
+    JpegSplitState* entry;    // [segments], and the other per-segment records
+    JpegSplitState* end[2];
+    JpegSplitRecord* rec;
+    uint32_t* first;
+    JpegSplitInterval* ivl;   // [intervals]
+};
+
+struct SplitTotals {
+    int64_t segments, words;
+};
+
+JpegSplitCarve carve_split(Carver& c, int n_files, const Totals& t, const SplitTotals& st) {
+    JpegSplitCarve k;
+    k.base = carve(c, n_files, t.blocks);
+    k.diag = reinterpret_cast<JpegSplitDiag*>(c.floats(t.intervals * 4));
+    k.seg_first = reinterpret_cast<uint32_t*>(c.floats(t.intervals + 1));
+    k.word_first = reinterpret_cast<uint32_t*>(c.floats(t.intervals + 1));
+    k.ulen = reinterpret_cast<uint32_t*>(c.floats(t.intervals));
+    k.words = reinterpret_cast<uint32_t*>(c.floats(st.words));
+    k.entry = reinterpret_cast<JpegSplitState*>(c.floats(st.segments * 2));
+    k.end[0] = reinterpret_cast<JpegSplitState*>(c.floats(st.segments * 2));
+    k.end[1] = reinterpret_cast<JpegSplitState*>(c.floats(st.segments * 2));
+    k.rec = reinterpret_cast<JpegSplitRecord*>(c.floats(st.segments * 4));
+    k.first = reinterpret_cast<uint32_t*>(c.floats(st.segments));
+    k.ivl = reinterpret_cast<JpegSplitInterval*>(c.floats(t.intervals * 4));
+    return k;
+}
+
+// What the device computes per interval, on the host copy: the same clamp, the same two counts.
+SplitTotals split_totals(const swf_jpeg_file* files, int n, const uint32_t* iv, int segment_bytes) {
+    SplitTotals st = {0, 0};
+    size_t g = 0;
+    for (int i = 0; i < n; ++i)
+        for (int32_t k = 0; k < files[i].intervals; ++k, ++g) {
+            const uint32_t end = std::min(iv[2 * g + 1], files[i].data_bytes), begin = std::min(iv[2 * g], end);
+            st.segments += jpegsplit_segments(end - begin, (uint32_t)segment_bytes);
+            st.words += jpegsplit_words(end - begin);
+        }
+    return st;
+}
+
+// The coefficient area, 16 bytes per store (a block is 128 bytes and the area is carved at 256): the write pass stores only the
+// coefficients the stream holds.
+__global__ __launch_bounds__(kJpegSplitThreads) void jpegsplit_zero_kernel(uint4* __restrict__ p, uint64_t n) {
+    for (uint64_t i = blockIdx.x * (uint64_t)kJpegSplitThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kJpegSplitThreads)
+        p[i] = make_uint4(0, 0, 0, 0);
+}
+
+// Interval g's bytes in its file, clamped as jpegdec_interval clamps them.
+__device__ __forceinline__ void interval_bytes(const swf_jpeg_file& file, const uint32_t* __restrict__ intervals, uint32_t g, uint32_t& begin,
+                                               uint32_t& end) {
+    end = min(intervals[2 * (size_t)g + 1], file.data_bytes);
+    begin = min(intervals[2 * (size_t)g], end);
+}
+
+// The prefix sums stop at the totals the host carved for, whatever the device copy of the intervals says.
+__global__ __launch_bounds__(kJpegSplitThreads) void jpegsplit_place_kernel(const swf_jpeg_file* __restrict__ files, int n,
+                                                                             const uint32_t* __restrict__ intervals,
+                                                                             const uint32_t* __restrict__ interval_first, uint32_t ni,
+                                                                             uint32_t segment_bytes, uint32_t max_segments, uint32_t max_words,
+                                                                             uint32_t* __restrict__ seg_first, uint32_t* __restrict__ word_first) {
+    __shared__ uint32_t ss[kJpegSplitThreads], sw[kJpegSplitThreads];
+    const int tid = threadIdx.x;
+    const uint32_t per = ni / kJpegSplitThreads + 1u;
+    const uint32_t g0 = min((uint32_t)tid * per, ni), g1 = min(g0 + per, ni);
+    uint64_t segs = 0, words = 0;
+    for (uint32_t g = g0; g < g1; ++g) {
+        uint32_t begin, end;
+        interval_bytes(files[file_of(interval_first, n, g)], intervals, g, begin, end);
+        segs += jpegsplit_segments(end - begin, segment_bytes), words += jpegsplit_words(end - begin);
+    }
+    ss[tid] = (uint32_t)min(segs, (uint64_t)max_segments), sw[tid] = (uint32_t)min(words, (uint64_t)max_words);
+    __syncthreads();
+    uint64_t bs = 0, bw = 0;
+    for (int t = 0; t < tid; ++t) bs += ss[t], bw += sw[t];
+    for (uint32_t g = g0; g < g1; ++g) {
+        seg_first[g] = (uint32_t)min(bs, (uint64_t)max_segments), word_first[g] = (uint32_t)min(bw, (uint64_t)max_words);
+        uint32_t begin, end;
+        interval_bytes(files[file_of(interval_first, n, g)], intervals, g, begin, end);
+        bs += jpegsplit_segments(end - begin, segment_bytes), bw += jpegsplit_words(end - begin);
+    }
+    if (tid == kJpegSplitThreads - 1) seg_first[ni] = (uint32_t)min(bs, (uint64_t)max_segments), word_first[ni] = (uint32_t)min(bw, (uint64_t)max_words);
+}
+
+__global__ __launch_bounds__(kJpegSplitThreads) void jpegsplit_unstuff_kernel(const uint8_t* __restrict__ data,
+                                                                               const swf_jpeg_file* __restrict__ files, int n,
+                                                                               const uint32_t* __restrict__ intervals,
+                                                                               const uint32_t* __restrict__ interval_first,
+                                                                               const uint32_t* __restrict__ word_first, uint32_t* __restrict__ words,
+                                                                               uint32_t* __restrict__ ulen) {
+    __shared__ uint32_t stop, kept[kJpegSplitThreads];
+    const uint32_t g = blockIdx.x;
+    const int tid = threadIdx.x;
+    const swf_jpeg_file& file = files[file_of(interval_first, n, g)];
+    const uint8_t* bytes = data + file.data_off;
+    uint32_t begin, end;
+    interval_bytes(file, intervals, g, begin, end);
+    const uint64_t room = 4ull * (word_first[g + 1] - word_first[g]);   // the interval's words: its whole length when the tables agree
+    if (end - begin > room) end = begin + (uint32_t)room;
+    if (tid == 0) stop = end;
+    __syncthreads();
+    const uint32_t mine = jpegsplit_unstuff_find(bytes, begin, end, tid, kJpegSplitThreads);
+    if (mine < end) atomicMin(&stop, mine);
+    __syncthreads();
+    const uint32_t upto = stop;
+    const uint32_t count = jpegsplit_unstuff_count(bytes, begin, end, upto, tid, kJpegSplitThreads);
+    kept[tid] = count;
+    __syncthreads();
+    uint32_t at = 0;
+    for (int t = 0; t < tid; ++t) at += kept[t];
+    jpegsplit_unstuff_scatter(bytes, begin, end, upto, tid, kJpegSplitThreads, reinterpret_cast<uint8_t*>(words + word_first[g]), at);
+    if (tid == kJpegSplitThreads - 1) ulen[g] = at + count;
+}
+
+// What a lane of the per-segment kernels needs of its interval.
+struct SplitLane {
+    uint32_t g, s, nseg, index;
+    int f;
+};
+__device__ __forceinline__ SplitLane split_lane(uint32_t gs, int n, uint32_t ni, const uint32_t* __restrict__ interval_first,
+                                                const uint32_t* __restrict__ seg_first) {
+    SplitLane l;
+    l.g = (uint32_t)file_of(seg_first, (int)ni, gs);
+    l.s = gs - seg_first[l.g];
+    l.nseg = seg_first[l.g + 1] - seg_first[l.g];
+    l.f = file_of(interval_first, n, l.g);
+    l.index = l.g - interval_first[l.f];
+    return l;
+}
+__device__ __forceinline__ JpegSplitArrays split_arrays(const JpegSplitCarve& k, uint32_t first_segment) {
+    JpegSplitArrays a;
+    a.entry = k.entry + first_segment, a.end[0] = k.end[0] + first_segment, a.end[1] = k.end[1] + first_segment;
+    a.rec = k.rec + first_segment, a.first = k.first + first_segment;
+    return a;
+}
+
+// One wave per workgroup, as jpegdec_entropy_kernel and for its reasons; STORE: the write pass.
+template <bool STORE>
+__global__ __launch_bounds__(kJpegDecEntropyThreads) void jpegsplit_segment_kernel(const swf_jpeg_file* __restrict__ files, int n, uint32_t ni,
+                                                                                    uint32_t segment_bytes, JpegSplitCarve k) {
+    __shared__ swf_jpeg_file shared_file;
+    __shared__ uint8_t zigzag[64];
+    const uint32_t gs = blockIdx.x * (uint32_t)kJpegDecEntropyThreads + threadIdx.x;
+    const bool active = gs < k.seg_first[ni];
+    SplitLane l = {0, 0, 0, 0, -1};
+    if (active) l = split_lane(gs, n, ni, k.base.interval_first, k.seg_first);
+    const int f0 = __builtin_amdgcn_readfirstlane(l.f);   // lane 0 is active: the grid has no workgroup past the last segment
+    const bool one_file = __ballot(active && l.f != f0) == 0 && f0 >= 0;
+    zigzag[threadIdx.x] = kJpegDecZigzag[threadIdx.x];
+    if (one_file) {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(files + f0);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&shared_file);
+        for (int i = threadIdx.x; i < (int)(sizeof(swf_jpeg_file) / 4); i += kJpegDecEntropyThreads) dst[i] = src[i];
+    }
+    __syncthreads();
+    if (!active) return;
+    const swf_jpeg_file& file = one_file ? shared_file : files[l.f];
+    const JpegSplitGeom geom = jpegsplit_geom(file, l.index);
+    const JpegSplitArrays a = split_arrays(k, k.seg_first[l.g]);
+    const uint32_t* words = k.words + k.word_first[l.g];
+    if (STORE)
+        jpegsplit_write(file, geom, zigzag, words, k.ulen[l.g], l.s, l.nseg, segment_bytes, a, k.ivl[l.g],
+                        k.base.coefs + (size_t)k.base.block_first[l.f] * 64);
+    else
+        jpegsplit_speculate(file, geom, zigzag, words, k.ulen[l.g], l.s, l.nseg, segment_bytes, a);
+}
+
+__global__ __launch_bounds__(kJpegSplitThreads) void jpegsplit_sync_kernel(const swf_jpeg_file* __restrict__ files, int n, uint32_t segment_bytes,
+                                                                            JpegSplitCarve k) {
+    __shared__ swf_jpeg_file file;
+    __shared__ uint8_t zigzag[64];
+    __shared__ uint32_t sum[kJpegSplitThreads], failed[kJpegSplitThreads], wrongs[kJpegSplitThreads];
+    const uint32_t g = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int f = file_of(k.base.interval_first, n, g);
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(files + f);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(&file);
+        for (int i = tid; i < (int)(sizeof(swf_jpeg_file) / 4); i += kJpegSplitThreads) dst[i] = src[i];
+        if (tid < 64) zigzag[tid] = kJpegDecZigzag[tid];
+    }
+    __syncthreads();
+    const uint32_t nseg = k.seg_first[g + 1] - k.seg_first[g];
+    if (nseg == 0) return;   // only when the device's intervals are not the host's
+    const JpegSplitGeom geom = jpegsplit_geom(file, g - k.base.interval_first[f]);
+    const JpegSplitArrays a = split_arrays(k, k.seg_first[g]);
+    const uint32_t* words = k.words + k.word_first[g];
+    const uint32_t ulen = k.ulen[g];
+    uint32_t last = 0;
+    for (uint32_t r = 1; r < nseg; ++r) {   // after round r the records of segments 0 .. r are final
+        const bool changed = jpegsplit_round(file, geom, zigzag, words, ulen, nseg, segment_bytes, a, r, tid, kJpegSplitThreads);
+        last = r;
+        if (!__syncthreads_or(changed)) break;   // also orders this round's stores before the next round's loads
+    }
+    jpegsplit_settle_sums(nseg, a, tid, kJpegSplitThreads, sum, failed, wrongs);
+    __syncthreads();
+    jpegsplit_settle(geom, nseg, a, last, tid, kJpegSplitThreads, sum, failed, wrongs, k.ivl + g, k.diag + g);
+}
+
+__global__ __launch_bounds__(kJpegSplitThreads) void jpegsplit_dc_kernel(const swf_jpeg_file* __restrict__ files, int n, JpegSplitCarve k,
+                                                                          int32_t* __restrict__ status) {
+    __shared__ uint32_t sums[3 * kJpegSplitThreads], stop;
+    const uint32_t g = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int f = file_of(k.base.interval_first, n, g);
+    if (k.seg_first[g + 1] == k.seg_first[g]) return;
+    const swf_jpeg_file& file = files[f];   // its geometry only
+    const JpegSplitGeom geom = jpegsplit_geom(file, g - k.base.interval_first[f]);
+    const JpegSplitInterval iv = k.ivl[g];
+    int16_t* coefs = k.base.coefs + (size_t)k.base.block_first[f] * 64;
+    if (tid == 0) stop = geom.nblk;
+    jpegsplit_dc_sums(file, geom, iv, coefs, tid, kJpegSplitThreads, sums);
+    __syncthreads();
+    const uint32_t mine = jpegsplit_dc_walk(file, geom, iv, coefs, tid, kJpegSplitThreads, sums, false, geom.nblk);
+    if (mine < geom.nblk) atomicMin(&stop, mine);
+    __syncthreads();
+    const uint32_t over = stop;
+    jpegsplit_dc_walk(file, geom, iv, coefs, tid, kJpegSplitThreads, sums, true, over);
+    const int kind = jpegsplit_kind(geom, iv, over);
+    if (tid == 0 && kind != SWF_JPEG_STREAM_OK) atomicMax(&status[f], kind);
+}
+
+bool split_segment_ok(int segment_bytes) { return segment_bytes >= 32 && segment_bytes <= 4096 && segment_bytes % 4 == 0; }
+
+}  // namespace
+
+int jpegdec_split_check(const swf_jpeg_file* files_host, int n_files, const uint32_t* intervals_host, int segment_bytes) {
+    if (!intervals_host) return fail(SWF_ERR_NULL, "jpeg_decode_split: NULL host intervals");
+    if (!split_segment_ok(segment_bytes))
+        return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode_split: segment_bytes %d (a multiple of 4 in 32 .. 4096)", segment_bytes);
+    const SplitTotals st = split_totals(files_host, n_files, intervals_host, segment_bytes);
+    if (st.segments > 0x7fffffffLL || st.words > 0x7fffffffLL)
+        return fail(SWF_ERR_UNSUPPORTED, "jpeg_decode_split: %lld segments and %lld words of data in one call (2^31 - 1 at most)",
+                    (long long)st.segments, (long long)st.words);
+    return SWF_OK;
+}
+
+size_t jpegdec_split_workspace_bytes(const swf_jpeg_file* files_host, int n_files, const uint32_t* intervals_host, int segment_bytes) {
+    const Totals t = totals(files_host, n_files);
+    Carver c = Carver::measure();
+    carve_split(c, n_files, t, split_totals(files_host, n_files, intervals_host, segment_bytes));
+    return c.bytes();
+}
+
+int jpegdec_split_decode(const uint8_t* data, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int n_files,
+                         const uint32_t* intervals_dev, const uint32_t* intervals_host, int segment_bytes, uint8_t* out, int32_t* status,
+                         int layout, void* workspace, size_t workspace_bytes, hipStream_t stream) {
+    const Totals t = totals(files_host, n_files);
+    const SplitTotals st = split_totals(files_host, n_files, intervals_host, segment_bytes);
+    Carver c(workspace, workspace_bytes);
+    const JpegSplitCarve k = carve_split(c, n_files, t, st);
+    if (!c.ok()) return fail(SWF_ERR_WORKSPACE, "jpeg_decode_split: workspace of %zu bytes, %zu needed", workspace_bytes, c.bytes());
+    // Tools only (SWF_DEBUG_SWITCHES=1), as in jpegdec_decode, with this call's own bits: 1 both prefix-sum launches and the zero fill,
+    // 2 unstuff, 4 speculate, 8 synchronise, 16 write, 32 DC, 64 IDCT, 128 finish; all by default.
+    const char* e = debug_env("SWF_JPEG_DECODE_STAGES");
+    const int stages = e ? atoi(e) : 255;
+    const uint32_t ni = (uint32_t)t.intervals, seg = (uint32_t)segment_bytes;
+    const unsigned seg_grid = (unsigned)cdiv64(st.segments, kJpegDecEntropyThreads);
+    if (stages & 1) {
+        hipLaunchKernelGGL(jpegdec_place_kernel, dim3(1), dim3(kJpegDecThreads), 0, stream, files_dev, n_files, k.base.interval_first,
+                           k.base.block_first, status);
+        SWF_TRY(check_launch("jpegdec_place_kernel"));
+        hipLaunchKernelGGL(jpegsplit_place_kernel, dim3(1), dim3(kJpegSplitThreads), 0, stream, files_dev, n_files, intervals_dev,
+                           (const uint32_t*)k.base.interval_first, ni, seg, (uint32_t)st.segments, (uint32_t)st.words, k.seg_first, k.word_first);
+        SWF_TRY(check_launch("jpegsplit_place_kernel"));
+        hipLaunchKernelGGL(jpegsplit_zero_kernel, dim3((unsigned)std::min<int64_t>(cdiv64(t.blocks * 8, kJpegSplitThreads), 65536)),
+                           dim3(kJpegSplitThreads), 0, stream, reinterpret_cast<uint4*>(k.base.coefs), (uint64_t)t.blocks * 8);
+        SWF_TRY(check_launch("jpegsplit_zero_kernel"));
+    }
+    if (stages & 2) {
+        hipLaunchKernelGGL(jpegsplit_unstuff_kernel, dim3(ni), dim3(kJpegSplitThreads), 0, stream, data, files_dev, n_files, intervals_dev,
+                           (const uint32_t*)k.base.interval_first, (const uint32_t*)k.word_first, k.words, k.ulen);
+        SWF_TRY(check_launch("jpegsplit_unstuff_kernel"));
+    }
+    if (stages & 4) {
+        hipLaunchKernelGGL(jpegsplit_segment_kernel<false>, dim3(seg_grid), dim3(kJpegDecEntropyThreads), 0, stream, files_dev, n_files, ni, seg, k);
+        SWF_TRY(check_launch("jpegsplit_segment_kernel<speculate>"));
+    }
+    if (stages & 8) {
+        hipLaunchKernelGGL(jpegsplit_sync_kernel, dim3(ni), dim3(kJpegSplitThreads), 0, stream, files_dev, n_files, seg, k);
+        SWF_TRY(check_launch("jpegsplit_sync_kernel"));
+    }
+    if (stages & 16) {
+        hipLaunchKernelGGL(jpegsplit_segment_kernel<true>, dim3(seg_grid), dim3(kJpegDecEntropyThreads), 0, stream, files_dev, n_files, ni, seg, k);
+        SWF_TRY(check_launch("jpegsplit_segment_kernel<write>"));
+    }
+    if (stages & 32) {
+        hipLaunchKernelGGL(jpegsplit_dc_kernel, dim3(ni), dim3(kJpegSplitThreads), 0, stream, files_dev, n_files, k, status);
+        SWF_TRY(check_launch("jpegsplit_dc_kernel"));
+    }
+    if (stages & 64) {
+        hipLaunchKernelGGL(jpegdec_idct_kernel, dim3((unsigned)cdiv64(t.blocks, kJpegDecThreads)), dim3(kJpegDecThreads), 0, stream, files_dev,
+                           n_files, (const uint32_t*)k.base.block_first, (const int16_t*)k.base.coefs, k.base.planes);
+        SWF_TRY(check_launch("jpegdec_idct_kernel"));
+    }
+    if (!(stages & 128)) return SWF_OK;
+    const unsigned gx = (unsigned)std::min<int64_t>(cdiv64(t.max_pixels, kJpegDecThreads), 4096);
+    hipLaunchKernelGGL(jpegdec_finish_kernel, dim3(gx, (unsigned)n_files), dim3(kJpegDecThreads), 0, stream, files_dev,
+                       (const uint32_t*)k.base.block_first, (const uint8_t*)k.base.planes, out, layout);
     return check_launch("jpegdec_finish_kernel");
 }
 

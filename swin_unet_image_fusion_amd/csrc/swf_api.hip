@@ -2517,9 +2517,10 @@ size_t swf_jpeg_decode_workspace_bytes(const swf_jpeg_file* files_host, int32_t 
     return check_jpeg_files(files_host, n_files) == SWF_OK ? jpegdec_workspace_bytes(files_host, n_files) : 0;
 }
 
-int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
-                    const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
-                    size_t workspace_bytes, swf_stream_t stream) {
+// What swf_jpeg_decode and swf_jpeg_decode_split check alike: pointers, layout, descriptors, every file's place in both buffers.
+static int check_jpeg_decode_args(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev,
+                                  int32_t n_files, const uint32_t* intervals_dev, const uint8_t* out, size_t out_bytes, const int32_t* status,
+                                  int32_t layout) {
     if (!data || !files_host || !files_dev || !intervals_dev || !out || !status)
         return fail(SWF_ERR_NULL, "jpeg_decode: NULL data, descriptors, intervals, output or status");
     if (layout != SWF_JPEG_OUT_BGR && layout != SWF_JPEG_OUT_RGB && layout != SWF_JPEG_OUT_GRAY)
@@ -2542,10 +2543,34 @@ int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file*
     for (size_t i = 1; i < ranges.size(); ++i)
         if (ranges[i].first < ranges[i - 1].second)
             return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: the pixels of two files overlap at byte %llu of the output", (unsigned long long)ranges[i].first);
+    return SWF_OK;
+}
+
+int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
+                    const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
+                    size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_jpeg_decode_args(data, data_bytes, files_host, files_dev, n_files, intervals_dev, out, out_bytes, status, layout));
     const size_t need = jpegdec_workspace_bytes(files_host, n_files);
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return jpegdec_decode(data, files_host, files_dev, n_files, intervals_dev, out, status, layout, workspace, workspace_bytes, as_stream(stream));
+}
+
+size_t swf_jpeg_decode_split_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files, const uint32_t* intervals_host, int32_t segment_bytes) {
+    if (check_jpeg_files(files_host, n_files) != SWF_OK || jpegdec_split_check(files_host, n_files, intervals_host, segment_bytes) != SWF_OK) return 0;
+    return jpegdec_split_workspace_bytes(files_host, n_files, intervals_host, segment_bytes);
+}
+
+int swf_jpeg_decode_split(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
+                          const uint32_t* intervals_dev, const uint32_t* intervals_host, int32_t segment_bytes, uint8_t* out, size_t out_bytes,
+                          int32_t* status, int32_t layout, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_jpeg_decode_args(data, data_bytes, files_host, files_dev, n_files, intervals_dev, out, out_bytes, status, layout));
+    SWF_TRY(jpegdec_split_check(files_host, n_files, intervals_host, segment_bytes));
+    const size_t need = jpegdec_split_workspace_bytes(files_host, n_files, intervals_host, segment_bytes);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "jpeg_decode_split: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return jpegdec_split_decode(data, files_host, files_dev, n_files, intervals_dev, intervals_host, segment_bytes, out, status, layout, workspace,
+                                workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

@@ -123,7 +123,7 @@ class ResidentPairs:
         return cls(torch.from_numpy(ir_host).to(device), torch.from_numpy(vis_host).to(device), items)
 
     @classmethod
-    def from_folder(cls, path, device="cuda", decode="pil") -> "ResidentPairs":
+    def from_folder(cls, path, device="cuda", decode="pil", entropy="interval") -> "ResidentPairs":
         """Every file below a directory named `ir` and below one named `vis` under `path`, each list sorted, paired by position
         (a015:38-50).  Decoded with PIL: ir as mode "L" (the gray image), vis as RGB reversed to cv2's BGR.  The reference decodes with
         cv2.imread, which is not available here: DECODE PARITY WITH cv2.imread IS UNPINNED (JPEG decoding and colour-to-gray conversion
@@ -132,9 +132,13 @@ class ResidentPairs:
         decode="device": the files that begin with FF D8 and that swf_jpeg_parse accepts (baseline JPEG, include/swinfuse.h) are decoded
         by swf_jpeg_decode straight into the arenas, ir as gray and vis as BGR, in groups whose coefficient workspace (192 bytes per
         8 x 8 block) stays under 256 MiB; every other file goes through PIL as above.  The store is byte-equal to decode="pil"'s with
-        Pillow on libjpeg-turbo.  GPU only."""
+        Pillow on libjpeg-turbo.  GPU only.  entropy: the entropy pass of those calls, "interval", "split" or "auto" as
+        imaging.decode_jpeg_into describes them; for the latter two a group's budget also counts the split pass's tables (the unstuffed
+        bytes and 44 bytes per segment)."""
         if decode not in ("pil", "device"):
             raise ValueError(f"decode {decode!r}: expected 'pil' or 'device'")
+        if entropy not in ("interval", "split", "auto"):
+            raise ValueError(f"entropy {entropy!r}: expected 'interval', 'split' or 'auto'")
         if decode == "device" and torch.device(device).type != "cuda":
             raise RuntimeError(f"ResidentPairs.from_folder(decode='device'): the store would live on {device}; the decoder runs on the GPU only")
         from PIL import Image
@@ -149,7 +153,7 @@ class ResidentPairs:
         if len(ir_paths) != len(vis_paths):
             raise ValueError(f"{path}: {len(ir_paths)} ir files but {len(vis_paths)} vis files")
         if decode == "device":
-            return cls._from_files_device(ir_paths, vis_paths, torch.device(device))
+            return cls._from_files_device(ir_paths, vis_paths, torch.device(device), entropy)
         pairs = []
         for ip, vp in zip(ir_paths, vis_paths):
             with Image.open(ip) as im:
@@ -160,7 +164,7 @@ class ResidentPairs:
         return cls.from_arrays(pairs, list(zip(ir_paths, vis_paths)), device=device)
 
     @classmethod
-    def _from_files_device(cls, ir_paths: List[str], vis_paths: List[str], device: torch.device) -> "ResidentPairs":
+    def _from_files_device(cls, ir_paths: List[str], vis_paths: List[str], device: torch.device, entropy: str = "interval") -> "ResidentPairs":
         """from_folder(decode="device") behind the pairing.  Per file: its bytes and the parser's descriptor, or PIL's array."""
         from PIL import Image
 
@@ -182,6 +186,16 @@ class ResidentPairs:
             data, x = entry
             return (x[0].H, x[0].W) if data is not None else tuple(x.shape[:2])
 
+        # Bytes of a file in a group's budget: coefficients and samples, and what the split pass adds to them.  An estimate on the safe
+        # side of a soft budget: "auto" counts the split tables although the group's call may take the interval path, and the 256-byte
+        # alignment of the carved arrays (a few KB per call) is left out; imaging.split_workspace_bytes gives a call's exact size.
+        def workspace(x):
+            if entropy == "interval":
+                return x[0].blocks * 192
+            raw = x[1][:, 1].astype(np.int64) - x[1][:, 0]
+            segments = np.maximum(1, -(-raw // imaging._SEGMENT_BYTES))
+            return x[0].blocks * 192 + int((4 * -(-raw // 4) + 44 * segments + 48).sum())
+
         irs, viss = [read(p, "L") for p in ir_paths], [read(p, "RGB") for p in vis_paths]
         for i, (a, b) in enumerate(zip(irs, viss)):
             if shape(a) != shape(b):
@@ -189,23 +203,23 @@ class ResidentPairs:
         items, ir_end, vis_end = cls._place([shape(a) for a in irs], list(zip(ir_paths, vis_paths)))
         ir_arena, vis_arena = torch.zeros(ir_end, dtype=torch.uint8, device=device), torch.zeros(vis_end, dtype=torch.uint8, device=device)
         for arena, entries, paths, col, layout in ((ir_arena, irs, ir_paths, 0, "gray"), (vis_arena, viss, vis_paths, 1, "bgr")):
-            group, blocks, pending = [], 0, []
+            group, used, pending = [], 0, []
 
             def flush():
                 if group:
                     st = imaging.decode_jpeg_into(arena, [items[i][col] for i in group], [entries[i][0] for i in group],
-                                                  [entries[i][1] for i in group], layout)
+                                                  [entries[i][1] for i in group], layout, entropy)
                     pending.append((st, [paths[i] for i in group]))
 
             for i, (data, x) in enumerate(entries):
                 if data is None:
                     arena[items[i][col]:items[i][col] + x.size].copy_(torch.from_numpy(x.reshape(-1)))
                     continue
-                if group and ((blocks + x[0].blocks) * 192 > _DECODE_BUDGET or len(group) >= _DECODE_GROUP_FILES):
+                if group and (used + workspace(x) > _DECODE_BUDGET or len(group) >= _DECODE_GROUP_FILES):
                     flush()
-                    group, blocks = [], 0
+                    group, used = [], 0
                 group.append(i)
-                blocks += x[0].blocks
+                used += workspace(x)
             flush()
             for st, names in pending:
                 imaging.check_stream_status(st.cpu().tolist(), names)

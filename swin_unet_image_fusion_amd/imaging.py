@@ -10,6 +10,8 @@ they hold.  Decoded by Pillow; the bytes are not libjpeg's: parity with libjpeg'
 
 `decode_jpeg(files)` = the input end: baseline JPEG files parsed on the host (swf_jpeg_parse) and decoded in four HIP launches over all
 files of the call (swf_jpeg_decode), pixels equal to Pillow's on libjpeg-turbo bit for bit; `jpeg_info(data)` exposes the parse.
+`entropy="split"` decodes in parallel inside every restart interval (swf_jpeg_decode_split), which is what files without restart
+markers need; `"auto"` chooses by the call's longest interval.  The result does not depend on the choice.
 """
 from __future__ import annotations
 
@@ -160,10 +162,43 @@ def jpeg_info(data: bytes) -> dict:
             "intervals": len(iv)}
 
 
-def decode_jpeg_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes], parsed: Sequence[tuple], layout: str) -> Tensor:
-    """One swf_jpeg_decode call: file i's pixels to out[offsets[i]:] (flat uint8 on the GPU) in `layout`.  One upload of the files' bytes
-    and one of the descriptors and interval tables; four launches on the current stream.  -> the device int32 stream status per file."""
+ENTROPY = ("interval", "split", "auto")
+# Both set from profiles/r19_jpeg_split.json (one MI355X, 640x480 quality-75 files, tools/jpeg_decode_bench.py --entropy both).
+# Segments of 128 bytes: within 10 % of the fastest size on colour files without restart markers at every count measured (256 bytes is
+# the fastest there), and ahead of 256 on gray files and on files with an interval per MCU row.
+_SEGMENT_BYTES = 128
+# entropy="auto" takes the split path when an interval of the call is longer than this many bytes.  Measured on either side: intervals of
+# 2.1 KB (colour, one per MCU row) lose to the interval path from 256 files up (0.44 x at 1 024), intervals of 6.2 KB (noise content, one
+# per MCU row) win 1.29 x at 256 files, and whole scans of 52 KB and more win 10 x to 35 x.
+_SPLIT_AUTO_BYTES = 4096
+
+
+def choose_entropy(entropy: str, parsed: Sequence[tuple]) -> str:
+    """"interval" or "split" for a call over `parsed` ((descriptor, intervals) per file); ValueError for an unknown `entropy`."""
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy {entropy!r}: expected one of {list(ENTROPY)}")
+    if entropy != "auto":
+        return entropy
+    longest = max((int((iv[:, 1].astype(np.int64) - iv[:, 0]).max()) for _, iv in parsed if len(iv)), default=0)
+    return "split" if longest > _SPLIT_AUTO_BYTES else "interval"
+
+
+def split_workspace_bytes(parsed: Sequence[tuple], segment_bytes: int = _SEGMENT_BYTES) -> int:
+    """Bytes of workspace swf_jpeg_decode_split needs for these files; 0 for what it refuses.  Host only."""
+    n = len(parsed)
+    descs = (L.JpegFile * n)(*[d for d, _ in parsed])
+    iv = np.ascontiguousarray(np.concatenate([iv.reshape(-1) for _, iv in parsed]), dtype=np.uint32)
+    return L.lib().swf_jpeg_decode_split_workspace_bytes(descs, n, iv.ctypes.data, int(segment_bytes))
+
+
+def decode_jpeg_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes], parsed: Sequence[tuple], layout: str,
+                     entropy: str = "interval", segment_bytes: int = _SEGMENT_BYTES) -> Tensor:
+    """One decoder call: file i's pixels to out[offsets[i]:] (flat uint8 on the GPU) in `layout`.  One upload of the files' bytes and one
+    of the descriptors and interval tables; the launches go to the current stream.  entropy "interval" is swf_jpeg_decode (one lane per
+    restart interval), "split" is swf_jpeg_decode_split with segments of `segment_bytes` (lanes inside an interval: for files without
+    restart markers), "auto" chooses by the call's longest interval.  -> the device int32 stream status per file."""
     code, _ = _LAYOUTS[layout]
+    entropy = choose_entropy(entropy, parsed)
     out = _u8(out, "out")
     lib, dev, n = L.lib(), out.device, len(files)
     descs = (L.JpegFile * n)()
@@ -172,15 +207,21 @@ def decode_jpeg_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes]
         d.data_off, d.out_off = pos, int(offsets[i])
         descs[i] = d
         pos += len(data)
-    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8)] + [iv.reshape(-1).view(np.uint8) for _, iv in parsed])
+    intervals = np.ascontiguousarray(np.concatenate([iv.reshape(-1) for _, iv in parsed]), dtype=np.uint32)
+    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8), intervals.view(np.uint8)])
     tables_dev = torch.from_numpy(tables).to(dev)
     data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    head = (data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n, tables_dev.data_ptr() + n * C.sizeof(L.JpegFile))
+    if entropy == "split":
+        need = lib.swf_jpeg_decode_split_workspace_bytes(descs, n, intervals.ctypes.data, int(segment_bytes))
+        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+        L.check(lib.swf_jpeg_decode_split(*head, intervals.ctypes.data, int(segment_bytes), out.data_ptr(), out.numel(), status.data_ptr(), code,
+                                          workspace.data_ptr(), need, _stream(dev)))
+        return status
     need = lib.swf_jpeg_decode_workspace_bytes(descs, n)
     workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    status = torch.empty((n,), dtype=torch.int32, device=dev)
-    L.check(lib.swf_jpeg_decode(data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n,
-                                tables_dev.data_ptr() + n * C.sizeof(L.JpegFile), out.data_ptr(), out.numel(), status.data_ptr(), code,
-                                workspace.data_ptr(), need, _stream(dev)))
+    L.check(lib.swf_jpeg_decode(*head, out.data_ptr(), out.numel(), status.data_ptr(), code, workspace.data_ptr(), need, _stream(dev)))
     return status
 
 
@@ -191,14 +232,18 @@ def check_stream_status(statuses: Sequence[int], names: Optional[Sequence] = Non
             raise ValueError(f"file {names[i] if names is not None else i}: corrupt JPEG data: {_STREAM_KINDS.get(s, s)} (status {s})")
 
 
-def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True):
+def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True, entropy: str = "interval",
+                segment_bytes: int = _SEGMENT_BYTES):
     """Baseline JPEG files (the scope of swf_jpeg_decode in include/swinfuse.h) -> one uint8 tensor per file, (H, W, 3) for "rgb" and
     "bgr", (H, W) for "gray": views into one flat device tensor, equal to np.asarray(PIL.Image.open(f).convert(mode)) with Pillow on
     libjpeg-turbo.  A file the parser refuses raises NotImplementedError (out of scope) or ValueError (broken) naming its index.  The
     stream statuses are read once after the call; a file whose data ended early raises ValueError, unless strict=False: then
-    (images, statuses) is returned and such a file's image is partly zero coefficients."""
+    (images, statuses) is returned and such a file's image is partly zero coefficients.  `entropy` and `segment_bytes`: the entropy pass,
+    as decode_jpeg_into describes them; the result does not depend on them."""
     if layout not in _LAYOUTS:
         raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
+    if entropy not in ENTROPY:
+        raise ValueError(f"entropy {entropy!r}: expected one of {list(ENTROPY)}")
     files = [bytes(f) for f in files]
     if not files:
         raise ValueError("no files")
@@ -212,7 +257,7 @@ def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", stri
         offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
         end = offsets[-1] + d.H * d.W * px
     out = torch.empty(end, dtype=torch.uint8, device=dev)
-    statuses = decode_jpeg_into(out, offsets, files, parsed, layout).cpu().tolist()
+    statuses = decode_jpeg_into(out, offsets, files, parsed, layout, entropy, segment_bytes).cpu().tolist()
     images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
     if strict:
         check_stream_status(statuses)

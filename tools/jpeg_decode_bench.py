@@ -6,9 +6,12 @@ decode="pil" against decode="device" on a folder of pairs, wall time.  The files
 "smooth" is synthetic_pair noise at 1/8 resolution enlarged bicubically plus +-4 of noise (photograph-like statistics); "noise" is
 synthetic_pair itself, the longest streams a file of this size can have.  Median of --iters timed calls after --warmup, HIP events for
 the device side, the host clock for Pillow and the folder; the spread (min, max) is stated beside every median.  One JSON line per
-workload; --out also writes the list to a file.
+workload; --out also writes the list to a file.  --entropy split (or both: the two paths in one process on the same files) times
+swf_jpeg_decode_split at every --segment-bytes, its eight stages (SPLIT_STAGES says how the synchronise and DC launches are timed), and
+reads the rounds it took from its diagnostics records.
 
     python tools/jpeg_decode_bench.py [--iters 20] [--warmup 3] [--counts 1 16 64 256 1024] [--out profiles/r18_jpeg_decode.json]
+    python tools/jpeg_decode_bench.py --entropy both --segment-bytes 64 128 256 512 --counts 1 64 256 1024 --out profiles/r19_jpeg_split.json
     python tools/jpeg_decode_bench.py --rehearse      # no GPU: builds small workloads, parses them and times Pillow only
 """
 import argparse
@@ -33,6 +36,14 @@ import __graft_entry__ as entry
 H, W, QUALITY = 480, 640, 75
 HOST_THREADS = 16
 STAGES = (("place_launch_ms", 1), ("entropy_launch_ms", 2), ("idct_launch_ms", 4), ("finish_launch_ms", 8))
+# (name, stage bits timed, stage bits whose median is taken off).  A stage alone runs on the workspace a whole call left.  That is the
+# stage's own work for all but two: the synchronise launch alone would find every segment already decoded from its true state and run
+# one round that changes nothing, and the DC launch alone would sum predictors as if they were differences.  So synchronise is timed
+# behind the speculation that resets the records, DC behind the write decode that stores the differences, and the median of the first
+# launch alone is subtracted.
+SPLIT_STAGES = (("place_and_zero_launches_ms", 1, 0), ("unstuff_launch_ms", 2, 0), ("speculate_launch_ms", 4, 0),
+                ("synchronise_launch_ms", 4 | 8, 4), ("write_launch_ms", 16, 0), ("dc_launch_ms", 16 | 32, 16), ("idct_launch_ms", 64, 0),
+                ("finish_launch_ms", 128, 0))
 
 
 def spread(times):
@@ -106,9 +117,9 @@ def pillow_times(files, mode, iters, warmup):
 
 
 class DeviceCall:
-    """swf_jpeg_decode over `files` with everything allocated and uploaded once."""
+    """swf_jpeg_decode, or swf_jpeg_decode_split at `segment_bytes`, over `files` with everything allocated and uploaded once."""
 
-    def __init__(self, files, layout, dev):
+    def __init__(self, files, layout, dev, segment_bytes=None):
         from swin_unet_image_fusion_amd import _lib as L, imaging
         from swin_unet_image_fusion_amd.modules import _stream
         self.L, self.lib, n = L, L.lib(), len(files)
@@ -129,7 +140,11 @@ class DeviceCall:
         tables = np.concatenate([np.frombuffer(self.descs, dtype=np.uint8)] + [iv.reshape(-1).view(np.uint8) for _, iv in parsed])
         self.tables = torch.from_numpy(tables.copy()).to(dev)
         self.data = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
-        self.need = self.lib.swf_jpeg_decode_workspace_bytes(self.descs, n)
+        self.base = self.need = self.lib.swf_jpeg_decode_workspace_bytes(self.descs, n)
+        self.segment_bytes = segment_bytes
+        self.iv_host = np.ascontiguousarray(np.concatenate([iv.reshape(-1) for _, iv in parsed]), dtype=np.uint32)
+        if segment_bytes:
+            self.need = self.lib.swf_jpeg_decode_split_workspace_bytes(self.descs, n, self.iv_host.ctypes.data, segment_bytes)
         self.out = torch.empty(end, dtype=torch.uint8, device=dev)
         self.status = torch.empty(n, dtype=torch.int32, device=dev)
         self.ws = torch.empty(self.need, dtype=torch.uint8, device=dev)
@@ -138,9 +153,20 @@ class DeviceCall:
         self.blocks = sum(d.blocks for d, _ in parsed)
 
     def __call__(self):
+        if self.segment_bytes:
+            return self.L.check(self.lib.swf_jpeg_decode_split(
+                self.data.data_ptr(), self.data.numel(), self.descs, self.tables.data_ptr(), self.n,
+                self.tables.data_ptr() + self.n * C.sizeof(self.L.JpegFile), self.iv_host.ctypes.data, self.segment_bytes, self.out.data_ptr(),
+                self.out.numel(), self.status.data_ptr(), self.code, self.ws.data_ptr(), self.need, self.stream))
         self.L.check(self.lib.swf_jpeg_decode(self.data.data_ptr(), self.data.numel(), self.descs, self.tables.data_ptr(), self.n,
                                               self.tables.data_ptr() + self.n * C.sizeof(self.L.JpegFile), self.out.data_ptr(), self.out.numel(),
                                               self.status.data_ptr(), self.code, self.ws.data_ptr(), self.need, self.stream))
+
+    def diag(self):
+        """The split call's record per interval, summed up: segments, and the rounds and wrong speculations the intervals took."""
+        d = self.ws[self.base:self.base + 16 * self.intervals].cpu().numpy().view(np.uint32).reshape(-1, 4).astype(np.int64)
+        return {"segments": int(d[:, 0].sum()), "segments_per_interval_max": int(d[:, 0].max()), "rounds_median": float(np.median(d[:, 1])),
+                "rounds_max": int(d[:, 1].max()), "wrong_speculations": int(d[:, 2].sum())}
 
     def timed(self, iters, warmup, stages=None):
         os.environ.pop("SWF_JPEG_DECODE_STAGES", None)
@@ -160,12 +186,7 @@ def workload(images, n, gray, rows, content, args, dev):
                    f"max of {args.iters} after {args.warmup}",
            "files": n, "gray": gray, "interval_per_mcu_row": rows, "content": content, "bytes_per_file": round(sum(len(f) for f in files) / n, 1)}
     iters = args.iters if n <= 16 else max(3, args.iters // 4)   # Pillow: whole seconds per pass at the larger counts
-    if dev is not None:
-        call = DeviceCall(files, layout, dev)
-        res.update(intervals=call.intervals, blocks=call.blocks, workspace_mb=round(call.need / 2 ** 20, 2), host_parse_ms=round(call.parse_ms, 3))
-        res["hip_call_ms"] = call.timed(args.iters, args.warmup)
-        for name, bit in STAGES:
-            res[name] = call.timed(args.iters, args.warmup, bit)
+    def check(call):
         call()
         torch.cuda.synchronize()
         assert call.status.cpu().tolist() == [0] * n
@@ -174,12 +195,44 @@ def workload(images, n, gray, rows, content, args, dev):
             want = pillow_decode(files[k], mode)
             want = want[..., ::-1] if not gray else want
             assert np.array_equal(flat[call.ranges[k][0]:call.ranges[k][1]].reshape(want.shape), want)
+
+    if dev is not None and args.entropy != "split":
+        call = DeviceCall(files, layout, dev)
+        res.update(intervals=call.intervals, blocks=call.blocks, workspace_mb=round(call.need / 2 ** 20, 2), host_parse_ms=round(call.parse_ms, 3))
+        res["hip_call_ms"] = call.timed(args.iters, args.warmup)
+        for name, bit in STAGES:
+            res[name] = call.timed(args.iters, args.warmup, bit)
+        check(call)
         res["files_per_second"] = round(n / res["hip_call_ms"]["median"] * 1e3, 1)
+    if dev is not None and args.entropy != "interval":
+        res["split"] = {}
+        for seg in args.segment_bytes:
+            call = DeviceCall(files, layout, dev, seg)
+            r = {"workspace_mb": round(call.need / 2 ** 20, 2), "hip_call_ms": call.timed(args.iters, args.warmup)}
+            alone = {}
+            for name, bits, minus in SPLIT_STAGES:
+                t = call.timed(args.iters, args.warmup, bits)
+                if minus:   # timed behind the launch that prepares its input: that launch's median comes off
+                    r[name] = {"median": round(t["median"] - alone[minus]["median"], 4), "with_stages": bits, "with_stages_ms": t,
+                               "minus_stages": minus}
+                else:
+                    r[name] = alone[bits] = t
+            r["stages_sum_ms"] = round(sum(r[name]["median"] for name, _, _ in SPLIT_STAGES), 4)
+            check(call)
+            r.update(call.diag())
+            if "hip_call_ms" in res:
+                r["speedup_vs_interval"] = round(res["hip_call_ms"]["median"] / r["hip_call_ms"]["median"], 3)
+                r["faster_beyond_the_spread"] = r["hip_call_ms"]["max"] < res["hip_call_ms"]["min"]
+            res["split"][str(seg)] = r
+        res.setdefault("intervals", call.intervals)
     one, many, in_flight = pillow_times(files, mode, iters, min(args.warmup, 1))
     res["pillow_1_thread_ms"], res[f"pillow_{HOST_THREADS}_threads_ms"], res[f"pillow_{HOST_THREADS}_threads_files_in_flight"] = one, many, in_flight
-    if dev is not None:
+    if dev is not None and "hip_call_ms" in res:
         res["speedup_vs_pillow_1_thread"] = round(one["median"] / res["hip_call_ms"]["median"], 3)
         res[f"speedup_vs_pillow_{HOST_THREADS}_threads"] = round(many["median"] / res["hip_call_ms"]["median"], 3)
+    for r in res.get("split", {}).values():
+        r["speedup_vs_pillow_1_thread"] = round(one["median"] / r["hip_call_ms"]["median"], 3)
+        r[f"speedup_vs_pillow_{HOST_THREADS}_threads"] = round(many["median"] / r["hip_call_ms"]["median"], 3)
     print(json.dumps(res), flush=True)
     return res
 
@@ -199,8 +252,8 @@ def folder(images, pairs, args, dev):
                     f.write(files[k % len(files)])
         stores = {}
 
-        def load(decode):
-            stores[decode] = ResidentPairs.from_folder(root, device=dev, decode=decode)
+        def load(decode, entropy="interval"):
+            stores[decode] = ResidentPairs.from_folder(root, device=dev, decode=decode, entropy=entropy)
             torch.cuda.synchronize()
 
         res = {"what": f"ResidentPairs.from_folder on {pairs} pairs of {W}x{H} (ir gray, vis colour 4:2:0, quality {QUALITY}, smooth content, no "
@@ -209,6 +262,10 @@ def folder(images, pairs, args, dev):
         iters = max(2, args.iters // 8)
         res["decode_pil_ms"] = host_ms(lambda: load("pil"), iters, 1)
         res["decode_device_ms"] = host_ms(lambda: load("device"), iters, 1)
+        if args.entropy != "interval":
+            assert torch.equal(stores["pil"].ir_arena, stores["device"].ir_arena) and torch.equal(stores["pil"].vis_arena, stores["device"].vis_arena)
+            res["decode_device_split_ms"] = host_ms(lambda: load("device", "split"), iters, 1)
+            res["speedup_split"] = round(res["decode_pil_ms"]["median"] / res["decode_device_split_ms"]["median"], 3)
         assert torch.equal(stores["pil"].ir_arena, stores["device"].ir_arena) and torch.equal(stores["pil"].vis_arena, stores["device"].vis_arena)
         res["speedup"] = round(res["decode_pil_ms"]["median"] / res["decode_device_ms"]["median"], 3)
         print(json.dumps(res), flush=True)
@@ -224,6 +281,8 @@ def main():
     ap.add_argument("--counts", type=int, nargs="+", default=[1, 16, 64, 256, 1024])
     ap.add_argument("--distinct", type=int, default=32)
     ap.add_argument("--pairs", type=int, default=1024)
+    ap.add_argument("--entropy", choices=("interval", "split", "both"), default="interval", help="the entropy pass of the timed calls")
+    ap.add_argument("--segment-bytes", type=int, nargs="+", default=[128], help="segment sizes of the split calls")
     ap.add_argument("--rehearse", action="store_true", help="no GPU: small workloads, the host parse and Pillow only")
     ap.add_argument("--out", default=None, help="also write the list of results to this JSON file")
     args = ap.parse_args()
@@ -251,7 +310,7 @@ def main():
         results.append(folder(smooth, args.pairs, args, dev))
         cross = {}
         for key in ("pillow_1_thread_ms", f"pillow_{HOST_THREADS}_threads_ms"):
-            wins = [r["files"] for r in results[:len(args.counts)] if r["hip_call_ms"]["median"] < r[key]["median"]]
+            wins = [r["files"] for r in results[:len(args.counts)] if "hip_call_ms" in r and r["hip_call_ms"]["median"] < r[key]["median"]]
             cross[key] = min(wins) if wins else None
         results.append({"what": "the smallest measured count of colour files without restart markers at which one swf_jpeg_decode call takes less "
                                 "time than Pillow (null: at none of the counts measured); the counts between two measured ones were not measured",
