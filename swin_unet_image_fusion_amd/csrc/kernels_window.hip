@@ -42,7 +42,7 @@ constexpr size_t cmax(size_t a, size_t b) { return a > b ? a : b; }
 struct AttnMfmaArgs {
     const float* Q[2]; const float* K[2]; const float* V[2]; float* O[2]; const float* table[2];
     unsigned short* Ohi[2]; unsigned short* Olo[2];   // non-null: O is written as split-bf16 planes (row stride ldo) instead
-    const unsigned short* Q16[2]; const unsigned short* K16[2]; const unsigned short* V16[2];   // non-null: Q (pre-scaled bf16), K (bf16), V (fp16)
+    const unsigned short* Q16[2]; const unsigned short* K16[2]; const unsigned short* V16[2];   // non-null: Q (pre-scaled), K, V as f16 (deep-level GEMM epilogue, kernels_deep.hip SP_EPI_QKV16)
     int ldq, ldk, ldv, ldo, B, H, W, heads, shift;
 };
 

@@ -259,6 +259,9 @@ def make_module(c: Case) -> nn.Module:
         m = MyModel(**CONFIGS[c.cfg].model_kwargs(act))
     m.eval()
     load_recipe_into(m, seed=c.seed, flavor="stress")
+    if getattr(c, "regime", ""):     # bwd_width_cases.Case: the weights of a sharp softmax, applied in place after the recipe
+        from tests import regime_cases
+        regime_cases.apply_to_module(m, c.regime)
     return m
 
 

@@ -66,6 +66,7 @@ def ln_slots(c: int) -> int:
 class Case(BT.Case):
     route: str = ""           # attention: the expected kernel;  lds_kb: its LDS request as the table states it (0: not stated)
     lds_kb: int = 0
+    regime: str = ""          # a regime of tests/regime_cases.py, applied to the module's weights after the recipe ("": none)
 
     @property
     def metric(self) -> str:
@@ -79,9 +80,9 @@ def _att(name, d, heads, C, win, bhw, route, lds_kb=0, **kw) -> Case:
                 lds_kb=lds_kb, **kw)
 
 
-def _blk(name, C, hidden, win, bhw, route) -> Case:
+def _blk(name, C, hidden, win, bhw, route, **kw) -> Case:
     b, h, w = bhw
-    return Case("block", name, (), C=C, heads=8, head_dim=C // 8, hidden=hidden, win=win, B=b, H=h, W=w, route=route)
+    return Case("block", name, (), C=C, heads=8, head_dim=C // 8, hidden=hidden, win=win, B=b, H=h, W=w, route=route, **kw)
 
 
 _ATTENTION = [

@@ -126,12 +126,13 @@ def _finish(case, st, expect, guarded, r, outs):
     return r
 
 
-def run_block(case, sched, x, y, *, block=0, swap=False, in_place=False, short=0, expect=L.OK, shift=None, cross=None):
+def run_block(case, sched, x, y, *, block=0, swap=False, in_place=False, short=0, expect=L.OK, shift=None, cross=None, blocks=None):
     """One swf_basic_block_fwd_route call.  x / y: NHWC device tensors (y None: one stream).  block: which BasicBlock of the case's
     module (a stage has four).  swap: the y stream's parameters travel in the x slot and the other way round.  in_place: the outputs
-    are the inputs.  short: bytes withheld from the queried workspace.  Returns outputs (NHWC), the route code and the status."""
+    are the inputs.  short: bytes withheld from the queried workspace.  blocks: device BasicBlocks to run instead of the case's own
+    (tests/test_gpu_regimes.py: the case's module with other weights).  Returns outputs (NHWC), the route code and the status."""
     lib = L.lib()
-    blk = _blocks(case)[block]
+    blk = (blocks or _blocks(case))[block]
     sp = [blk._stream_params(s) for s in (("y", "x") if swap else ("x", "y"))]
     dual = y is not None
     b, h, w, _ = x.shape
