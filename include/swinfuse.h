@@ -653,6 +653,51 @@ size_t swf_jpeg_workspace_bytes(const swf_jpeg_desc* desc, int32_t B, int32_t H,
 int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint8_t* header_dev, uint8_t* out, size_t capacity,
                     int32_t* lengths, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- PNG encoder: the same loop with lossless files, so that the 8-bit levels the fusion metrics are defined on are stored exactly ----
+ * 8-bit gray [B][H][W] (colour type 0) or RGB [B][H][W][3] (colour type 2), not interlaced.  Every conforming decoder returns the input
+ * pixels.  THE BYTES ARE NOT libpng's OR Pillow's; claimed is only that, and that the filtered stream below is a function of the pixels:
+ *   file     signature, IHDR, ONE IDAT, IEND; no other chunk.  The IDAT is a zlib stream: header 0x78 0x01, deflate blocks, Adler-32.
+ *   filter   per row the five PNG filters (None, Sub, Up, Average floor((a + b) / 2), Paeth with ties in the order a, b, c) of the
+ *            unfiltered bytes channels to the left and one row up, zero outside the image; the row takes the filter with the smallest
+ *            sum of min(x, 256 - x) over its filtered bytes, ties to the lowest filter number (libpng's heuristic).  The stream is
+ *            every row's filter byte followed by its filtered bytes.
+ *   blocks   rows_per_block rows of the stream make one deflate block (the last one what is left); BFINAL on the last block only.
+ *   tokens   literals and matches at distance 1 only (no dictionary search): in a block, every maximal stretch of bytes that repeat
+ *            their predecessor (which may lie in the block before, never before the stream) is cut into chunks of 258 from its start;
+ *            a chunk of 3 or more is one match, a shorter one literals.  Each block ends with the end-of-block symbol.
+ *   codes    per block a Huffman code over its literal/length histogram, limited to 15 bits and complete (Kraft sum 1): Huffman's
+ *            lengths where they fit, else lengths cut to the limit and repaired from the limit's level; least frequent symbols take the
+ *            longest codes, ties by symbol number.  The distance code gives symbols 0 and 1 one bit each (no decoder sees a one-code
+ *            tree).  The header codes the lengths with 16, 17 and 18 as zlib does, the code-length code limited to 7 bits the same way.
+ *            A block takes the fixed code instead where that is smaller.  No stored blocks.
+ *   sums     Adler-32 and the IDAT's CRC-32 are combined from per-row and per-1024-byte values; no lane walks a whole stream.
+ * swf_png_capacity_bytes and swf_png_workspace_bytes are host-only. */
+typedef struct swf_png_desc {
+    int32_t channels;         /* 1 (gray) or 3 (RGB) */
+    int32_t rows_per_block;   /* rows of the image per deflate block; 0 = the default, 16 */
+    int32_t reserved;         /* 0 */
+} swf_png_desc;
+/* The most bytes one image's file can take, proved, not measured: 63 bytes of framing (signature 8, IHDR 25, IDAT's length, type and
+ * CRC 12, zlib's header 2 and Adler-32 4, IEND 12), and per block at most 17 + 3 * 19 + 7 * (286 + 30) header bits (every length coded
+ * by itself costs at most the code-length code's 7 bits, and a repeat symbol stands for three lengths or more in at most 7 + 7), 15
+ * bits per stream byte (no code is longer; a match covers three bytes or more in at most 15 + 5 + 1) and 15 for the end-of-block symbol;
+ * the fixed code is taken only where it is smaller.  0 for what the encoder would refuse. */
+size_t swf_png_capacity_bytes(const swf_png_desc* desc, int32_t H, int32_t W);
+/* Bytes of workspace swf_png_encode needs (the carve of kernels_png.hip run without memory): per image the filtered stream, one
+ * 16-bit token per stream byte, two Adler sums per row, and per block its code table, header, size and bit offset.  0 for what the
+ * encoder would refuse. */
+size_t swf_png_workspace_bytes(const swf_png_desc* desc, int32_t B, int32_t H, int32_t W);
+/* pixels: device [B][H][W][channels] uint8.  out: device [B][capacity], capacity >= swf_png_capacity_bytes; out[b][0 .. lengths[b]) <-
+ * the file of image b; nothing outside out[b][0 .. capacity), lengths and the workspace is written.  lengths: device int32 [B].  Six
+ * launches (filter, tokens and codes, framing, emit, CRC segments, CRC); no allocation, no copy to the host and no synchronisation,
+ * so the call can be captured into a hipGraph on one stream.  The bytes of an image depend on that image and the descriptor alone: not
+ * on B, the rest of the batch, an earlier use of the workspace, or timing.
+ * SWF_ERR_NULL for a NULL pointer; SWF_ERR_BAD_SHAPE for B, H or W < 1, channels not 1 or 3, rows_per_block < 0 or reserved != 0;
+ * SWF_ERR_UNSUPPORTED for B H W channels, B times the stream or swf_png_capacity_bytes > 2^31 - 1 (lengths is int32) or a block of more
+ * than 2^22 stream bytes; SWF_ERR_WORKSPACE for a workspace or a capacity below the queries; all before anything is launched. */
+int swf_png_encode(const swf_png_desc* desc, const uint8_t* pixels, uint8_t* out, size_t capacity, int32_t* lengths, int32_t B, int32_t H,
+                   int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- baseline JPEG decoder: the input end of the same loop, many files per call ----------------------------------------------------
  * Pixels equal to Pillow's on libjpeg-turbo (Image.open(...).convert(mode)), bit for bit: libjpeg's default decode path is three
  * integer-only pieces, restated here from the published format and the published libjpeg sources.

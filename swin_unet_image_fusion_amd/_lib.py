@@ -153,6 +153,10 @@ class JpegDesc(C.Structure):   # swf_jpeg_desc
 JPEG_444, JPEG_420 = 0, 1   # SWF_JPEG_444, SWF_JPEG_420
 
 
+class PngDesc(C.Structure):   # swf_png_desc
+    _fields_ = [("channels", C.c_int32), ("rows_per_block", C.c_int32), ("reserved", C.c_int32)]
+
+
 class JpegHuff(C.Structure):   # swf_jpeg_huff
     _fields_ = [("mincode", C.c_int32 * 17), ("maxcode", C.c_int32 * 17), ("valptr", C.c_int32 * 17), ("vals", C.c_uint8 * 256),
                 ("look", C.c_uint16 * 256), ("defined", C.c_int32)]
@@ -281,6 +285,9 @@ SIGNATURES = {
     "swf_jpeg_capacity_bytes": (_sz, [P(JpegDesc), _i32, _i32]),
     "swf_jpeg_workspace_bytes": (_sz, [P(JpegDesc), _i32, _i32, _i32]),
     "swf_jpeg_encode": (C.c_int, [P(JpegDesc), _vp, _vp, _vp, _sz, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_png_capacity_bytes": (_sz, [P(PngDesc), _i32, _i32]),
+    "swf_png_workspace_bytes": (_sz, [P(PngDesc), _i32, _i32, _i32]),
+    "swf_png_encode": (C.c_int, [P(PngDesc), _vp, _vp, _sz, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_jpeg_parse": (C.c_int, [_vp, _sz, P(JpegFile), _vp, _sz, P(_sz)]),
     "swf_jpeg_decode_workspace_bytes": (_sz, [_vp, _i32]),
     "swf_jpeg_decode": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),

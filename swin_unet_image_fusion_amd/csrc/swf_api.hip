@@ -19,6 +19,7 @@
 #include "kernels_comparative.h"
 #include "kernels_jpeg.h"
 #include "kernels_jpegdec.h"
+#include "kernels_png.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2495,6 +2496,43 @@ int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint
     if (!workspace || workspace_bytes < need)
         return fail(SWF_ERR_WORKSPACE, "jpeg_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return jpeg_encode(*desc, pixels, header_dev, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// PNG encoder.  One check of the descriptor and one of the shape serve the two queries and the call.
+static int check_png_desc(const swf_png_desc* d) {
+    if (!d) return fail(SWF_ERR_NULL, "png: NULL descriptor");
+    if (!png_desc_ok(*d))
+        return fail(SWF_ERR_BAD_SHAPE, "png: channels=%d rows_per_block=%d reserved=%d (channels 1 or 3, rows_per_block >= 0, reserved 0)",
+                    d->channels, d->rows_per_block, d->reserved);
+    return SWF_OK;
+}
+
+static int check_png_shape(const swf_png_desc& d, int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "png: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!png_shape_ok(d, B, H, W))
+        return fail(SWF_ERR_UNSUPPORTED, "png: B=%d H=%d W=%d rows_per_block=%d: B H W channels, the streams of the batch and one image's "
+                    "capacity must fit int32, and a block %lld stream bytes", B, H, W, d.rows_per_block, (long long)kPngMaxBlockBytes);
+    return SWF_OK;
+}
+
+size_t swf_png_capacity_bytes(const swf_png_desc* desc, int32_t H, int32_t W) {
+    return check_png_desc(desc) == SWF_OK && check_png_shape(*desc, 1, H, W) == SWF_OK ? png_capacity_bytes(*desc, H, W) : 0;
+}
+
+size_t swf_png_workspace_bytes(const swf_png_desc* desc, int32_t B, int32_t H, int32_t W) {
+    return check_png_desc(desc) == SWF_OK && check_png_shape(*desc, B, H, W) == SWF_OK ? png_workspace_bytes(*desc, B, H, W) : 0;
+}
+
+int swf_png_encode(const swf_png_desc* desc, const uint8_t* pixels, uint8_t* out, size_t capacity, int32_t* lengths, int32_t B, int32_t H,
+                   int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    SWF_TRY(check_png_desc(desc));
+    if (!pixels || !out || !lengths) return fail(SWF_ERR_NULL, "png_encode: NULL pixels, output or lengths");
+    SWF_TRY(check_png_shape(*desc, B, H, W));
+    const size_t cap = png_capacity_bytes(*desc, H, W), need = png_workspace_bytes(*desc, B, H, W);
+    if (capacity < cap) return fail(SWF_ERR_WORKSPACE, "png_encode: capacity of %zu bytes per image, %zu needed", capacity, cap);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "png_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return png_encode(*desc, pixels, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // Baseline JPEG decoder.  The parse and the workspace query are host-only; the call checks the host copy of the descriptors, every

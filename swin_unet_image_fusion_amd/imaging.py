@@ -8,6 +8,11 @@ libswinfuse on the current stream, no host round trip.
 encoder as three HIP launches (swf_jpeg_encode), the files of a batch left in device memory until `JpegBatch.to_bytes()` copies what
 they hold.  Decoded by Pillow; the bytes are not libjpeg's: parity with libjpeg's stream is not claimed.
 
+`encode_png(images_u8)` = the same step with lossless PNG files (swf_png_encode, six HIP launches): 8-bit gray or RGB, every row filtered
+by libpng's heuristic, deflate with matches at distance 1 and one length-limited Huffman code per block of rows.  Every conforming decoder
+returns the input pixels; the bytes are not libpng's or Pillow's: parity with their files is not claimed.  `fuse_images(..., as_uint8=True)`
+on a store built from gray sources, followed by `encode_png`, stores the fused Y levels exactly.
+
 `decode_jpeg(files)` = the input end: baseline JPEG files parsed on the host (swf_jpeg_parse) and decoded in four HIP launches over all
 files of the call (swf_jpeg_decode), pixels equal to Pillow's on libjpeg-turbo bit for bit; `jpeg_info(data)` exposes the parse.
 `entropy="split"` decodes in parallel inside every restart interval (swf_jpeg_decode_split), which is what files without restart
@@ -128,6 +133,34 @@ def encode_jpeg(images_u8: Tensor, quality: int = 75, subsampling: str = "4:2:0"
     L.check(lib.swf_jpeg_encode(C.byref(desc), images_u8.data_ptr(), header.data_ptr(), data.data_ptr(), capacity, lengths.data_ptr(),
                                 b, h, w, workspace.data_ptr(), need, _stream(dev)))
     return JpegBatch(data, lengths)
+
+
+class PngBatch(JpegBatch):
+    """The files of one `encode_png` call, laid out as a JpegBatch is."""
+
+
+def encode_png(images_u8: Tensor, rows_per_block: Optional[int] = None) -> PngBatch:
+    """images_u8 (B,H,W,3) RGB or (B,H,W) gray, uint8 on the GPU -> their PNG files (the format of swf_png_encode in include/swinfuse.h:
+    colour type 2 or 0, 8 bits, one IDAT).  `rows_per_block` rows of the image make one deflate block (None: the library's default, 16).
+    Six launches on the current stream and no copy to the host."""
+    images_u8 = _u8(images_u8, "images")
+    if images_u8.dim() not in (3, 4) or (images_u8.dim() == 4 and images_u8.shape[-1] != 3):
+        raise ValueError(f"expected RGB (B,H,W,3) or gray (B,H,W), got {tuple(images_u8.shape)}")
+    if rows_per_block is not None and int(rows_per_block) < 1:
+        raise ValueError(f"rows_per_block {rows_per_block!r}: expected None or a positive number of rows")
+    b, h, w = images_u8.shape[:3]
+    desc = L.PngDesc(1 if images_u8.dim() == 3 else 3, 0 if rows_per_block is None else int(rows_per_block), 0)
+    lib, dev = L.lib(), images_u8.device
+    capacity = lib.swf_png_capacity_bytes(C.byref(desc), h, w)
+    need = lib.swf_png_workspace_bytes(C.byref(desc), b, h, w)
+    if capacity == 0 or need == 0:   # the queries refuse what the call refuses, before any launch: let the call name the reason
+        L.check(lib.swf_png_encode(C.byref(desc), 1, 1, 0, 1, b, h, w, None, 0, None))
+    data = torch.empty((b, capacity), dtype=torch.uint8, device=dev)
+    lengths = torch.empty((b,), dtype=torch.int32, device=dev)
+    workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(lib.swf_png_encode(C.byref(desc), images_u8.data_ptr(), data.data_ptr(), capacity, lengths.data_ptr(), b, h, w,
+                               workspace.data_ptr(), need, _stream(dev)))
+    return PngBatch(data, lengths)
 
 
 # ---- the decoder ---------------------------------------------------------------------------------------------------------------------
