@@ -19,17 +19,19 @@
 //  * V is computed in the non-transposed form (tokens in rows): its accumulator registers are the key slots of the A operand
 //    of O^T = V^T.P^T.  Virtual channel 4*head+3 of V is the constant 1 (zero weights, bias 1): row 4*head+3 of O^T is the
 //    softmax denominator, summed by the MFMA from the same f16-rounded P as the numerator.
-//  * The 8 heads of a query block share ONE O^T accumulator: head h's product lands in rows 4h..4h+3, i.e. registers
-//    4(h>>1).. of lane half h&1; 4 selects per head copy them out of the per-head product tile.
+//  * The 8 heads of a query block share ONE O^T accumulator: head h's rows 4h..4h+3 are registers 4(h>>1).. of lane half h&1.
+//    P.V runs per head on the 16x16x32 shape (a head's four V rows against its P, not the 32 rows of all heads: win_frag.h,
+//    mfma16_f16); 4 selects per head copy the four result registers into the accumulator of the lane half they belong to.
 //  * Biases ride on a constant-one k slot (the padding of the 24 -> 32 channel tile), the residual is the C operand of the
 //    projection and fc2 MFMAs: no epilogue arithmetic for either.
 //  * The relative-position bias matrix (variant without shift mask) of the wave's (stream, query block) lives in 32
 //    registers for the whole launch and is the C operand of the S^T MFMAs.  The shift mask (a001:217-315) of the edge windows
 //    is structural in this layout: "last window row" masks whole key tiles, "last window column" masks whole lanes.
 //
-// Arithmetic (SWF_PREC_FAST): linear layers split-bf16 x3 (fp32-grade) on v_mfma_f32_32x32x16_bf16; Q.K^T and P.V on
-// v_mfma_f32_32x32x16_f16 (f16 operands are 8x closer to fp32 than bf16 at the same rate); LayerNorm statistics,
-// softmax, ELU, residual stream, accumulators fp32; exp via v_exp_f32 (Wq, bq and the bias matrix carry log2(e)).
+// Arithmetic (SWF_PREC_FAST): linear layers split-bf16 x3 (fp32-grade) on v_mfma_f32_32x32x16_bf16; Q.K^T on
+// v_mfma_f32_32x32x16_f16, P.V on v_mfma_f32_16x16x32_f16 (f16 operands are 8x closer to fp32 than bf16 at the same rate;
+// SURVEY 7(3)); LayerNorm statistics, softmax, ELU, residual stream, accumulators fp32; exp via v_exp_f32 (Wq, bq and the bias
+// matrix carry log2(e)).
 #include "win_host.h"
 
 namespace swf {
@@ -55,14 +57,16 @@ struct G24 {
     static constexpr int V_LN1G = 0, V_LN1B = 12, V_LN2G = 24, V_LN2B = 36, V_B2 = 48;
     static constexpr size_t p_bias = p_vec + 2 * 64 * 4;         // fp32 [query block 2][lane 64][key tile 2][reg 16]
     static constexpr size_t p_total = p_bias + size_t(2) * 2 * 16 * 64 * 4;
-    // LDS (bytes): K images [buf 2][stream 2][key tile 2][k-step 2] x 1 KB, V^T images [buf 2][stream 2][pv-step 4] x 1 KB, vectors
-    static constexpr size_t l_k = 0, l_v = l_k + 16 * 1024, l_vec = l_v + 16 * 1024, l_total = l_vec + 2 * 2 * 64 * 4;
+    // LDS (bytes): K images [buf 2][stream 2][key tile 2][k-step 2] x 1 KB, V^T images [buf 2][stream 2][pv-step 4] x 1 KB, vectors,
+    // 4 KB of zeros
+    static constexpr size_t l_k = 0, l_v = l_k + 16 * 1024, l_vec = l_v + 16 * 1024, l_zero = l_vec + 2 * 2 * 64 * 4,
+                            l_total = l_zero + kPvZeroBytes;   // l_zero: what the non-matching lanes of the P.V A read see (win_frag.h)
     // 16x16 windows (window24w16_kernel): the bias section holds one S^T tile per key-tile / query-tile distance kt - qb + 7
     // (a tile = two window rows of 16 tokens, so the relative positions of a tile pair depend on that distance only):
     // fp32 [distance 15][lane 64][reg 16]
     static constexpr size_t p_total16 = p_bias + size_t(15) * 64 * 16 * 4;
-    // LDS: K images [stream 2][key tile 8][k-step 2] x 1 KB, V^T images [stream 2][pv-step 16] x 1 KB (single-buffered), vectors
-    static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_total16 = l_vec16 + 2 * 2 * 64 * 4;
+    // LDS: K images [stream 2][key tile 8][k-step 2] x 1 KB, V^T images [stream 2][pv-step 16] x 1 KB (single-buffered), vectors, zeros
+    static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_zero16 = l_vec16 + 2 * 2 * 64 * 4, l_total16 = l_zero16 + kPvZeroBytes;
 };
 
 // LayerNorm (eps 1e-5, biased variance) of the lane's token — 12 of its 24 channels sit in this lane (registers 0..11 of
@@ -107,8 +111,17 @@ __device__ __forceinline__ void raw_frags(const f32x16& res, u32x4 (&xh)[2], u32
     split8(n + 8, xh[1], xl[1]);
 }
 
-// Attention of one wave over one chunk of 64 keys: 32 queries x 64 keys x 8 heads.  ksrc / vsrc: the chunk's K and V^T operand
-// images in LDS (+ lane); qf: the wave's own Q fragments; bias: relative-position bias tiles of the chunk, C operand of the S^T
+// The lane's base of the P.V A read (win_frag.h: mfma16_f16): lane l is row 4g + c of k-group l >> 4; a matching lane reads slot
+// 32 hf + c of the V^T block (the head's 4h and the pv-step are added as immediates), every other lane the zero region.
+// vblk: byte offset of the chunk's first V^T block in LDS, zreg: of the zero region.
+__device__ __forceinline__ const u32x4* pv_src24(const char* smem, int lane, unsigned vblk, unsigned zreg) {
+    const unsigned off = pv_match(lane) ? vblk + (unsigned)(((lane & 32) + (lane & 3)) * 16) : zreg + (unsigned)kPvZeroBase;
+    return reinterpret_cast<const u32x4*>(smem + off);
+}
+
+// Attention of one wave over one chunk of 64 keys: 32 queries x 64 keys x 8 heads.  ksrc: the chunk's K operand images in LDS
+// (+ lane); vsrc: the lane's base of the P.V A read (pv_src24: slot 32 hf + c of the chunk's V^T image, or the zero region);
+// qf: the wave's own Q fragments; bias: relative-position bias tiles of the chunk, C operand of the S^T
 // MFMAs (with -inf where the shift mask applies).  o is the O^T accumulator: registers 4a..4a+3 of lane half p = channels 0..2
 // and softmax denominator of head 2a + p; passed in and returned.  ONLINE = false (8x8 / 7x7 windows): the chunk is the whole
 // window and o comes in as zero.
@@ -121,10 +134,9 @@ __device__ __forceinline__ void raw_frags(const f32x16& res, u32x4 (&xh)[2], u32
 template <bool ONLINE>
 __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[2], const f32x16 (&bias)[2], bool half1,
                                             f32x16 o, float* mrun = nullptr) {
-    const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     // Register budget (three, ideally four waves per SIMD): the K / V^T fragments are read from LDS per head (a head's two K
     // fragments serve both S^T passes) instead of being held across the head loop, and a head's P tile is exponentiated, packed
-    // and multiplied eight keys at a time, so that at most the bias (32), the score tile (32, shrinking), the product tile (16)
+    // and multiplied eight keys at a time, so that at most the bias (32), the score tile (32, shrinking), the product rows (4)
     // and the output tile (16) are live together.
 #pragma unroll
     for (int h = 0; h < 8; ++h) {
@@ -160,24 +172,26 @@ __device__ __forceinline__ f32x16 attention24(const u32x4* ksrc, const u32x4* vs
         qm[2 * sub + 1] |= nmb << 16;
         s0 = mfma_f16(ka0, qm, bias[0]);
         s1 = mfma_f16(ka1, qm, bias[1]);
-        // O^T tile of this head = V^T . P^T over the 64 keys; P = exp2(S - max) in f16, one pv-step (16 keys = registers
-        // 8s'.. of key tile kt) at a time: the exponentials of step ps+1 issue under the MFMA of step ps
-        f32x16 t;
+        // O^T rows of this head = V^T . P^T over the 64 keys on the 16x16x32 shape (win_frag.h: mfma16_f16); P = exp2(S - max)
+        // in f16, one pv-step (16 keys = registers 8s'.. of key tile kt) at a time: the exponentials of step ps+1 issue under the
+        // MFMA of step ps
+        f32x4 t;
 #pragma unroll
         for (int ps = 0; ps < 4; ++ps) {
             float p[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) p[j] = __builtin_amdgcn_exp2f((ps >> 1) ? s1[8 * (ps & 1) + j] : s0[8 * (ps & 1) + j]);
             const u32x4 pf = pack8_f16(p);
-            const u32x4 va = vsrc[ps * 64];
-            t = mfma_f16(va, pf, ps == 0 ? zero16 : t);
+            const u32x4 va = vsrc[ps * 64 + h * 4];   // head h = slots 4h .. 4h+3 of the block: an instruction immediate
+            t = mfma16_f16(va, pf, ps == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : t);
             __builtin_amdgcn_sched_barrier(0);
         }
-        // rows 4h .. 4h+3 (3 channels + denominator) = registers 4(h>>1) .. +3 of lane half h & 1
+        // t = rows 4h .. 4h+3 (3 channels + denominator) of the lane's query, in both lane halves; they belong into registers
+        // 4(h>>1) .. +3 of lane half h & 1
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int i = 4 * (h >> 1) + j;
-            o[i] = keep ? (ONLINE ? __builtin_fmaf(o[i], alpha, t[i]) : t[i]) : o[i];
+            o[i] = keep ? (ONLINE ? __builtin_fmaf(o[i], alpha, t[j]) : t[j]) : o[i];
         }
         __builtin_amdgcn_sched_barrier(0);   // one head at a time: interleaving heads doubles the live score tiles
     }
@@ -283,7 +297,10 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
                 for (int e = 0; e < 4; ++e) bias[kt][q4 * 4 + e] = t[e];
             }
     };
-    if constexpr (ATT) load_bias();
+    if constexpr (ATT) {
+        load_bias();
+        pv_fill_zeros<256>(smem + G::l_zero, tid);
+    }
     const bool half1 = hf != 0;
     const bool col_masked = half1 != (((r >> 2) & 1) != 0);   // last-window-column variant: this lane's keys lie across the seam
     __syncthreads();
@@ -320,13 +337,12 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
         // ---- LN1, then Q (own stream's weights), K and V (weights of the stream that attends to these tokens) ----
         u32x4 qf[2];
         {
-            // the residual rows are NOT kept in registers across the attention phase (16 registers of a 168 budget): they are
-            // read again — an L2 hit, the lines were fetched microseconds ago — as the C operand of the projection
-            f32x16 x0;
-            load_rows24(irs, tokoff, x0);
+            // the residual rows STAY in registers across the attention phase (12 registers; the P.V product of a head is 4
+            // registers, not a 16-register tile) and are the C operand of the projection
+            load_rows24(irs, tokoff, res);
             u32x4 xh[2], xl[2];
-            if constexpr (RAW) raw_frags(x0, xh, xl);
-            else layernorm_frags(x0, vec, G::V_LN1G, G::V_LN1B, xh, xl);
+            if constexpr (RAW) raw_frags(res, xh, xl);
+            else layernorm_frags(res, vec, G::V_LN1G, G::V_LN1B, xh, xl);
             f32x16 acc = zero16;
             if (!(RAW && ws == 1)) {   // (wave-uniform) RAW: the key / value stream has no queries
 #pragma unroll
@@ -375,7 +391,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
         {
             const bool rowv = args.shift && wy == nwy - 1, colv = args.shift && wx == nwx - 1;
             const u32x4* ksrc = kimg + ((buf * 2 + ws) * 4) * 64 + lane;
-            const u32x4* vsrc = vimg + ((buf * 2 + ws) * 4) * 64 + lane;
+            const u32x4* vsrc = pv_src24(smem, lane_w, (unsigned)(G::l_v + ((buf * 2 + ws) * 4) * 1024), (unsigned)G::l_zero);
             if (rowv || colv) {
                 const float pen0 = ((rowv && qb == 1) || (colv && col_masked)) ? -INFINITY : 0.f;
                 const float pen1 = ((rowv && qb == 0) || (colv && col_masked)) ? -INFINITY : 0.f;
@@ -388,8 +404,7 @@ __global__ __launch_bounds__(256, W24_WAVES) void window24_kernel(WinArgs args) 
 
         // ---- normalise, output projection + bias + residual: res is the C operand ----
         SWF_WF_FENCE();
-        if constexpr (RAW) res = zero16;
-        else load_rows24(irs, tokoff, res);
+        if constexpr (RAW) res = zero16;   // CrossAttention.forward: no residual
         res = project24<G>(WF, o, res);
         } else {   // MLP half: the rows as they are
             load_rows24(irs, tokoff, res);
@@ -475,6 +490,7 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
     const float* vec = lvec + (ws * 2 + hf) * 64;
     const bool half1 = hf != 0;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    pv_fill_zeros<256>(smem16 + G::l_zero16, tid);
     __syncthreads();
 
     for (int win = blockIdx.x; win < nwin; win += gridDim.x) {
@@ -542,7 +558,6 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
         // ---- phase B: per tile attention over 256 keys, projection, LN2, MLP, store ----
         const bool rowv = args.shift && wy == nwy - 1, colv = args.shift && wx == nwx - 1;
         const u32x4* ksrc = kimg + (ws * 16) * 64 + lane;
-        const u32x4* vsrc = vimg + (ws * 16) * 64 + lane;
 #pragma unroll 1
         for (int jj = 0; jj < 4; ++jj) {
             const int j = 4 * pw + jj;   // query tile
@@ -566,7 +581,9 @@ __global__ __launch_bounds__(256, 2) void window24w16_kernel(WinArgs args) {
                         }
                     if (colv) col_seam16(bias, r);
                 }
-                o = attention24<true>(ksrc + (2 * c) * 2 * 64, vsrc + (4 * c) * 64, qf[0], bias, half1, o, mrun);
+                // (the chunk offset is part of the matching lanes' base only: the zero region is one chunk's worth)
+                const u32x4* vsrc = pv_src24(smem16, lane, (unsigned)(G::l_v16 + (ws * 16 + 4 * c) * 1024), (unsigned)G::l_zero16);
+                o = attention24<true>(ksrc + (2 * c) * 2 * 64, vsrc, qf[0], bias, half1, o, mrun);
             }
             // the next tile's Q fragments move up
 #pragma unroll
@@ -682,7 +699,7 @@ __global__ __launch_bounds__(256) void pack24_kernel(WinPackArgs a) {
     if (p.attn.bias_table) pack_rel_bias<true>(reinterpret_cast<float*>(dst + G::p_bias), p.attn.bias_table, a.ws, gtid, gsz);
 }
 
-// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 65 KB of LDS per workgroup (dynamic
+// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 69 KB of LDS per workgroup (dynamic
 // allocation), two workgroups per CU, 1-D grid.
 struct L24 {
     static constexpr int C = 24, D = 3, HID_WIDE = 96, HID_NARROW = 4, PACK_GRID = 32, WAVES = W24_WAVES;

@@ -42,12 +42,13 @@ struct G48 {
     static constexpr size_t p_vec = size_t(NFRAG) * 1024;
     static constexpr size_t p_bias = (p_vec + size_t(VSTREAM) * 4 + 15) / 16 * 16;   // fp32 [query block 2][key tile 2][reg/4 4][lane 64][4]
     static constexpr size_t p_total = p_bias + size_t(2) * 2 * 16 * 64 * 4;
-    // LDS: K images [stream 2][key tile 2][vch tile 2][k-step 2] x 1 KB, V^T images [stream 2][vch tile 2][pv-step 4] x 1 KB, vectors
-    static constexpr size_t l_k = 0, l_v = 16 * 1024, l_vec = 32 * 1024, l_total = l_vec + size_t(2) * VSTREAM * 4;
+    // LDS: K images [stream 2][key tile 2][vch tile 2][k-step 2] x 1 KB, V^T images [stream 2][vch tile 2][pv-step 4] x 1 KB, vectors,
+    // 4 KB of zeros (what the non-matching lanes of the P.V A read see: win_frag.h)
+    static constexpr size_t l_k = 0, l_v = 16 * 1024, l_vec = 32 * 1024, l_zero = l_vec + size_t(2) * VSTREAM * 4, l_total = l_zero + kPvZeroBytes;
     // 16x16 windows (window48w16_kernel): bias tiles by key-tile / query-tile distance, fp32 [distance 15][reg/4 4][lane 64][4];
-    // LDS of ONE stream: K images [key tile 8][vch tile 2][k-step 2] x 1 KB, V^T images [vch tile 2][pv-step 16] x 1 KB, vectors
+    // LDS of ONE stream: K images [key tile 8][vch tile 2][k-step 2] x 1 KB, V^T images [vch tile 2][pv-step 16] x 1 KB, vectors, zeros
     static constexpr size_t p_total16 = p_bias + size_t(15) * 16 * 64 * 4;
-    static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_total16 = l_vec16 + size_t(2) * VSTREAM * 4;
+    static constexpr size_t l_k16 = 0, l_v16 = 32 * 1024, l_vec16 = 64 * 1024, l_zero16 = l_vec16 + size_t(2) * VSTREAM * 4, l_total16 = l_zero16 + kPvZeroBytes;
 };
 
 // launch modes of window48_kernel: win_level.h (WIN_BLOCK, WIN_ATTN, WIN_MLP; RAW = no LayerNorm, no residual)
@@ -93,16 +94,26 @@ __device__ __forceinline__ void layernorm48(const f32x16& x0, const f32x16& x1, 
     split8(n + 16, xh[2], xl[2]);
 }
 
-// Attention of one wave: 32 queries x 64 keys x 8 heads.  ksrc / vsrc: the stream's K and V^T operand images in LDS (+ lane);
+// The lane's base of the P.V A read in V^T tile T (win_frag.h: mfma16_f16): lane l is row 4g + c of k-group l >> 4; a head is 8 rows,
+// row groups 0 / 1 deliver its channels 0..3 (to lane half 0), row groups 2 / 3 channels 4, 5, the denominator and the spare row
+// (to lane half 1): a matching lane reads slot 32 hf + 4 (g >> 1) + c of the block (the head's 8 hq and the pv-step are added as
+// immediates), every other lane the zero region.  vblk: byte offset of the tile's first V^T block of the chunk, zreg: of the zeros.
+__device__ __forceinline__ const u32x4* pv_src48(const char* smem, int lane, unsigned vblk, unsigned zreg) {
+    const unsigned off = pv_match(lane) ? vblk + (unsigned)(((lane & 32) + ((lane >> 1) & 4) + (lane & 3)) * 16) : zreg + (unsigned)kPvZeroBase;
+    return reinterpret_cast<const u32x4*>(smem + off);
+}
+
+// Attention of one wave: 32 queries x 64 keys x 8 heads.  ksrc: the stream's K operand images in LDS (+ lane); vsrc[T]: the lane's
+// base of the P.V A read in V^T tile T (pv_src48);
 // qf[tile][k-step]: the wave's own Q fragments; bias: relative-position bias of (stream, query block), with -inf where the shift
 // mask applies (the reference assigns -1e10 to those scores: probability exactly 0).  Returns the two O^T tiles: registers 4q..4q+3 of tile T = head 4T+q:
 // lane half 0 channels 0..3, lane half 1 channels 4, 5, the softmax denominator, 0.
 // ONLINE (16x16 windows): the 64 keys are one chunk of a window's 256 — o is not cleared but rescaled, o = o * 2^(m_old - m_new) + t,
-// with the running maximum mrun[head] kept as the f16 value the second S^T pass subtracts; VSTEPS = pv-steps per V^T tile of the image.
+// with the running maximum mrun[head] kept as the f16 value the second S^T pass subtracts.
 // (Signature: o stays the array reference this function always took — unlike attention24, whose single tile goes by value; mrun is
 // a plain pointer, unused when !ONLINE.)
-template <bool ONLINE, int VSTEPS = 4>
-__device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc, const u32x4 (&qf)[2][2], const f32x16 (&bias)[2],
+template <bool ONLINE>
+__device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* const (&vsrc)[2], const u32x4 (&qf)[2][2], const f32x16 (&bias)[2],
                                             bool half1, f32x16 (&o)[2], float* mrun = nullptr) {
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if constexpr (!ONLINE) { o[0] = zero16; o[1] = zero16; }
@@ -142,7 +153,7 @@ __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc
             mrun[h] = mnew;
         }
         qm[2 * sub + 1] |= half1 ? ((unsigned)__builtin_bit_cast(unsigned short, nm) << 16) : 0u;
-        f32x16 t;
+        f32x4 t;   // the head's rows of the lane's query: lane half 0 channels 0..3, lane half 1 channels 4, 5, denominator, spare
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
             f32x16 sc = mfma_f16(kt ? ka1 : ka0, qm, bias[kt]);
@@ -152,13 +163,13 @@ __device__ __forceinline__ void attention48(const u32x4* ksrc, const u32x4* vsrc
 #pragma unroll
                 for (int j = 0; j < 8; ++j) p[j] = __builtin_amdgcn_exp2f(sc[8 * s2 + j]);
                 const u32x4 pf = pack8_f16(p);
-                const u32x4 va = vsrc[(T * VSTEPS + 2 * kt + s2) * 64];
-                t = mfma_f16(va, pf, (kt == 0 && s2 == 0) ? zero16 : t);
+                const u32x4 va = vsrc[T][(2 * kt + s2) * 64 + hq * 8];
+                t = mfma16_f16(va, pf, (kt == 0 && s2 == 0) ? f32x4{0.f, 0.f, 0.f, 0.f} : t);
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
 #pragma unroll
-        for (int j = 0; j < 4; ++j) o[T][4 * hq + j] = ONLINE ? __builtin_fmaf(o[T][4 * hq + j], alpha, t[4 * hq + j]) : t[4 * hq + j];
+        for (int j = 0; j < 4; ++j) o[T][4 * hq + j] = ONLINE ? __builtin_fmaf(o[T][4 * hq + j], alpha, t[j]) : t[j];
         __builtin_amdgcn_sched_barrier(0);   // one head at a time
     }
 }
@@ -198,6 +209,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
     const bool half1 = hf != 0;
     const bool col_masked = half1 != (((r >> 2) & 1) != 0);
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (ATT) pv_fill_zeros<256>(smem + G::l_zero, tid);   // visible after the first window's barriers
 
     for (int win = blockIdx.x; win < nwin; win += gridDim.x) {
         SWF_WF_FENCE();
@@ -243,7 +255,8 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
                 for (int i = 0; i < 6; ++i) dst[i] = m == 0 ? WF(G::F_QKV + ((m * 2 + T) * 3) * 2 + i) : WK(G::F_QKV + ((m * 2 + T) * 3) * 2 + i);
             };
             req(0, wq[0]);
-            f32x16 x0, x1;
+            // the residual rows stay in registers across the attention phase: C operand of the projection
+            f32x16 &x0 = res0, &x1 = res1;
             load_rows(x0, x1);
             if (win == (int)blockIdx.x) {
                 // the fp32 vectors of both streams -> LDS, once per launch: requested BEHIND the first window's rows and first
@@ -310,7 +323,8 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
         {
             const bool rowv = args.shift && wy == nwy - 1, colv = args.shift && wx == nwx - 1;
             const u32x4* ksrc = kimg + (ws * 8) * 64 + lane;
-            const u32x4* vsrc = vimg + (ws * 8) * 64 + lane;
+            const u32x4* const vsrc[2] = {pv_src48(smem, lane, (unsigned)(G::l_v + (ws * 8) * 1024), (unsigned)G::l_zero),
+                                          pv_src48(smem, lane, (unsigned)(G::l_v + (ws * 8 + 4) * 1024), (unsigned)G::l_zero)};
             if (rowv || colv) {   // wave-uniform: the mask is a whole key tile / a whole lane, folded into the C operand once per window
                 const float pen0 = ((rowv && qb == 1) || (colv && col_masked)) ? -INFINITY : 0.f;
                 const float pen1 = ((rowv && qb == 0) || (colv && col_masked)) ? -INFINITY : 0.f;
@@ -323,8 +337,7 @@ __global__ __launch_bounds__(256, W48_WAVES) void window48_kernel(WinArgs args) 
         // ---- normalise (denominator: lane half 1, register 4q+2), output projection + bias + residual ----
         u32x4 wpj[16];   // all 16 projection fragments ([out tile 2][k-step 4][hi, lo]): requested here, in flight under the normalisation
         SWF_WF_FENCE();
-        if constexpr (RAW) { res0 = zero16; res1 = zero16; }
-        else load_rows(res0, res1);
+        if constexpr (RAW) { res0 = zero16; res1 = zero16; }   // CrossAttention.forward: no residual
 #pragma unroll
         for (int i = 0; i < 16; ++i) wpj[i] = WF(G::F_P + i);
         SWF_WF_FENCE();
@@ -464,6 +477,7 @@ __global__ __launch_bounds__(256, 2) void window48w16_kernel(WinArgs args) {
     const float* vecv = lvec + ws * G::VSTREAM + 2 * G::VHF;        // V bias [tile][32]
     const bool half1 = hf != 0;
     const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    pv_fill_zeros<256>(smem48 + G::l_zero16, tid);
     __syncthreads();
 
     for (int win = blockIdx.x; win < nwin; win += gridDim.x) {
@@ -575,8 +589,11 @@ __global__ __launch_bounds__(256, 2) void window48w16_kernel(WinArgs args) {
                     load_bias_tiles(wrs, loff, (int)G::p_bias, d0, bias);
                     if (colv) col_seam16(bias, r);
                 }
-                // key tiles 2c, 2c + 1: 4 K fragments each, 4 pv-steps of each V^T tile
-                attention48<true, 16>(kimg + (2 * c) * 4 * 64 + lane, vimg + (4 * c) * 64 + lane, qf[0], bias, half1, o, mrun);
+                // key tiles 2c, 2c + 1: 4 K fragments each, 4 pv-steps of each V^T tile (the chunk and tile offsets are part of the
+                // matching lanes' base only: the zero region is one chunk of one tile)
+                const u32x4* const vsrc[2] = {pv_src48(smem48, lane, (unsigned)(G::l_v16 + (4 * c) * 1024), (unsigned)G::l_zero16),
+                                              pv_src48(smem48, lane, (unsigned)(G::l_v16 + (16 + 4 * c) * 1024), (unsigned)G::l_zero16)};
+                attention48<true>(kimg + (2 * c) * 4 * 64 + lane, vsrc, qf[0], bias, half1, o, mrun);
             }
             // the second tile's Q fragments move up
 #pragma unroll
@@ -735,7 +752,7 @@ __global__ __launch_bounds__(256) void pack48_kernel(WinPackArgs a) {
     if (p.attn.bias_table) pack_rel_bias<false>(reinterpret_cast<float*>(dst + G::p_bias), p.attn.bias_table, a.ws, gtid, gsz);
 }
 
-// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 69 KB of LDS per workgroup (dynamic),
+// The level as the shared host entries see it (win_host.h).  Static LDS; 16x16 windows: 73 KB of LDS per workgroup (dynamic),
 // two workgroups per CU, grid.y = stream.
 struct L48 {
     static constexpr int C = 48, D = 6, HID_WIDE = 192, HID_NARROW = 96, PACK_GRID = 64, WAVES = W48_WAVES;

@@ -30,6 +30,31 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
 __device__ __forceinline__ f32x16 mfma_f16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
 }
+// P.V of ONE head on the 16x16x32 shape (levels 0 / 1: a head's V rows are 4 / 8 of the 32 virtual channels of a V^T image, so
+// the 32-row product of the 32x32x16 shape is 7/8 resp. 3/4 another head's V times this head's P).  16 cycles against 32.
+//   B = the P fragment exactly as pack8_f16 leaves it: lane l is column n = l & 15 and k-group kg = l >> 4 = 2 hf + qh, where
+//       qh is bit 4 of the lane's QUERY — lanes with qh = 1 hold queries 16..31, not a second k-group of queries 0..15.
+//   A = a per-lane read of the V^T image: row m = l & 15 = 4 g + c takes, for k-group kg, the image slot of lane half kg >> 1
+//       when (kg & 1) == (g & 1) and 16 bytes of zeros otherwise (pv_match), so row group g sums the keys of both lane halves
+//       against the queries of half g & 1 only.
+//   D: register j of lane l = row 4 (l >> 4) + j, column l & 15, i.e. row group g = l >> 4 = 2 hf + qh: the lane receives rows
+//       4 (g >> 1) .. +3 of ITS OWN query (16 qh + n = l & 31) — at level 0 both lane halves get the head's four rows.
+//       (kernels_win24.hip: pv_src24), at level 1 lane half hf the rows 4 hf .. +3 of the head's eight (kernels_win48.hip: pv_src48).
+__device__ __forceinline__ f32x4 mfma16_f16(u32x4 a, u32x4 b, f32x4 c) {
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+}
+__device__ __forceinline__ bool pv_match(int lane) { return ((lane >> 4) & 1) == ((lane >> 2) & 1); }
+// The lanes that do not match read zeros: a 4 KB LDS region filled once per launch.  Their base sits 128 bytes into it, so that the
+// one address they share never falls into the banks of the 64-byte run (level 1: the two adjacent runs) that the matching lanes of
+// the same 16-lane group read; image and zero region are 256-byte aligned.  The head / pv-step offsets are instruction immediates
+// added to either base (at most 3 * 1024 + 7 * 64 at level 0, 3 * 1024 + 3 * 128 at level 1).
+constexpr int kPvZeroBytes = 4096, kPvZeroBase = 128;
+static_assert(kPvZeroBase + 3 * 1024 + 7 * 64 + 16 <= kPvZeroBytes, "zero region covers every immediate");
+template <int NTHREADS>
+__device__ __forceinline__ void pv_fill_zeros(char* zreg, int tid) {
+    for (int i = tid; i < kPvZeroBytes / 16; i += NTHREADS) reinterpret_cast<u32x4*>(zreg)[i] = u32x4{0u, 0u, 0u, 0u};
+}
+
 // acc += a . b over one 16-deep k-step with split-bf16 operands (a = a_hi + a_lo, b = b_hi + b_lo): three MFMAs, small cross
 // terms first so they are not absorbed by the large hi.hi partial sums
 __device__ __forceinline__ f32x16 mma3(u32x4 ahi, u32x4 alo, u32x4 bhi, u32x4 blo, f32x16 acc) {
