@@ -819,6 +819,81 @@ int swf_jpeg_decode_split(const uint8_t* data, size_t data_bytes, const swf_jpeg
                           int32_t n_files, const uint32_t* intervals_dev, const uint32_t* intervals_host, int32_t segment_bytes, uint8_t* out,
                           size_t out_bytes, int32_t* status, int32_t layout, void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- PNG decoder: the files swf_png_encode, libpng and Pillow write, many files per call -------------------------------------------------
+ * Pixels equal to Pillow's (Image.open(...).convert("L" | "RGB")), bit for bit.
+ *   scope    non-interlaced PNG of bit depth 8, colour types 0 (gray), 2 (RGB), 3 (palette), 4 (gray + alpha) and 6 (RGBA); any number
+ *            of IDAT chunks of any length, zero included; any ancillary chunks.
+ *   parse    host only.  SWF_ERR_UNSUPPORTED (a caller falls back to another decoder): bit depths 1, 2, 4 and 16, Adam7 interlacing, an
+ *            acTL chunk (animated PNG), a critical chunk other than IHDR PLTE IDAT IEND, a file of 2^32 - 1 bytes or more, H (1 + W bpp)
+ *            or the IDAT payload above 2^31 - 1.  SWF_ERR_BAD_SHAPE (broken): a bad signature, a chunk running past the file, no IHDR
+ *            in front, a second IHDR or PLTE, W or H of 0, an unknown colour type, depth, compression, filter or interlace method, a
+ *            CRC-32 mismatch in IHDR or PLTE, no IDAT, IDATs that are not consecutive, type 3 without a PLTE in front of the IDATs, no
+ *            IEND, a bad zlib header (CM = 8, CINFO <= 7, FCHECK, FDICT clear; its two bytes may lie in different IDATs).  The CRC-32 of
+ *            IDAT chunks is NOT checked: the integrity of the pixel data rests on the stream's Adler-32, which the device verifies.
+ *            (Pillow does not appear to check IDAT CRCs either; this was inferred from its behaviour, not verified in its sources.)
+ *   gather   each file's IDAT ranges are copied into one contiguous, 16-byte aligned, zero-padded zlib stream in the workspace.
+ *   inflate  one wavefront per file; stored, fixed and dynamic blocks, distances up to 32 768 into the file's own earlier output.  The
+ *            symbol chain is serial; the lanes share the table construction and the byte copies.  It stops when the final block ends or
+ *            at the first error.  Bytes beyond H (1 + W bpp) are counted, never written.
+ *   Adler-32 over the inflated bytes, in parallel, against the four bytes behind the final block.
+ *   unfilter None, Sub, Up, Average floor((a + b) / 2), Paeth (ties a, b, c), 64 rows in flight, a row a pixel behind the row above.
+ *   finish   to gray: the sample of types 0 and 4 (alpha dropped), (19595 R + 38470 G + 7471 B + 32768) >> 16 of types 2, 6 and of the
+ *            palette colour of type 3.  To RGB / BGR: the samples of types 2 and 6 (alpha dropped), the palette colour, the gray sample
+ *            three times.  A palette index at or beyond the PLTE's length is black.  tRNS is ignored for every type.
+ *   status   per file, in this order: the stream's own end (SWF_PNG_STREAM_TRUNCATED: the bits run out before the final block ends;
+ *            _CODE: BTYPE 3, stored LEN != ~NLEN, HLIT > 286 or HDIST > 30, an over-subscribed or incomplete set of code lengths other
+ *            than an empty distance set or the single one-bit distance code zlib allows, no code for end-of-block, a repeat code with
+ *            nothing to repeat or running past HLIT + HDIST, bits that start no code, literal/length symbols 286 and 287, distance
+ *            symbols 30 and 31; _DISTANCE: a distance reaching before the first output byte); _TRUNCATED for fewer than H (1 + W bpp)
+ *            bytes or fewer than four bytes behind the final block; _LONG for more bytes than expected (the image is complete; the
+ *            Adler-32 covers bytes that were dropped and is not compared); _ADLER; _FILTER for a filter byte above 4 in a file whose
+ *            stream was sound.  Whole rows the stream delivered are unfiltered and converted up to the first bad filter byte; the rows
+ *            behind are zero.
+ * Every kernel terminates on every input: the loops are bounded by the bits and the output space remaining, no workgroup waits for
+ * another, and the waits inside a workgroup are barriers every lane reaches.
+ * swf_png_parse and the workspace query are host-only and touch no GPU. */
+enum { SWF_PNG_OUT_BGR = 0, SWF_PNG_OUT_RGB = 1, SWF_PNG_OUT_GRAY = 2 };   /* the values of SWF_JPEG_OUT_*: [H][W][3], [H][W][3], [H][W] */
+enum { SWF_PNG_STREAM_OK = 0, SWF_PNG_STREAM_TRUNCATED = 1, SWF_PNG_STREAM_CODE = 2, SWF_PNG_STREAM_DISTANCE = 3, SWF_PNG_STREAM_LONG = 4,
+       SWF_PNG_STREAM_ADLER = 5, SWF_PNG_STREAM_FILTER = 6 };
+typedef struct swf_png_file {
+    uint64_t data_off;             /* SET BY THE CALLER: where the file's bytes start in swf_png_decode's data buffer */
+    uint64_t out_off;              /* SET BY THE CALLER: where its pixels go in swf_png_decode's output buffer */
+    uint32_t data_bytes;           /* the file's size */
+    int32_t H, W;
+    int32_t color_type;            /* 0, 2, 3, 4 or 6 */
+    int32_t bpp;                   /* bytes per pixel: 1, 3, 1, 2, 4 */
+    int32_t palette_entries;       /* PLTE's length for type 3 (1 .. 256), else 0 */
+    uint32_t idat_ranges;          /* IDAT chunks, empty ones included */
+    uint32_t idat_bytes;           /* their payload in all: the zlib stream's length */
+    uint8_t palette[768];          /* RGB triples; zero from palette_entries on */
+} swf_png_file;
+/* Host only.  data[0 .. n): one file.  *file <- its descriptor (data_off = out_off = 0), *ranges_needed <- file->idat_ranges.  ranges: NULL
+ * (a size query), or room for ranges_cap pairs of uint32: pair i <- (offset in the file, length) of the payload of IDAT chunk i;
+ * SWF_ERR_WORKSPACE when ranges_cap < file->idat_ranges.  The refusals are listed above; SWF_ERR_NULL for a NULL data, file or
+ * ranges_needed. */
+int swf_png_parse(const uint8_t* data, size_t n, swf_png_file* file, uint32_t* ranges, size_t ranges_cap, size_t* ranges_needed);
+/* Bytes of workspace swf_png_decode needs for these files (the carve of kernels_pngdec.hip run without memory): three uint32 per file
+ * and one (prefix sums), a 48-byte record per file, per file its zlib stream + 16 and its H (1 + W bpp) inflated bytes, each rounded up
+ * to 16.  0 for what the call would refuse.  Host only. */
+size_t swf_png_decode_workspace_bytes(const swf_png_file* files_host, int32_t n_files);
+/* data: device buffer of data_bytes bytes holding every file at its data_off.  files_host / files_dev: the n_files descriptors in host
+ * memory, where they are checked, and the same bytes in device memory, where the kernels read them.  ranges_dev: device, the pairs
+ * swf_png_parse wrote, all files' one after another in file order.  out: device buffer of out_bytes bytes; file i's pixels <- out +
+ * out_off in `layout`, H W 3 or H W bytes.  status: device int32 [n_files] <- SWF_PNG_STREAM_* of each file.  Six launches (prefix sums;
+ * gather and zero fill; inflate; Adler-32; unfilter; finish); no allocation, no copy to the host and no synchronisation, so the call can
+ * be captured into a hipGraph on one stream.  A file's pixels and status depend on that file alone: not on the other files, their order,
+ * an earlier use of the workspace, or timing.  Whatever the FILE BYTES are, nothing outside the file's own workspace areas, pixels and
+ * status word is written, and nothing outside its bytes is read; the descriptors are trusted to be what swf_png_parse wrote (the host
+ * copy is checked), and a range that leaves the file or the stream's area ends the gather of that file.
+ * SWF_ERR_NULL for a NULL pointer; SWF_ERR_BAD_SHAPE for n_files < 1, an unknown layout, a descriptor swf_png_parse could not have
+ * written, a file that leaves the data buffer, or pixels that leave the output buffer or overlap another file's; SWF_ERR_UNSUPPORTED
+ * for more than 65535 files, or inflated bytes, stream bytes or ranges above 2^31 - 1 in one call; SWF_ERR_WORKSPACE for a workspace
+ * below the query; all before anything is launched.  With SWF_DEBUG_SWITCHES=1, SWF_PNG_DECODE_STAGES selects the launches by its bits:
+ * 1 prefix sums, 2 gather, 4 inflate, 8 Adler-32, 16 unfilter, 32 finish. */
+int swf_png_decode(const uint8_t* data, size_t data_bytes, const swf_png_file* files_host, const swf_png_file* files_dev, int32_t n_files,
+                   const uint32_t* ranges_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
+                   size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- resident paired dataset: the reference's training-time input transform (a015_dataset.py:57-66, :89-103) in one launch --------
  * The decoded uint8 images of a training set lie in two device arenas (gray [H][W], BGR [H][W][3], cv2.imread layouts).  A batch is
  * described by B rows; the launch writes ir = u8/255 and vis_y = cv2's uint8 luma/255 (the BGR->YCrCb restatement above) of the crop

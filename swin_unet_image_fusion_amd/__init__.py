@@ -6,7 +6,7 @@ by hand-written HIP kernels behind a C-ABI (`include/swinfuse.h`, `libswinfuse.s
 """
 from .config import CONFIGS, FusionConfig, load_recipe_into, synthetic_pair  # noqa: F401
 from .data import PairLoader, ResidentPairs, sample_crop_params  # noqa: F401
-from .imaging import JpegBatch, PngBatch, decode_jpeg, encode_jpeg, encode_png, jpeg_info  # noqa: F401
+from .imaging import JpegBatch, PngBatch, decode_jpeg, decode_png, encode_jpeg, encode_png, jpeg_info, png_info  # noqa: F401
 from .inference import test_fusion  # noqa: F401
 from .loss import MyLoss  # noqa: F401
 from .metrics import (COMPARATIVE_DEFAULTS, COMPARATIVE_NAMES, FIDELITY_DEFAULTS, FIDELITY_NAMES, METRIC_NAMES, PERCEPTION_DEFAULTS,  # noqa: F401

@@ -170,6 +170,15 @@ class JpegFile(C.Structure):   # swf_jpeg_file: written by swf_jpeg_parse; data_
                 ("quant", (C.c_uint16 * 64) * 4), ("dc", JpegHuff * 4), ("ac", JpegHuff * 4)]
 
 
+class PngFile(C.Structure):   # swf_png_file: written by swf_png_parse; data_off and out_off are the caller's
+    _fields_ = [("data_off", C.c_uint64), ("out_off", C.c_uint64), ("data_bytes", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32),
+                ("color_type", C.c_int32), ("bpp", C.c_int32), ("palette_entries", C.c_int32), ("idat_ranges", C.c_uint32),
+                ("idat_bytes", C.c_uint32), ("palette", C.c_uint8 * 768)]
+
+
+# SWF_PNG_STREAM_*; the layouts are SWF_JPEG_OUT_*'s values
+PNG_STREAM_OK, PNG_STREAM_TRUNCATED, PNG_STREAM_CODE, PNG_STREAM_DISTANCE, PNG_STREAM_LONG, PNG_STREAM_ADLER, PNG_STREAM_FILTER = range(7)
+
 JPEG_OUT_BGR, JPEG_OUT_RGB, JPEG_OUT_GRAY = 0, 1, 2                              # SWF_JPEG_OUT_*
 JPEG_STREAM_OK, JPEG_STREAM_TRUNCATED, JPEG_STREAM_RUN, JPEG_STREAM_CODE = 0, 1, 2, 3   # SWF_JPEG_STREAM_*
 
@@ -293,6 +302,9 @@ SIGNATURES = {
     "swf_jpeg_decode": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
     "swf_jpeg_decode_split_workspace_bytes": (_sz, [_vp, _i32, _vp, _i32]),
     "swf_jpeg_decode_split": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _i32, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
+    "swf_png_parse": (C.c_int, [_vp, _sz, P(PngFile), _vp, _sz, P(_sz)]),
+    "swf_png_decode_workspace_bytes": (_sz, [_vp, _i32]),
+    "swf_png_decode": (C.c_int, [_vp, _sz, _vp, _vp, _i32, _vp, _vp, _sz, _vp, _i32, _vp, _sz, _vp]),
     "swf_paired_crop_rows_bytes": (_sz, [_i32]),
     "swf_paired_crop_rows_check": (C.c_int, [_vp, _i32, C.c_uint64, C.c_uint64]),
     "swf_paired_crop_resize_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),

@@ -20,6 +20,7 @@
 #include "kernels_jpeg.h"
 #include "kernels_jpegdec.h"
 #include "kernels_png.h"
+#include "kernels_pngdec.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2609,6 +2610,58 @@ int swf_jpeg_decode_split(const uint8_t* data, size_t data_bytes, const swf_jpeg
         return fail(SWF_ERR_WORKSPACE, "jpeg_decode_split: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
     return jpegdec_split_decode(data, files_host, files_dev, n_files, intervals_dev, intervals_host, segment_bytes, out, status, layout, workspace,
                                 workspace_bytes, as_stream(stream));
+}
+
+// PNG decoder.  The parse and the workspace query are host-only; the call checks the host copy of the descriptors, every file's place in
+// the data buffer and every file's pixels in the output buffer before the first launch.
+int swf_png_parse(const uint8_t* data, size_t n, swf_png_file* file, uint32_t* ranges, size_t ranges_cap, size_t* ranges_needed) {
+    if (!data || !file || !ranges_needed) return fail(SWF_ERR_NULL, "png_parse: NULL data, descriptor or count");
+    return pngdec_parse(data, n, file, ranges, ranges ? ranges_cap : 0, ranges_needed);
+}
+
+static int check_png_files(const swf_png_file* files, int32_t n_files) {
+    if (!files) return fail(SWF_ERR_NULL, "png_decode: NULL descriptors");
+    if (n_files < 1) return fail(SWF_ERR_BAD_SHAPE, "png_decode: %d files", n_files);
+    if (n_files > kPngDecMaxFiles) return fail(SWF_ERR_UNSUPPORTED, "png_decode: %d files in one call (%d at most)", n_files, kPngDecMaxFiles);
+    for (int32_t i = 0; i < n_files; ++i) SWF_TRY(pngdec_file_ok(files[i], i));
+    if (pngdec_workspace_bytes(files, n_files) == 0)
+        return fail(SWF_ERR_UNSUPPORTED, "png_decode: more than 2^31 - 1 inflated bytes, stream bytes or IDAT ranges in one call");
+    return SWF_OK;
+}
+
+size_t swf_png_decode_workspace_bytes(const swf_png_file* files_host, int32_t n_files) {
+    return check_png_files(files_host, n_files) == SWF_OK ? pngdec_workspace_bytes(files_host, n_files) : 0;
+}
+
+int swf_png_decode(const uint8_t* data, size_t data_bytes, const swf_png_file* files_host, const swf_png_file* files_dev, int32_t n_files,
+                   const uint32_t* ranges_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
+                   size_t workspace_bytes, swf_stream_t stream) {
+    if (!data || !files_host || !files_dev || !ranges_dev || !out || !status)
+        return fail(SWF_ERR_NULL, "png_decode: NULL data, descriptors, ranges, output or status");
+    if (layout != SWF_PNG_OUT_BGR && layout != SWF_PNG_OUT_RGB && layout != SWF_PNG_OUT_GRAY)
+        return fail(SWF_ERR_BAD_SHAPE, "png_decode: layout %d (0 BGR, 1 RGB, 2 gray)", layout);
+    SWF_TRY(check_png_files(files_host, n_files));
+    const uint64_t px = layout == SWF_PNG_OUT_GRAY ? 1 : 3;
+    std::vector<std::pair<uint64_t, uint64_t>> spans((size_t)n_files);
+    for (int32_t i = 0; i < n_files; ++i) {
+        const swf_png_file& f = files_host[i];
+        if (f.data_off > data_bytes || f.data_bytes > data_bytes - f.data_off)
+            return fail(SWF_ERR_BAD_SHAPE, "png_decode: file %d: bytes [%llu, + %u) leave the data buffer of %zu bytes", i,
+                        (unsigned long long)f.data_off, f.data_bytes, data_bytes);
+        const uint64_t n = (uint64_t)f.H * f.W * px;
+        if (f.out_off > out_bytes || n > out_bytes - f.out_off)
+            return fail(SWF_ERR_BAD_SHAPE, "png_decode: file %d: pixels [%llu, + %llu) leave the output buffer of %zu bytes", i,
+                        (unsigned long long)f.out_off, (unsigned long long)n, out_bytes);
+        spans[(size_t)i] = {f.out_off, f.out_off + n};
+    }
+    std::sort(spans.begin(), spans.end());
+    for (size_t i = 1; i < spans.size(); ++i)
+        if (spans[i].first < spans[i - 1].second)
+            return fail(SWF_ERR_BAD_SHAPE, "png_decode: the pixels of two files overlap at byte %llu of the output", (unsigned long long)spans[i].first);
+    const size_t need = pngdec_workspace_bytes(files_host, n_files);
+    if (!workspace || workspace_bytes < need)
+        return fail(SWF_ERR_WORKSPACE, "png_decode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    return pngdec_decode(data, files_host, files_dev, n_files, ranges_dev, out, status, layout, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

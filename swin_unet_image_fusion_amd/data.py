@@ -129,7 +129,11 @@ class ResidentPairs:
         cv2.imread, which is not available here: DECODE PARITY WITH cv2.imread IS UNPINNED (JPEG decoding and colour-to-gray conversion
         may differ in the last bits; lossless gray/RGB files decode alike).
 
-        decode="device": the files that begin with FF D8 and that swf_jpeg_parse accepts (baseline JPEG, include/swinfuse.h) are decoded
+        decode="device": the files that begin with the PNG signature and that swf_png_parse accepts (non-interlaced, 8 bits) are decoded by
+        swf_png_decode, ir as gray and vis as BGR, in groups budgeted by their workspace (the zlib stream and the inflated bytes) under
+        the same 256 MiB and file-count limits; a PNG whose device status is non-zero is decoded again through PIL, and PIL's verdict
+        stands, pixels or exception, so on PNGs the store is the one decode="pil" returns and the call raises where that raises.  JPEG
+        and PNG files may be mixed in one folder.  The files that begin with FF D8 and that swf_jpeg_parse accepts (baseline JPEG, include/swinfuse.h) are decoded
         by swf_jpeg_decode straight into the arenas, ir as gray and vis as BGR, in groups whose coefficient workspace (192 bytes per
         8 x 8 block) stays under 256 MiB; every other file goes through PIL as above.  The store is byte-equal to decode="pil"'s with
         Pillow on libjpeg-turbo.  GPU only.  entropy: the entropy pass of those calls, "interval", "split" or "auto" as
@@ -178,9 +182,20 @@ class ResidentPairs:
                     return data, imaging.parse_jpeg(data)
                 except (NotImplementedError, ValueError):
                     pass
+            elif data[:8] == imaging.PNG_SIGNATURE:
+                try:
+                    return data, imaging.parse_png(data)
+                except (NotImplementedError, ValueError):
+                    pass
+            return None, pil_array(p, mode)
+
+        def is_png(x):
+            return isinstance(x[0], L.PngFile)
+
+        def pil_array(p, mode):
             with Image.open(p) as im:
                 a = np.array(im.convert(mode), dtype=np.uint8)
-            return None, (a if mode == "L" else np.ascontiguousarray(a[..., ::-1]))
+            return a if mode == "L" else np.ascontiguousarray(a[..., ::-1])
 
         def shape(entry):
             data, x = entry
@@ -190,6 +205,8 @@ class ResidentPairs:
         # side of a soft budget: "auto" counts the split tables although the group's call may take the interval path, and the 256-byte
         # alignment of the carved arrays (a few KB per call) is left out; imaging.split_workspace_bytes gives a call's exact size.
         def workspace(x):
+            if is_png(x):   # the stream and the inflated bytes, each rounded up to 16 (swf_png_decode_workspace_bytes adds 60 bytes per file)
+                return x[0].idat_bytes + 48 + x[0].H * (1 + x[0].W * x[0].bpp) + 76
             if entropy == "interval":
                 return x[0].blocks * 192
             raw = x[1][:, 1].astype(np.int64) - x[1][:, 0]
@@ -203,26 +220,39 @@ class ResidentPairs:
         items, ir_end, vis_end = cls._place([shape(a) for a in irs], list(zip(ir_paths, vis_paths)))
         ir_arena, vis_arena = torch.zeros(ir_end, dtype=torch.uint8, device=device), torch.zeros(vis_end, dtype=torch.uint8, device=device)
         for arena, entries, paths, col, layout in ((ir_arena, irs, ir_paths, 0, "gray"), (vis_arena, viss, vis_paths, 1, "bgr")):
-            group, used, pending = [], 0, []
+            # JPEG and PNG files go to their own decoder calls: a group of each kind is open at a time, under the same budget
+            groups, used, pending = {False: [], True: []}, {False: 0, True: 0}, []
 
-            def flush():
+            def flush(png):
+                group = groups[png]
                 if group:
-                    st = imaging.decode_jpeg_into(arena, [items[i][col] for i in group], [entries[i][0] for i in group],
-                                                  [entries[i][1] for i in group], layout, entropy)
-                    pending.append((st, [paths[i] for i in group]))
+                    args = (arena, [items[i][col] for i in group], [entries[i][0] for i in group], [entries[i][1] for i in group], layout)
+                    st = imaging.decode_png_into(*args) if png else imaging.decode_jpeg_into(*args, entropy)
+                    pending.append((png, st, list(group)))
+                groups[png], used[png] = [], 0
 
             for i, (data, x) in enumerate(entries):
                 if data is None:
                     arena[items[i][col]:items[i][col] + x.size].copy_(torch.from_numpy(x.reshape(-1)))
                     continue
-                if group and (used + workspace(x) > _DECODE_BUDGET or len(group) >= _DECODE_GROUP_FILES):
-                    flush()
-                    group, used = [], 0
-                group.append(i)
-                used += workspace(x)
-            flush()
-            for st, names in pending:
-                imaging.check_stream_status(st.cpu().tolist(), names)
+                png = is_png(x)
+                if groups[png] and (used[png] + workspace(x) > _DECODE_BUDGET or len(groups[png]) >= _DECODE_GROUP_FILES):
+                    flush(png)
+                groups[png].append(i)
+                used[png] += workspace(x)
+            flush(False)
+            flush(True)
+            for png, st, group in pending:
+                st = st.cpu().tolist()
+                if not png:
+                    imaging.check_stream_status(st, [paths[i] for i in group])
+                    continue
+                # a PNG with a non-zero status is decoded again through PIL, whose verdict stands: its pixels (a stream longer than the
+                # image, which Pillow accepts) or its exception (OSError for a truncated stream or a wrong Adler-32)
+                for i, s in zip(group, st):
+                    if s:
+                        a = pil_array(paths[i], "L" if col == 0 else "RGB")
+                        arena[items[i][col]:items[i][col] + a.size].copy_(torch.from_numpy(a.reshape(-1)))
         return cls(ir_arena, vis_arena, items)
 
     def split(self, ratio: float, generator: Optional[torch.Generator] = None) -> Tuple[List[int], List[int]]:

@@ -17,6 +17,11 @@ on a store built from gray sources, followed by `encode_png`, stores the fused Y
 files of the call (swf_jpeg_decode), pixels equal to Pillow's on libjpeg-turbo bit for bit; `jpeg_info(data)` exposes the parse.
 `entropy="split"` decodes in parallel inside every restart interval (swf_jpeg_decode_split), which is what files without restart
 markers need; `"auto"` chooses by the call's longest interval.  The result does not depend on the choice.
+
+`decode_png(files)` = the same for PNG files, so that what `encode_png` and `test_fusion(format="png")` write can be read back on the
+device: non-interlaced 8-bit files of every colour type parsed on the host (swf_png_parse) and decoded in six HIP launches over all files
+of the call (swf_png_decode: gather, inflate with one wavefront per file, Adler-32, unfilter, conversion), pixels equal to Pillow's bit
+for bit; `png_info(data)` exposes the parse.
 """
 from __future__ import annotations
 
@@ -294,5 +299,104 @@ def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", stri
     images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
     if strict:
         check_stream_status(statuses)
+        return images
+    return images, statuses
+
+
+# ---- the PNG decoder -----------------------------------------------------------------------------------------------------------------
+PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
+_PNG_STREAM_KINDS = {L.PNG_STREAM_TRUNCATED: "the compressed data ends early", L.PNG_STREAM_CODE: "an invalid deflate block or code",
+                     L.PNG_STREAM_DISTANCE: "a match reaching before the first byte", L.PNG_STREAM_LONG: "more data than the image holds",
+                     L.PNG_STREAM_ADLER: "the Adler-32 of the pixel data does not match", L.PNG_STREAM_FILTER: "a filter type above 4"}
+_RANGES_GUESS = 64   # pairs the first parse of a file has room for; a file with more IDAT chunks is parsed a second time
+
+
+def parse_png(data: bytes, index: int = 0) -> Tuple["L.PngFile", np.ndarray]:
+    """swf_png_parse on the host: -> (descriptor, (IDAT chunks, 2) uint32 array of (offset, length)).  NotImplementedError for a file
+    outside the decoder's scope, ValueError for a broken one, both naming `index`."""
+    lib, desc, need = L.lib(), L.PngFile(), C.c_size_t(0)
+    src = C.cast(C.c_char_p(data), C.c_void_p)
+    ranges = np.empty((_RANGES_GUESS, 2), dtype=np.uint32)
+    st = lib.swf_png_parse(src, len(data), C.byref(desc), ranges.ctypes.data, len(ranges), C.byref(need))
+    if st == L.ERR_WORKSPACE:
+        ranges = np.empty((need.value, 2), dtype=np.uint32)
+        st = lib.swf_png_parse(src, len(data), C.byref(desc), ranges.ctypes.data, len(ranges), C.byref(need))
+    try:
+        L.check(st)
+    except (NotImplementedError, ValueError) as e:
+        raise type(e)(f"file {index}: {e}") from None
+    return desc, ranges[:need.value].copy()
+
+
+def png_info(data: bytes) -> dict:
+    """What the parser reads from a file's chunks."""
+    d, ranges = parse_png(data)
+    return {"height": d.H, "width": d.W, "color_type": d.color_type, "bytes_per_pixel": d.bpp, "palette_entries": d.palette_entries,
+            "idat_chunks": len(ranges), "idat_bytes": d.idat_bytes}
+
+
+def png_workspace_bytes(parsed: Sequence[tuple]) -> int:
+    """Bytes of workspace swf_png_decode needs for these files; 0 for what it refuses.  Host only."""
+    n = len(parsed)
+    return L.lib().swf_png_decode_workspace_bytes((L.PngFile * n)(*[d for d, _ in parsed]), n)
+
+
+def decode_png_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes], parsed: Sequence[tuple], layout: str) -> Tensor:
+    """One decoder call (swf_png_decode, six launches on the current stream): file i's pixels to out[offsets[i]:] (flat uint8 on the GPU)
+    in `layout`.  One upload of the files' bytes and one of the descriptors and IDAT ranges.  -> the device int32 status per file."""
+    code, _ = _LAYOUTS[layout]
+    out = _u8(out, "out")
+    lib, dev, n = L.lib(), out.device, len(files)
+    descs = (L.PngFile * n)()
+    pos = 0
+    for i, ((d, _), data) in enumerate(zip(parsed, files)):
+        d.data_off, d.out_off = pos, int(offsets[i])
+        descs[i] = d
+        pos += len(data)
+    ranges = np.ascontiguousarray(np.concatenate([r.reshape(-1) for _, r in parsed]), dtype=np.uint32)
+    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8), ranges.view(np.uint8)])
+    tables_dev = torch.from_numpy(tables).to(dev)
+    data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
+    status = torch.empty((n,), dtype=torch.int32, device=dev)
+    need = lib.swf_png_decode_workspace_bytes(descs, n)
+    workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    L.check(lib.swf_png_decode(data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n,
+                               tables_dev.data_ptr() + n * C.sizeof(L.PngFile), out.data_ptr(), out.numel(), status.data_ptr(), code,
+                               workspace.data_ptr(), need, _stream(dev)))
+    return status
+
+
+def check_png_status(statuses: Sequence[int], names: Optional[Sequence] = None) -> None:
+    """ValueError for the first file with a non-zero status, naming it and the kind."""
+    for i, s in enumerate(statuses):
+        if s:
+            raise ValueError(f"file {names[i] if names is not None else i}: corrupt PNG data: {_PNG_STREAM_KINDS.get(s, s)} (status {s})")
+
+
+def decode_png(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True):
+    """PNG files (the scope of swf_png_decode in include/swinfuse.h: non-interlaced, 8 bits, colour types 0, 2, 3, 4, 6) -> one uint8 tensor
+    per file, (H, W, 3) for "rgb" and "bgr", (H, W) for "gray": views into one flat device tensor, equal to
+    np.asarray(PIL.Image.open(f).convert(mode)).  A file the parser refuses raises NotImplementedError (out of scope) or ValueError
+    (broken) naming its index.  The statuses are read once after the call; a file with a non-zero status raises ValueError naming it and
+    the kind, unless strict=False: then (images, statuses) is returned, and the rows such a file did not reach are zero."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("no files")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"decode_png: the decoder runs on the GPU only, got {dev}")
+    parsed = [parse_png(f, i) for i, f in enumerate(files)]
+    px = _LAYOUTS[layout][1]
+    offsets, end = [], 0
+    for d, _ in parsed:
+        offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
+        end = offsets[-1] + d.H * d.W * px
+    out = torch.empty(end, dtype=torch.uint8, device=dev)
+    statuses = decode_png_into(out, offsets, files, parsed, layout).cpu().tolist()
+    images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
+    if strict:
+        check_png_status(statuses)
         return images
     return images, statuses
