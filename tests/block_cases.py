@@ -260,9 +260,10 @@ def ln1_params(c: Case):
     return (g(0), b(0)), (g(1), b(1))
 
 
-def reference(c: Case, dtype=torch.float64):
-    """(out_x, out_y), NCHW, evaluated in `dtype` (a one-stream case: compare out_x)."""
-    x, y = (t.to(dtype) for t in inputs(c))
+def reference(c: Case, dtype=torch.float64, images=None):
+    """(out_x, out_y), NCHW, evaluated in `dtype` (a one-stream case: compare out_x).  images: evaluate these images of the batch only
+    (images do not see each other: tests/block_pass_cases.py gates a sample of a large batch)."""
+    x, y = (t.to(dtype) if images is None else t[list(images)].to(dtype) for t in inputs(c))
     sd = {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in state(c).items()}
     kw = dict(num_heads=c.heads, dims_per_head=c.head_dim, window_size=(c.win, c.win))
     with torch.no_grad():

@@ -29,4 +29,7 @@ def test_bench_two_ranks_share_the_gpu():
     assert d["n_gpus"] == 2 and d["steps"] == 8 and d["value"] > 0 and d["scaling"] == "weak"
     assert d["config"]["global_batch"] == 8 and d["config"]["hip_graph"] and d["config"]["graph_equals_eager"]
     assert d["config"]["steps_in_flight"] >= 2 and "gloo" in d["config"]["collective"]
-    assert abs(d["value"] - 8 * 8 / (d["ms_per_step"] * 8e-3)) / d["value"] < 1e-3
+    # value and ms_per_step are one measurement, each rounded for printing: value to 0.01 pairs/s, ms_per_step to 1e-4 ms (under 1e-4
+    # relative at a millisecond or more).  A purely relative bound is below the print rounding on a box slow enough for a value under 5.
+    want = 8 * 8 / (d["ms_per_step"] * 8e-3)
+    assert d["ms_per_step"] >= 1 and abs(d["value"] - want) <= 0.005 + 1e-4 * want

@@ -304,7 +304,10 @@ def _bitwise(case, sched, run, routes_of, expected, expected_in_place):
     base = run(case, sched, x, y, in_place=False)
     assert routes_of(base) == expected
     assert _same(base.outs, run(case, sched, x, y, in_place=False).outs), "two calls differ"
-    for i in range(case.B):   # capped grids, stride loops, tiles that span images
+    # B = 3 reaches: another image's offset in the batch, and at the deep levels token tiles that span images.  It does NOT reach the
+    # stride loops of the capped grids of levels 0 - 2: at most 12 windows, so every workgroup runs its loop body once.  The later passes
+    # of those loops are held to first-pass launches and to the oracle by tests/test_gpu_block_passes.py (tests/block_pass_cases.py).
+    for i in range(case.B):
         one = run(case, sched, x[i:i + 1].clone(), y[i:i + 1].clone(), in_place=False)   # fresh allocations: the kernels ask for 16-byte alignment
         assert routes_of(one) == expected
         assert _same(one.outs, [o[i:i + 1] for o in base.outs]), f"image {i} differs from the same image run alone"
