@@ -17,10 +17,6 @@
 #include "kernels_structure.h"
 #include "kernels_perception.h"
 #include "kernels_comparative.h"
-#include "kernels_jpeg.h"
-#include "kernels_jpegdec.h"
-#include "kernels_png.h"
-#include "kernels_pngdec.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2310,9 +2306,7 @@ int swf_fusion_loss(const swf_loss_desc* desc, const float* fusion, const float*
                     int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     if (!desc || !fusion || !ir || !vis || !terms) return fail(SWF_ERR_NULL, "fusion_loss: NULL descriptor, image or terms");
     SWF_TRY(check_fusion_loss(desc, B, H, W));
-    const size_t need = fusion_loss_workspace_bytes(*desc, B, H, W, grad_fusion != nullptr);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "fusion_loss: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    SWF_TRY(need_workspace("fusion_loss", workspace, workspace_bytes, fusion_loss_workspace_bytes(*desc, B, H, W, grad_fusion != nullptr)));
     return fusion_loss(*desc, fusion, ir, vis, terms, grad_fusion, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -2336,8 +2330,7 @@ static int metric_call(const char* name, const char* holds, int (*check_desc)(co
     SWF_TRY(check_metric_shape(name, holds, B, H, W));
     if (check_desc) SWF_TRY(check_desc(*desc));
     const size_t need = bytes(B, H, W);
-    if (need > 0 && (!workspace || workspace_bytes < need))
-        return fail(SWF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", name, workspace ? workspace_bytes : (size_t)0, need);
+    if (need > 0) SWF_TRY(need_workspace(name, workspace, workspace_bytes, need));
     return run(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -2407,9 +2400,7 @@ int swf_fusion_perception(const swf_perception_desc* desc, const float* fusion, 
     if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_perception: NULL descriptor, image or output");
     SWF_TRY(check_perception_shape(B, H, W));
     SWF_TRY(check_perception_desc(*desc));
-    const size_t need = fusion_perception_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "fusion_perception: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    SWF_TRY(need_workspace("fusion_perception", workspace, workspace_bytes, fusion_perception_workspace_bytes(B, H, W)));
     return fusion_perception(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
@@ -2444,224 +2435,8 @@ int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion
     if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_comparative: NULL descriptor, image or output");
     SWF_TRY(check_comparative_shape(B, H, W));
     SWF_TRY(check_comparative_desc(*desc));
-    const size_t need = fusion_comparative_workspace_bytes(B, H, W);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "fusion_comparative: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
+    SWF_TRY(need_workspace("fusion_comparative", workspace, workspace_bytes, fusion_comparative_workspace_bytes(B, H, W)));
     return fusion_comparative(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
-// Baseline JPEG encoder.  One check of the descriptor and one of the shape serve the four queries and the call.
-static int check_jpeg_desc(const swf_jpeg_desc* d) {
-    if (!d) return fail(SWF_ERR_NULL, "jpeg: NULL descriptor");
-    if (!jpeg_desc_ok(*d))
-        return fail(SWF_ERR_BAD_SHAPE, "jpeg: channels=%d subsampling=%d quality=%d (channels 1 or 3, subsampling 0 (4:4:4) or, with three "
-                    "channels, 1 (4:2:0), quality 1..100)", d->channels, d->subsampling, d->quality);
-    return SWF_OK;
-}
-
-static int check_jpeg_shape(const swf_jpeg_desc& d, int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "jpeg: empty tensor (B=%d H=%d W=%d)", B, H, W);
-    if (!jpeg_shape_ok(d, B, H, W))
-        return fail(SWF_ERR_UNSUPPORTED, "jpeg: B=%d H=%d W=%d: H, W <= 65535 (the frame header's 16 bits), B H W and one image's capacity "
-                    "within int32", B, H, W);
-    return SWF_OK;
-}
-
-size_t swf_jpeg_header_bytes(const swf_jpeg_desc* desc) { return check_jpeg_desc(desc) == SWF_OK ? jpeg_header_bytes(*desc) : 0; }
-
-int swf_jpeg_header(const swf_jpeg_desc* desc, int32_t H, int32_t W, uint8_t* host_out, size_t n) {
-    SWF_TRY(check_jpeg_desc(desc));
-    if (!host_out) return fail(SWF_ERR_NULL, "jpeg_header: NULL output");
-    if (H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "jpeg_header: empty image (H=%d W=%d)", H, W);
-    if (H > 65535 || W > 65535) return fail(SWF_ERR_UNSUPPORTED, "jpeg_header: H=%d W=%d beyond the frame header's 16 bits", H, W);
-    if (n < jpeg_header_bytes(*desc)) return fail(SWF_ERR_WORKSPACE, "jpeg_header: room for %zu bytes, %zu needed", n, jpeg_header_bytes(*desc));
-    jpeg_header(*desc, H, W, host_out);
-    return SWF_OK;
-}
-
-size_t swf_jpeg_capacity_bytes(const swf_jpeg_desc* desc, int32_t H, int32_t W) {
-    return check_jpeg_desc(desc) == SWF_OK && check_jpeg_shape(*desc, 1, H, W) == SWF_OK ? jpeg_capacity_bytes(*desc, H, W) : 0;
-}
-
-size_t swf_jpeg_workspace_bytes(const swf_jpeg_desc* desc, int32_t B, int32_t H, int32_t W) {
-    return check_jpeg_desc(desc) == SWF_OK && check_jpeg_shape(*desc, B, H, W) == SWF_OK ? jpeg_workspace_bytes(*desc, B, H, W) : 0;
-}
-
-int swf_jpeg_encode(const swf_jpeg_desc* desc, const uint8_t* pixels, const uint8_t* header_dev, uint8_t* out, size_t capacity,
-                    int32_t* lengths, int32_t B, int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    SWF_TRY(check_jpeg_desc(desc));
-    if (!pixels || !out || !lengths) return fail(SWF_ERR_NULL, "jpeg_encode: NULL pixels, output or lengths");
-    SWF_TRY(check_jpeg_shape(*desc, B, H, W));
-    const size_t cap = jpeg_capacity_bytes(*desc, H, W), need = jpeg_workspace_bytes(*desc, B, H, W);
-    if (capacity < cap) return fail(SWF_ERR_WORKSPACE, "jpeg_encode: capacity of %zu bytes per image, %zu needed", capacity, cap);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "jpeg_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return jpeg_encode(*desc, pixels, header_dev, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
-// PNG encoder.  One check of the descriptor and one of the shape serve the two queries and the call.
-static int check_png_desc(const swf_png_desc* d) {
-    if (!d) return fail(SWF_ERR_NULL, "png: NULL descriptor");
-    if (!png_desc_ok(*d))
-        return fail(SWF_ERR_BAD_SHAPE, "png: channels=%d rows_per_block=%d reserved=%d (channels 1 or 3, rows_per_block >= 0, reserved 0)",
-                    d->channels, d->rows_per_block, d->reserved);
-    return SWF_OK;
-}
-
-static int check_png_shape(const swf_png_desc& d, int32_t B, int32_t H, int32_t W) {
-    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "png: empty tensor (B=%d H=%d W=%d)", B, H, W);
-    if (!png_shape_ok(d, B, H, W))
-        return fail(SWF_ERR_UNSUPPORTED, "png: B=%d H=%d W=%d rows_per_block=%d: B H W channels, the streams of the batch and one image's "
-                    "capacity must fit int32, and a block %lld stream bytes", B, H, W, d.rows_per_block, (long long)kPngMaxBlockBytes);
-    return SWF_OK;
-}
-
-size_t swf_png_capacity_bytes(const swf_png_desc* desc, int32_t H, int32_t W) {
-    return check_png_desc(desc) == SWF_OK && check_png_shape(*desc, 1, H, W) == SWF_OK ? png_capacity_bytes(*desc, H, W) : 0;
-}
-
-size_t swf_png_workspace_bytes(const swf_png_desc* desc, int32_t B, int32_t H, int32_t W) {
-    return check_png_desc(desc) == SWF_OK && check_png_shape(*desc, B, H, W) == SWF_OK ? png_workspace_bytes(*desc, B, H, W) : 0;
-}
-
-int swf_png_encode(const swf_png_desc* desc, const uint8_t* pixels, uint8_t* out, size_t capacity, int32_t* lengths, int32_t B, int32_t H,
-                   int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    SWF_TRY(check_png_desc(desc));
-    if (!pixels || !out || !lengths) return fail(SWF_ERR_NULL, "png_encode: NULL pixels, output or lengths");
-    SWF_TRY(check_png_shape(*desc, B, H, W));
-    const size_t cap = png_capacity_bytes(*desc, H, W), need = png_workspace_bytes(*desc, B, H, W);
-    if (capacity < cap) return fail(SWF_ERR_WORKSPACE, "png_encode: capacity of %zu bytes per image, %zu needed", capacity, cap);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "png_encode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return png_encode(*desc, pixels, out, capacity, lengths, B, H, W, workspace, workspace_bytes, as_stream(stream));
-}
-
-// Baseline JPEG decoder.  The parse and the workspace query are host-only; the call checks the host copy of the descriptors, every
-// file's place in the data buffer and every file's pixels in the output buffer before the first launch.
-int swf_jpeg_parse(const uint8_t* data, size_t n, swf_jpeg_file* file, uint32_t* intervals, size_t intervals_cap, size_t* intervals_needed) {
-    if (!data || !file || !intervals_needed) return fail(SWF_ERR_NULL, "jpeg_parse: NULL data, descriptor or count");
-    return jpegdec_parse(data, n, file, intervals, intervals ? intervals_cap : 0, intervals_needed);
-}
-
-static int check_jpeg_files(const swf_jpeg_file* files, int32_t n_files) {
-    if (!files) return fail(SWF_ERR_NULL, "jpeg_decode: NULL descriptors");
-    if (n_files < 1) return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: %d files", n_files);
-    if (n_files > kJpegDecMaxFiles) return fail(SWF_ERR_UNSUPPORTED, "jpeg_decode: %d files in one call (%d at most)", n_files, kJpegDecMaxFiles);
-    for (int32_t i = 0; i < n_files; ++i) SWF_TRY(jpegdec_file_ok(files[i], i));
-    if (jpegdec_workspace_bytes(files, n_files) == 0) return fail(SWF_ERR_UNSUPPORTED, "jpeg_decode: more than 2^31 - 1 blocks or intervals in one call");
-    return SWF_OK;
-}
-
-size_t swf_jpeg_decode_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files) {
-    return check_jpeg_files(files_host, n_files) == SWF_OK ? jpegdec_workspace_bytes(files_host, n_files) : 0;
-}
-
-// What swf_jpeg_decode and swf_jpeg_decode_split check alike: pointers, layout, descriptors, every file's place in both buffers.
-static int check_jpeg_decode_args(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev,
-                                  int32_t n_files, const uint32_t* intervals_dev, const uint8_t* out, size_t out_bytes, const int32_t* status,
-                                  int32_t layout) {
-    if (!data || !files_host || !files_dev || !intervals_dev || !out || !status)
-        return fail(SWF_ERR_NULL, "jpeg_decode: NULL data, descriptors, intervals, output or status");
-    if (layout != SWF_JPEG_OUT_BGR && layout != SWF_JPEG_OUT_RGB && layout != SWF_JPEG_OUT_GRAY)
-        return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: layout %d (0 BGR, 1 RGB, 2 gray)", layout);
-    SWF_TRY(check_jpeg_files(files_host, n_files));
-    const uint64_t px = layout == SWF_JPEG_OUT_GRAY ? 1 : 3;
-    std::vector<std::pair<uint64_t, uint64_t>> ranges((size_t)n_files);
-    for (int32_t i = 0; i < n_files; ++i) {
-        const swf_jpeg_file& f = files_host[i];
-        if (f.data_off > data_bytes || f.data_bytes > data_bytes - f.data_off)
-            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: file %d: bytes [%llu, + %u) leave the data buffer of %zu bytes", i,
-                        (unsigned long long)f.data_off, f.data_bytes, data_bytes);
-        const uint64_t n = (uint64_t)f.H * f.W * px;
-        if (f.out_off > out_bytes || n > out_bytes - f.out_off)
-            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: file %d: pixels [%llu, + %llu) leave the output buffer of %zu bytes", i,
-                        (unsigned long long)f.out_off, (unsigned long long)n, out_bytes);
-        ranges[(size_t)i] = {f.out_off, f.out_off + n};
-    }
-    std::sort(ranges.begin(), ranges.end());
-    for (size_t i = 1; i < ranges.size(); ++i)
-        if (ranges[i].first < ranges[i - 1].second)
-            return fail(SWF_ERR_BAD_SHAPE, "jpeg_decode: the pixels of two files overlap at byte %llu of the output", (unsigned long long)ranges[i].first);
-    return SWF_OK;
-}
-
-int swf_jpeg_decode(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
-                    const uint32_t* intervals_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
-                    size_t workspace_bytes, swf_stream_t stream) {
-    SWF_TRY(check_jpeg_decode_args(data, data_bytes, files_host, files_dev, n_files, intervals_dev, out, out_bytes, status, layout));
-    const size_t need = jpegdec_workspace_bytes(files_host, n_files);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "jpeg_decode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return jpegdec_decode(data, files_host, files_dev, n_files, intervals_dev, out, status, layout, workspace, workspace_bytes, as_stream(stream));
-}
-
-size_t swf_jpeg_decode_split_workspace_bytes(const swf_jpeg_file* files_host, int32_t n_files, const uint32_t* intervals_host, int32_t segment_bytes) {
-    if (check_jpeg_files(files_host, n_files) != SWF_OK || jpegdec_split_check(files_host, n_files, intervals_host, segment_bytes) != SWF_OK) return 0;
-    return jpegdec_split_workspace_bytes(files_host, n_files, intervals_host, segment_bytes);
-}
-
-int swf_jpeg_decode_split(const uint8_t* data, size_t data_bytes, const swf_jpeg_file* files_host, const swf_jpeg_file* files_dev, int32_t n_files,
-                          const uint32_t* intervals_dev, const uint32_t* intervals_host, int32_t segment_bytes, uint8_t* out, size_t out_bytes,
-                          int32_t* status, int32_t layout, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    SWF_TRY(check_jpeg_decode_args(data, data_bytes, files_host, files_dev, n_files, intervals_dev, out, out_bytes, status, layout));
-    SWF_TRY(jpegdec_split_check(files_host, n_files, intervals_host, segment_bytes));
-    const size_t need = jpegdec_split_workspace_bytes(files_host, n_files, intervals_host, segment_bytes);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "jpeg_decode_split: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return jpegdec_split_decode(data, files_host, files_dev, n_files, intervals_dev, intervals_host, segment_bytes, out, status, layout, workspace,
-                                workspace_bytes, as_stream(stream));
-}
-
-// PNG decoder.  The parse and the workspace query are host-only; the call checks the host copy of the descriptors, every file's place in
-// the data buffer and every file's pixels in the output buffer before the first launch.
-int swf_png_parse(const uint8_t* data, size_t n, swf_png_file* file, uint32_t* ranges, size_t ranges_cap, size_t* ranges_needed) {
-    if (!data || !file || !ranges_needed) return fail(SWF_ERR_NULL, "png_parse: NULL data, descriptor or count");
-    return pngdec_parse(data, n, file, ranges, ranges ? ranges_cap : 0, ranges_needed);
-}
-
-static int check_png_files(const swf_png_file* files, int32_t n_files) {
-    if (!files) return fail(SWF_ERR_NULL, "png_decode: NULL descriptors");
-    if (n_files < 1) return fail(SWF_ERR_BAD_SHAPE, "png_decode: %d files", n_files);
-    if (n_files > kPngDecMaxFiles) return fail(SWF_ERR_UNSUPPORTED, "png_decode: %d files in one call (%d at most)", n_files, kPngDecMaxFiles);
-    for (int32_t i = 0; i < n_files; ++i) SWF_TRY(pngdec_file_ok(files[i], i));
-    if (pngdec_workspace_bytes(files, n_files) == 0)
-        return fail(SWF_ERR_UNSUPPORTED, "png_decode: more than 2^31 - 1 inflated bytes, stream bytes or IDAT ranges in one call");
-    return SWF_OK;
-}
-
-size_t swf_png_decode_workspace_bytes(const swf_png_file* files_host, int32_t n_files) {
-    return check_png_files(files_host, n_files) == SWF_OK ? pngdec_workspace_bytes(files_host, n_files) : 0;
-}
-
-int swf_png_decode(const uint8_t* data, size_t data_bytes, const swf_png_file* files_host, const swf_png_file* files_dev, int32_t n_files,
-                   const uint32_t* ranges_dev, uint8_t* out, size_t out_bytes, int32_t* status, int32_t layout, void* workspace,
-                   size_t workspace_bytes, swf_stream_t stream) {
-    if (!data || !files_host || !files_dev || !ranges_dev || !out || !status)
-        return fail(SWF_ERR_NULL, "png_decode: NULL data, descriptors, ranges, output or status");
-    if (layout != SWF_PNG_OUT_BGR && layout != SWF_PNG_OUT_RGB && layout != SWF_PNG_OUT_GRAY)
-        return fail(SWF_ERR_BAD_SHAPE, "png_decode: layout %d (0 BGR, 1 RGB, 2 gray)", layout);
-    SWF_TRY(check_png_files(files_host, n_files));
-    const uint64_t px = layout == SWF_PNG_OUT_GRAY ? 1 : 3;
-    std::vector<std::pair<uint64_t, uint64_t>> spans((size_t)n_files);
-    for (int32_t i = 0; i < n_files; ++i) {
-        const swf_png_file& f = files_host[i];
-        if (f.data_off > data_bytes || f.data_bytes > data_bytes - f.data_off)
-            return fail(SWF_ERR_BAD_SHAPE, "png_decode: file %d: bytes [%llu, + %u) leave the data buffer of %zu bytes", i,
-                        (unsigned long long)f.data_off, f.data_bytes, data_bytes);
-        const uint64_t n = (uint64_t)f.H * f.W * px;
-        if (f.out_off > out_bytes || n > out_bytes - f.out_off)
-            return fail(SWF_ERR_BAD_SHAPE, "png_decode: file %d: pixels [%llu, + %llu) leave the output buffer of %zu bytes", i,
-                        (unsigned long long)f.out_off, (unsigned long long)n, out_bytes);
-        spans[(size_t)i] = {f.out_off, f.out_off + n};
-    }
-    std::sort(spans.begin(), spans.end());
-    for (size_t i = 1; i < spans.size(); ++i)
-        if (spans[i].first < spans[i - 1].second)
-            return fail(SWF_ERR_BAD_SHAPE, "png_decode: the pixels of two files overlap at byte %llu of the output", (unsigned long long)spans[i].first);
-    const size_t need = pngdec_workspace_bytes(files_host, n_files);
-    if (!workspace || workspace_bytes < need)
-        return fail(SWF_ERR_WORKSPACE, "png_decode: workspace of %zu bytes, %zu needed", workspace ? workspace_bytes : (size_t)0, need);
-    return pngdec_decode(data, files_host, files_dev, n_files, ranges_dev, out, status, layout, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

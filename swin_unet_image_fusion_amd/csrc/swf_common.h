@@ -15,6 +15,12 @@ namespace swf {
 char* err_buf();
 int fail(int status, const char* fmt, ...);
 
+// The workspace refusal of every entry that takes one: SWF_OK, or SWF_ERR_WORKSPACE with `who`, what was given and what is needed.
+inline int need_workspace(const char* who, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (workspace && workspace_bytes >= need) return SWF_OK;
+    return fail(SWF_ERR_WORKSPACE, "%s: workspace of %zu bytes, %zu needed", who, workspace ? workspace_bytes : (size_t)0, need);
+}
+
 inline hipStream_t as_stream(swf_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // Check the launch that was just enqueued (no sync: only launch-configuration errors show up here).

@@ -18,12 +18,13 @@ from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from . import imaging
 from .modules import _stream
 
 __all__ = ["sample_crop_params", "ResidentPairs", "PairLoader"]
@@ -32,6 +33,40 @@ _ROW = np.dtype(L.CropRow)
 _ALIGN = 16
 _DECODE_BUDGET = 256 << 20     # bytes of coefficient workspace one swf_jpeg_decode call of from_folder(decode="device") may take
 _DECODE_GROUP_FILES = 4096     # and files per call
+
+
+class _Codec(NamedTuple):
+    """A format from_folder(decode="device") hands to the device; a file is its codec's by its first bytes."""
+    magic: bytes
+    parse: Callable                # the file's bytes -> (descriptor, rows); NotImplementedError or ValueError sends the file to PIL
+    budget: Callable               # (parsed, entropy) -> bytes of the file in a group's budget
+    decode_into: Callable          # (arena, offsets, files, parsed, layout, entropy) -> the device status per file
+    refuse: Optional[Callable]     # (statuses, paths) raises for a non-zero status; None: such a file is decoded again through PIL, whose
+                                   # verdict stands: its pixels (a stream longer than the image) or its OSError (truncated, wrong Adler-32)
+
+
+# Bytes of a file in a group's budget: coefficients and samples, and what the split pass adds to them.  An estimate on the safe side of a
+# soft budget: "auto" counts the split tables although the group's call may take the interval path, and the 256-byte alignment of the
+# carved arrays (a few KB per call) is left out; imaging.split_workspace_bytes gives a call's exact size.
+def _jpeg_budget(x, entropy: str) -> int:
+    if entropy == "interval":
+        return x[0].blocks * 192
+    raw = x[1][:, 1].astype(np.int64) - x[1][:, 0]
+    segments = np.maximum(1, -(-raw // imaging._SEGMENT_BYTES))
+    return x[0].blocks * 192 + int((4 * -(-raw // 4) + 44 * segments + 48).sum())
+
+
+def _png_budget(x, entropy: str) -> int:   # the stream and the inflated bytes, each rounded up to 16 (the query adds 60 bytes per file)
+    return x[0].idat_bytes + 48 + x[0].H * (1 + x[0].W * x[0].bpp) + 76
+
+
+def _png_into(arena, offsets, files, parsed, layout, entropy):   # no entropy pass to choose
+    return imaging.decode_png_into(arena, offsets, files, parsed, layout)
+
+
+# In the order an arena's open groups are flushed.
+_CODECS = (_Codec(b"\xff\xd8", imaging.parse_jpeg, _jpeg_budget, imaging.decode_jpeg_into, imaging.check_stream_status),
+           _Codec(imaging.PNG_SIGNATURE, imaging.parse_png, _png_budget, _png_into, None))
 
 
 def sample_crop_params(H: int, W: int, size=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), p_flip: float = 0.5,
@@ -172,25 +207,16 @@ class ResidentPairs:
         """from_folder(decode="device") behind the pairing.  Per file: its bytes and the parser's descriptor, or PIL's array."""
         from PIL import Image
 
-        from . import imaging
-
-        def read(p, mode):   # -> (bytes, parsed) for the decoder, or (None, array) from PIL
+        def read(p, mode):   # -> (bytes, codec, parsed) for the decoder, or (None, None, array) from PIL
             with open(p, "rb") as f:
                 data = f.read()
-            if data[:2] == b"\xff\xd8":
-                try:
-                    return data, imaging.parse_jpeg(data)
-                except (NotImplementedError, ValueError):
-                    pass
-            elif data[:8] == imaging.PNG_SIGNATURE:
-                try:
-                    return data, imaging.parse_png(data)
-                except (NotImplementedError, ValueError):
-                    pass
-            return None, pil_array(p, mode)
-
-        def is_png(x):
-            return isinstance(x[0], L.PngFile)
+            for codec in _CODECS:
+                if data.startswith(codec.magic):
+                    try:
+                        return data, codec, codec.parse(data)
+                    except (NotImplementedError, ValueError):
+                        break
+            return None, None, pil_array(p, mode)
 
         def pil_array(p, mode):
             with Image.open(p) as im:
@@ -198,20 +224,8 @@ class ResidentPairs:
             return a if mode == "L" else np.ascontiguousarray(a[..., ::-1])
 
         def shape(entry):
-            data, x = entry
+            data, _, x = entry
             return (x[0].H, x[0].W) if data is not None else tuple(x.shape[:2])
-
-        # Bytes of a file in a group's budget: coefficients and samples, and what the split pass adds to them.  An estimate on the safe
-        # side of a soft budget: "auto" counts the split tables although the group's call may take the interval path, and the 256-byte
-        # alignment of the carved arrays (a few KB per call) is left out; imaging.split_workspace_bytes gives a call's exact size.
-        def workspace(x):
-            if is_png(x):   # the stream and the inflated bytes, each rounded up to 16 (swf_png_decode_workspace_bytes adds 60 bytes per file)
-                return x[0].idat_bytes + 48 + x[0].H * (1 + x[0].W * x[0].bpp) + 76
-            if entropy == "interval":
-                return x[0].blocks * 192
-            raw = x[1][:, 1].astype(np.int64) - x[1][:, 0]
-            segments = np.maximum(1, -(-raw // imaging._SEGMENT_BYTES))
-            return x[0].blocks * 192 + int((4 * -(-raw // 4) + 44 * segments + 48).sum())
 
         irs, viss = [read(p, "L") for p in ir_paths], [read(p, "RGB") for p in vis_paths]
         for i, (a, b) in enumerate(zip(irs, viss)):
@@ -220,39 +234,37 @@ class ResidentPairs:
         items, ir_end, vis_end = cls._place([shape(a) for a in irs], list(zip(ir_paths, vis_paths)))
         ir_arena, vis_arena = torch.zeros(ir_end, dtype=torch.uint8, device=device), torch.zeros(vis_end, dtype=torch.uint8, device=device)
         for arena, entries, paths, col, layout in ((ir_arena, irs, ir_paths, 0, "gray"), (vis_arena, viss, vis_paths, 1, "bgr")):
-            # JPEG and PNG files go to their own decoder calls: a group of each kind is open at a time, under the same budget
-            groups, used, pending = {False: [], True: []}, {False: 0, True: 0}, []
+            # every format's files go to its own decoder calls: a group of each is open at a time, under the same budget
+            groups, used, pending = {c: [] for c in _CODECS}, {c: 0 for c in _CODECS}, []
 
-            def flush(png):
-                group = groups[png]
+            def place(i, a):
+                arena[items[i][col]:items[i][col] + a.size].copy_(torch.from_numpy(a.reshape(-1)))
+
+            def flush(codec):
+                group = groups[codec]
                 if group:
-                    args = (arena, [items[i][col] for i in group], [entries[i][0] for i in group], [entries[i][1] for i in group], layout)
-                    st = imaging.decode_png_into(*args) if png else imaging.decode_jpeg_into(*args, entropy)
-                    pending.append((png, st, list(group)))
-                groups[png], used[png] = [], 0
+                    st = codec.decode_into(arena, [items[i][col] for i in group], [entries[i][0] for i in group], [entries[i][2] for i in group],
+                                           layout, entropy)
+                    pending.append((codec, st, list(group)))
+                groups[codec], used[codec] = [], 0
 
-            for i, (data, x) in enumerate(entries):
+            for i, (data, codec, x) in enumerate(entries):
                 if data is None:
-                    arena[items[i][col]:items[i][col] + x.size].copy_(torch.from_numpy(x.reshape(-1)))
+                    place(i, x)
                     continue
-                png = is_png(x)
-                if groups[png] and (used[png] + workspace(x) > _DECODE_BUDGET or len(groups[png]) >= _DECODE_GROUP_FILES):
-                    flush(png)
-                groups[png].append(i)
-                used[png] += workspace(x)
-            flush(False)
-            flush(True)
-            for png, st, group in pending:
+                if groups[codec] and (used[codec] + codec.budget(x, entropy) > _DECODE_BUDGET or len(groups[codec]) >= _DECODE_GROUP_FILES):
+                    flush(codec)
+                groups[codec].append(i)
+                used[codec] += codec.budget(x, entropy)
+            for codec in _CODECS:   # JPEG before PNG
+                flush(codec)
+            for codec, st, group in pending:   # the statuses are read after every call of the arena has been queued
                 st = st.cpu().tolist()
-                if not png:
-                    imaging.check_stream_status(st, [paths[i] for i in group])
+                if codec.refuse:
+                    codec.refuse(st, [paths[i] for i in group])
                     continue
-                # a PNG with a non-zero status is decoded again through PIL, whose verdict stands: its pixels (a stream longer than the
-                # image, which Pillow accepts) or its exception (OSError for a truncated stream or a wrong Adler-32)
-                for i, s in zip(group, st):
-                    if s:
-                        a = pil_array(paths[i], "L" if col == 0 else "RGB")
-                        arena[items[i][col]:items[i][col] + a.size].copy_(torch.from_numpy(a.reshape(-1)))
+                for i in (i for i, s in zip(group, st) if s):
+                    place(i, pil_array(paths[i], "L" if col == 0 else "RGB"))
         return cls(ir_arena, vis_arena, items)
 
     def split(self, ratio: float, generator: Optional[torch.Generator] = None) -> Tuple[List[int], List[int]]:

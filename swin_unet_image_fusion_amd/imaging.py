@@ -26,7 +26,7 @@ for bit; `png_info(data)` exposes the parse.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -118,79 +118,160 @@ def encode_jpeg(images_u8: Tensor, quality: int = 75, subsampling: str = "4:2:0"
     include/swinfuse.h; "4:2:0" is what Pillow, and so save_image, writes by default).  `subsampling` is the chroma's: a gray batch
     has none.  Three launches on the current stream and no copy to the host: the header of a (shape, mode, quality) is built on the
     host once and kept on the device."""
-    images_u8 = _u8(images_u8, "images")
-    if images_u8.dim() not in (3, 4) or (images_u8.dim() == 4 and images_u8.shape[-1] != 3):
-        raise ValueError(f"expected RGB (B,H,W,3) or gray (B,H,W), got {tuple(images_u8.shape)}")
+    images_u8 = _images(images_u8)
     if subsampling not in _SUBSAMPLING:
         raise ValueError(f"subsampling {subsampling!r}: expected one of {sorted(_SUBSAMPLING)}")
-    b, h, w = images_u8.shape[:3]
-    gray = images_u8.dim() == 3
+    gray, lib = images_u8.dim() == 3, L.lib()
     desc = L.JpegDesc(1 if gray else 3, L.JPEG_444 if gray else _SUBSAMPLING[subsampling], int(quality))
-    lib, dev = L.lib(), images_u8.device
-    capacity = lib.swf_jpeg_capacity_bytes(C.byref(desc), h, w)
-    need = lib.swf_jpeg_workspace_bytes(C.byref(desc), b, h, w)
-    if capacity == 0 or need == 0:   # the queries refuse what the call refuses, before any launch: let the call name the reason
-        L.check(lib.swf_jpeg_encode(C.byref(desc), 1, None, 1, 0, 1, b, h, w, None, 0, None))
-    header = _jpeg_header(desc, dev, h, w)
-    data = torch.empty((b, capacity), dtype=torch.uint8, device=dev)
-    lengths = torch.empty((b,), dtype=torch.int32, device=dev)
-    workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    L.check(lib.swf_jpeg_encode(C.byref(desc), images_u8.data_ptr(), header.data_ptr(), data.data_ptr(), capacity, lengths.data_ptr(),
-                                b, h, w, workspace.data_ptr(), need, _stream(dev)))
-    return JpegBatch(data, lengths)
+    return _encode(JpegBatch, images_u8, desc, lib.swf_jpeg_capacity_bytes, lib.swf_jpeg_workspace_bytes, lib.swf_jpeg_encode, _jpeg_header)
 
 
 class PngBatch(JpegBatch):
     """The files of one `encode_png` call, laid out as a JpegBatch is."""
 
 
+def _images(images_u8: Tensor) -> Tensor:
+    """What both encoders take."""
+    images_u8 = _u8(images_u8, "images")
+    if images_u8.dim() not in (3, 4) or (images_u8.dim() == 4 and images_u8.shape[-1] != 3):
+        raise ValueError(f"expected RGB (B,H,W,3) or gray (B,H,W), got {tuple(images_u8.shape)}")
+    return images_u8
+
+
+def _encode(batch_type, images_u8: Tensor, desc, capacity_bytes, workspace_bytes, encode, header=None):
+    """Both encoders behind their options: the two queries, the three allocations and the call.  `header` (JPEG) gives the device tensor
+    the call takes after the pixels."""
+    b, h, w = images_u8.shape[:3]
+    dev = images_u8.device
+    capacity, need = capacity_bytes(C.byref(desc), h, w), workspace_bytes(C.byref(desc), b, h, w)
+    if capacity == 0 or need == 0:   # the queries refuse what the call refuses, before any launch: let the call name the reason
+        L.check(encode(C.byref(desc), 1, *((None,) if header else ()), 1, 0, 1, b, h, w, None, 0, None))
+    head = (header(desc, dev, h, w).data_ptr(),) if header else ()
+    data = torch.empty((b, capacity), dtype=torch.uint8, device=dev)
+    lengths = torch.empty((b,), dtype=torch.int32, device=dev)
+    workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    L.check(encode(C.byref(desc), images_u8.data_ptr(), *head, data.data_ptr(), capacity, lengths.data_ptr(), b, h, w, workspace.data_ptr(),
+                   need, _stream(dev)))
+    return batch_type(data, lengths)
+
+
 def encode_png(images_u8: Tensor, rows_per_block: Optional[int] = None) -> PngBatch:
     """images_u8 (B,H,W,3) RGB or (B,H,W) gray, uint8 on the GPU -> their PNG files (the format of swf_png_encode in include/swinfuse.h:
     colour type 2 or 0, 8 bits, one IDAT).  `rows_per_block` rows of the image make one deflate block (None: the library's default, 16).
     Six launches on the current stream and no copy to the host."""
-    images_u8 = _u8(images_u8, "images")
-    if images_u8.dim() not in (3, 4) or (images_u8.dim() == 4 and images_u8.shape[-1] != 3):
-        raise ValueError(f"expected RGB (B,H,W,3) or gray (B,H,W), got {tuple(images_u8.shape)}")
+    images_u8 = _images(images_u8)
     if rows_per_block is not None and int(rows_per_block) < 1:
         raise ValueError(f"rows_per_block {rows_per_block!r}: expected None or a positive number of rows")
-    b, h, w = images_u8.shape[:3]
-    desc = L.PngDesc(1 if images_u8.dim() == 3 else 3, 0 if rows_per_block is None else int(rows_per_block), 0)
-    lib, dev = L.lib(), images_u8.device
-    capacity = lib.swf_png_capacity_bytes(C.byref(desc), h, w)
-    need = lib.swf_png_workspace_bytes(C.byref(desc), b, h, w)
-    if capacity == 0 or need == 0:   # the queries refuse what the call refuses, before any launch: let the call name the reason
-        L.check(lib.swf_png_encode(C.byref(desc), 1, 1, 0, 1, b, h, w, None, 0, None))
-    data = torch.empty((b, capacity), dtype=torch.uint8, device=dev)
-    lengths = torch.empty((b,), dtype=torch.int32, device=dev)
-    workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    L.check(lib.swf_png_encode(C.byref(desc), images_u8.data_ptr(), data.data_ptr(), capacity, lengths.data_ptr(), b, h, w,
-                               workspace.data_ptr(), need, _stream(dev)))
-    return PngBatch(data, lengths)
+    desc, lib = L.PngDesc(1 if images_u8.dim() == 3 else 3, 0 if rows_per_block is None else int(rows_per_block), 0), L.lib()
+    return _encode(PngBatch, images_u8, desc, lib.swf_png_capacity_bytes, lib.swf_png_workspace_bytes, lib.swf_png_encode)
 
 
-# ---- the decoder ---------------------------------------------------------------------------------------------------------------------
+# ---- the decoders: what the two formats share ------------------------------------------------------------------------------------------
 _LAYOUTS = {"bgr": (L.JPEG_OUT_BGR, 3), "rgb": (L.JPEG_OUT_RGB, 3), "gray": (L.JPEG_OUT_GRAY, 1)}
-_STREAM_KINDS = {L.JPEG_STREAM_TRUNCATED: "the data ends inside a code", L.JPEG_STREAM_RUN: "a run past coefficient 63",
-                 L.JPEG_STREAM_CODE: "an undefined code or a DC value out of range"}
-_INTERVALS_GUESS = 256   # pairs the first parse of a file has room for; a file with more is parsed a second time
 _OUT_ALIGN = 16
+
+
+class _Decoder(NamedTuple):
+    """A format, as the shared decode path sees it."""
+    noun: str                # in messages
+    file_type: type          # the ctypes descriptor of a file
+    parse: str               # the library's parse entry
+    guess: int               # pairs the first parse of a file has room for; a file with more is parsed a second time
+    kinds: Dict[int, str]    # a device status -> what it says
+    entry: Callable          # (rows_host, **options) -> (the library's decode entry, what it and its query take behind the tables)
+
+
+def _parse(dec: _Decoder, data: bytes, index: int) -> Tuple[C.Structure, np.ndarray]:
+    lib, desc, need = L.lib(), dec.file_type(), C.c_size_t(0)
+    parse = getattr(lib, dec.parse)
+    src = C.cast(C.c_char_p(data), C.c_void_p)
+    rows = np.empty((dec.guess, 2), dtype=np.uint32)
+    st = parse(src, len(data), C.byref(desc), rows.ctypes.data, len(rows), C.byref(need))
+    if st == L.ERR_WORKSPACE:
+        rows = np.empty((need.value, 2), dtype=np.uint32)
+        st = parse(src, len(data), C.byref(desc), rows.ctypes.data, len(rows), C.byref(need))
+    try:
+        L.check(st)
+    except (NotImplementedError, ValueError) as e:
+        raise type(e)(f"file {index}: {e}") from None
+    return desc, rows[:need.value].copy()
+
+
+def _file_tables(file_type, parsed: Sequence[tuple], files: Sequence[bytes], offsets: Sequence[int], dev):
+    """What a decode call reads: -> (descriptors placed in both buffers, the files' interval or range rows on the host, descriptors and
+    rows on the device in one upload, the files' bytes in another, the status tensor)."""
+    n = len(files)
+    descs = (file_type * n)()
+    pos = 0
+    for i, ((d, _), data) in enumerate(zip(parsed, files)):
+        d.data_off, d.out_off = pos, int(offsets[i])
+        descs[i] = d
+        pos += len(data)
+    rows = np.ascontiguousarray(np.concatenate([r.reshape(-1) for _, r in parsed]), dtype=np.uint32)
+    tables_dev = torch.from_numpy(np.concatenate([np.frombuffer(descs, dtype=np.uint8), rows.view(np.uint8)])).to(dev)
+    data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
+    return descs, rows, tables_dev, data_dev, torch.empty((n,), dtype=torch.int32, device=dev)
+
+
+def _decode_into(dec: _Decoder, out: Tensor, offsets, files, parsed, code: int, **options) -> Tensor:
+    """One decode call on the workspace its query asks for.  -> the device int32 status per file."""
+    out = _u8(out, "out")
+    lib, dev, n = L.lib(), out.device, len(files)
+    descs, rows, tables_dev, data_dev, status = _file_tables(dec.file_type, parsed, files, offsets, dev)
+    entry, extra = dec.entry(rows, **options)
+    need = getattr(lib, entry + "_workspace_bytes")(descs, n, *extra)
+    workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+    L.check(getattr(lib, entry)(data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n,
+                                tables_dev.data_ptr() + n * C.sizeof(dec.file_type), *extra, out.data_ptr(), out.numel(), status.data_ptr(), code,
+                                workspace.data_ptr(), need, _stream(dev)))
+    return status
+
+
+def _check_status(dec: _Decoder, statuses: Sequence[int], names: Optional[Sequence]) -> None:
+    for i, s in enumerate(statuses):
+        if s:
+            raise ValueError(f"file {names[i] if names is not None else i}: corrupt {dec.noun} data: {dec.kinds.get(s, s)} (status {s})")
+
+
+def _decode(dec: _Decoder, who: str, files: Sequence[bytes], layout: str, device, strict: bool, into):
+    """decode_jpeg and decode_png: `into(out, offsets, files, parsed, layout)` is the format's decode-into call."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
+    files = [bytes(f) for f in files]
+    if not files:
+        raise ValueError("no files")
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise RuntimeError(f"{who}: the decoder runs on the GPU only, got {dev}")
+    parsed = [_parse(dec, f, i) for i, f in enumerate(files)]
+    px = _LAYOUTS[layout][1]
+    offsets, end = [], 0
+    for d, _ in parsed:
+        offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
+        end = offsets[-1] + d.H * d.W * px
+    out = torch.empty(end, dtype=torch.uint8, device=dev)
+    statuses = into(out, offsets, files, parsed, layout).cpu().tolist()
+    images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
+    if strict:
+        _check_status(dec, statuses, None)
+        return images
+    return images, statuses
+
+
+# ---- the JPEG decoder ------------------------------------------------------------------------------------------------------------------
+def _jpeg_entry(intervals, entropy, segment_bytes):
+    return ("swf_jpeg_decode_split", (intervals.ctypes.data, int(segment_bytes))) if entropy == "split" else ("swf_jpeg_decode", ())
+
+
+_JPEG = _Decoder("JPEG", L.JpegFile, "swf_jpeg_parse", 256,
+                 {L.JPEG_STREAM_TRUNCATED: "the data ends inside a code", L.JPEG_STREAM_RUN: "a run past coefficient 63",
+                  L.JPEG_STREAM_CODE: "an undefined code or a DC value out of range"}, _jpeg_entry)
 
 
 def parse_jpeg(data: bytes, index: int = 0) -> Tuple["L.JpegFile", np.ndarray]:
     """swf_jpeg_parse on the host: -> (descriptor, (intervals, 2) uint32 array of (begin, end) byte offsets).  NotImplementedError for a
     file outside the decoder's scope, ValueError for a broken one, both naming `index`."""
-    lib, desc, need = L.lib(), L.JpegFile(), C.c_size_t(0)
-    src = C.cast(C.c_char_p(data), C.c_void_p)
-    iv = np.empty((_INTERVALS_GUESS, 2), dtype=np.uint32)
-    st = lib.swf_jpeg_parse(src, len(data), C.byref(desc), iv.ctypes.data, len(iv), C.byref(need))
-    if st == L.ERR_WORKSPACE:
-        iv = np.empty((need.value, 2), dtype=np.uint32)
-        st = lib.swf_jpeg_parse(src, len(data), C.byref(desc), iv.ctypes.data, len(iv), C.byref(need))
-    try:
-        L.check(st)
-    except (NotImplementedError, ValueError) as e:
-        raise type(e)(f"file {index}: {e}") from None
-    return desc, iv[:need.value].copy()
+    return _parse(_JPEG, data, index)
 
 
 def jpeg_info(data: bytes) -> dict:
@@ -236,38 +317,12 @@ def decode_jpeg_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes]
     restart interval), "split" is swf_jpeg_decode_split with segments of `segment_bytes` (lanes inside an interval: for files without
     restart markers), "auto" chooses by the call's longest interval.  -> the device int32 stream status per file."""
     code, _ = _LAYOUTS[layout]
-    entropy = choose_entropy(entropy, parsed)
-    out = _u8(out, "out")
-    lib, dev, n = L.lib(), out.device, len(files)
-    descs = (L.JpegFile * n)()
-    pos = 0
-    for i, ((d, _), data) in enumerate(zip(parsed, files)):
-        d.data_off, d.out_off = pos, int(offsets[i])
-        descs[i] = d
-        pos += len(data)
-    intervals = np.ascontiguousarray(np.concatenate([iv.reshape(-1) for _, iv in parsed]), dtype=np.uint32)
-    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8), intervals.view(np.uint8)])
-    tables_dev = torch.from_numpy(tables).to(dev)
-    data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
-    status = torch.empty((n,), dtype=torch.int32, device=dev)
-    head = (data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n, tables_dev.data_ptr() + n * C.sizeof(L.JpegFile))
-    if entropy == "split":
-        need = lib.swf_jpeg_decode_split_workspace_bytes(descs, n, intervals.ctypes.data, int(segment_bytes))
-        workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-        L.check(lib.swf_jpeg_decode_split(*head, intervals.ctypes.data, int(segment_bytes), out.data_ptr(), out.numel(), status.data_ptr(), code,
-                                          workspace.data_ptr(), need, _stream(dev)))
-        return status
-    need = lib.swf_jpeg_decode_workspace_bytes(descs, n)
-    workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    L.check(lib.swf_jpeg_decode(*head, out.data_ptr(), out.numel(), status.data_ptr(), code, workspace.data_ptr(), need, _stream(dev)))
-    return status
+    return _decode_into(_JPEG, out, offsets, files, parsed, code, entropy=choose_entropy(entropy, parsed), segment_bytes=segment_bytes)
 
 
 def check_stream_status(statuses: Sequence[int], names: Optional[Sequence] = None) -> None:
     """ValueError for the first file whose entropy-coded data ended early, naming it and the kind."""
-    for i, s in enumerate(statuses):
-        if s:
-            raise ValueError(f"file {names[i] if names is not None else i}: corrupt JPEG data: {_STREAM_KINDS.get(s, s)} (status {s})")
+    _check_status(_JPEG, statuses, names)
 
 
 def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True, entropy: str = "interval",
@@ -278,54 +333,24 @@ def decode_jpeg(files: Sequence[bytes], layout: str = "rgb", device="cuda", stri
     stream statuses are read once after the call; a file whose data ended early raises ValueError, unless strict=False: then
     (images, statuses) is returned and such a file's image is partly zero coefficients.  `entropy` and `segment_bytes`: the entropy pass,
     as decode_jpeg_into describes them; the result does not depend on them."""
-    if layout not in _LAYOUTS:
-        raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
-    if entropy not in ENTROPY:
+    if layout in _LAYOUTS and entropy not in ENTROPY:   # an unknown layout is named first, by _decode
         raise ValueError(f"entropy {entropy!r}: expected one of {list(ENTROPY)}")
-    files = [bytes(f) for f in files]
-    if not files:
-        raise ValueError("no files")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"decode_jpeg: the decoder runs on the GPU only, got {dev}")
-    parsed = [parse_jpeg(f, i) for i, f in enumerate(files)]
-    px = _LAYOUTS[layout][1]
-    offsets, end = [], 0
-    for d, _ in parsed:
-        offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
-        end = offsets[-1] + d.H * d.W * px
-    out = torch.empty(end, dtype=torch.uint8, device=dev)
-    statuses = decode_jpeg_into(out, offsets, files, parsed, layout, entropy, segment_bytes).cpu().tolist()
-    images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
-    if strict:
-        check_stream_status(statuses)
-        return images
-    return images, statuses
+    return _decode(_JPEG, "decode_jpeg", files, layout, device, strict, lambda *args: decode_jpeg_into(*args, entropy, segment_bytes))
 
 
 # ---- the PNG decoder -----------------------------------------------------------------------------------------------------------------
 PNG_SIGNATURE = b"\x89PNG\r\n\x1a\n"
-_PNG_STREAM_KINDS = {L.PNG_STREAM_TRUNCATED: "the compressed data ends early", L.PNG_STREAM_CODE: "an invalid deflate block or code",
-                     L.PNG_STREAM_DISTANCE: "a match reaching before the first byte", L.PNG_STREAM_LONG: "more data than the image holds",
-                     L.PNG_STREAM_ADLER: "the Adler-32 of the pixel data does not match", L.PNG_STREAM_FILTER: "a filter type above 4"}
-_RANGES_GUESS = 64   # pairs the first parse of a file has room for; a file with more IDAT chunks is parsed a second time
+_PNG = _Decoder("PNG", L.PngFile, "swf_png_parse", 64,
+                {L.PNG_STREAM_TRUNCATED: "the compressed data ends early", L.PNG_STREAM_CODE: "an invalid deflate block or code",
+                 L.PNG_STREAM_DISTANCE: "a match reaching before the first byte", L.PNG_STREAM_LONG: "more data than the image holds",
+                 L.PNG_STREAM_ADLER: "the Adler-32 of the pixel data does not match", L.PNG_STREAM_FILTER: "a filter type above 4"},
+                lambda ranges: ("swf_png_decode", ()))
 
 
 def parse_png(data: bytes, index: int = 0) -> Tuple["L.PngFile", np.ndarray]:
     """swf_png_parse on the host: -> (descriptor, (IDAT chunks, 2) uint32 array of (offset, length)).  NotImplementedError for a file
     outside the decoder's scope, ValueError for a broken one, both naming `index`."""
-    lib, desc, need = L.lib(), L.PngFile(), C.c_size_t(0)
-    src = C.cast(C.c_char_p(data), C.c_void_p)
-    ranges = np.empty((_RANGES_GUESS, 2), dtype=np.uint32)
-    st = lib.swf_png_parse(src, len(data), C.byref(desc), ranges.ctypes.data, len(ranges), C.byref(need))
-    if st == L.ERR_WORKSPACE:
-        ranges = np.empty((need.value, 2), dtype=np.uint32)
-        st = lib.swf_png_parse(src, len(data), C.byref(desc), ranges.ctypes.data, len(ranges), C.byref(need))
-    try:
-        L.check(st)
-    except (NotImplementedError, ValueError) as e:
-        raise type(e)(f"file {index}: {e}") from None
-    return desc, ranges[:need.value].copy()
+    return _parse(_PNG, data, index)
 
 
 def png_info(data: bytes) -> dict:
@@ -344,33 +369,12 @@ def png_workspace_bytes(parsed: Sequence[tuple]) -> int:
 def decode_png_into(out: Tensor, offsets: Sequence[int], files: Sequence[bytes], parsed: Sequence[tuple], layout: str) -> Tensor:
     """One decoder call (swf_png_decode, six launches on the current stream): file i's pixels to out[offsets[i]:] (flat uint8 on the GPU)
     in `layout`.  One upload of the files' bytes and one of the descriptors and IDAT ranges.  -> the device int32 status per file."""
-    code, _ = _LAYOUTS[layout]
-    out = _u8(out, "out")
-    lib, dev, n = L.lib(), out.device, len(files)
-    descs = (L.PngFile * n)()
-    pos = 0
-    for i, ((d, _), data) in enumerate(zip(parsed, files)):
-        d.data_off, d.out_off = pos, int(offsets[i])
-        descs[i] = d
-        pos += len(data)
-    ranges = np.ascontiguousarray(np.concatenate([r.reshape(-1) for _, r in parsed]), dtype=np.uint32)
-    tables = np.concatenate([np.frombuffer(descs, dtype=np.uint8), ranges.view(np.uint8)])
-    tables_dev = torch.from_numpy(tables).to(dev)
-    data_dev = torch.frombuffer(bytearray(b"".join(files)), dtype=torch.uint8).to(dev)
-    status = torch.empty((n,), dtype=torch.int32, device=dev)
-    need = lib.swf_png_decode_workspace_bytes(descs, n)
-    workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
-    L.check(lib.swf_png_decode(data_dev.data_ptr(), data_dev.numel(), descs, tables_dev.data_ptr(), n,
-                               tables_dev.data_ptr() + n * C.sizeof(L.PngFile), out.data_ptr(), out.numel(), status.data_ptr(), code,
-                               workspace.data_ptr(), need, _stream(dev)))
-    return status
+    return _decode_into(_PNG, out, offsets, files, parsed, _LAYOUTS[layout][0])
 
 
 def check_png_status(statuses: Sequence[int], names: Optional[Sequence] = None) -> None:
     """ValueError for the first file with a non-zero status, naming it and the kind."""
-    for i, s in enumerate(statuses):
-        if s:
-            raise ValueError(f"file {names[i] if names is not None else i}: corrupt PNG data: {_PNG_STREAM_KINDS.get(s, s)} (status {s})")
+    _check_status(_PNG, statuses, names)
 
 
 def decode_png(files: Sequence[bytes], layout: str = "rgb", device="cuda", strict: bool = True):
@@ -379,24 +383,4 @@ def decode_png(files: Sequence[bytes], layout: str = "rgb", device="cuda", stric
     np.asarray(PIL.Image.open(f).convert(mode)).  A file the parser refuses raises NotImplementedError (out of scope) or ValueError
     (broken) naming its index.  The statuses are read once after the call; a file with a non-zero status raises ValueError naming it and
     the kind, unless strict=False: then (images, statuses) is returned, and the rows such a file did not reach are zero."""
-    if layout not in _LAYOUTS:
-        raise ValueError(f"layout {layout!r}: expected one of {sorted(_LAYOUTS)}")
-    files = [bytes(f) for f in files]
-    if not files:
-        raise ValueError("no files")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise RuntimeError(f"decode_png: the decoder runs on the GPU only, got {dev}")
-    parsed = [parse_png(f, i) for i, f in enumerate(files)]
-    px = _LAYOUTS[layout][1]
-    offsets, end = [], 0
-    for d, _ in parsed:
-        offsets.append(-(-end // _OUT_ALIGN) * _OUT_ALIGN)
-        end = offsets[-1] + d.H * d.W * px
-    out = torch.empty(end, dtype=torch.uint8, device=dev)
-    statuses = decode_png_into(out, offsets, files, parsed, layout).cpu().tolist()
-    images = [out[o:o + d.H * d.W * px].view((d.H, d.W, 3) if px == 3 else (d.H, d.W)) for o, (d, _) in zip(offsets, parsed)]
-    if strict:
-        check_png_status(statuses)
-        return images
-    return images, statuses
+    return _decode(_PNG, "decode_png", files, layout, device, strict, decode_png_into)

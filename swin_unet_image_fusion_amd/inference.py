@@ -26,7 +26,8 @@ def test_fusion(model, store: ResidentPairs, out_dir, quality: int = 75, subsamp
     written, so the device works while the host writes.  format="png" writes lossless PNG files instead (`imaging.encode_png`): their
     decoded pixels are fuse_images' output exactly; `quality` and `subsampling` are ignored, and a suffix left at its default becomes
     "_MKX_SELF.png"."""
-    if format not in ("jpeg", "png"):
+    encoders = {"jpeg": lambda rgb: encode_jpeg(rgb, quality=quality, subsampling=subsampling), "png": encode_png}
+    if format not in encoders:
         raise ValueError(f"format {format!r}: expected 'jpeg' or 'png'")
     if format == "png" and suffix == _DEFAULT_SUFFIX:
         suffix = "_MKX_SELF.png"
@@ -50,7 +51,7 @@ def test_fusion(model, store: ResidentPairs, out_dir, quality: int = 75, subsamp
                 ir = store.ir_arena[ir_off:ir_off + h * w].view(1, h, w)
                 vis = store.vis_arena[vis_off:vis_off + 3 * h * w].view(1, h, w, 3)
                 rgb = fuse_images(model, ir, vis, as_uint8=True)
-                batch = encode_png(rgb) if format == "png" else encode_jpeg(rgb, quality=quality, subsampling=subsampling)
+                batch = encoders[format](rgb)
                 stem = os.path.splitext(os.path.basename(str(ir_path)))[0]
                 if pending is not None:
                     flush(pending)
