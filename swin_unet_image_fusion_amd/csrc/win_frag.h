@@ -109,7 +109,11 @@ __device__ __forceinline__ float max_halves(float v) { float a, b; halves(v, a, 
 __device__ __forceinline__ float max3f(float a, float b, float c) { return __builtin_fmaxf(__builtin_fmaxf(a, b), c); }
 
 // ELU(alpha = 1) for the fast tier: exp(v) - 1 through v_exp_f32.  Near 0 the subtraction cancels, leaving an ABSOLUTE error of
-// ~1e-7 on activations of order 1 — four orders below the tier's error budget; the exact tier keeps expm1f.
+// ~1e-7 whatever |v| is.  That is four orders below the tier's error budget ONLY while fc1's outputs and fc2's weights are of
+// order 1: fc2 multiplies it.  Measured (DESIGN "Operand magnitude", tests/test_gpu_range.py; elu_exp2 below behaves the same):
+// with fc1 x 2^-12 and fc2 x 2^12 the ELU adds 2 .. 15 % to a block's rel-L2, with 2^-16 / 2^16 it is the whole error, 3.5 .. 11x
+// the tier's formats (5e-4 .. 8e-4 rel-L2, max-rel at the 1e-3 gate); the crossing lies between the two.  The exact tier keeps
+// expm1f.
 __device__ __forceinline__ float elu_fast(float v) { return v > 0.f ? v : __builtin_amdgcn_exp2f(v * kLog2e) - 1.0f; }
 
 // Position of key `tok` (0..63) inside a V^T row, the order in which the S^T accumulators hold the keys (a layout the writer of a

@@ -15,6 +15,19 @@ still names the kernel that has to run.
                of an image is the same vector, or nearly
     a_b        a, then b
 
+Regimes of operand MAGNITUDE (tests/test_gpu_range.py on the GPU, tests/test_range_cases_host.py on the CPU): the logits keep their size,
+the operands of the f16 and split-bf16 products and of the fp32 ELU move towards the ends of their formats.  K is a power of two's
+exponent, so the first two leave the float64 oracle's output unchanged bit for bit.
+
+    vscale+K   v_for_heads.weight and .bias x 2^K, linear_projection.weight x 2^-K (its bias untouched): V and the un-normalised P.V sum
+               towards the top (+) or the subnormals (-) of f16
+    qkbal+K    q_for_heads.weight and .bias x 2^K, k_for_heads.weight and .bias x 2^-K: the same logits out of an unbalanced Q and K
+    mlpsmallK  auto_path_mlp.mlp_{x,y}_1.weight and .bias x 2^-K, mlp_{x,y}_2.weight x 2^K: ELU arguments of order 2^-K, where exp2(u) - 1
+               cancels, times a large fc2.  Not function-preserving (ELU is not linear); no WindowAttention case has an MLP
+    spikeA     inputs only: with c0 = C // 3, x[:, c0] = A x[:, c0] + A and y[:, c0] = A y[:, c0] - A: one channel dominates the mean
+               and the variance of every LayerNorm row, with opposite sign in the two streams.  Errors of a spike rung are taken PER OUTPUT
+               CHANNEL (worst_errors): the untouched residual in channel c0 would otherwise set the scale and hide the rest
+
 The float64 reference is the CPU oracle on the transformed module's state_dict; `emulation` is tests/format_emulation.py on the same
 state: the oracle in float64 with the roundings the fast tier's kernels declare."""
 from __future__ import annotations
@@ -42,6 +55,17 @@ EXACT = ("gain16", "gain64", "ramp+1", "ramp-1", "table8", "flat1e-2")
 BACKWARD = ("gain4", "gain16", "ramp+1", "table8")
 MFMA_REGIME = "gain16"                                            # backward_tier = "mfma" against the default tier on the block case
 RAMP_SLOPE, RAMP_KEEP = 4.0, 0.25
+# magnitude ladders: (group, where it runs) in tests/test_gpu_range.py
+RANGE_FORWARD = ("vscale-16", "vscale-12", "vscale+12", "qkbal-12", "qkbal+12", "mlpsmall12", "mlpsmall16", "spike16", "spike64")
+RANGE_ATTENTION = ("vscale-16", "vscale+12", "qkbal-12", "qkbal+12")          # no spike: nothing normalises the input of WindowAttention alone
+RANGE_EXACT = ("vscale+12", "qkbal-12", "mlpsmall16", "spike16")
+RANGE_BACKWARD = ("vscale+12", "qkbal+12")
+RANGE_BWD_NAMES = ("att_d12_w8", "att_d48_w8", "refused_att_d48_w16", "block_c96_w8")
+RANGE_MFMA_REGIME = "vscale+12"
+RANGE_ATTENTION_SPIKES = ("spike16", "spike1024")                             # in the envelope record only: what an un-normalised outlier costs
+RANGE_BEYOND = ("vscale+16", "qkbal-16")                                      # the first rungs past the edge of f16: never on the GPU
+FUNCTION_PRESERVING = ("vscale", "qkbal")
+OPS = ("gain", "table", "ramp", "flat", "vscale", "qkbal", "mlpsmall", "spike")
 MAX_SEED_TRIES = 8                                                # next seed = the case's + SEED_STEP, at most this many times
 SEED_STEP = 100000
 
@@ -50,7 +74,7 @@ SEED_STEP = 100000
 def parse(regime: str) -> List[Tuple[str, float]]:
     ops = []
     for part in regime.split("_"):
-        op = next((o for o in ("gain", "table", "ramp", "flat") if part.startswith(o)), None)
+        op = next((o for o in OPS if part.startswith(o)), None)
         if op is None:
             raise ValueError(f"unknown regime {regime!r}")
         ops.append((op, float(part[len(op):])))
@@ -63,11 +87,32 @@ def apply_to_module(m: nn.Module, regime: str) -> nn.Module:
     assert atts, "no WindowAttention in the module"
     with torch.no_grad():
         for op, arg in parse(regime):
+            if op == "mlpsmall":
+                mlps = [a for a in m.modules() if hasattr(a, "mlp_x_1")]
+                if not mlps:
+                    raise ValueError(f"{regime!r} needs an MLP: it does not apply to WindowAttention alone")
+                for a in mlps:
+                    for s in ("x", "y"):
+                        if hasattr(a, f"mlp_{s}_1"):
+                            fc1, fc2 = getattr(a, f"mlp_{s}_1"), getattr(a, f"mlp_{s}_2")
+                            fc1.weight.mul_(2.0 ** -arg)
+                            fc1.bias.mul_(2.0 ** -arg)
+                            fc2.weight.mul_(2.0 ** arg)
             for a in atts:
                 if op == "gain":
                     a.q_for_heads.weight.mul_(arg)
                     if a.q_for_heads.bias is not None:
                         a.q_for_heads.bias.mul_(arg)
+                elif op == "vscale":
+                    a.v_for_heads.weight.mul_(2.0 ** arg)
+                    if a.v_for_heads.bias is not None:
+                        a.v_for_heads.bias.mul_(2.0 ** arg)
+                    a.linear_projection.weight.mul_(2.0 ** -arg)
+                elif op == "qkbal":
+                    for lin, k in ((a.q_for_heads, arg), (a.k_for_heads, -arg)):
+                        lin.weight.mul_(2.0 ** k)
+                        if lin.bias is not None:
+                            lin.bias.mul_(2.0 ** k)
                 elif op == "table":
                     a.relative_position_bias_table.mul_(arg)
                 elif op == "ramp":
@@ -80,8 +125,14 @@ def apply_to_module(m: nn.Module, regime: str) -> nn.Module:
 
 
 def transform_inputs(regime: str, ins: Tuple[torch.Tensor, ...], seed: int) -> Tuple[torch.Tensor, ...]:
-    """The input part of `regime` (only `flat` has one); `seed`: the case's."""
+    """The input part of `regime` (`flat` and `spike` have one); `seed`: the case's."""
     for op, arg in parse(regime):
+        if op == "spike":
+            x, y = (t.clone() for t in ins)
+            c0 = x.shape[1] // 3
+            x[:, c0] = arg * x[:, c0] + arg
+            y[:, c0] = arg * y[:, c0] - arg
+            ins = (x, y)
         if op == "flat":
             ins = tuple(G.randn((t.shape[0], t.shape[1], 1, 1), seed + 31 + k) + arg * t for k, t in enumerate(ins))
     return ins
@@ -150,13 +201,22 @@ DROPPED: Tuple[Tuple[str, str], ...] = tuple((i, "gain64") for i in (
     "block_c384h8x48_hid1536_w8_b2_8x8_cross_shift_fp32"))
 
 
+# ... and of the magnitude ladders, by the same rule (kept apart: the sharp-softmax tables above are a committed record)
+RANGE_SEED_OVERRIDE: Dict[Tuple[str, str], int] = {}
+RANGE_DROPPED: Tuple[Tuple[str, str], ...] = ()
+
+
+def _seed(cid: str, regime: str, default: int) -> int:
+    return SEED_OVERRIDE.get((cid, regime), RANGE_SEED_OVERRIDE.get((cid, regime), default))
+
+
 def seeded(case, regime: str):
-    return replace(case, seed=SEED_OVERRIDE.get((case.id, regime), case.seed))
+    return replace(case, seed=_seed(case.id, regime, case.seed))
 
 
 def pairs(cases, regimes) -> List[tuple]:
     """(case with the regime's seed, regime) of every rung that is kept"""
-    return [(seeded(c, r), r) for c in cases for r in regimes if (c.id, r) not in DROPPED]
+    return [(seeded(c, r), r) for c in cases for r in regimes if (c.id, r) not in DROPPED + RANGE_DROPPED]
 
 
 def pair_id(p) -> str:
@@ -165,10 +225,11 @@ def pair_id(p) -> str:
 
 def backward_case(name: str, regime: str) -> BW.Case:
     c = BP.find(name) if name == BWD_PHASED else BW.find(name)
-    return replace(c, name=f"{c.name}-{regime}", regime=regime, seed=SEED_OVERRIDE.get((name, regime), c.seed))
+    return replace(c, name=f"{c.name}-{regime}", regime=regime, seed=_seed(name, regime, c.seed))
 
 
 BACKWARD_CASES = [backward_case(n, r) for n in BWD_THREAD + (BWD_PHASED, BWD_BLOCK) for r in BACKWARD if (n, r) not in DROPPED]
+RANGE_BACKWARD_CASES = [backward_case(n, r) for n in RANGE_BWD_NAMES for r in RANGE_BACKWARD if (n, r) not in RANGE_DROPPED]
 
 
 # ---- modules, inputs, references ------------------------------------------------------------------------------------------------------
@@ -233,10 +294,20 @@ def emulation(case, regime: str):
 
 @functools.lru_cache(maxsize=None)
 def emulation_errors(case, regime: str) -> Tuple[float, float]:
-    """(rel-L2, max-rel) of the emulation against the float64 oracle, the worst output"""
-    return worst_errors(emulation(case, regime), reference64(case, regime))
+    """(rel-L2, max-rel) of the emulation against the float64 oracle, the worst output (a spike rung: the worst channel)"""
+    return worst_errors(emulation(case, regime), reference64(case, regime), regime)
 
 
-def worst_errors(got, ref) -> Tuple[float, float]:
-    errs = [G.rel_err(g, r) for g, r in zip(got, ref)]
-    return max(e[0] for e in errs), max(e[1] for e in errs)
+def per_channel(regime: str) -> bool:
+    return any(op == "spike" for op, _ in parse(regime))
+
+
+def worst_errors(got, ref, regime: str = BASE) -> Tuple[float, float]:
+    """(rel-L2, max-rel), the worst of the outputs (NCHW).  A spike regime: each output channel against that channel's own reference,
+    the worst channel."""
+    if per_channel(regime):
+        errs = [G.rel_err(g[:, c], r[:, c]) for g, r in zip(got, ref) for c in range(r.shape[1])]
+    else:
+        errs = [G.rel_err(g, r) for g, r in zip(got, ref)]
+    nan = float("nan")        # max() would pass over a NaN that is not its first argument
+    return tuple(nan if any(e[i] != e[i] for e in errs) else max(e[i] for e in errs) for i in (0, 1))

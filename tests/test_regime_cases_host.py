@@ -178,7 +178,9 @@ def test_every_family_is_reached_and_differs_where_the_source_does():
     assert {RC.family(c) for c in RC.ATTN_CASES} == {"win", "core16"}
     f = FE.FORMATS
     assert all(v.split_linear and v.qkv_f16 and v.p_f16 for v in f.values())
-    assert f["win"] == f["qkvattn"] and f["win"].max_f16 and f["win"].den_rounded and f["win"].scale_in_weights and f["win"].chunk == 0
+    # the attention arithmetic of "qkvattn" is "win"'s; its MLP is the deep levels' (tests/test_range_cases_host.py holds the ELU field)
+    assert replace(f["win"], elu="") == replace(f["qkvattn"], elu="") and f["win"].elu != f["qkvattn"].elu
+    assert f["win"].max_f16 and f["win"].den_rounded and f["win"].scale_in_weights and f["win"].chunk == 0
     assert f["win16"] == replace(f["win"], chunk=64)
     assert not f["core8"].max_f16 and not f["core8"].den_rounded and not f["core8"].scale_in_weights and f["core8"].chunk == 0
     assert not f["core16"].max_f16 and f["core16"].den_rounded and f["core16"].chunk == 32
