@@ -1191,6 +1191,66 @@ int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion
                            double* out /* device [B][SWF_COMPARATIVE_COUNT] */, int32_t B, int32_t H, int32_t W,
                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
+/* ---- feature mutual information: FMI_pixel, FMI_dct, FMI_w, FMI_edge, four values per image in one call ---------------------------
+ * Haghighat and Razian's feature mutual information, the row of the infrared / visible fusion tables the calls above lack.  Restated
+ * from memory of the method and of the common open evaluators; no copy of the paper or of an evaluator is available to this build:
+ * PARITY WITH ANY OF THEM IS UNPINNED.  These definitions are this project's, and where a paper or an evaluator differs the text here
+ * holds.
+ * Feature planes.  For X of A = ir, B = vis, F = fusion, L_X = the H x W plane of levels of the metrics above (the same quantiser,
+ * NaN -> 0).  T(X) is
+ *   pixel  L_X, H x W
+ *   edge   |sx| + |sy| of the 3 x 3 Sobel pair (sx = [-1 0 1; -2 0 2; -1 0 1], sy = [1 2 1; 0 0 0; -1 -2 -1]) on L_X with replicated
+ *          borders, H x W; exact integers
+ *   w      one level of the decimated orthonormal Haar transform with QM's formulas: per 2 x 2 block [a b; c d] LL = (a + b + c + d) / 2,
+ *          LH = (a + b - c - d) / 2, HL = (a - b + c - d) / 2, HH = (a - b - c + d) / 2, an odd trailing row or column dropped; the four
+ *          sub-bands laid out as the mosaic [LL LH; HL HH], 2 floor(H / 2) x 2 floor(W / 2); multiples of 1/2, exact
+ *   dct    the orthonormal 2-D DCT-II D_H L_X D_W^T, D_n[k][i] = s_k sqrt(2 / n) cos(pi (2 i + 1) k / (2 n)), s_0 = 1 / sqrt 2, s_k = 1
+ *          otherwise, the cosine argument reduced in integers first (m = ((2 i + 1) k) mod 4 n, then cospi(m / (2 n))); every
+ *          coefficient then snapped to rint(T / dct_step) dct_step, ties to even.  The snap makes the value well defined: without it
+ *          the windows of a flat or symmetric image would normalise rounding noise of 1e-13 up to full range.
+ * FMI of one feature.  The plane is h x w', the window is window x window, every window wholly inside the plane:
+ * (h - window + 1)(w' - window + 1) windows; the value is 0 when that count is <= 0.  The l = window^2 samples of a window are read
+ * column-major, k = (column offset) window + (row offset), as MATLAB's (:) does.  For a pair (X, F) with window samples x_k, f_k:
+ *   1  if x_k = f_k for every k, I(X, F) = 1.
+ *   2  otherwise the window pdf: x'_k = 1 for all k when max x = min x, else x'_k = (x_k - min x) / (max x - min x);
+ *      p_k = x'_k / sum x'; q_k from f the same way; P_k = sum_{i <= k} p_i, Q_k likewise.
+ *   3  c = sum (p_k - 1 / l)(q_k - 1 / l) / sqrt(sum (p_k - 1 / l)^2 sum (q_k - 1 / l)^2), 0 when the denominator is 0.
+ *   4  with k counted from 1: mu_p = sum k p_k, sigma_p = sqrt(max(sum k^2 p_k - mu_p^2, 0)); mu_q, sigma_q likewise.
+ *   5  the Frechet bound G_ij = min(P_i, Q_j) if c >= 0, max(P_i + Q_j - 1, 0) if c < 0.
+ *   6  rho = sum_ij (G_ij - P_i Q_j) / (sigma_p sigma_q), 0 when sigma_p sigma_q = 0.
+ *   7  phi = clamp(c / rho, 0, 1), 0 when rho = 0.
+ *   8  the joint cdf J_ij = phi G_ij + (1 - phi) P_i Q_j.
+ *   9  the joint pdf j_ij = (J_ij - J_(i-1)j) - (J_i(j-1) - J_(i-1)(j-1)), J = 0 at index -1, the parentheses as written.
+ *   10 with H(t) = -sum_{t > 0} t log2 t: I(X, F) = 2 (H(p) + H(q) - H(j)) / (H(p) + H(q)), 0 when H(p) + H(q) = 0.
+ * The window's value is (I(A, F) + I(B, F)) / 2; FMI is the mean over all windows.
+ * So F = A = B gives 1 for every feature that has a window; a 3 x 3 image has one pixel window and no 'w' window at window 3 (its Haar
+ * plane is 2 x 2); an axis shorter than the window gives 0.
+ * Known differences from the evaluators as recalled: they estimate the joint distribution with further special cases and offer a
+ * 'gradient' feature and other wavelets, which are left out here; FMI_EDGE is this project's name for the Sobel plane.
+ * Usual constants: window 3, dct_step 2^-16.
+ * Arithmetic.  fp64 throughout after the quantiser.  The DCT is two dense fp64 products per plane on the matrix cores against
+ * matrices the call builds.  One thread evaluates one window; sums over a window run in the order of k (rows i outer, columns j inner
+ * for the cells); the windows' values go through per-tile partials added in a fixed order; no atomics: results are bit-identical from
+ * call to call, and an image's row does not depend on the rest of its batch.
+ * Workspace (every carve rounded up to 256 bytes), N = H W, hh = floor(H / 2), wh = floor(W / 2), t(h, w) = ceil(max(h - 2, 0) / 16)
+ * ceil(max(w - 2, 0) / 16): doubles H^2, W^2 (the DCT matrices), 3 B N, 3 B N (operand and product of the transforms), 12 B hh wh (the
+ * Haar mosaics), B (3 t(H, W) + t(2 hh, 2 wh)) (per-tile sums). */
+typedef struct swf_feature_desc {
+    double window, dct_step;
+} swf_feature_desc;   /* defaults 3, 2^-16 */
+enum { SWF_FEATURE_FMI_PIXEL, SWF_FEATURE_FMI_DCT, SWF_FEATURE_FMI_W, SWF_FEATURE_FMI_EDGE, SWF_FEATURE_COUNT };
+/* 0 for a shape swf_fusion_feature would refuse */
+size_t swf_fusion_feature_workspace_bytes(int32_t B, int32_t H, int32_t W);
+/* fusion, ir, vis: [B][H][W] fp32.  out: device double [B][SWF_FEATURE_COUNT], one row per image.  The call writes every workspace
+ * element it reads, allocates nothing and does not synchronise the host, so it can be captured into a hipGraph on one stream; it
+ * writes nothing outside out and its workspace.
+ * SWF_ERR_BAD_SHAPE for B, H or W <= 0, for a window that is not 3 or 5 and for a dct_step that is not finite and > 0;
+ * SWF_ERR_UNSUPPORTED for H or W > 16384 (the DCT matrices are dense; the work grows as H W (H + W)), H W > 2^30 or B > 21845 (three
+ * transform planes per image); all before anything is launched. */
+int swf_fusion_feature(const swf_feature_desc* desc, const float* fusion, const float* ir, const float* vis,
+                       double* out /* device [B][SWF_FEATURE_COUNT] */, int32_t B, int32_t H, int32_t W,
+                       void* workspace, size_t workspace_bytes, swf_stream_t stream);
+
 /* ---- optimiser: torch.optim.Adam's step over a whole parameter group in one launch (a016:67, :165) --------------------------------
  * Per element, in torch's non-capturable order:  g' = clip * g (+ weight_decay * p);  m += (g' - m)(1 - beta1);
  * v = beta2 v + (1 - beta2) g'^2;  p -= step_size * m / (sqrt(v) / bc2_sqrt + eps), IEEE sqrt and division, no atomics.

@@ -9,9 +9,9 @@ from .data import PairLoader, ResidentPairs, sample_crop_params  # noqa: F401
 from .imaging import JpegBatch, PngBatch, decode_jpeg, decode_png, encode_jpeg, encode_png, jpeg_info, png_info  # noqa: F401
 from .inference import test_fusion  # noqa: F401
 from .loss import MyLoss  # noqa: F401
-from .metrics import (COMPARATIVE_DEFAULTS, COMPARATIVE_NAMES, FIDELITY_DEFAULTS, FIDELITY_NAMES, METRIC_NAMES, PERCEPTION_DEFAULTS,  # noqa: F401
-                      PERCEPTION_NAMES, STRUCTURE_DEFAULTS, STRUCTURE_NAMES, FusionMetrics, fusion_comparative, fusion_fidelity, fusion_metrics,
-                      fusion_perception, fusion_structure)
+from .metrics import (COMPARATIVE_DEFAULTS, COMPARATIVE_NAMES, FEATURE_DEFAULTS, FEATURE_NAMES, FIDELITY_DEFAULTS, FIDELITY_NAMES,  # noqa: F401
+                      METRIC_NAMES, PERCEPTION_DEFAULTS, PERCEPTION_NAMES, STRUCTURE_DEFAULTS, STRUCTURE_NAMES, FusionMetrics,
+                      fusion_comparative, fusion_feature, fusion_fidelity, fusion_metrics, fusion_perception, fusion_structure)
 from .modules import (AddAndLayerNormWithOtherModule, AutoPathMLP, AutoPathWinAtt, BasicBlock, MyModel,  # noqa: F401
                       MyPadding, NormalAndShiftWinsBlockPair, PatchMergingAndLinearLayer, SelfAndCrossBlockPair,
                       StateRecorder, WindowAttention, get_encoder_or_decoder_block)

@@ -146,6 +146,13 @@ class ComparativeDesc(C.Structure):   # swf_comparative_desc: Q_TE's order q, Q_
 COMPARATIVE_COUNT = 6   # SWF_COMPARATIVE_COUNT
 
 
+class FeatureDesc(C.Structure):   # swf_feature_desc: the window's side (3 or 5) and the snap of the DCT coefficients
+    _fields_ = [(n, C.c_double) for n in ("window", "dct_step")]
+
+
+FEATURE_COUNT = 4   # SWF_FEATURE_COUNT
+
+
 class JpegDesc(C.Structure):   # swf_jpeg_desc
     _fields_ = [("channels", C.c_int32), ("subsampling", C.c_int32), ("quality", C.c_int32)]
 
@@ -331,6 +338,8 @@ SIGNATURES = {
     "swf_fusion_perception": (C.c_int, [P(PerceptionDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_fusion_comparative_workspace_bytes": (_sz, [_i32, _i32, _i32]),
     "swf_fusion_comparative": (C.c_int, [P(ComparativeDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "swf_fusion_feature_workspace_bytes": (_sz, [_i32, _i32, _i32]),
+    "swf_fusion_feature": (C.c_int, [P(FeatureDesc), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_adam_table_bytes": (_sz, [_i32, _i64]),
     "swf_adam_table_fill": (C.c_int, [_vp, _sz, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "swf_adam_grad_norm": (C.c_int, [C.c_double, _vp, _vp, _sz, _i32, _vp, _vp]),

@@ -17,6 +17,7 @@
 #include "kernels_structure.h"
 #include "kernels_perception.h"
 #include "kernels_comparative.h"
+#include "kernels_feature.h"
 #include "kernels_metrics.h"
 #include "metric_frag.h"
 #include "kernels_optim.h"
@@ -2437,6 +2438,35 @@ int swf_fusion_comparative(const swf_comparative_desc* desc, const float* fusion
     SWF_TRY(check_comparative_desc(*desc));
     SWF_TRY(need_workspace("fusion_comparative", workspace, workspace_bytes, fusion_comparative_workspace_bytes(B, H, W)));
     return fusion_comparative(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
+}
+
+// The feature-mutual-information call: dense DCT matrices, three transform planes per image.
+static int check_feature_shape(int32_t B, int32_t H, int32_t W) {
+    if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "fusion_feature: empty tensor (B=%d H=%d W=%d)", B, H, W);
+    if (!feature_shape_ok(B, H, W))
+        return fail(SWF_ERR_UNSUPPORTED, "fusion_feature: B=%d H=%d W=%d exceeds the int32 indices of the dense transforms "
+                    "(H, W <= 16384, H W <= 2^30, B <= 21845)", B, H, W);
+    return SWF_OK;
+}
+
+size_t swf_fusion_feature_workspace_bytes(int32_t B, int32_t H, int32_t W) {
+    return check_feature_shape(B, H, W) == SWF_OK ? fusion_feature_workspace_bytes(B, H, W) : 0;
+}
+
+static int check_feature_desc(const swf_feature_desc& d) {
+    if (!(d.window == 3.0 || d.window == 5.0) || !std::isfinite(d.dct_step) || !(d.dct_step > 0.0))
+        return fail(SWF_ERR_BAD_SHAPE, "fusion_feature: constants window=%g dct_step=%g (window 3 or 5, dct_step finite and > 0)", d.window,
+                    d.dct_step);
+    return SWF_OK;
+}
+
+int swf_fusion_feature(const swf_feature_desc* desc, const float* fusion, const float* ir, const float* vis, double* out, int32_t B,
+                       int32_t H, int32_t W, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    if (!desc || !fusion || !ir || !vis || !out) return fail(SWF_ERR_NULL, "fusion_feature: NULL descriptor, image or output");
+    SWF_TRY(check_feature_shape(B, H, W));
+    SWF_TRY(check_feature_desc(*desc));
+    SWF_TRY(need_workspace("fusion_feature", workspace, workspace_bytes, fusion_feature_workspace_bytes(B, H, W)));
+    return fusion_feature(*desc, fusion, ir, vis, out, B, H, W, workspace, workspace_bytes, as_stream(stream));
 }
 
 // torch.optim.Adam over a table of tensors.  Every argument check, the table's own rows included, comes before the first HIP call.

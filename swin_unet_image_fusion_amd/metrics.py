@@ -65,6 +65,29 @@ frequencies, H = entropy with log2, H_b = H / 8 (base 256), sums over non-zero b
 So F = A = B gives Qmi = 2 (not flat), Qsf = 0, Qm = 1 (not flat), Qp = 1; three flat images give Qmi = 0, Qte = 0, Qncie = 1 - log_256 3,
 Qsf = 0, Qm = 0 (1 under 2 pixels in an axis: no coefficients), Qp = 1.
 
+Feature mutual information comes from a sixth fused HIP call on the same levels, fp64 throughout (swf_fusion_feature: `fusion_feature`,
+or `FusionMetrics(feature=True)`; with the five switches on, all 39 values): FMI_pixel, FMI_dct, FMI_w and FMI_edge.  Restated from
+memory of Haghighat & Razian's method and of the common open evaluators: PARITY WITH ANY OF THEM IS UNPINNED, and where they differ,
+this text holds.  The feature plane T(X) of X = A, B, F is
+  pixel  the levels, H x W.
+  edge   |sx| + |sy| of the 3x3 Sobel pair on the levels with replicated borders, H x W (exact integers).
+  w      one level of the decimated orthonormal Haar transform (Qm's formulas, an odd trailing row or column dropped), the sub-bands as
+         the mosaic [LL LH; HL HH], 2 floor(H / 2) x 2 floor(W / 2) (multiples of 1/2: exact).
+  dct    the orthonormal 2-D DCT-II D_H L D_W^T, D_n[k][i] = s_k sqrt(2 / n) cos(pi (2 i + 1) k / (2 n)), s_0 = 1 / sqrt 2, else 1, the
+         argument reduced in integers (m = ((2 i + 1) k) mod 4 n, cospi(m / (2 n))), every coefficient snapped to
+         rint(T / dct_step) dct_step, ties to even; without the snap the windows of a flat or symmetric image would normalise rounding
+         noise up to full range.
+FMI of a feature is the mean, over every window x window patch that lies wholly inside the plane (0 when there is none), of
+(I(A, F) + I(B, F)) / 2.  The l = window^2 samples of a patch are read column-major (MATLAB's (:)).  I(X, F) = 1 if x_k = f_k for every
+k.  Otherwise x'_k = 1 when max x = min x, else (x_k - min x) / (max x - min x); p_k = x'_k / sum x', q_k from f likewise, P and Q their
+running sums; c = sum (p_k - 1/l)(q_k - 1/l) / sqrt(sum (p_k - 1/l)^2 sum (q_k - 1/l)^2), 0 when the denominator is 0; with k counted
+from 1, mu_p = sum k p_k, sigma_p = sqrt(max(sum k^2 p_k - mu_p^2, 0)); G_ij = min(P_i, Q_j) if c >= 0, max(P_i + Q_j - 1, 0) if c < 0
+(the Frechet bounds); rho = sum_ij (G_ij - P_i Q_j) / (sigma_p sigma_q), 0 when sigma_p sigma_q = 0; phi = clamp(c / rho, 0, 1), 0 when
+rho = 0; the joint cdf J_ij = phi G_ij + (1 - phi) P_i Q_j; the joint pdf j_ij = (J_ij - J_(i-1)j) - (J_i(j-1) - J_(i-1)(j-1)), J = 0 at
+index -1; with H(t) = -sum_{t > 0} t log2 t, I(X, F) = 2 (H(p) + H(q) - H(j)) / (H(p) + H(q)), 0 when H(p) + H(q) = 0.
+So F = A = B gives 1 for every feature that has a window; a 3x3 image has one pixel window and no 'w' window (its Haar plane is 2x2); an
+axis shorter than the window gives 0.
+
 The definitions are restated from the published ones and the common open evaluators; no MATLAB, VIFB or sewar copy is available to
 this build, so parity with any of them is unpinned.  `MyLoss(choose_ms_ssim=False).calcu_ssim_loss` is a different
 thing: the training loss's kornia-style SSIM on unit-range floats, returned as a loss; SSIM as a metric on levels is `fusion_structure`'s.
@@ -81,8 +104,8 @@ from . import _lib as L
 from .modules import _ptr, _stream, _workspace
 
 __all__ = ["METRIC_NAMES", "QABF_DEFAULTS", "FIDELITY_NAMES", "FIDELITY_DEFAULTS", "STRUCTURE_NAMES", "STRUCTURE_DEFAULTS", "PERCEPTION_NAMES",
-           "PERCEPTION_DEFAULTS", "COMPARATIVE_NAMES", "COMPARATIVE_DEFAULTS", "fusion_metrics", "fusion_fidelity", "fusion_structure",
-           "fusion_perception", "fusion_comparative", "FusionMetrics"]
+           "PERCEPTION_DEFAULTS", "COMPARATIVE_NAMES", "COMPARATIVE_DEFAULTS", "FEATURE_NAMES", "FEATURE_DEFAULTS", "fusion_metrics",
+           "fusion_fidelity", "fusion_structure", "fusion_perception", "fusion_comparative", "fusion_feature", "FusionMetrics"]
 
 METRIC_NAMES = ("EN", "MI", "SD", "SF", "AG", "CC", "SCD", "MSE", "PSNR", "Qabf")   # the order of the header's SWF_METRIC_* enum
 QABF_DEFAULTS = {"Tg": 0.9994, "kg": -15.0, "Dg": 0.5, "Ta": 0.9879, "ka": -22.0, "Da": 0.8}   # Xydeas & Petrovic
@@ -98,6 +121,8 @@ COMPARATIVE_NAMES = ("Qmi", "Qte", "Qncie", "Qm", "Qsf", "Qp")                  
 COMPARATIVE_DEFAULTS = {"q": 1.85, "alpha1": 1.0, "alpha2": 1.0,                                  # Tsallis order, Q_M's scale exponents
                         "min_wavelength": 3.0, "mult": 2.1, "sigma_onf": 0.55, "k": 2.0, "cutoff": 0.5, "g": 10.0, "eps": 1e-4,   # Kovesi
                         "C": 1e-4, "ep": 1.0, "eM": 1.0, "em": 1.0}                                # Zhao's stabiliser and exponents
+FEATURE_NAMES = ("FMI_pixel", "FMI_dct", "FMI_w", "FMI_edge")                        # the order of the header's SWF_FEATURE_* enum
+FEATURE_DEFAULTS = {"window": 3.0, "dct_step": 2.0 ** -16}                           # the window's side (3 or 5), the DCT coefficients' snap
 
 
 def _check_images(fusion: Tensor, ir: Tensor, vis: Tensor) -> None:
@@ -133,6 +158,7 @@ _FAMILIES = {
     "perception": _Family(PERCEPTION_NAMES, PERCEPTION_DEFAULTS, L.PerceptionDesc, L.PERCEPTION_COUNT, "swf_fusion_perception", "constant(s)"),
     "comparative": _Family(COMPARATIVE_NAMES, COMPARATIVE_DEFAULTS, L.ComparativeDesc, L.COMPARATIVE_COUNT, "swf_fusion_comparative",
                            "constant(s)"),
+    "feature": _Family(FEATURE_NAMES, FEATURE_DEFAULTS, L.FeatureDesc, L.FEATURE_COUNT, "swf_fusion_feature", "constant(s)"),
 }
 
 
@@ -200,18 +226,29 @@ def fusion_comparative(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> 
     return _call("comparative", fusion, ir, vis, constants)
 
 
+def fusion_feature(fusion: Tensor, ir: Tensor, vis: Tensor, **constants) -> Tensor:
+    """-> (B, 4) float64 tensor on the inputs' device, row b = the FEATURE_NAMES values of image b: feature mutual information on the
+    level plane, the snapped DCT, one Haar level and the Sobel edge plane.  Inputs as for fusion_metrics, at most 16384 pixels in an axis
+    and 21845 images (NotImplementedError beyond: the DCT matrices are dense).  Keyword arguments replace constants (FEATURE_DEFAULTS);
+    a window other than 3 or 5, or a dct_step that is not finite and > 0, raises ValueError.  One library call on the current stream, no
+    host synchronisation; bit-identical from call to call."""
+    return _call("feature", fusion, ir, vis, constants)
+
+
 class FusionMetrics:
     """Running mean of the ten metrics over every image passed to update(); with `fidelity=True` the FIDELITY_NAMES values (constants:
     `fidelity_constants`) follow the ten, with `structure=True` the STRUCTURE_NAMES values (constants: `structure_constants`) follow
     those, with `perception=True` the PERCEPTION_NAMES values (constants: `perception_constants`) follow those, with `comparative=True` the
     COMPARATIVE_NAMES values (constants: `comparative_constants`) follow those: 10, 15, 19 or 24 values without the last two groups, five
-    more with the perception group, six more with the comparative group (up to 35).  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
+    more with the perception group, six more with the comparative group (up to 35); with `feature=True` the FEATURE_NAMES values (constants:
+    `feature_constants`) follow the comparative group's place, four more (up to 39).  The sum lives on the device and update() does not synchronise; compute() reads it back once.  The
     image count is a host int (`count`): the batch size is known on the host, so counting there needs no synchronisation and no
     device scalar."""
 
     def __init__(self, fidelity: bool = False, fidelity_constants: Optional[dict] = None, structure: bool = False,
                  structure_constants: Optional[dict] = None, perception: bool = False, perception_constants: Optional[dict] = None,
-                 comparative: bool = False, comparative_constants: Optional[dict] = None, **qabf_constants):
+                 comparative: bool = False, comparative_constants: Optional[dict] = None, feature: bool = False,
+                 feature_constants: Optional[dict] = None, **qabf_constants):
         self.qabf_constants = qabf_constants
         self.fidelity = bool(fidelity)
         self.fidelity_constants = dict(fidelity_constants or {})
@@ -221,9 +258,11 @@ class FusionMetrics:
         self.perception_constants = dict(perception_constants or {})
         self.comparative = bool(comparative)
         self.comparative_constants = dict(comparative_constants or {})
+        self.feature = bool(feature)
+        self.feature_constants = dict(feature_constants or {})
         families = (("metrics", True, self.qabf_constants), ("fidelity", self.fidelity, self.fidelity_constants),
                     ("structure", self.structure, self.structure_constants), ("perception", self.perception, self.perception_constants),
-                    ("comparative", self.comparative, self.comparative_constants))
+                    ("comparative", self.comparative, self.comparative_constants), ("feature", self.feature, self.feature_constants))
         for kind, _, constants in families:
             _desc(kind, constants)   # refuse a misspelt constant here, not at the first batch, of a family that is off too
         self._families = [(kind, constants) for kind, on, constants in families if on]
