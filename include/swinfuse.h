@@ -54,6 +54,26 @@ typedef enum swf_status {
  *         fall back to FP32 kernels (never to the host). */
 typedef enum swf_precision { SWF_PREC_FP32 = 0, SWF_PREC_FAST = 1 } swf_precision;
 
+/* The pointwise activation of the MLPs (a003), of the patch merge / un-merge layers (a011:230-237) and of the fusion head (a013:134):
+ * the reference's MLP_ACTIVATION_FUNC, as torch.nn defines each.  A zero-initialised descriptor is ELU(alpha = 1), the reference's
+ * configured default, with `param` ignored.  param: alpha of SWF_ACT_ELU, negative_slope of SWF_ACT_LEAKY_RELU (any finite value),
+ * ignored by the other kinds.  An unknown kind or a non-finite parameter that is read: SWF_ERR_UNSUPPORTED before anything is launched
+ * and before the workspace is looked at.
+ * Only the default kind runs the fused fast-tier kernels (they keep ELU in exp2 units inside their packed weight images).  Under
+ * SWF_PREC_FAST every other kind takes the generic family at that precision: split-bf16 GEMMs with the activation in their epilogue,
+ * the f16 MFMA attention core, the unfused patch path; block routes report SWF_BLOCK_ROUTE_GENERIC, patch routes
+ * SWF_PATCH_ROUTE_GENERIC.  The backward takes act' from the recomputed pre-activation; for the default kind it is unchanged. */
+typedef enum swf_act_kind {
+    SWF_ACT_ELU1 = 0,        /* nn.ELU(alpha = 1) */
+    SWF_ACT_ELU = 1,         /* nn.ELU(alpha = param) */
+    SWF_ACT_RELU = 2,        /* nn.ReLU */
+    SWF_ACT_LEAKY_RELU = 3,  /* nn.LeakyReLU(negative_slope = param) */
+    SWF_ACT_GELU = 4,        /* nn.GELU(approximate = "none"), erff */
+    SWF_ACT_GELU_TANH = 5,   /* nn.GELU(approximate = "tanh"), tanhf */
+    SWF_ACT_SILU = 6         /* nn.SiLU: v / (1 + expf(-v)) */
+} swf_act_kind;
+typedef struct swf_activation { int32_t kind; float param; } swf_activation;
+
 typedef struct swf_linear { const float* weight; /* [out][in] row-major (nn.Linear / 1x1 Conv2d) */
                             const float* bias;   /* [out] or NULL */ } swf_linear;
 typedef struct swf_norm   { const float* gamma; const float* beta; } swf_norm; /* LayerNorm over C, eps 1e-5 */
@@ -101,13 +121,14 @@ typedef struct swf_block_desc {
     int32_t cross;         /* use_cross_attr: x'=WA_x(q=x,k=y,v=y), y'=WA_y(q=y,k=x,v=x) (a002_AutoPathWinAtt.py:67-82) */
     int32_t precision;     /* swf_precision */
     int32_t schedule;      /* swf_schedule */
+    swf_activation act;    /* mlp_activation_func between fc1 and fc2; zero = ELU(alpha = 1) */
 } swf_block_desc;
 
 typedef struct swf_block_stream_params {   /* one modality stream of one BasicBlock */
     swf_norm ln1;              /* stage_1.norm_layer_{1|2}  (a004_AddAndLayerNormWithOtherModule.py:16-18) */
     swf_attn_params attn;      /* auto_path_win_att.window_attention_{x|y} */
     swf_norm ln2;              /* stage_2.norm_layer_{1|2} */
-    swf_linear fc1, fc2;       /* auto_path_mlp.mlp_{x|y}_1 [hidden][C], mlp_{x|y}_2 [C][hidden]; ELU(alpha=1) between (a003_AutoPathMLP.py:21-44) */
+    swf_linear fc1, fc2;       /* auto_path_mlp.mlp_{x|y}_1 [hidden][C], mlp_{x|y}_2 [C][hidden]; the activation between them (a003_AutoPathMLP.py:21-44) is the descriptor's or the entry's swf_activation */
 } swf_block_stream_params;
 
 /* stage_1 of a BasicBlock for both streams: out = in + Attention(LN(in), ...) (a004:29-38 with
@@ -504,7 +525,8 @@ int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_
                 void* workspace, size_t workspace_bytes, swf_stream_t stream);
 
 /* ---- token-level pieces used by the inner reference modules ------------------------------------ */
-/* out[tokens][n_out] = act(in[tokens][n_in] . W^T + b) (+ residual); act 0 = none, 1 = ELU(alpha=1).
+/* out[tokens][n_out] = act(in[tokens][n_in] . W^T + b) (+ residual); act 0 = none, 1 = the activation: ELU(alpha = 1) here, the
+ * swf_activation argument in swf_linear_fwd_act / swf_linear_fwd_prec_act.
  * nn.Linear (a001:42-61) and 1x1 nn.Conv2d on NHWC tokens (a003:21-22, a011:60-63).  Exact fp32. */
 int swf_linear_fwd(const swf_linear* lin, const float* in, const float* residual, float* out,
                    int64_t tokens, int32_t n_in, int32_t n_out, int32_t act, swf_stream_t stream);
@@ -514,7 +536,8 @@ size_t swf_linear_workspace_bytes(int32_t precision, int64_t tokens, int32_t n_i
 int swf_linear_fwd_prec(const swf_linear* lin, int32_t precision, const float* in, const float* residual, float* out,
                         int64_t tokens, int32_t n_in, int32_t n_out, int32_t act,
                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
-/* my_layer_norm (a004:54-72): LayerNorm over C of [tokens][C], eps 1e-5; elu != 0 applies ELU after. */
+/* my_layer_norm (a004:54-72): LayerNorm over C of [tokens][C], eps 1e-5; elu != 0 applies the activation after: ELU(alpha = 1) here,
+ * the swf_activation argument in swf_layernorm_fwd_act. */
 int swf_layernorm_fwd(const swf_norm* ln, const float* in, float* out, int64_t tokens, int32_t C, int32_t elu,
                       swf_stream_t stream);
 /* MyPadding encoder side (a006:122-131): reflect-pad bottom/right by (pad_h,pad_w); [B][H][W][C] ->
@@ -524,6 +547,68 @@ int swf_reflect_pad_fwd(const float* in, float* out, int32_t B, int32_t H, int32
 /* MyPadding decoder side (a006:133-146): top-left crop [B][Hp][Wp][C] -> [B][H][W][C]. */
 int swf_crop_fwd(const float* in, float* out, int32_t B, int32_t Hp, int32_t Wp, int32_t H, int32_t W, int32_t C,
                  swf_stream_t stream);
+
+/* ---- the entries without a descriptor, with the activation as an argument ----------------------------------------------------------
+ * swf_<entry>_act(act, ...) is swf_<entry>(...) with `act` (NULL = the zero descriptor = ELU(alpha = 1)) in place of ELU: the same
+ * arguments in the same order behind it, the same workspace query (no workspace depends on the activation: the backward keeps either
+ * the pre-activation or the activation in the one hidden buffer it always had), the same results for a default descriptor bit for bit.
+ * The entries above are these with act = NULL.  Under SWF_PREC_FAST a non-default activation takes the generic family (swf_activation). */
+int swf_mlp_fwd_act(const swf_activation* act, int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                    const float* x_in, const float* y_in, float* x_out, float* y_out,
+                    int64_t tokens, int32_t channels, int32_t hidden,
+                    void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_mlp_fwd_drop_act(const swf_activation* act, const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens,
+                         int32_t channels, int32_t hidden, const swf_dropout* drop, int32_t stream_id,
+                         void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_mlp_bwd_opt_act(const swf_activation* act, const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                        const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                        const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route,
+                        void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_patch_merge_fwd_act(const swf_activation* act, const swf_patch_params* p, const float* in, float* out,
+                            int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                            int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w,
+                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_patch_unmerge_fwd_act(const swf_activation* act, const swf_patch_params* p, const float* in, const float* skip, float* out,
+                              int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout,
+                              int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout,
+                              void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_patch_merge_fwd_prec_act(const swf_activation* act, int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                                 const float* x_in, const float* y_in, float* x_out, float* y_out,
+                                 int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                                 int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w,
+                                 const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
+                                 void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_patch_unmerge_fwd_prec_act(const swf_activation* act, int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                                   const float* x_in, const float* y_in, const float* x_skip, const float* y_skip,
+                                   float* x_out, float* y_out,
+                                   int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout,
+                                   int32_t merge_h, int32_t merge_w, int32_t Hout, int32_t Wout,
+                                   const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route,
+                                   void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_patch_layer_bwd_opt_act(const swf_activation* act, const swf_patch_params* p, const float* in, const float* gout, float* gin,
+                                const swf_patch_grads* gp, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                                int32_t merge_h, int32_t merge_w, int32_t encoder, const swf_bwd_options* opt, swf_bwd_route* route,
+                                void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_final_head_fwd_act(const swf_activation* act, const swf_head_params* p, const float* x, const float* y, float* out,
+                           int32_t B, int32_t H, int32_t W, int32_t ksize,
+                           void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_final_head_bwd_act(const swf_activation* act, const swf_head_params* p, const float* x, const float* y, const float* gout,
+                           float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize,
+                           int32_t batch_stats, void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_final_head_bwd_sums_act(const swf_activation* act, const swf_head_params* p, const float* x, const float* y, const float* gout,
+                                float* sums_out, int32_t B, int32_t H, int32_t W, int32_t ksize,
+                                void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_final_head_bwd_synced_act(const swf_activation* act, const swf_head_params* p, const float* x, const float* y, const float* gout,
+                                  const float* sums, int64_t count, float* gx, float* gy, const swf_head_grads* gp,
+                                  int32_t B, int32_t H, int32_t W, int32_t ksize,
+                                  void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_linear_fwd_act(const swf_activation* act_fn, const swf_linear* lin, const float* in, const float* residual, float* out,
+                       int64_t tokens, int32_t n_in, int32_t n_out, int32_t act, swf_stream_t stream);
+int swf_linear_fwd_prec_act(const swf_activation* act_fn, const swf_linear* lin, int32_t precision, const float* in, const float* residual,
+                            float* out, int64_t tokens, int32_t n_in, int32_t n_out, int32_t act,
+                            void* workspace, size_t workspace_bytes, swf_stream_t stream);
+int swf_layernorm_fwd_act(const swf_activation* act, const swf_norm* ln, const float* in, float* out, int64_t tokens, int32_t C, int32_t elu,
+                          swf_stream_t stream);
 
 /* ---- layout helpers for the NCHW module API (a007_utils.py:7-26 are the reference's permutes) */
 int swf_nchw_to_nhwc(const float* in, float* out, int32_t B, int32_t C, int32_t H, int32_t W, swf_stream_t stream);
@@ -542,6 +627,7 @@ typedef struct swf_model_desc {
     int32_t head_ksize;                  /* final_conv_layer_kernel_size */
     int32_t precision;                   /* swf_precision */
     int32_t schedule;                    /* swf_schedule */
+    swf_activation act;                  /* mlp_activation_func of every block, patch layer and the head; zero = ELU(alpha = 1) */
 } swf_model_desc;
 
 /* The weights live in ONE fp32 device arena whose layout the library defines.  Parameter i has

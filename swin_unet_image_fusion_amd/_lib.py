@@ -31,6 +31,14 @@ class Norm(C.Structure):
     _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p)]
 
 
+class Activation(C.Structure):   # swf_activation: zero-initialised = ELU(alpha = 1), param ignored
+    _fields_ = [("kind", C.c_int32), ("param", C.c_float)]
+
+
+# swf_act_kind
+ACT_ELU1, ACT_ELU, ACT_RELU, ACT_LEAKY_RELU, ACT_GELU, ACT_GELU_TANH, ACT_SILU = range(7)
+
+
 class AttnDesc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("heads", C.c_int32), ("head_dim", C.c_int32),
                 ("win_h", C.c_int32), ("win_w", C.c_int32), ("shift", C.c_int32)]
@@ -41,7 +49,8 @@ class AttnParams(C.Structure):
 
 
 class BlockDesc(C.Structure):
-    _fields_ = [("attn", AttnDesc), ("hidden", C.c_int32), ("cross", C.c_int32), ("precision", C.c_int32), ("schedule", C.c_int32)]
+    _fields_ = [("attn", AttnDesc), ("hidden", C.c_int32), ("cross", C.c_int32), ("precision", C.c_int32), ("schedule", C.c_int32),
+                ("act", Activation)]
 
 
 class BlockStreamParams(C.Structure):
@@ -101,7 +110,7 @@ class ModelDesc(C.Structure):
     _fields_ = [("levels", C.c_int32), ("in_dims", C.c_int32 * SWF_MAX_LEVELS), ("out_dims", C.c_int32 * SWF_MAX_LEVELS),
                 ("heads", C.c_int32), ("head_dim", C.c_int32 * SWF_MAX_LEVELS), ("mlp_ratio", C.c_int32),
                 ("win_h", C.c_int32), ("win_w", C.c_int32), ("merge_h", C.c_int32), ("merge_w", C.c_int32),
-                ("head_ksize", C.c_int32), ("precision", C.c_int32), ("schedule", C.c_int32)]
+                ("head_ksize", C.c_int32), ("precision", C.c_int32), ("schedule", C.c_int32), ("act", Activation)]
 
 
 class LossDesc(C.Structure):
@@ -351,6 +360,13 @@ SIGNATURES = {
     "swf_final_head_bwd_sums": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
     "swf_final_head_bwd_synced": (C.c_int, [P(HeadParams), _vp, _vp, _vp, _vp, _i64, _vp, _vp, P(HeadGrads), _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
 }
+
+# swf_<entry>_act: the activation (NULL = ELU(alpha = 1)) in front of the arguments of swf_<entry>
+for _name in ("swf_mlp_fwd", "swf_mlp_fwd_drop", "swf_mlp_bwd_opt", "swf_patch_merge_fwd", "swf_patch_unmerge_fwd", "swf_patch_merge_fwd_prec",
+              "swf_patch_unmerge_fwd_prec", "swf_patch_layer_bwd_opt", "swf_final_head_fwd", "swf_final_head_bwd", "swf_final_head_bwd_sums",
+              "swf_final_head_bwd_synced", "swf_linear_fwd", "swf_linear_fwd_prec", "swf_layernorm_fwd"):
+    SIGNATURES[_name + "_act"] = (SIGNATURES[_name][0], [P(Activation)] + SIGNATURES[_name][1])
+del _name
 
 _lib: Optional[C.CDLL] = None
 

@@ -11,7 +11,8 @@
 //                        (both have a matrix-core twin that returns the same bits, kernels_bwdgemm.hip; dx() and dw() choose by BwdTier)
 //   bwd_colsum_kernel    db  = column sums of dY, same chunking
 //   ln_bwd_kernel        LayerNorm backward per token (+ the residual branch's gradient) and per-wave partial d gamma / d beta
-//   elu_bwd_kernel       du = dh . (h > 0 ? 1 : h + 1)     (ELU'(u) from the saved output: exp(u) = h + 1 for u <= 0)
+//   elu_bwd_kernel       du = dh . (h > 0 ? 1 : h + 1)     (ELU'(u) from the saved output: exp(u) = h + 1 for u <= 0; ELU(alpha = 1) only)
+//   act_bwd_kernel       du = dh . act'(u)                 (every other swf_activation: from the recomputed PRE-activation, act_fn.h)
 //   attn_bwd_kernel      per (window, head): recomputes the scores (bias, shift mask assigned as -1e10: a001:310), softmax statistics and
 //                        dS = P . (dP - rowsum(dP . P)); thread = query for dQ, thread = key for dK / dV, thread = table entry for the
 //                        relative-position bias gradient — every sum in a fixed order
@@ -166,6 +167,19 @@ __global__ __launch_bounds__(256) void elu_bwd_kernel(float* __restrict__ dh, co
     if (i >= count) return;
     const float hv = h[i];
     dh[i] *= hv > 0.f ? 1.0f : hv + 1.0f;
+}
+// every other activation: dh *= act'(u) from the PRE-activation u (GELU and SiLU are not monotone, a LeakyReLU of slope <= 0 loses the
+// sign: the output does not determine the derivative)
+__global__ __launch_bounds__(256) void act_bwd_kernel(float* __restrict__ dh, const float* __restrict__ u, int64_t count, swf_activation act) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= count) return;
+    dh[i] *= act_grad(u[i], act.kind, act.param);
+}
+// du = dh . act'(u) in place, then u -> act(u) in place (the hidden buffer now holds what the default path recomputes into it)
+int act_bwd_from_u(float* dh, float* u, int64_t count, const swf_activation& act, hipStream_t st) {
+    hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)cdiv64(count, 256)), dim3(256), 0, st, dh, u, count, act);
+    SWF_TRY(check_launch("act_bwd"));
+    return launch_act_inplace(u, count, Act(act), st);
 }
 
 // LayerNorm backward (eps 1e-5, biased variance; a004:54-72 / nn.LayerNorm):  with xhat = (x - mean) rstd, g = dy gamma:
@@ -721,8 +735,10 @@ size_t block_ws(const swf_block_desc& d, int nstream, int B, int H, int W, bool 
 // The forward intermediates of both streams in the exact tier: xn, q, k, v, o, x1, xn2, h (and hd).  With `drop` (stream s = mask
 // stream s): o holds the DROPPED attention values (site 0), x1 = x + dropped projection (site 1), hd = the dropped hidden activation
 // (site 2) next to the undropped h; a site with p = 0 runs exactly the kernels of drop == nullptr.
+// `keep_u` (the backward of a non-default activation): h holds the PRE-activation u = fc1(xn2) and hd is not written; the caller turns
+// u into h, and h into hd, once it has taken act'(u) (act_bwd_from_u).
 int block_forward(const swf_block_desc& d, int nstream, const swf_block_stream_params* const* pp, const float* const* xin, BlockBufs* b,
-                  const swf_dropout* drop, int B, int H, int W, hipStream_t st) {
+                  const swf_dropout* drop, int B, int H, int W, hipStream_t st, bool keep_u = false) {
     const int64_t N = (int64_t)B * H * W;
     const int C = d.attn.channels, HD = d.attn.heads * d.attn.head_dim, hid = d.hidden;
     const bool cross = d.cross && nstream == 2;
@@ -755,8 +771,8 @@ int block_forward(const swf_block_desc& d, int nstream, const swf_block_stream_p
     SWF_TRY(launch_layernorm(l2, nstream, N, C, 0, st));
     GemmBatch g1{};
     for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{b[s].xn2, pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, b[s].h};
-    SWF_TRY(launch_gemm_f32(g1, nstream, (int)N, hid, C, C, hid, 1, st));
-    if (pm > 0.f)
+    SWF_TRY(launch_gemm_f32(g1, nstream, (int)N, hid, C, C, hid, keep_u ? Act(0) : Act(d.act), st));
+    if (pm > 0.f && !keep_u)
         for (int s = 0; s < nstream; ++s) SWF_TRY(launch_dropout_mul(b[s].h, b[s].hd, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
     return SWF_OK;
 }
@@ -785,7 +801,8 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
     const float pa = drop ? drop->attn_p : 0.f, pj = drop ? drop->proj_p : 0.f, pm = drop ? drop->mlp_p : 0.f;
 
     // ---- recompute the forward intermediates (exact tier; with dropout the same masks as the forward: same seed) ----
-    SWF_TRY(block_forward(d, nstream, pp, xin, b, drop, B, H, W, st));
+    const bool from_u = !act_is_default(d.act);   // act' from the pre-activation; the default takes ELU' from h as it always did
+    SWF_TRY(block_forward(d, nstream, pp, xin, b, drop, B, H, W, st, from_u));
     auto G = [&](int s) -> const swf_block_stream_grads& { static const swf_block_stream_grads none{}; return gp[s] ? *gp[s] : none; };
     // ---- MLP half, reverse (dropout: g2 = dL/d(fc2 output) through site 3, dW2 from the dropped hd, the hidden gradient through site 2
     //      and ELU' of the undropped h; the residual branch is not masked.  dxn is free until the Q/K/V reverse: it holds g2 / g1) ----
@@ -793,10 +810,15 @@ int basic_block_bwd_impl(const swf_block_desc& d, const swf_block_stream_params*
         const float* g2 = gout[s];
         if (pm > 0.f) { SWF_TRY(launch_dropout_mul(gout[s], b[s].dxn, N * C, drop_site(drop->seed, s, kDropMlpOut, pm), st)); g2 = b[s].dxn; }
         SWF_TRY(dx(g2, pp[s]->fc2.weight, b[s].dh, N, C, hid, 0, tier, st));                                       // dh = g2 . W2
+        if (from_u) {   // h holds u: du = dh . mask . act'(u), then h = act(u) and hd = its dropped copy for dW2
+            if (pm > 0.f) SWF_TRY(launch_dropout_mul(b[s].dh, b[s].dh, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
+            SWF_TRY(act_bwd_from_u(b[s].dh, b[s].h, N * hid, d.act, st));
+            if (pm > 0.f) SWF_TRY(launch_dropout_mul(b[s].h, b[s].hd, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
+        }
         SWF_TRY(dw(g2, b[s].hd, G(s).fc2.weight, G(s).fc2.bias, N, C, hid, scratch, tier, st));                     // dW2, db2
-        if (pm > 0.f) {
+        if (!from_u && pm > 0.f) {
             SWF_TRY(launch_dropout_elu_bwd(b[s].dh, b[s].h, N * hid, drop_site(drop->seed, s, kDropHidden, pm), st));
-        } else {
+        } else if (!from_u) {
             hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, b[s].dh, b[s].h, N * hid);
             SWF_TRY(check_launch("elu_bwd"));
         }
@@ -992,7 +1014,7 @@ size_t mlp_ws(int64_t N, int C, int hid, bool bwd, bool masks) {
 // one stream of AutoPathMLP.forward (a003:46-50) under autograd: out = fc2(ELU(fc1(x))); with dropout out = d3(fc2(d2(ELU(fc1(x)))))
 int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
                  const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout* drop, int stream_id, const BwdTier& tier, void* workspace,
-                 size_t workspace_bytes, hipStream_t st) {
+                 size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_bwd: token count");
     Carver ws(workspace, workspace_bytes);
     const bool pm = drop && drop->mlp_p > 0.f;
@@ -1002,18 +1024,24 @@ int mlp_bwd_impl(const swf_linear& fc1, const swf_linear& fc2, const float* x, c
     static const swf_linear_grad none{};
     GemmBatch gb{};
     gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
-    SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, 1, st));                          // h = ELU(fc1 x)
+    const bool from_u = !act_is_default(act);   // as basic_block_bwd_impl
+    SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, from_u ? Act(0) : Act(1), st));   // h = ELU(fc1 x), or u = fc1 x
     const float* g = gout;
     if (pm) {
-        SWF_TRY(launch_dropout_mul(h, hd, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
+        if (!from_u) SWF_TRY(launch_dropout_mul(h, hd, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
         SWF_TRY(launch_dropout_mul(gout, gf, N * C, drop_site(drop->seed, stream_id, kDropMlpOut, drop->mlp_p), st));
         g = gf;
     }
     SWF_TRY(dx(g, fc2.weight, dh, N, C, hid, 0, tier, st));
+    if (from_u) {
+        if (pm) SWF_TRY(launch_dropout_mul(dh, dh, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
+        SWF_TRY(act_bwd_from_u(dh, h, N * hid, act, st));
+        if (pm) SWF_TRY(launch_dropout_mul(h, hd, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
+    }
     SWF_TRY(dw(g, hd, (g2 ? *g2 : none).weight, (g2 ? *g2 : none).bias, N, C, hid, scratch, tier, st));
-    if (pm) {
+    if (!from_u && pm) {
         SWF_TRY(launch_dropout_elu_bwd(dh, h, N * hid, drop_site(drop->seed, stream_id, kDropHidden, drop->mlp_p), st));
-    } else {
+    } else if (!from_u) {
         hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(N * hid, 256)), dim3(256), 0, st, dh, h, N * hid);
         SWF_TRY(check_launch("elu_bwd"));
     }
@@ -1070,25 +1098,25 @@ size_t mlp_bwd_ws(int64_t N, int C, int hid) { return mlp_ws(N, C, hid, true, fa
 size_t mlp_drop_ws(int64_t N, int C, int hid) { return std::max(mlp_ws(N, C, hid, false, true), mlp_ws(N, C, hid, true, true)); }
 
 int mlp_bwd(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1, const swf_linear_grad* g2,
-            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier) {
-    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, nullptr, 0, tier, workspace, workspace_bytes, st);
+            int64_t N, int C, int hid, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier, const swf_activation& act) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, nullptr, 0, tier, workspace, workspace_bytes, st, act);
 }
 int mlp_bwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* g1,
                  const swf_linear_grad* g2, int64_t N, int C, int hid, const swf_dropout& drop, int stream_id, void* workspace, size_t workspace_bytes,
-                 hipStream_t st, const BwdTier& tier) {
-    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, &drop, stream_id, tier, workspace, workspace_bytes, st);
+                 hipStream_t st, const BwdTier& tier, const swf_activation& act) {
+    return mlp_bwd_impl(fc1, fc2, x, gout, gx, g1, g2, N, C, hid, &drop, stream_id, tier, workspace, workspace_bytes, st, act);
 }
 
 // one stream of AutoPathMLP.forward with dropout (exact fp32): out = dropout3(fc2(dropout2(ELU(fc1(x)))))
 int mlp_fwd_drop(const swf_linear& fc1, const swf_linear& fc2, const float* x, float* out, int64_t N, int C, int hid, const swf_dropout& drop,
-                 int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st) {
+                 int stream_id, void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
     if (N > INT32_MAX / std::max(C, hid)) return fail(SWF_ERR_UNSUPPORTED, "mlp_fwd_drop: token count");
     Carver ws(workspace, workspace_bytes);
     float* h = carve_mlp_bwd(ws, N, C, hid, false, true).h;
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "mlp_fwd_drop workspace too small (need %zu B)", ws.bytes());
     GemmBatch gb{};
     gb.p[0] = GemmProb{x, fc1.weight, fc1.bias, nullptr, h};
-    SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, 1, st));
+    SWF_TRY(launch_gemm_f32(gb, 1, (int)N, hid, C, C, hid, Act(act), st));
     const bool pm = drop.mlp_p > 0.f;
     if (pm) SWF_TRY(launch_dropout_mul(h, h, N * hid, drop_site(drop.seed, stream_id, kDropHidden, drop.mlp_p), st));
     GemmBatch g2{};
@@ -1157,7 +1185,7 @@ size_t patch_bwd_ws(int B, int H, int W, int Cin, int Cout, int mh, int mw, int 
 }
 
 int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int B, int H, int W, int Cin,
-              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier) {
+              int Cout, int mh, int mw, int encoder, void* workspace, size_t workspace_bytes, hipStream_t st, const BwdTier& tier, const swf_activation& act) {
     // H x W: the layer's INPUT map (encoder: full map, divisible by the merging size; decoder: the merged map)
     if (encoder && (H % mh || W % mw)) return fail(SWF_ERR_BAD_SHAPE, "patch backward: map %dx%d not divisible by the merging size", H, W);
     const int Hm = encoder ? H / mh : H, Wm = encoder ? W / mw : W;
@@ -1172,7 +1200,9 @@ int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, flo
     const swf_patch_grads& g = gp ? *gp : none;
     const unsigned blocks_img = (unsigned)cdiv64(n * (int64_t)mh * mw * (encoder ? Cin : Cout), 256);
     const float* rows = in;
-    // ---- recompute: rows -> conv -> LayerNorm -> ELU (in merged-token order; ELU commutes with the depth-to-space permutation) ----
+    // ---- recompute: rows -> conv -> LayerNorm -> activation (in merged-token order; a pointwise activation commutes with the
+    //      depth-to-space permutation).  A non-default activation keeps the LayerNorm output itself in A: act' is taken from it ----
+    const bool from_u = !act_is_default(act);
     if (encoder) {
         hipLaunchKernelGGL(patch_permute_kernel, dim3(blocks_img), dim3(256), 0, st, in, Z, B, Hm, Wm, Cin, mh, mw, 0);
         SWF_TRY(check_launch("patch space-to-depth"));
@@ -1183,7 +1213,7 @@ int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, flo
     SWF_TRY(launch_gemm_f32(gb, 1, (int)n, Nn, K, K, Nn, 0, st));
     LnBatch lb{};
     lb.p[0] = LnProb{U, A, p.ln.gamma, p.ln.beta};
-    SWF_TRY(launch_layernorm(lb, 1, n, Nn, 1, st));   // A = ELU(LN(U))
+    SWF_TRY(launch_layernorm(lb, 1, n, Nn, from_u ? Act(0) : Act(1), st));   // A = ELU(LN(U)), or LN(U)
     // ---- reverse ----
     const float* gA = gout;   // gradient w.r.t. A in merged-token order
     if (!encoder) {           // the output image -> merged-token order
@@ -1192,8 +1222,9 @@ int patch_bwd(const swf_patch_params& p, const float* in, const float* gout, flo
         gA = V;
     }
     if (hipMemcpyAsync(dV, gA, (size_t)n * Nn * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail(SWF_ERR_HIP, "patch backward: copy failed");
-    hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(n * Nn, 256)), dim3(256), 0, st, dV, A, n * Nn);   // dV = gA . ELU'(.)
-    SWF_TRY(check_launch("elu_bwd"));
+    if (from_u) hipLaunchKernelGGL(act_bwd_kernel, dim3((unsigned)cdiv64(n * Nn, 256)), dim3(256), 0, st, dV, A, n * Nn, act);   // dV = gA . act'(LN(U))
+    else hipLaunchKernelGGL(elu_bwd_kernel, dim3((unsigned)cdiv64(n * Nn, 256)), dim3(256), 0, st, dV, A, n * Nn);   // dV = gA . ELU'(.)
+    SWF_TRY(check_launch(from_u ? "act_bwd" : "elu_bwd"));
     float* dU = V;            // (V is free again)
     SWF_TRY(ln_bwd(U, p.ln.gamma, dV, nullptr, dU, g.ln.gamma, g.ln.beta, n, Nn, scratch, st));
     SWF_TRY(dw(dU, rows, g.conv.weight, g.conv.bias, n, Nn, K, scratch, tier, st));
@@ -1217,7 +1248,7 @@ int add_tensors(const float* a, const float* b, float* out, int64_t n, hipStream
 }
 
 // ---- final head backward (a013:126-152 under autograd; BatchNorm in eval mode = a per-channel affine map of its running statistics) ------
-// forward:  t1 = conv1(cat(x, y)) [2 ch];  t2 = a t1 + c,  a = gamma / sqrt(var + eps),  c = beta - mean a;  t3 = ELU(t2);  out = conv2(t3)
+// forward:  t1 = conv1(cat(x, y)) [2 ch];  t2 = a t1 + c,  a = gamma / sqrt(var + eps),  c = beta - mean a;  t3 = act(t2);  out = conv2(t3)
 // Both convolutions read reflect-padded maps ('same', padding_mode='reflect'): the adjoint folds the padded gradient back, here in gather
 // form — a pixel sums over every (output pixel, tap) pair whose reflected source it is — so every sum has a fixed order.
 namespace {
@@ -1245,10 +1276,10 @@ __global__ __launch_bounds__(256) void head_t1_kernel(const float* __restrict__ 
 }
 
 // out[pixel][ci] = sum over (output pixel o, tap k) with reflect(o + k - r) == pixel of g[o][co] w[co][ci][k]: the adjoint of a reflect-'same'
-// convolution with CO output and 2 input channels.  post != 0: multiply channel ci by ELU'(a[ci] t1[ci] + c[ci]) (the head's dt2).
+// convolution with CO output and 2 input channels.  post != 0: multiply channel ci by act'(a[ci] t1[ci] + c[ci]) (the head's dt2).
 __global__ __launch_bounds__(256) void head_conv_adjoint_kernel(const float* __restrict__ g, const float* __restrict__ w, float* __restrict__ out,
                                                                  int CO, const float* __restrict__ t1, float a0, float c0, float a1, float c1,
-                                                                 int post, int B, int H, int W, int ks) {
+                                                                 int post, int B, int H, int W, int ks, swf_activation act) {
     const int64_t total = (int64_t)B * H * W, e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int r = ks / 2, px = (int)(e % W), py = (int)((e / W) % H);
@@ -1270,15 +1301,16 @@ __global__ __launch_bounds__(256) void head_conv_adjoint_kernel(const float* __r
         }
     if (post) {
         const float u0 = a0 * t1[2 * e] + c0, u1 = a1 * t1[2 * e + 1] + c1;
-        acc[0] *= u0 > 0.f ? 1.0f : expf(u0);
-        acc[1] *= u1 > 0.f ? 1.0f : expf(u1);
+        acc[0] *= act_grad(u0, act.kind, act.param);
+        acc[1] *= act_grad(u1, act.kind, act.param);
     }
     out[2 * e] = acc[0]; out[2 * e + 1] = acc[1];
 }
 
 // per-pixel rows whose column sums are the conv2 gradients: [ci][ky][kx] gout t3(reflected source), then gout (bias)
 __global__ __launch_bounds__(256) void head_rows2_kernel(const float* __restrict__ gout, const float* __restrict__ t1, float* __restrict__ rows,
-                                                          float a0, float c0, float a1, float c1, int B, int H, int W, int ks) {
+                                                          float a0, float c0, float a1, float c1, int B, int H, int W, int ks,
+                                                          swf_activation act) {
     const int64_t total = (int64_t)B * H * W, e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int r = ks / 2, px = (int)(e % W), py = (int)((e / W) % H), NC = 2 * ks * ks + 1;
@@ -1289,8 +1321,8 @@ __global__ __launch_bounds__(256) void head_rows2_kernel(const float* __restrict
         for (int kx = 0; kx < ks; ++kx) {
             const int64_t sidx = (b * H + reflect2(py + ky - r, H)) * W + reflect2(px + kx - r, W);
             const float u0 = a0 * t1[2 * sidx] + c0, u1 = a1 * t1[2 * sidx + 1] + c1;
-            row[(0 * ks + ky) * ks + kx] = g * (u0 > 0.f ? u0 : expm1f(u0));
-            row[(1 * ks + ky) * ks + kx] = g * (u1 > 0.f ? u1 : expm1f(u1));
+            row[(0 * ks + ky) * ks + kx] = g * act_apply(u0, act.kind, act.param);
+            row[(1 * ks + ky) * ks + kx] = g * act_apply(u1, act.kind, act.param);
         }
     row[NC - 1] = g;
 }
@@ -1448,24 +1480,24 @@ int head_stats_finish(const float* sums, int64_t count, int pass, float* mean, f
 //          t1 and dt2 are computed again, nothing is kept from phase 1.
 static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf_head_params& p, const float* x, const float* y,
                           const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, int batch_stats,
-                          void* workspace, size_t workspace_bytes, hipStream_t st);
+                          void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act);
 
 int head_bwd(const swf_head_params& p, const float* x, const float* y, const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B,
-             int H, int W, int ks, int batch_stats, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return head_bwd_phase(0, nullptr, 0, p, x, y, gout, gx, gy, gp, B, H, W, ks, batch_stats, workspace, workspace_bytes, st);
+             int H, int W, int ks, int batch_stats, void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
+    return head_bwd_phase(0, nullptr, 0, p, x, y, gout, gx, gy, gp, B, H, W, ks, batch_stats, workspace, workspace_bytes, st, act);
 }
 int head_bwd_sums(const swf_head_params& p, const float* x, const float* y, const float* gout, float* sums_out, int B, int H, int W, int ks,
-                  void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return head_bwd_phase(1, sums_out, 0, p, x, y, gout, nullptr, nullptr, nullptr, B, H, W, ks, 1, workspace, workspace_bytes, st);
+                  void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
+    return head_bwd_phase(1, sums_out, 0, p, x, y, gout, nullptr, nullptr, nullptr, B, H, W, ks, 1, workspace, workspace_bytes, st, act);
 }
 int head_bwd_apply(const swf_head_params& p, const float* x, const float* y, const float* gout, const float* sums, int64_t n_global, float* gx,
-                   float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, void* workspace, size_t workspace_bytes, hipStream_t st) {
-    return head_bwd_phase(2, const_cast<float*>(sums), n_global, p, x, y, gout, gx, gy, gp, B, H, W, ks, 1, workspace, workspace_bytes, st);
+                   float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
+    return head_bwd_phase(2, const_cast<float*>(sums), n_global, p, x, y, gout, gx, gy, gp, B, H, W, ks, 1, workspace, workspace_bytes, st, act);
 }
 
 static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf_head_params& p, const float* x, const float* y,
                           const float* gout, float* gx, float* gy, const swf_head_grads* gp, int B, int H, int W, int ks, int batch_stats,
-                          void* workspace, size_t workspace_bytes, hipStream_t st) {
+                          void* workspace, size_t workspace_bytes, hipStream_t st, const swf_activation& act) {
     if (ks < 1 || ks % 2 == 0 || ks / 2 >= H || ks / 2 >= W) return fail(SWF_ERR_PAD, "head backward: kernel %d on a %dx%d map", ks, H, W);
     const int64_t n = (int64_t)B * H * W;
     const int nc1 = 4 * ks * ks + 6, nc2 = 2 * ks * ks + 1;
@@ -1486,8 +1518,8 @@ static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf
     const swf_head_grads& g = gp ? *gp : none;
     hipLaunchKernelGGL(head_t1_kernel, dim3(blocks), dim3(256), 0, st, x, y, t1, p, B, H, W, ks);
     SWF_TRY(check_launch("head_t1"));
-    // dt2 = adjoint(conv2)(gout) . ELU'(t2)
-    hipLaunchKernelGGL(head_conv_adjoint_kernel, dim3(blocks), dim3(256), 0, st, gout, p.conv2_w, dt2, 1, t1, a[0], c[0], a[1], c[1], 1, B, H, W, ks);
+    // dt2 = adjoint(conv2)(gout) . act'(t2)
+    hipLaunchKernelGGL(head_conv_adjoint_kernel, dim3(blocks), dim3(256), 0, st, gout, p.conv2_w, dt2, 1, t1, a[0], c[0], a[1], c[1], 1, B, H, W, ks, act);
     SWF_TRY(check_launch("head adjoint conv2"));
     auto colsums = [&](int nc, float* out_host_layout) -> int {   // column sums of rows [n][nc] -> part tail (device)
         SWF_TRY(colsum(rows, part, n, nc, st));
@@ -1499,7 +1531,7 @@ static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf
         return hipMemcpyAsync(dst, src, (size_t)count * 4, hipMemcpyDeviceToDevice, st) == hipSuccess ? SWF_OK : fail(SWF_ERR_HIP, "head backward: copy failed");
     };
     if (phase != 1 && (g.conv2_w || g.conv2_b)) {
-        hipLaunchKernelGGL(head_rows2_kernel, dim3(blocks), dim3(256), 0, st, gout, t1, rows, a[0], c[0], a[1], c[1], B, H, W, ks);
+        hipLaunchKernelGGL(head_rows2_kernel, dim3(blocks), dim3(256), 0, st, gout, t1, rows, a[0], c[0], a[1], c[1], B, H, W, ks, act);
         SWF_TRY(check_launch("head rows2"));
         SWF_TRY(colsums(nc2, sums));
         SWF_TRY(copy(g.conv2_w, sums, 2 * ks * ks));
@@ -1536,7 +1568,7 @@ static int head_bwd_phase(int phase, float* sums_io, int64_t n_global, const swf
         hipLaunchKernelGGL(head_dt1_kernel, dim3(blocks), dim3(256), 0, st, dt2, t1, dt1, a[0], a[1], hm[0], hm[1], is[0], is[1], k1[0], k1[1], k2[0],
                            k2[1], n);
         SWF_TRY(check_launch("head dt1"));
-        hipLaunchKernelGGL(head_conv_adjoint_kernel, dim3(blocks), dim3(256), 0, st, dt1, p.conv1_w, din, 2, t1, 0.f, 0.f, 0.f, 0.f, 0, B, H, W, ks);
+        hipLaunchKernelGGL(head_conv_adjoint_kernel, dim3(blocks), dim3(256), 0, st, dt1, p.conv1_w, din, 2, t1, 0.f, 0.f, 0.f, 0.f, 0, B, H, W, ks, act);
         SWF_TRY(check_launch("head adjoint conv1"));
     }
     hipLaunchKernelGGL(head_split_kernel, dim3(blocks), dim3(256), 0, st, din, gx, gy, n);

@@ -14,8 +14,6 @@ namespace swf {
 
 using namespace wf;
 
-__device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expm1f(v); }
-
 // ------------------------------------------------------------------------------------------
 // GEMM: out[M][N] = act(A[M][K] . W[N][K]^T + bias) (+res)
 // 64x64 output tile per 256-thread workgroup, 4 waves as 2x2, each wave 2x2 MFMA tiles of 16x16,
@@ -25,7 +23,7 @@ __device__ __forceinline__ float elu1(float v) { return v > 0.f ? v : expm1f(v);
 constexpr int GBM = 64, GBN = 64, GBK = 16, GLD = GBK + 4;
 
 __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmBatch batch, int M, int N, int K, int lda, int ldo,
-                                                        int act, int vecA, int vecW) {
+                                                        Act act, int vecA, int vecW) {
     const GemmProb pr = batch.p[blockIdx.z];
     __shared__ __attribute__((aligned(16))) float As[GBM * GLD];
     __shared__ __attribute__((aligned(16))) float Ws[GBN * GLD];
@@ -96,7 +94,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmBatch batch, int M, i
                 const int row = brow + wr * 32 + m * 16 + fq * 4 + j;
                 if (row >= M) continue;
                 float v = acc[m][n][j] + bv;
-                if (act == 1) v = elu1(v);
+                if (act.on) v = act_apply(v, act);
                 const int64_t o = (int64_t)row * ldo + col;
                 if (pr.res) v = pr.res[o] + v;
                 pr.out[o] = v;
@@ -104,7 +102,7 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(GemmBatch batch, int M, i
         }
 }
 
-int launch_gemm_f32(const GemmBatch& batch, int nprob, int M, int N, int K, int lda, int ldo, int act,
+int launch_gemm_f32(const GemmBatch& batch, int nprob, int M, int N, int K, int lda, int ldo, Act act,
                     hipStream_t stream) {
     if (M <= 0 || N <= 0 || K <= 0) return fail(SWF_ERR_BAD_SHAPE, "gemm: empty problem %dx%dx%d", M, N, K);
     int vecA = (lda % 4 == 0) && (K % 4 == 0), vecW = (K % 4 == 0);
@@ -129,7 +127,7 @@ constexpr int XBK = 32, XLD = XBK + 8;   // 80-B rows: conflict-free ds_read_b12
 // splitk > 1, writes its raw partial tile to batch.scratch[(z)][M][N]; gemm_splitk_reduce_kernel sums the
 // slices in fixed order (bitwise reproducible, no atomics) and applies bias / activation / residual.
 __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M, int N, int K, int lda, int ldo,
-                                                           int act, int vecA, int vecW, int splitk, int kchunk) {
+                                                           Act act, int vecA, int vecW, int splitk, int kchunk) {
     const int prob = blockIdx.z / splitk, slice = blockIdx.z % splitk;
     const GemmProb pr = batch.p[prob];
     const int kbeg = slice * kchunk, kend = min(K, kbeg + kchunk);
@@ -225,7 +223,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M
                     continue;
                 }
                 float v = acc[m][n][j] + bv;
-                if (act == 1) v = elu1(v);
+                if (act.on) v = act_apply(v, act);
                 const int64_t o = (int64_t)row * ldo + col;
                 if (pr.res) v = pr.res[o] + v;
                 pr.out[o] = v;
@@ -233,7 +231,7 @@ __global__ __launch_bounds__(256) void gemm_bf16x3_kernel(GemmBatch batch, int M
         }
 }
 
-__global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmBatch batch, int M, int N, int ldo, int act, int splitk) {
+__global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmBatch batch, int M, int N, int ldo, Act act, int splitk) {
     const int prob = blockIdx.y;
     const GemmProb pr = batch.p[prob];
     const int64_t total = (int64_t)M * N;
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmBatch batch
                 v.x += t.x; v.y += t.y; v.z += t.z; v.w += t.w;
             }
             if (pr.bias) { v.x += pr.bias[col]; v.y += pr.bias[col + 1]; v.z += pr.bias[col + 2]; v.w += pr.bias[col + 3]; }
-            if (act == 1) { v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w); }
+            if (act.on) { v.x = act_apply(v.x, act); v.y = act_apply(v.y, act); v.z = act_apply(v.z, act); v.w = act_apply(v.w, act); }
             const int64_t o = row * ldo + col;
             if (pr.res) {
                 const float4 r = *reinterpret_cast<const float4*>(pr.res + o);
@@ -266,7 +264,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmBatch batch
         float v = 0.f;
         for (int s = 0; s < splitk; ++s) v += part[s * total + e];   // fixed order
         if (pr.bias) v += pr.bias[col];
-        if (act == 1) v = elu1(v);
+        if (act.on) v = act_apply(v, act);
         const int64_t o = row * ldo + col;
         if (pr.res) v = pr.res[o] + v;
         pr.out[o] = v;
@@ -278,7 +276,7 @@ __global__ __launch_bounds__(256) void gemm_splitk_reduce_kernel(GemmBatch batch
 // (the multi-GPU contract).  Long-K GEMMs are exactly the small-M, weight-streaming ones of the deep levels.
 int gemm_splitk_for(int K) { return K >= 1024 ? 4 : (K >= 384 ? 2 : 1); }
 
-int launch_gemm_bf16x3(const GemmBatch& batch, int nprob, int M, int N, int K, int lda, int ldo, int act,
+int launch_gemm_bf16x3(const GemmBatch& batch, int nprob, int M, int N, int K, int lda, int ldo, Act act,
                        hipStream_t stream) {
     if (M <= 0 || N <= 0 || K <= 0) return fail(SWF_ERR_BAD_SHAPE, "gemm: empty problem %dx%dx%d", M, N, K);
     int vecA = (lda % 4 == 0), vecW = (K % 4 == 0);
@@ -311,7 +309,7 @@ int launch_gemm_bf16x3(const GemmBatch& batch, int nprob, int M, int N, int K, i
 // ------------------------------------------------------------------------------------------
 constexpr int LBK = 64, LLD = LBK + 8;
 
-__global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, int M, int N, int C, int act, int ct_per_wg) {
+__global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, int M, int N, int C, Act act, int ct_per_wg) {
     extern __shared__ __attribute__((aligned(16))) char lsm[];
     const LnGemmProb pr = batch.p[blockIdx.z];
     const int KP = (C + 31) / 32 * 32;          // K padded to the MFMA k-step
@@ -434,7 +432,7 @@ __global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, i
                 if (row >= M) continue;
                 float v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { v[j] = acc[m][n][j] + bv[j]; if (act == 1) v[j] = elu1(v[j]); }
+                for (int j = 0; j < 4; ++j) { v[j] = acc[m][n][j] + bv[j]; if (act.on) v[j] = act_apply(v[j], act); }
                 float* o = pr.out + (int64_t)row * N + col;
                 if (col + 3 < N && (N & 3) == 0) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
                 else {
@@ -450,7 +448,7 @@ __global__ __launch_bounds__(256) void lngemm_bf16x3_kernel(LnGemmBatch batch, i
 // B=16, the C=96 block gains 13 us, C=192 loses 20 us and C=384 loses 50 us (few column tiles per A tile).
 bool lngemm_supported(int C) { return C % 4 == 0 && C >= 4 && C <= 128; }
 
-int launch_lngemm_bf16x3(const LnGemmBatch& batch, int nprob, int M, int N, int C, int act, hipStream_t stream) {
+int launch_lngemm_bf16x3(const LnGemmBatch& batch, int nprob, int M, int N, int C, Act act, hipStream_t stream) {
     if (M <= 0 || N <= 0 || C <= 0) return fail(SWF_ERR_BAD_SHAPE, "lngemm: empty problem");
     if (!lngemm_supported(C)) return fail(SWF_ERR_UNSUPPORTED, "lngemm: C=%d", C);
     for (int i = 0; i < nprob; ++i) {
@@ -474,7 +472,7 @@ int launch_lngemm_bf16x3(const LnGemmBatch& batch, int nprob, int M, int N, int 
 // ------------------------------------------------------------------------------------------
 // LayerNorm over C per token.  L lanes (power of two) cooperate on a token.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void layernorm_kernel(LnBatch batch, int64_t tokens, int C, int L, int elu) {
+__global__ __launch_bounds__(256) void layernorm_kernel(LnBatch batch, int64_t tokens, int C, int L, Act act) {
     const LnProb pr = batch.p[blockIdx.y];
     const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t tok = gt / L;
@@ -493,7 +491,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnBatch batch, int64_t t
     float* y = pr.out + tok * C;
     for (int c = sub; c < C; c += L) {
         float r = (x[c] - mean) * rstd * pr.gamma[c] + pr.beta[c];
-        if (elu) r = elu1(r);
+        if (act.on) r = act_apply(r, act);
         y[c] = r;
     }
 }
@@ -501,7 +499,7 @@ __global__ __launch_bounds__(256) void layernorm_kernel(LnBatch batch, int64_t t
 // Single-pass variant for C % 4 == 0: the token row lives in registers (L lanes per token, each lane
 // NCH float4 chunks at stride L), one read and one write of the tensor.
 template <int NCH>
-__global__ __launch_bounds__(256) void layernorm_vec_kernel(LnBatch batch, int64_t tokens, int C, int L, int elu) {
+__global__ __launch_bounds__(256) void layernorm_vec_kernel(LnBatch batch, int64_t tokens, int C, int L, Act act) {
     const LnProb pr = batch.p[blockIdx.y];
     const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const int64_t tok = gt / L;
@@ -543,7 +541,7 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnBatch batch, int64
             r.y = (v[i].y - mean) * rstd * g.y + b.y;
             r.z = (v[i].z - mean) * rstd * g.z + b.z;
             r.w = (v[i].w - mean) * rstd * g.w + b.w;
-            if (elu) { r.x = elu1(r.x); r.y = elu1(r.y); r.z = elu1(r.z); r.w = elu1(r.w); }
+            if (act.on) { r.x = act_apply(r.x, act); r.y = act_apply(r.y, act); r.z = act_apply(r.z, act); r.w = act_apply(r.w, act); }
             if (pr.out_hi) {
                 bf16x4 hi, lo;
                 split4(r, hi, lo);
@@ -556,7 +554,7 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(LnBatch batch, int64
     }
 }
 
-int launch_layernorm(const LnBatch& batch, int nprob, int64_t tokens, int C, int elu, hipStream_t stream) {
+int launch_layernorm(const LnBatch& batch, int nprob, int64_t tokens, int C, Act act, hipStream_t stream) {
     bool vec = (C % 4 == 0) && C <= 1024;
     bool split = false;
     for (int i = 0; i < nprob; ++i) split |= batch.p[i].out_hi != nullptr;
@@ -576,17 +574,29 @@ int launch_layernorm(const LnBatch& batch, int nprob, int64_t tokens, int C, int
         const int nch = cdiv(chunks, L);
         const int64_t threads = tokens * L;
         dim3 grid((unsigned)cdiv64(threads, 256), nprob);
-        if (nch == 1) hipLaunchKernelGGL(layernorm_vec_kernel<1>, grid, dim3(256), 0, stream, batch, tokens, C, L, elu);
-        else if (nch == 2) hipLaunchKernelGGL(layernorm_vec_kernel<2>, grid, dim3(256), 0, stream, batch, tokens, C, L, elu);
-        else hipLaunchKernelGGL(layernorm_vec_kernel<4>, grid, dim3(256), 0, stream, batch, tokens, C, L, elu);
+        if (nch == 1) hipLaunchKernelGGL(layernorm_vec_kernel<1>, grid, dim3(256), 0, stream, batch, tokens, C, L, act);
+        else if (nch == 2) hipLaunchKernelGGL(layernorm_vec_kernel<2>, grid, dim3(256), 0, stream, batch, tokens, C, L, act);
+        else hipLaunchKernelGGL(layernorm_vec_kernel<4>, grid, dim3(256), 0, stream, batch, tokens, C, L, act);
         return check_launch("layernorm_vec");
     }
     int L = 1;
     while (L < 64 && L * 4 < C) L <<= 1;
     const int64_t threads = tokens * L;
     dim3 grid((unsigned)cdiv64(threads, 256), nprob);
-    hipLaunchKernelGGL(layernorm_kernel, grid, dim3(256), 0, stream, batch, tokens, C, L, elu);
+    hipLaunchKernelGGL(layernorm_kernel, grid, dim3(256), 0, stream, batch, tokens, C, L, act);
     return check_launch("layernorm");
+}
+
+// h[i] = act(h[i]): the backward of a non-default activation recomputes the pre-activation into the hidden buffer, takes act' from
+// it and then turns it into the activation in place (kernels_bwd.hip)
+__global__ __launch_bounds__(256) void act_inplace_kernel(float* __restrict__ h, int64_t n, Act act) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) h[i] = act_apply(h[i], act);
+}
+int launch_act_inplace(float* h, int64_t n, Act act, hipStream_t stream) {
+    if (n <= 0 || !act.on) return SWF_OK;
+    hipLaunchKernelGGL(act_inplace_kernel, dim3((unsigned)cdiv64(n, 256)), dim3(256), 0, stream, h, n, act);
+    return check_launch("act_inplace");
 }
 
 // ------------------------------------------------------------------------------------------
@@ -788,7 +798,7 @@ int launch_crop(const PtrPair& pp, int nprob, int B, int Hp, int Wp, int Hm, int
 
 template <int VEC>
 __global__ __launch_bounds__(256) void unmerge_scatter_kernel(PtrPair pp, int B, int Hm, int Wm, int Cout, int mh, int mw,
-                                                              int Hout, int Wout) {
+                                                              int Hout, int Wout, Act act) {
     const float* z = pp.in[blockIdx.y];
     float* out = pp.out[blockIdx.y];
     const float* skip = pp.aux[blockIdx.y];
@@ -803,25 +813,25 @@ __global__ __launch_bounds__(256) void unmerge_scatter_kernel(PtrPair pp, int B,
         const int64_t src = (((int64_t)b * Hm + my) * Wm + mx) * Kz + (ph * mw + pw) * Cout + c;
         if constexpr (VEC == 4) {
             float4 v = *reinterpret_cast<const float4*>(z + src);
-            v.x = elu1(v.x); v.y = elu1(v.y); v.z = elu1(v.z); v.w = elu1(v.w);
+            v.x = act_apply(v.x, act); v.y = act_apply(v.y, act); v.z = act_apply(v.z, act); v.w = act_apply(v.w, act);
             if (skip) {
                 const float4 k = *reinterpret_cast<const float4*>(skip + e * 4);
                 v.x += k.x; v.y += k.y; v.z += k.z; v.w += k.w;
             }
             *reinterpret_cast<float4*>(out + e * 4) = v;
         } else {
-            float v = elu1(z[src]);
+            float v = act_apply(z[src], act);
             if (skip) v += skip[e];
             out[e] = v;
         }
     }
 }
 
-// LayerNorm over the mh*mw*Cout conv outputs of a merged token, then depth-to-space + ELU (+ skip) in the same launch
+// LayerNorm over the mh*mw*Cout conv outputs of a merged token, then depth-to-space + activation (+ skip) in the same launch
 // (a011:107-117): layernorm_vec_kernel's arithmetic, unmerge_scatter_kernel's index map, no normalised intermediate.
 template <int NCH>
 __global__ __launch_bounds__(256) void ln_unmerge_scatter_kernel(LnBatch batch, PtrPair pp, int64_t tokens, int L, int Hm, int Wm,
-                                                                 int Cout, int mh, int mw, int Hout, int Wout) {
+                                                                 int Cout, int mh, int mw, int Hout, int Wout, Act act) {
     const LnProb pr = batch.p[blockIdx.y];
     float* out = pp.out[blockIdx.y];
     const float* skip = pp.aux[blockIdx.y];
@@ -862,10 +872,10 @@ __global__ __launch_bounds__(256) void ln_unmerge_scatter_kernel(LnBatch batch, 
         if (ch < chunks) {
             const float4 g = g4[ch], bb = b4[ch];
             float4 r;
-            r.x = elu1((v[i].x - mean) * rstd * g.x + bb.x);
-            r.y = elu1((v[i].y - mean) * rstd * g.y + bb.y);
-            r.z = elu1((v[i].z - mean) * rstd * g.z + bb.z);
-            r.w = elu1((v[i].w - mean) * rstd * g.w + bb.w);
+            r.x = act_apply((v[i].x - mean) * rstd * g.x + bb.x, act);
+            r.y = act_apply((v[i].y - mean) * rstd * g.y + bb.y, act);
+            r.z = act_apply((v[i].z - mean) * rstd * g.z + bb.z, act);
+            r.w = act_apply((v[i].w - mean) * rstd * g.w + bb.w, act);
             const int p = (4 * ch) / Cout, c = (4 * ch) % Cout;   // Cout % 4 == 0: a chunk never straddles sub-pixels
             const int y = my * mh + p / mw, xo = mx * mw + p % mw;
             if (y < Hout && xo < Wout) {
@@ -893,7 +903,7 @@ bool ln_unmerge_scatter_supported(const LnBatch& batch, const PtrPair& pp, int n
 }
 
 int launch_ln_unmerge_scatter(const LnBatch& batch, const PtrPair& pp, int nprob, int B, int Hm, int Wm, int Cout, int mh, int mw,
-                              int Hout, int Wout, hipStream_t stream) {
+                              int Hout, int Wout, hipStream_t stream, Act act) {
     if (!ln_unmerge_scatter_supported(batch, pp, nprob, Cout, mh, mw)) return fail(SWF_ERR_UNSUPPORTED, "ln_unmerge_scatter: shape / alignment");
     if ((int64_t)B * Hout * Wout > INT32_MAX || (int64_t)B * Hm * Wm > INT32_MAX) return fail(SWF_ERR_UNSUPPORTED, "ln_unmerge_scatter: more than 2^31 pixels");
     const int64_t tokens = (int64_t)B * Hm * Wm;
@@ -902,14 +912,14 @@ int launch_ln_unmerge_scatter(const LnBatch& batch, const PtrPair& pp, int nprob
     while (L < 64 && L < chunks) L <<= 1;   // as launch_layernorm picks them: same summation order
     const int nch = cdiv(chunks, L);
     dim3 grid((unsigned)cdiv64(tokens * L, 256), nprob);
-    if (nch == 1) hipLaunchKernelGGL(ln_unmerge_scatter_kernel<1>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout);
-    else if (nch == 2) hipLaunchKernelGGL(ln_unmerge_scatter_kernel<2>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout);
-    else hipLaunchKernelGGL(ln_unmerge_scatter_kernel<4>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout);
+    if (nch == 1) hipLaunchKernelGGL(ln_unmerge_scatter_kernel<1>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout, act);
+    else if (nch == 2) hipLaunchKernelGGL(ln_unmerge_scatter_kernel<2>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout, act);
+    else hipLaunchKernelGGL(ln_unmerge_scatter_kernel<4>, grid, dim3(256), 0, stream, batch, pp, tokens, L, Hm, Wm, Cout, mh, mw, Hout, Wout, act);
     return check_launch("ln_unmerge_scatter");
 }
 
 int launch_unmerge_scatter(const PtrPair& pp, int nprob, int B, int Hm, int Wm, int Cout, int mh, int mw, int Hout,
-                           int Wout, hipStream_t stream) {
+                           int Wout, hipStream_t stream, Act act) {
     if ((int64_t)B * Hout * Wout > INT32_MAX) return fail(SWF_ERR_UNSUPPORTED, "unmerge_scatter: more than 2^31 pixels");
     bool vec = Cout % 4 == 0;
     for (int i = 0; i < nprob; ++i) {
@@ -919,8 +929,8 @@ int launch_unmerge_scatter(const PtrPair& pp, int nprob, int B, int Hm, int Wm, 
     }
     const int64_t total = (int64_t)B * Hout * Wout * Cout / (vec ? 4 : 1);
     dim3 grid((unsigned)std::min<int64_t>(cdiv64(total, 256), 8192), nprob);
-    if (vec) hipLaunchKernelGGL(unmerge_scatter_kernel<4>, grid, dim3(256), 0, stream, pp, B, Hm, Wm, Cout, mh, mw, Hout, Wout);
-    else hipLaunchKernelGGL(unmerge_scatter_kernel<1>, grid, dim3(256), 0, stream, pp, B, Hm, Wm, Cout, mh, mw, Hout, Wout);
+    if (vec) hipLaunchKernelGGL(unmerge_scatter_kernel<4>, grid, dim3(256), 0, stream, pp, B, Hm, Wm, Cout, mh, mw, Hout, Wout, act);
+    else hipLaunchKernelGGL(unmerge_scatter_kernel<1>, grid, dim3(256), 0, stream, pp, B, Hm, Wm, Cout, mh, mw, Hout, Wout, act);
     return check_launch("unmerge_scatter");
 }
 
@@ -929,7 +939,7 @@ int launch_unmerge_scatter(const PtrPair& pp, int nprob, int B, int Hm, int Wm, 
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void head_conv1_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                          float* __restrict__ tmp, swf_head_params p, int B, int H, int W,
-                                                         int ks) {
+                                                         int ks, Act act) {
     const int64_t total = (int64_t)B * H * W;
     const int r = ks / 2;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
@@ -952,8 +962,8 @@ __global__ __launch_bounds__(256) void head_conv1_kernel(const float* __restrict
         }
         a0 = (a0 - p.bn_mean[0]) / sqrtf(p.bn_var[0] + 1e-5f) * p.bn_gamma[0] + p.bn_beta[0];
         a1 = (a1 - p.bn_mean[1]) / sqrtf(p.bn_var[1] + 1e-5f) * p.bn_gamma[1] + p.bn_beta[1];
-        tmp[e * 2 + 0] = elu1(a0);
-        tmp[e * 2 + 1] = elu1(a1);
+        tmp[e * 2 + 0] = act_apply(a0, act);
+        tmp[e * 2 + 1] = act_apply(a1, act);
     }
 }
 
@@ -980,10 +990,10 @@ __global__ __launch_bounds__(256) void head_conv2_kernel(const float* __restrict
 }
 
 int launch_head_conv1(const float* x, const float* y, float* tmp, const swf_head_params& p, int B, int H, int W, int ks,
-                      hipStream_t stream) {
+                      hipStream_t stream, Act act) {
     const int64_t total = (int64_t)B * H * W;
     dim3 grid((unsigned)std::min<int64_t>(cdiv64(total, 256), 16384));
-    hipLaunchKernelGGL(head_conv1_kernel, grid, dim3(256), 0, stream, x, y, tmp, p, B, H, W, ks);
+    hipLaunchKernelGGL(head_conv1_kernel, grid, dim3(256), 0, stream, x, y, tmp, p, B, H, W, ks, act);
     return check_launch("head_conv1");
 }
 int launch_head_conv2(const float* tmp, float* out, const swf_head_params& p, int B, int H, int W, int ks,
@@ -994,13 +1004,15 @@ int launch_head_conv2(const float* tmp, float* out, const swf_head_params& p, in
     return check_launch("head_conv2");
 }
 
-// Both 3x3 convolutions in one launch: a 64x16 output tile per workgroup; the x / y tile (halo 2) and the ELU(BN(conv1)) tile
+// Both 3x3 convolutions in one launch: a 64x16 output tile per workgroup; the x / y tile (halo 2) and the act(BN(conv1)) tile
 // (halo 1) live in LDS, so the two-channel intermediate never reaches HBM.  Out-of-image positions hold the value at the
 // reflected coordinate (what 'reflect' padding reads), computed there with the same tap order as the two kernels above:
 // bit-identical results.
+// ELU1: the default activation as a compile-time fact, so that its kernel keeps the registers it had before activations were a choice.
 constexpr int kHeadTW = 64, kHeadTH = 16;
+template <bool ELU1>
 __global__ __launch_bounds__(256) void head_fused3_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                          float* __restrict__ out, swf_head_params p, int H, int W) {
+                                                          float* __restrict__ out, swf_head_params p, int H, int W, Act act) {
     constexpr int TW = kHeadTW, TH = kHeadTH, IW = TW + 4, IH = TH + 4, MW = TW + 2, MH = TH + 2;
     __shared__ float sx[IH][IW], sy[IH][IW], t0[MH][MW], t1[MH][MW];
     const int tx0 = blockIdx.x * TW, ty0 = blockIdx.y * TH;
@@ -1038,8 +1050,8 @@ __global__ __launch_bounds__(256) void head_fused3_kernel(const float* __restric
             }
         a0 = (a0 - m0) / sqrtf(v0 + 1e-5f) * g0 + be0;
         a1 = (a1 - m1) / sqrtf(v1 + 1e-5f) * g1 + be1;
-        t0[iy][ix] = elu1(a0);
-        t1[iy][ix] = elu1(a1);
+        t0[iy][ix] = ELU1 ? act_apply(a0, SWF_ACT_ELU1, 0.f) : act_apply(a0, act);
+        t1[iy][ix] = ELU1 ? act_apply(a1, SWF_ACT_ELU1, 0.f) : act_apply(a1, act);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < TH * TW; i += 256) {
@@ -1059,15 +1071,16 @@ __global__ __launch_bounds__(256) void head_fused3_kernel(const float* __restric
 }
 
 int launch_head(const float* x, const float* y, float* tmp, float* out, const swf_head_params& p, int B, int H, int W, int ks,
-                hipStream_t stream) {
+                hipStream_t stream, Act act) {
     if (ks == 3 && H >= 2 && W >= 2 && B <= 65535) {
         dim3 grid((unsigned)cdiv(W, kHeadTW), (unsigned)cdiv(H, kHeadTH), (unsigned)B);
         if (grid.y <= 65535) {
-            hipLaunchKernelGGL(head_fused3_kernel, grid, dim3(256), 0, stream, x, y, out, p, H, W);
+            if (act_is_default(act.fn)) hipLaunchKernelGGL(head_fused3_kernel<true>, grid, dim3(256), 0, stream, x, y, out, p, H, W, act);
+            else hipLaunchKernelGGL(head_fused3_kernel<false>, grid, dim3(256), 0, stream, x, y, out, p, H, W, act);
             return check_launch("head_fused3");
         }
     }
-    SWF_TRY(launch_head_conv1(x, y, tmp, p, B, H, W, ks, stream));
+    SWF_TRY(launch_head_conv1(x, y, tmp, p, B, H, W, ks, stream, act));
     return launch_head_conv2(tmp, out, p, B, H, W, ks, stream);
 }
 

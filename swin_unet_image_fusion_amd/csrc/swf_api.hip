@@ -226,7 +226,7 @@ static int mlp_halfblock_generic(const swf_block_desc* desc, const swf_block_str
     if (fold_ln) {
         LnGemmBatch l1{};
         for (int s = 0; s < nstream; ++s) l1.p[s] = LnGemmProb{res[s], pp[s]->ln2.gamma, pp[s]->ln2.beta, pp[s]->fc1.weight, pp[s]->fc1.bias, bufs.hb[s]};
-        SWF_TRY(launch_lngemm_bf16x3(l1, nstream, (int)N, hid, C, 1, stream));
+        SWF_TRY(launch_lngemm_bf16x3(l1, nstream, (int)N, hid, C, Act(desc->act), stream));
     } else {
         LnBatch lb{};
         lb.p[0] = LnProb{x_in, bufs.xn[0], px->ln2.gamma, px->ln2.beta};
@@ -235,7 +235,7 @@ static int mlp_halfblock_generic(const swf_block_desc* desc, const swf_block_str
         GemmBatch g1{};
         g1.scratch = bufs.sk; g1.scratch_floats = bufs.sk_floats;
         for (int s = 0; s < nstream; ++s) g1.p[s] = GemmProb{bufs.xn[s], pp[s]->fc1.weight, pp[s]->fc1.bias, nullptr, bufs.hb[s]};
-        SWF_TRY(launch_gemm(fast, g1, nstream, (int)N, hid, C, C, hid, 1, stream));
+        SWF_TRY(launch_gemm(fast, g1, nstream, (int)N, hid, C, C, hid, Act(desc->act), stream));
     }
     SWF_TRY(launch_gemm(fast, g2, nstream, (int)N, C, hid, hid, C, 0, stream));
     return SWF_OK;
@@ -476,7 +476,7 @@ static int check_block(const swf_block_desc* desc, const swf_block_stream_params
         SWF_TRY(check_stream_params(py, "y-stream", attn, mlp));
         if (!y_in || !y_out) return fail(SWF_ERR_NULL, "y tensors are NULL with dual-path params");
     }
-    return SWF_OK;
+    return check_activation(desc->act, "block");
 }
 
 // Fused window-block route: the packed weight images of both streams (callers without pre-packed ones), then two temporary output maps
@@ -513,7 +513,10 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
                             const swf_block_stream_params* const* next_p = nullptr, bool* ln1_ready = nullptr, int* route = nullptr) {
     // next_p / ln1_ready: see deep_block_impl; every other path ignores the planes and leaves *ln1_ready false
     // route (or nullptr; the caller zeroes it): the family and the flags of what ran, set where it is launched (swf_block_route)
-    if (desc->precision == SWF_PREC_FAST && py && window_block_supported(*desc, B, H, W)) {
+    // The fused families keep ELU(alpha = 1) inside their kernels and packed images: any other activation is one more thing they do not
+    // cover, and the block takes the generic family at its precision.
+    const bool fused_act = act_is_default(desc->act);
+    if (fused_act && desc->precision == SWF_PREC_FAST && py && window_block_supported(*desc, B, H, W)) {
         if (ln1_ready) *ln1_ready = false;
         const bool prepacked = prepacked_x && prepacked_y;   // model path: weights were packed once (swf_model_pack_weights)
         const size_t pb = window_block_packed_bytes(*desc);
@@ -553,7 +556,7 @@ static int basic_block_impl(const swf_block_desc* desc, const swf_block_stream_p
     const uintptr_t tbits = reinterpret_cast<uintptr_t>(x_in) | reinterpret_cast<uintptr_t>(y_in) | reinterpret_cast<uintptr_t>(x_out) |
                             reinterpret_cast<uintptr_t>(y_out);
     static const bool no_deep = debug_env("SWF_NO_DEEP") != nullptr;   // A/B switch for tools/profile_block.py
-    if (deep_block_supported(*desc) && !no_deep && tbits % 16 == 0 && aligned16(px) && aligned16(py)) {
+    if (fused_act && deep_block_supported(*desc) && !no_deep && tbits % 16 == 0 && aligned16(px) && aligned16(py)) {
         Carver ws(workspace, workspace_bytes);
         return deep_block_impl(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, ws, stream, prepacked_x, prepacked_y, next_p, ln1_ready, route);
     }
@@ -647,7 +650,8 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
                             int B, int H, int W, int Cin, int Cout, int mh, int mw, int wh, int ww, void* workspace,
                             size_t workspace_bytes, hipStream_t stream, int fast = 0, const void* const* prr = nullptr,
                             const swf_block_stream_params* const* first_blk = nullptr, bool* ln1_ready = nullptr,
-                            PatchTrace* trace = nullptr) {
+                            PatchTrace* trace = nullptr, const swf_activation& act = {}) {
+    // act: a non-default activation takes the generic route at the requested precision (the fused kernels hold ELU(alpha = 1))
     // prr: per-stream packed images of the register-resident kernel (pack_patch_rr; the model path has them) or nullptr
     // first_blk / ln1_ready: the parameters of the deep-level block that runs next on this workspace; when the whole-row deep patch
     // kernel runs, it also leaves that block's LN1 planes (deep_ln1_planes) and sets *ln1_ready
@@ -658,10 +662,11 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
     const int K = mh * mw * Cin;
     static const bool no_fused = debug_env("SWF_NO_FUSED_PATCH") != nullptr;   // A/B switches
     static const bool no_prr = debug_env("SWF_NO_PATCH_RR") != nullptr;
-    const bool use_prr = fast && !no_fused && !no_prr && prr && nstream == 2 && patch_rr_supported(0, Cin, Cout, mh, mw) &&
+    const bool fused_act = act_is_default(act);
+    const bool use_prr = fused_act && fast && !no_fused && !no_prr && prr && nstream == 2 && patch_rr_supported(0, Cin, Cout, mh, mw) &&
                          (int64_t)B * H * W * Cin < (int64_t(1) << 31);
-    const bool use_dp = fast && !no_fused && !use_prr && prr && deep_patch_supported(0, Cin, Cout, mh, mw) && (int64_t)B * H * W * Cin < (int64_t(1) << 31);
-    if (use_prr || use_dp || (fast && !no_fused && patch_fused_supported(K, Cout))) {   // one launch: gather -> conv -> LN -> ELU
+    const bool use_dp = fused_act && fast && !no_fused && !use_prr && prr && deep_patch_supported(0, Cin, Cout, mh, mw) && (int64_t)B * H * W * Cin < (int64_t(1) << 31);
+    if (use_prr || use_dp || (fused_act && fast && !no_fused && patch_fused_supported(K, Cout))) {   // one launch: gather -> conv -> LN -> ELU
         PatchFusedDesc d{};
         for (int s = 0; s < nstream; ++s) {
             d.in[s] = in[s]; d.out[s] = out[s]; d.skip[s] = nullptr;
@@ -709,7 +714,7 @@ static int patch_merge_impl(const swf_patch_params* const* p, int nstream, const
     }
     SWF_TRY(launch_merge_gather(pp, nstream, B, H, W, Cin, mh, mw, Hm, Wm, Ho, Wo, stream));
     SWF_TRY(launch_gemm(fast, gb, nstream, (int)N, Cout, K, K, Cout, 0, stream));
-    return launch_layernorm(lb, nstream, N, Cout, 1, stream);
+    return launch_layernorm(lb, nstream, N, Cout, Act(act), stream);
 }
 
 static int unmerge_shapes(int Hp, int Wp, int Hm, int Wm, int mh, int mw, int Hout, int Wout) {
@@ -724,7 +729,8 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
                               int Cout, int mh, int mw, int Hout, int Wout, void* workspace, size_t workspace_bytes,
                               hipStream_t stream, int fast = 0, const void* const* prr = nullptr, const char* warm = nullptr,
                               size_t warm_pb = 0, bool* warmed = nullptr, const swf_block_stream_params* const* next_blk = nullptr,
-                              bool* ln1_ready = nullptr, PatchTrace* trace = nullptr) {
+                              bool* ln1_ready = nullptr, PatchTrace* trace = nullptr, const swf_activation& act = {}) {
+    // act: as patch_merge_impl
     // next_blk / ln1_ready: the first block of the decoder stage that runs next (a deep-level stage on this workspace): the
     // column-sliced layer's second launch also leaves that block's LN1 planes (deep_ln1_planes over the output pixels)
     if (ln1_ready) *ln1_ready = false;
@@ -737,10 +743,11 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
     const bool need_crop = (Hm != Hp) || (Wm != Wp);
     static const bool no_fused = debug_env("SWF_NO_FUSED_PATCH") != nullptr;   // A/B switches
     static const bool no_prr = debug_env("SWF_NO_PATCH_RR") != nullptr;
-    const bool use_prr = fast && !no_fused && !no_prr && prr && nstream == 2 && patch_rr_supported(1, Cin, Cout, mh, mw) &&
+    const bool fused_act = act_is_default(act);
+    const bool use_prr = fused_act && fast && !no_fused && !no_prr && prr && nstream == 2 && patch_rr_supported(1, Cin, Cout, mh, mw) &&
                          (int64_t)B * Hp * Wp * Cin < (int64_t(1) << 31);
-    const bool use_dp = fast && !no_fused && !use_prr && prr && deep_patch_supported(1, Cin, Cout, mh, mw) && (int64_t)B * Hp * Wp * Cin < (int64_t(1) << 31);
-    if (use_prr || use_dp || (fast && !no_fused && patch_fused_supported(Cin, Kz))) {   // one launch: crop -> conv -> LN -> scatter -> ELU (+ skip)
+    const bool use_dp = fused_act && fast && !no_fused && !use_prr && prr && deep_patch_supported(1, Cin, Cout, mh, mw) && (int64_t)B * Hp * Wp * Cin < (int64_t(1) << 31);
+    if (use_prr || use_dp || (fused_act && fast && !no_fused && patch_fused_supported(Cin, Kz))) {   // one launch: crop -> conv -> LN -> scatter -> ELU (+ skip)
         PatchFusedDesc d{};
         for (int s = 0; s < nstream; ++s) {
             d.in[s] = in[s]; d.out[s] = out[s]; d.skip[s] = skip ? skip[s] : nullptr;
@@ -791,9 +798,9 @@ static int patch_unmerge_impl(const swf_patch_params* const* p, int nstream, con
     if (need_crop) SWF_TRY(launch_crop(cp, nstream, B, Hp, Wp, Hm, Wm, Cin, stream));
     SWF_TRY(launch_gemm(fast, gb, nstream, (int)N, Kz, Cin, Cin, Kz, 0, stream));
     if (ln_unmerge_scatter_supported(lb, sp, nstream, Cout, mh, mw))   // LN + depth-to-space + ELU (+ skip) in one launch
-        return launch_ln_unmerge_scatter(lb, sp, nstream, B, Hm, Wm, Cout, mh, mw, Hout, Wout, stream);
+        return launch_ln_unmerge_scatter(lb, sp, nstream, B, Hm, Wm, Cout, mh, mw, Hout, Wout, stream, Act(act));
     SWF_TRY(launch_layernorm(lb, nstream, N, Kz, 0, stream));
-    return launch_unmerge_scatter(sp, nstream, B, Hm, Wm, Cout, mh, mw, Hout, Wout, stream);
+    return launch_unmerge_scatter(sp, nstream, B, Hm, Wm, Cout, mh, mw, Hout, Wout, stream, Act(act));
 }
 
 // Every route of the two impls that the shape admits: the generic one in both tiers, and the deep-level kernels with the LN1 planes of
@@ -918,7 +925,7 @@ static int check_model_desc(const swf_model_desc* d) {
             return fail(SWF_ERR_BAD_SHAPE, "in_dims[%d]=%d != out_dims[%d]=%d", s, d->in_dims[s], s - 1, d->out_dims[s - 1]);
     }
     if (d->in_dims[0] != 1) return fail(SWF_ERR_UNSUPPORTED, "in_dims[0] must be 1 (single-channel IR / Y inputs, final head takes 2 channels)");
-    return SWF_OK;
+    return check_activation(d->act, "model");
 }
 
 // Layouts are cached per descriptor; the key is a canonical copy (unused levels and struct padding
@@ -931,7 +938,7 @@ static swf_model_desc canonical_desc(const swf_model_desc* d) {
     c.heads = d->heads; c.mlp_ratio = d->mlp_ratio;
     c.win_h = d->win_h; c.win_w = d->win_w; c.merge_h = d->merge_h; c.merge_w = d->merge_w;
     c.head_ksize = d->head_ksize;
-    c.precision = 0;   // the parameter layout does not depend on the arithmetic mode
+    c.precision = 0;   // the parameter layout depends on neither the arithmetic mode nor the activation
     return c;
 }
 
@@ -983,6 +990,7 @@ static swf_block_desc level_block_desc(const swf_model_desc* d, int lvl, bool en
     b.cross = 0;
     b.precision = d->precision;
     b.schedule = d->schedule;
+    b.act = d->act;
     return b;
 }
 
@@ -1013,7 +1021,7 @@ static int block_pair4_impl(const swf_block_desc* desc, const swf_block_stream_p
     {
         swf_block_desc dc = *desc;
         dc.cross = 1;
-        if (desc->precision == SWF_PREC_FAST && py && window_block_supported(dc, B, H, W) && window_block_out_of_place(dc)) {
+        if (act_is_default(dc.act) && desc->precision == SWF_PREC_FAST && py && window_block_supported(dc, B, H, W) && window_block_out_of_place(dc)) {
             Carver ws(workspace, workspace_bytes);
             const WindowBufs bufs = carve_window_block(ws, dc, (int64_t)B * H * W, packed != nullptr, true);
             if (workspace && ws.ok()) {   // (otherwise each cross block takes basic_block_impl's temporary-and-copy route, or fails there)
@@ -1233,7 +1241,7 @@ int swf_mlp_halfblock_fwd(const swf_block_desc* desc, const swf_block_stream_par
                           const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W,
                           void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     SWF_TRY(check_block(desc, px, py, x_in, y_in, x_out, y_out, B, H, W, false, true));
-    if (desc->precision == SWF_PREC_FAST) {
+    if (desc->precision == SWF_PREC_FAST && act_is_default(desc->act)) {
         const int st = mlp_half24(desc->attn.channels, desc->hidden, 0, px, py, x_in, y_in, x_out, y_out, (int64_t)B * H * W, workspace, workspace_bytes,
                                   as_stream(stream));
         if (st != SWF_ERR_UNSUPPORTED) return st;
@@ -1259,14 +1267,16 @@ size_t swf_mlp_workspace_bytes(int32_t precision, int64_t tokens, int32_t channe
     return std::max(m.bytes(), window_half_ws(channels, hidden));
 }
 
-int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in, const float* y_in,
-                float* x_out, float* y_out, int64_t tokens, int32_t channels, int32_t hidden, void* workspace, size_t workspace_bytes,
-                swf_stream_t stream) {
+int swf_mlp_fwd_act(const swf_activation* act_, int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py,
+                    const float* x_in, const float* y_in, float* x_out, float* y_out, int64_t tokens, int32_t channels, int32_t hidden,
+                    void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (precision != SWF_PREC_FP32 && precision != SWF_PREC_FAST) return fail(SWF_ERR_BAD_SHAPE, "mlp: unknown precision %d", precision);
     if (!px || !px->fc1.weight || !px->fc2.weight || !x_in || !x_out) return fail(SWF_ERR_NULL, "mlp: NULL argument");
     if (py && (!py->fc1.weight || !py->fc2.weight || !y_in || !y_out)) return fail(SWF_ERR_NULL, "mlp: NULL y-stream argument");
     if (tokens <= 0 || tokens > INT32_MAX || channels <= 0 || hidden <= 0) return fail(SWF_ERR_BAD_SHAPE, "mlp: bad sizes");
-    if (precision == SWF_PREC_FAST) {
+    SWF_TRY(check_activation(act, "mlp"));
+    if (precision == SWF_PREC_FAST && act_is_default(act)) {
         const int st = mlp_half24(channels, hidden, 1, px, py, x_in, y_in, x_out, y_out, tokens, workspace, workspace_bytes, as_stream(stream));
         if (st != SWF_ERR_UNSUPPORTED) return st;
     }
@@ -1280,10 +1290,15 @@ int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_
     const float* in[2] = {x_in, y_in};
     float* out[2] = {x_out, y_out};
     for (int s = 0; s < (py ? 2 : 1); ++s) {
-        SWF_TRY(swf_linear_fwd_prec(&pp[s]->fc1, precision, in[s], nullptr, hid, tokens, channels, hidden, 1, rest, rest_bytes, stream));
+        SWF_TRY(swf_linear_fwd_prec_act(&act, &pp[s]->fc1, precision, in[s], nullptr, hid, tokens, channels, hidden, 1, rest, rest_bytes, stream));
         SWF_TRY(swf_linear_fwd_prec(&pp[s]->fc2, precision, hid, nullptr, out[s], tokens, hidden, channels, 0, rest, rest_bytes, stream));
     }
     return SWF_OK;
+}
+int swf_mlp_fwd(int32_t precision, const swf_block_stream_params* px, const swf_block_stream_params* py, const float* x_in, const float* y_in,
+                float* x_out, float* y_out, int64_t tokens, int32_t channels, int32_t hidden, void* workspace, size_t workspace_bytes,
+                swf_stream_t stream) {
+    return swf_mlp_fwd_act(nullptr, precision, px, py, x_in, y_in, x_out, y_out, tokens, channels, hidden, workspace, workspace_bytes, stream);
 }
 
 int swf_basic_block_fwd(const swf_block_desc* desc, const swf_block_stream_params* px, const swf_block_stream_params* py,
@@ -1305,7 +1320,7 @@ int swf_basic_block_fwd_route(const swf_block_desc* desc, const swf_block_stream
 }
 
 size_t swf_basic_block_packed_bytes(const swf_block_desc* desc) {
-    if (!desc || desc->precision != SWF_PREC_FAST) return 0;
+    if (!desc || desc->precision != SWF_PREC_FAST || !act_is_default(desc->act)) return 0;
     return 2 * window_block_packed_bytes(*desc);
 }
 
@@ -1315,7 +1330,8 @@ int swf_basic_block_pack(const swf_block_desc* desc, const swf_block_stream_para
     SWF_TRY(check_stream_params(px, "x-stream", true, true));
     SWF_TRY(check_stream_params(py, "y-stream", true, true));
     const size_t pb = window_block_packed_bytes(*desc);
-    if (pb == 0 || desc->precision != SWF_PREC_FAST) return fail(SWF_ERR_UNSUPPORTED, "no fused kernel for C=%d hidden=%d", desc->attn.channels, desc->hidden);
+    if (pb == 0 || desc->precision != SWF_PREC_FAST || !act_is_default(desc->act))
+        return fail(SWF_ERR_UNSUPPORTED, "no fused kernel for C=%d hidden=%d activation kind %d", desc->attn.channels, desc->hidden, desc->act.kind);
     if (!packed || packed_bytes < 2 * pb) return fail(SWF_ERR_WORKSPACE, "packed buffer too small (need %zu B)", 2 * pb);
     return pack_window_block(*desc, *px, *py, packed, static_cast<char*>(packed) + pb, as_stream(stream));
 }
@@ -1324,7 +1340,7 @@ int swf_basic_block_fwd_packed(const swf_block_desc* desc, const void* packed, c
                                float* x_out, float* y_out, int32_t B, int32_t H, int32_t W, swf_stream_t stream) {
     if (!desc || !packed || !x_in || !y_in || !x_out || !y_out) return fail(SWF_ERR_NULL, "basic_block_fwd_packed: NULL argument");
     SWF_TRY(check_attn_desc(&desc->attn, B, H, W));
-    if (!window_block_supported(*desc, B, H, W)) return fail(SWF_ERR_UNSUPPORTED, "no fused kernel for this block shape");
+    if (!window_block_supported(*desc, B, H, W) || !act_is_default(desc->act)) return fail(SWF_ERR_UNSUPPORTED, "no fused kernel for this block shape and activation");
     const size_t pb = window_block_packed_bytes(*desc);
     return launch_window_block(*desc, packed, static_cast<const char*>(packed) + pb, x_in, y_in, x_out, y_out, B, H, W, as_stream(stream));
 }
@@ -1400,12 +1416,19 @@ size_t swf_mlp_drop_workspace_bytes(int64_t tokens, int32_t channels, int32_t hi
     return mlp_drop_ws(tokens, channels, hidden);
 }
 
-int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens, int32_t channels,
-                     int32_t hidden, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+int swf_mlp_fwd_drop_act(const swf_activation* act_, const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens,
+                         int32_t channels, int32_t hidden, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes,
+                         swf_stream_t stream) {
     if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !out) return fail(SWF_ERR_NULL, "mlp_fwd_drop: NULL argument");
     if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "mlp_fwd_drop: bad sizes");
     SWF_TRY(check_dropout(drop, "mlp_fwd_drop"));
-    return mlp_fwd_drop(*fc1, *fc2, x, out, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes, as_stream(stream));
+    const swf_activation act = act_or_default(act_);
+    SWF_TRY(check_activation(act, "mlp_fwd_drop"));
+    return mlp_fwd_drop(*fc1, *fc2, x, out, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes, as_stream(stream), act);
+}
+int swf_mlp_fwd_drop(const swf_linear* fc1, const swf_linear* fc2, const float* x, float* out, int64_t tokens, int32_t channels,
+                     int32_t hidden, const swf_dropout* drop, int32_t stream_id, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_mlp_fwd_drop_act(nullptr, fc1, fc2, x, out, tokens, channels, hidden, drop, stream_id, workspace, workspace_bytes, stream);
 }
 
 // ---- kernel families of the backward (swf_bwd_options / swf_bwd_route) -----------------------------------------------------------------
@@ -1506,16 +1529,25 @@ int swf_window_attention_bwd_opt(const swf_attn_desc* desc, const swf_attn_param
 static int mlp_bwd_entry(const char* what, bool need_drop, const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
                          const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
                          const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
-                         size_t workspace_bytes, swf_stream_t stream) {
+                         size_t workspace_bytes, swf_stream_t stream, const swf_activation* act_ = nullptr) {
+    const swf_activation act = act_or_default(act_);
     if (!fc1 || !fc2 || !fc1->weight || !fc2->weight || !x || !gout || !gx) return fail(SWF_ERR_NULL, "%s: NULL argument", what);
     if (tokens <= 0 || channels <= 0 || hidden <= 0 || stream_id < 0) return fail(SWF_ERR_BAD_SHAPE, "%s: bad sizes", what);
     if (need_drop || drop) SWF_TRY(check_dropout(drop, what));
+    SWF_TRY(check_activation(act, what));
     BwdTier tier;
     SWF_TRY(bwd_tier(opt, route, what, &tier));
     if (drop)
         return mlp_bwd_drop(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, *drop, stream_id, workspace, workspace_bytes,
-                            as_stream(stream), tier);
-    return mlp_bwd(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, workspace, workspace_bytes, as_stream(stream), tier);
+                            as_stream(stream), tier, act);
+    return mlp_bwd(*fc1, *fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, workspace, workspace_bytes, as_stream(stream), tier, act);
+}
+int swf_mlp_bwd_opt_act(const swf_activation* act, const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx,
+                        const swf_linear_grad* gfc1, const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden,
+                        const swf_dropout* drop, int32_t stream_id, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
+                        size_t workspace_bytes, swf_stream_t stream) {
+    return mlp_bwd_entry("mlp_bwd_opt", false, fc1, fc2, x, gout, gx, gfc1, gfc2, tokens, channels, hidden, drop, stream_id, opt, route, workspace,
+                         workspace_bytes, stream, act);
 }
 int swf_mlp_bwd(const swf_linear* fc1, const swf_linear* fc2, const float* x, const float* gout, float* gx, const swf_linear_grad* gfc1,
                 const swf_linear_grad* gfc2, int64_t tokens, int32_t channels, int32_t hidden, void* workspace, size_t workspace_bytes,
@@ -1568,14 +1600,23 @@ size_t swf_patch_layer_bwd_workspace_bytes(int32_t B, int32_t H, int32_t W, int3
     return patch_bwd_ws(B, H, W, Cin, Cout, merge_h, merge_w, encoder);
 }
 
+int swf_patch_layer_bwd_opt_act(const swf_activation* act_, const swf_patch_params* p, const float* in, const float* gout, float* gin,
+                                const swf_patch_grads* gp, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h,
+                                int32_t merge_w, int32_t encoder, const swf_bwd_options* opt, swf_bwd_route* route, void* workspace,
+                                size_t workspace_bytes, swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
+    if (!p || !p->conv.weight || !p->ln.gamma || !p->ln.beta || !in || !gout || !gin) return fail(SWF_ERR_NULL, "patch_layer_bwd: NULL argument");
+    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_layer_bwd: bad sizes");
+    SWF_TRY(check_activation(act, "patch_layer_bwd"));
+    BwdTier tier;
+    SWF_TRY(bwd_tier(opt, route, "patch_layer_bwd", &tier));
+    return patch_bwd(*p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, workspace, workspace_bytes, as_stream(stream), tier, act);
+}
 int swf_patch_layer_bwd_opt(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int32_t B,
                             int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t encoder,
                             const swf_bwd_options* opt, swf_bwd_route* route, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (!p || !p->conv.weight || !p->ln.gamma || !p->ln.beta || !in || !gout || !gin) return fail(SWF_ERR_NULL, "patch_layer_bwd: NULL argument");
-    if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_layer_bwd: bad sizes");
-    BwdTier tier;
-    SWF_TRY(bwd_tier(opt, route, "patch_layer_bwd", &tier));
-    return patch_bwd(*p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, workspace, workspace_bytes, as_stream(stream), tier);
+    return swf_patch_layer_bwd_opt_act(nullptr, p, in, gout, gin, gp, B, H, W, Cin, Cout, merge_h, merge_w, encoder, opt, route, workspace,
+                                       workspace_bytes, stream);
 }
 
 int swf_patch_layer_bwd(const swf_patch_params* p, const float* in, const float* gout, float* gin, const swf_patch_grads* gp, int32_t B, int32_t H,
@@ -1604,13 +1645,20 @@ int swf_final_head_batch_stats(const swf_head_params* p, const float* x, const f
     return head_batch_stats(*p, x, y, mean, var, running_mean, running_var, momentum, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
 }
 
-int swf_final_head_bwd(const swf_head_params* p, const float* x, const float* y, const float* gout, float* gx, float* gy, const swf_head_grads* gp,
-                       int32_t B, int32_t H, int32_t W, int32_t ksize, int32_t batch_stats, void* workspace, size_t workspace_bytes,
-                       swf_stream_t stream) {
+int swf_final_head_bwd_act(const swf_activation* act_, const swf_head_params* p, const float* x, const float* y, const float* gout, float* gx,
+                           float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize, int32_t batch_stats,
+                           void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (!p || !p->conv1_w || !p->conv2_w || !p->bn_gamma || !p->bn_beta || !p->bn_mean || !p->bn_var || !x || !y || !gout || !gx || !gy)
         return fail(SWF_ERR_NULL, "final_head_bwd: NULL argument");
     if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd: empty tensor");
-    return head_bwd(*p, x, y, gout, gx, gy, gp, B, H, W, ksize, batch_stats, workspace, workspace_bytes, as_stream(stream));
+    SWF_TRY(check_activation(act, "final_head_bwd"));
+    return head_bwd(*p, x, y, gout, gx, gy, gp, B, H, W, ksize, batch_stats, workspace, workspace_bytes, as_stream(stream), act);
+}
+int swf_final_head_bwd(const swf_head_params* p, const float* x, const float* y, const float* gout, float* gx, float* gy, const swf_head_grads* gp,
+                       int32_t B, int32_t H, int32_t W, int32_t ksize, int32_t batch_stats, void* workspace, size_t workspace_bytes,
+                       swf_stream_t stream) {
+    return swf_final_head_bwd_act(nullptr, p, x, y, gout, gx, gy, gp, B, H, W, ksize, batch_stats, workspace, workspace_bytes, stream);
 }
 
 // The head's BatchNorm over a batch that spans several calls or ranks: the entries above, split where the per-channel sums exist.
@@ -1633,24 +1681,38 @@ int swf_final_head_stats_finish(const float* sums, size_t sums_bytes, int64_t co
     return head_stats_finish(sums, count, pass, mean, var, running_mean, running_var, momentum, as_stream(stream));
 }
 
-int swf_final_head_bwd_sums(const swf_head_params* p, const float* x, const float* y, const float* gout, float* sums_out, int32_t B, int32_t H,
-                            int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+int swf_final_head_bwd_sums_act(const swf_activation* act_, const swf_head_params* p, const float* x, const float* y, const float* gout,
+                                float* sums_out, int32_t B, int32_t H, int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes,
+                                swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (!p || !p->conv1_w || !p->conv2_w || !p->bn_gamma || !p->bn_beta || !p->bn_mean || !p->bn_var || !x || !y || !gout || !sums_out)
         return fail(SWF_ERR_NULL, "final_head_bwd_sums: NULL argument");
     if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_sums: empty tensor");
-    return head_bwd_sums(*p, x, y, gout, sums_out, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
+    SWF_TRY(check_activation(act, "final_head_bwd_sums"));
+    return head_bwd_sums(*p, x, y, gout, sums_out, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream), act);
+}
+int swf_final_head_bwd_sums(const swf_head_params* p, const float* x, const float* y, const float* gout, float* sums_out, int32_t B, int32_t H,
+                            int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_final_head_bwd_sums_act(nullptr, p, x, y, gout, sums_out, B, H, W, ksize, workspace, workspace_bytes, stream);
 }
 
-int swf_final_head_bwd_synced(const swf_head_params* p, const float* x, const float* y, const float* gout, const float* sums, int64_t count,
-                              float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize, void* workspace,
-                              size_t workspace_bytes, swf_stream_t stream) {
+int swf_final_head_bwd_synced_act(const swf_activation* act_, const swf_head_params* p, const float* x, const float* y, const float* gout,
+                                  const float* sums, int64_t count, float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H,
+                                  int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (!p || !p->conv1_w || !p->conv2_w || !p->bn_gamma || !p->bn_beta || !p->bn_mean || !p->bn_var || !x || !y || !gout || !sums || !gx || !gy)
         return fail(SWF_ERR_NULL, "final_head_bwd_synced: NULL argument");
     if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_synced: empty tensor");
     if (count < (int64_t)B * H * W)
         return fail(SWF_ERR_BAD_SHAPE, "final_head_bwd_synced: a whole batch of %lld elements is smaller than this call's %lld", (long long)count,
                     (long long)B * H * W);
-    return head_bwd_apply(*p, x, y, gout, sums, count, gx, gy, gp, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream));
+    SWF_TRY(check_activation(act, "final_head_bwd_synced"));
+    return head_bwd_apply(*p, x, y, gout, sums, count, gx, gy, gp, B, H, W, ksize, workspace, workspace_bytes, as_stream(stream), act);
+}
+int swf_final_head_bwd_synced(const swf_head_params* p, const float* x, const float* y, const float* gout, const float* sums, int64_t count,
+                              float* gx, float* gy, const swf_head_grads* gp, int32_t B, int32_t H, int32_t W, int32_t ksize, void* workspace,
+                              size_t workspace_bytes, swf_stream_t stream) {
+    return swf_final_head_bwd_synced_act(nullptr, p, x, y, gout, sums, count, gx, gy, gp, B, H, W, ksize, workspace, workspace_bytes, stream);
 }
 
 int swf_add_fwd(const float* a, const float* b, float* out, int64_t count, swf_stream_t stream) {
@@ -1671,14 +1733,14 @@ int swf_block_pair4_fwd(const swf_block_desc* desc, const swf_block_stream_param
 // ---- one stage as the model runs it: images packed at the front of the workspace, then block_pair4_impl on the rest ----------------
 // Bytes of ONE image of the stage (0: this shape, tier and stream count run without images).  The window kernels need two streams.
 static size_t stage_image_bytes(const swf_block_desc& d, int nstream) {
-    if (d.precision != SWF_PREC_FAST) return 0;
+    if (d.precision != SWF_PREC_FAST || !act_is_default(d.act)) return 0;
     if (window_block_packed_bytes(d)) return nstream == 2 ? window_block_packed_bytes(d) : 0;
     return deep_block_packed_bytes(d);
 }
 // What block_pair4_impl and its four blocks carve when they run from images: a window-kernel stage only the two temporary maps of a
 // kernel that cannot run a cross block in place; every other stage what its largest block needs.
 static size_t stage_inner_ws(const swf_block_desc& d, int nstream, int B, int H, int W) {
-    if (d.precision == SWF_PREC_FAST && nstream == 2 && window_block_supported(d, B, H, W)) {
+    if (act_is_default(d.act) && d.precision == SWF_PREC_FAST && nstream == 2 && window_block_supported(d, B, H, W)) {
         Carver m = Carver::measure();
         carve_window_block(m, d, (int64_t)B * H * W, true, window_block_out_of_place(d));
         return m.bytes();
@@ -1767,29 +1829,44 @@ size_t swf_patch_workspace_bytes(int32_t B, int32_t H, int32_t W, int32_t Cin, i
     return unmerge_ws_any_crop(1, B, H, W, Cin, Cout, merge_h, merge_w);
 }
 
-int swf_patch_merge_fwd(const swf_patch_params* p, const float* in, float* out, int32_t B, int32_t H, int32_t W, int32_t Cin,
-                        int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, void* workspace,
-                        size_t workspace_bytes, swf_stream_t stream) {
+int swf_patch_merge_fwd_act(const swf_activation* act_, const swf_patch_params* p, const float* in, float* out, int32_t B, int32_t H, int32_t W,
+                            int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, void* workspace,
+                            size_t workspace_bytes, swf_stream_t stream) {
     if (!p || !in || !out || !p->conv.weight || !p->ln.gamma || !p->ln.beta) return fail(SWF_ERR_NULL, "patch_merge: NULL argument");
     if (B <= 0 || Cin <= 0 || Cout <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_merge: non-positive dims");
+    const swf_activation act = act_or_default(act_);
+    SWF_TRY(check_activation(act, "patch_merge"));
     const swf_patch_params* pp[2] = {p, nullptr};
     const float* ins[2] = {in, nullptr};
     float* outs[2] = {out, nullptr};
     return patch_merge_impl(pp, 1, ins, outs, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w, workspace, workspace_bytes,
-                            as_stream(stream));
+                            as_stream(stream), 0, nullptr, nullptr, nullptr, nullptr, act);
+}
+int swf_patch_merge_fwd(const swf_patch_params* p, const float* in, float* out, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                        int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, void* workspace,
+                        size_t workspace_bytes, swf_stream_t stream) {
+    return swf_patch_merge_fwd_act(nullptr, p, in, out, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w, workspace, workspace_bytes, stream);
 }
 
-int swf_patch_unmerge_fwd(const swf_patch_params* p, const float* in, const float* skip, float* out, int32_t B, int32_t Hp,
-                          int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w,
-                          int32_t Hout, int32_t Wout, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+int swf_patch_unmerge_fwd_act(const swf_activation* act_, const swf_patch_params* p, const float* in, const float* skip, float* out, int32_t B,
+                              int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w,
+                              int32_t Hout, int32_t Wout, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
     if (!p || !in || !out || !p->conv.weight || !p->ln.gamma || !p->ln.beta) return fail(SWF_ERR_NULL, "patch_unmerge: NULL argument");
     if (B <= 0 || Cin <= 0 || Cout <= 0 || merge_h <= 0 || merge_w <= 0) return fail(SWF_ERR_BAD_SHAPE, "patch_unmerge: non-positive dims");
+    const swf_activation act = act_or_default(act_);
+    SWF_TRY(check_activation(act, "patch_unmerge"));
     const swf_patch_params* pp[2] = {p, nullptr};
     const float* ins[2] = {in, nullptr};
     const float* sk[2] = {skip, nullptr};
     float* outs[2] = {out, nullptr};
     return patch_unmerge_impl(pp, 1, ins, skip ? sk : nullptr, outs, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout,
-                              workspace, workspace_bytes, as_stream(stream));
+                              workspace, workspace_bytes, as_stream(stream), 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr, act);
+}
+int swf_patch_unmerge_fwd(const swf_patch_params* p, const float* in, const float* skip, float* out, int32_t B, int32_t Hp,
+                          int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w,
+                          int32_t Hout, int32_t Wout, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_patch_unmerge_fwd_act(nullptr, p, in, skip, out, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout, workspace,
+                                     workspace_bytes, stream);
 }
 
 // ---- the pair of patch layers of one stage with the arithmetic tier as an argument -------------------------------------------------
@@ -1861,13 +1938,15 @@ size_t swf_patch_unmerge_prec_workspace_bytes(int32_t precision, int32_t dual, i
     return unmerge_prec_ws(precision, dual ? 2 : 1, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout);
 }
 
-int swf_patch_merge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in, const float* y_in,
-                             float* x_out, float* y_out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h,
-                             int32_t merge_w, int32_t win_h, int32_t win_w, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y,
-                             int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream_) {
+int swf_patch_merge_fwd_prec_act(const swf_activation* act_, int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                                 const float* x_in, const float* y_in, float* x_out, float* y_out, int32_t B, int32_t H, int32_t W, int32_t Cin,
+                                 int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t win_h, int32_t win_w, const swf_patch_ln1* ln1_x,
+                                 const swf_patch_ln1* ln1_y, int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream_) {
     SWF_TRY(check_patch_prec("patch_merge_prec", precision, px, py, x_in, y_in, x_out, y_out, ln1_x, ln1_y, B, Cin, Cout, merge_h, merge_w));
     int Hm, Wm, Ho, Wo;
     SWF_TRY(merge_shapes(H, W, merge_h, merge_w, win_h, win_w, &Hm, &Wm, &Ho, &Wo));
+    const swf_activation act = act_or_default(act_);
+    SWF_TRY(check_activation(act, "patch_merge_prec"));
     const int nstream = py ? 2 : 1, fast = precision == SWF_PREC_FAST;
     const size_t image = fast ? patch_image_bytes(0, Cin, Cout, merge_h, merge_w) : 0;
     Carver ws(workspace, workspace_bytes);
@@ -1887,18 +1966,27 @@ int swf_patch_merge_fwd_prec(int32_t precision, const swf_patch_params* px, cons
     bool ln1_ready = false;
     PatchTrace tr{};
     SWF_TRY(patch_merge_impl(pp, nstream, ins, outs, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w, bufs.inner, bufs.inner_bytes, stream,
-                             fast, image ? bufs.packed : nullptr, ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr));
+                             fast, image ? bufs.packed : nullptr, ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr, act));
     return finish_patch_prec("patch_merge_prec", tr, ln, nstream, (size_t)B * Ho * Wo * Cout * sizeof(bf16_raw), route, stream);
 }
+int swf_patch_merge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in, const float* y_in,
+                             float* x_out, float* y_out, int32_t B, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t merge_h,
+                             int32_t merge_w, int32_t win_h, int32_t win_w, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y,
+                             int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_patch_merge_fwd_prec_act(nullptr, precision, px, py, x_in, y_in, x_out, y_out, B, H, W, Cin, Cout, merge_h, merge_w, win_h, win_w,
+                                        ln1_x, ln1_y, route, workspace, workspace_bytes, stream);
+}
 
-int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in,
-                               const float* y_in, const float* x_skip, const float* y_skip, float* x_out, float* y_out, int32_t B, int32_t Hp,
-                               int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t Hout,
-                               int32_t Wout, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route, void* workspace,
-                               size_t workspace_bytes, swf_stream_t stream_) {
+int swf_patch_unmerge_fwd_prec_act(const swf_activation* act_, int32_t precision, const swf_patch_params* px, const swf_patch_params* py,
+                                   const float* x_in, const float* y_in, const float* x_skip, const float* y_skip, float* x_out, float* y_out,
+                                   int32_t B, int32_t Hp, int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h,
+                                   int32_t merge_w, int32_t Hout, int32_t Wout, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y,
+                                   int32_t* route, void* workspace, size_t workspace_bytes, swf_stream_t stream_) {
+    const swf_activation act = act_or_default(act_);
     SWF_TRY(check_patch_prec("patch_unmerge_prec", precision, px, py, x_in, y_in, x_out, y_out, ln1_x, ln1_y, B, Cin, Cout, merge_h, merge_w));
     if (py && (x_skip != nullptr) != (y_skip != nullptr)) return fail(SWF_ERR_NULL, "patch_unmerge_prec: skip is given for every stream or for none");
     SWF_TRY(unmerge_shapes(Hp, Wp, Hm, Wm, merge_h, merge_w, Hout, Wout));
+    SWF_TRY(check_activation(act, "patch_unmerge_prec"));
     const int nstream = py ? 2 : 1, fast = precision == SWF_PREC_FAST;
     const size_t image = fast ? patch_image_bytes(1, Cin, Cout, merge_h, merge_w) : 0;
     Carver ws(workspace, workspace_bytes);
@@ -1920,33 +2008,56 @@ int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, co
     PatchTrace tr{};
     SWF_TRY(patch_unmerge_impl(pp, nstream, ins, x_skip ? sk : nullptr, outs, B, Hp, Wp, Hm, Wm, Cin, Cout, merge_h, merge_w, Hout, Wout,
                                bufs.inner, bufs.inner_bytes, stream, fast, image ? bufs.packed : nullptr, nullptr, 0, nullptr,
-                               ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr));
+                               ln[0] ? blkp : nullptr, ln[0] ? &ln1_ready : nullptr, &tr, act));
     return finish_patch_prec("patch_unmerge_prec", tr, ln, nstream, (size_t)B * Hout * Wout * Cout * sizeof(bf16_raw), route, stream);
+}
+int swf_patch_unmerge_fwd_prec(int32_t precision, const swf_patch_params* px, const swf_patch_params* py, const float* x_in,
+                               const float* y_in, const float* x_skip, const float* y_skip, float* x_out, float* y_out, int32_t B, int32_t Hp,
+                               int32_t Wp, int32_t Hm, int32_t Wm, int32_t Cin, int32_t Cout, int32_t merge_h, int32_t merge_w, int32_t Hout,
+                               int32_t Wout, const swf_patch_ln1* ln1_x, const swf_patch_ln1* ln1_y, int32_t* route, void* workspace,
+                               size_t workspace_bytes, swf_stream_t stream) {
+    return swf_patch_unmerge_fwd_prec_act(nullptr, precision, px, py, x_in, y_in, x_skip, y_skip, x_out, y_out, B, Hp, Wp, Hm, Wm, Cin, Cout,
+                                          merge_h, merge_w, Hout, Wout, ln1_x, ln1_y, route, workspace, workspace_bytes, stream);
 }
 
 static float* carve_head_fwd(Carver& ws, int B, int H, int W) { return ws.floats((int64_t)B * H * W * 2); }   // conv1's two channels
 
-int swf_final_head_fwd(const swf_head_params* p, const float* x, const float* y, float* out, int32_t B, int32_t H, int32_t W,
-                       int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+int swf_final_head_fwd_act(const swf_activation* act_, const swf_head_params* p, const float* x, const float* y, float* out, int32_t B, int32_t H,
+                           int32_t W, int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (!p || !x || !y || !out) return fail(SWF_ERR_NULL, "final_head: NULL argument");
     if (B <= 0 || H <= 0 || W <= 0) return fail(SWF_ERR_BAD_SHAPE, "final_head: empty tensor");
     if (ksize <= 0 || ksize % 2 == 0) return fail(SWF_ERR_UNSUPPORTED, "final_head: even kernel size %d", ksize);
     if (ksize / 2 >= H || ksize / 2 >= W) return fail(SWF_ERR_PAD, "final_head: reflect pad %d >= map %dx%d", ksize / 2, H, W);
+    SWF_TRY(check_activation(act, "final_head"));
     Carver ws(workspace, workspace_bytes);
     float* tmp = carve_head_fwd(ws, B, H, W);
     // no size query: swinfuse.h documents 2*B*H*W floats, so exactly that many bytes are enough, aligned or not
     if (!workspace || ws.used > workspace_bytes) return fail(SWF_ERR_WORKSPACE, "final_head workspace too small (need %zu B)", ws.used);
-    return launch_head(x, y, tmp, out, *p, B, H, W, ksize, as_stream(stream));
+    return launch_head(x, y, tmp, out, *p, B, H, W, ksize, as_stream(stream), Act(act));
+}
+int swf_final_head_fwd(const swf_head_params* p, const float* x, const float* y, float* out, int32_t B, int32_t H, int32_t W,
+                       int32_t ksize, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_final_head_fwd_act(nullptr, p, x, y, out, B, H, W, ksize, workspace, workspace_bytes, stream);
 }
 
-int swf_linear_fwd(const swf_linear* lin, const float* in, const float* residual, float* out, int64_t tokens, int32_t n_in,
-                   int32_t n_out, int32_t act, swf_stream_t stream) {
+// `act` (0 / 1) says whether the activation `fn` is applied at all
+static Act linear_act(int act, const swf_activation& fn) { return act ? Act(fn) : Act(0); }
+
+int swf_linear_fwd_act(const swf_activation* act_fn, const swf_linear* lin, const float* in, const float* residual, float* out, int64_t tokens,
+                       int32_t n_in, int32_t n_out, int32_t act, swf_stream_t stream) {
+    const swf_activation fn = act_or_default(act_fn);
     if (!lin || !lin->weight || !in || !out) return fail(SWF_ERR_NULL, "linear: NULL argument");
     if (tokens <= 0 || tokens > INT32_MAX || n_in <= 0 || n_out <= 0) return fail(SWF_ERR_BAD_SHAPE, "linear: bad sizes");
     if (act != 0 && act != 1) return fail(SWF_ERR_UNSUPPORTED, "linear: activation %d", act);
+    SWF_TRY(check_activation(fn, "linear"));
     GemmBatch gb{};
     gb.p[0] = GemmProb{in, lin->weight, lin->bias, residual, out};
-    return launch_gemm_f32(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, act, as_stream(stream));
+    return launch_gemm_f32(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, linear_act(act, fn), as_stream(stream));
+}
+int swf_linear_fwd(const swf_linear* lin, const float* in, const float* residual, float* out, int64_t tokens, int32_t n_in,
+                   int32_t n_out, int32_t act, swf_stream_t stream) {
+    return swf_linear_fwd_act(nullptr, lin, in, residual, out, tokens, n_in, n_out, act, stream);
 }
 
 static GemmBatch carve_linear(Carver& ws, int64_t tokens, int32_t n_in, int32_t n_out) {   // fast tier: the split-K partials
@@ -1963,26 +2074,39 @@ size_t swf_linear_workspace_bytes(int32_t precision, int64_t tokens, int32_t n_i
     return m.bytes();
 }
 
-int swf_linear_fwd_prec(const swf_linear* lin, int32_t precision, const float* in, const float* residual, float* out, int64_t tokens,
-                        int32_t n_in, int32_t n_out, int32_t act, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
-    if (precision == SWF_PREC_FP32) return swf_linear_fwd(lin, in, residual, out, tokens, n_in, n_out, act, stream);
+int swf_linear_fwd_prec_act(const swf_activation* act_fn, const swf_linear* lin, int32_t precision, const float* in, const float* residual,
+                            float* out, int64_t tokens, int32_t n_in, int32_t n_out, int32_t act, void* workspace, size_t workspace_bytes,
+                            swf_stream_t stream) {
+    if (precision == SWF_PREC_FP32) return swf_linear_fwd_act(act_fn, lin, in, residual, out, tokens, n_in, n_out, act, stream);
+    const swf_activation fn = act_or_default(act_fn);
     if (precision != SWF_PREC_FAST) return fail(SWF_ERR_BAD_SHAPE, "linear: unknown precision %d", precision);
     if (!lin || !lin->weight || !in || !out) return fail(SWF_ERR_NULL, "linear: NULL argument");
     if (tokens <= 0 || tokens > INT32_MAX || n_in <= 0 || n_out <= 0) return fail(SWF_ERR_BAD_SHAPE, "linear: bad sizes");
     if (act != 0 && act != 1) return fail(SWF_ERR_UNSUPPORTED, "linear: activation %d", act);
+    SWF_TRY(check_activation(fn, "linear"));
     Carver ws(workspace, workspace_bytes);
     GemmBatch gb = carve_linear(ws, tokens, n_in, n_out);
     if (!ws.ok()) return fail(SWF_ERR_WORKSPACE, "linear: workspace too small (need %zu B)", ws.bytes());
     gb.p[0] = GemmProb{in, lin->weight, lin->bias, residual, out};
-    return launch_gemm_bf16x3(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, act, as_stream(stream));
+    return launch_gemm_bf16x3(gb, 1, (int)tokens, n_out, n_in, n_in, n_out, linear_act(act, fn), as_stream(stream));
+}
+int swf_linear_fwd_prec(const swf_linear* lin, int32_t precision, const float* in, const float* residual, float* out, int64_t tokens,
+                        int32_t n_in, int32_t n_out, int32_t act, void* workspace, size_t workspace_bytes, swf_stream_t stream) {
+    return swf_linear_fwd_prec_act(nullptr, lin, precision, in, residual, out, tokens, n_in, n_out, act, workspace, workspace_bytes, stream);
 }
 
-int swf_layernorm_fwd(const swf_norm* ln, const float* in, float* out, int64_t tokens, int32_t C, int32_t elu, swf_stream_t stream) {
+int swf_layernorm_fwd_act(const swf_activation* act_, const swf_norm* ln, const float* in, float* out, int64_t tokens, int32_t C, int32_t elu,
+                          swf_stream_t stream) {
+    const swf_activation act = act_or_default(act_);
     if (!ln || !ln->gamma || !ln->beta || !in || !out) return fail(SWF_ERR_NULL, "layernorm: NULL argument");
     if (tokens <= 0 || C <= 0) return fail(SWF_ERR_BAD_SHAPE, "layernorm: bad sizes");
+    SWF_TRY(check_activation(act, "layernorm"));
     LnBatch lb{};
     lb.p[0] = LnProb{in, out, ln->gamma, ln->beta};
-    return launch_layernorm(lb, 1, tokens, C, elu ? 1 : 0, as_stream(stream));
+    return launch_layernorm(lb, 1, tokens, C, linear_act(elu, act), as_stream(stream));
+}
+int swf_layernorm_fwd(const swf_norm* ln, const float* in, float* out, int64_t tokens, int32_t C, int32_t elu, swf_stream_t stream) {
+    return swf_layernorm_fwd_act(nullptr, ln, in, out, tokens, C, elu, stream);
 }
 
 int swf_reflect_pad_fwd(const float* in, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t pad_h, int32_t pad_w,
@@ -2072,7 +2196,7 @@ size_t swf_model_workspace_bytes(const swf_model_desc* desc, int32_t B, int32_t 
 }
 
 size_t swf_model_packed_bytes(const swf_model_desc* desc) {
-    if (check_model_desc(desc) != SWF_OK) return 0;
+    if (check_model_desc(desc) != SWF_OK || !act_is_default(desc->act)) return 0;   // (no image is read for another activation)
     return packed_plan(desc).total;
 }
 
@@ -2080,7 +2204,7 @@ int swf_model_pack_weights(const swf_model_desc* desc, const float* arena, void*
     SWF_TRY(check_model_desc(desc));
     if (!arena) return fail(SWF_ERR_NULL, "model_pack_weights: NULL arena");
     const PackedPlan plan = packed_plan(desc);
-    if (plan.total == 0) return SWF_OK;
+    if (plan.total == 0 || !act_is_default(desc->act)) return SWF_OK;
     if (!packed || packed_bytes < plan.total) return fail(SWF_ERR_WORKSPACE, "packed buffer too small (need %zu B)", plan.total);
     const ModelLayout* L = get_layout(desc);
     hipStream_t stream = as_stream(stream_);
@@ -2131,6 +2255,7 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
     // marks (swf_model_forward_profiled): 4 * levels + 2 events, recorded on the stream at the start and after every segment
     SWF_TRY(check_model_desc(desc));
     const PackedPlan plan = packed_plan(desc);
+    if (!act_is_default(desc->act)) packed = nullptr;   // every level runs the generic family: the images are not read
     if (!arena || !ir || !vis || !out) return fail(SWF_ERR_NULL, "model_forward: NULL tensor");
     if (B <= 0) return fail(SWF_ERR_BAD_SHAPE, "model_forward: empty batch");
     LevelShape ls[SWF_MAX_LEVELS];
@@ -2167,7 +2292,8 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
         ln1_carry = false;
         SWF_TRY(patch_merge_impl(pmp, 2, cur, bufs.act[s], B, ls[s].Hin, ls[s].Win, desc->in_dims[s], desc->out_dims[s], desc->merge_h,
                                  desc->merge_w, desc->win_h, desc->win_w, bufs.scratch, bufs.scratch_bytes, stream, desc->precision == SWF_PREC_FAST,
-                                 (packed && plan.penc_b[s]) ? prr_enc : nullptr, deep_stage ? first_blk : nullptr, deep_stage ? &ln1_carry : nullptr));
+                                 (packed && plan.penc_b[s]) ? prr_enc : nullptr, deep_stage ? first_blk : nullptr, deep_stage ? &ln1_carry : nullptr,
+                                 nullptr, desc->act));
         SWF_TRY(mark());
         // the first block of the next fused-kernel stage is warmed by this stage's last block
         const char* after = nullptr;
@@ -2227,7 +2353,7 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
                                    desc->out_dims[lvl], desc->in_dims[lvl], desc->merge_h, desc->merge_w, ls[lvl].Hin, ls[lvl].Win,
                                    bufs.scratch, bufs.scratch_bytes, stream, desc->precision == SWF_PREC_FAST, (packed && plan.pdec_b[j]) ? prr_dec : nullptr,
                                    warm_next ? after : nullptr, warm_next ? after_pb : 0, &warmed, next_deep ? next_first : nullptr,
-                                   next_deep ? &ln1_carry : nullptr));
+                                   next_deep ? &ln1_carry : nullptr, nullptr, desc->act));
         if (warm_next && !warmed) SWF_TRY(launch_l2_warm(after, 2 * after_pb, stream));
         SWF_TRY(mark());
     }
@@ -2235,7 +2361,7 @@ static int model_forward_impl(const swf_model_desc* desc, const float* arena, co
                        arena + L->h_c2w, arena + L->h_c2b};
     Carver hw(bufs.scratch, bufs.scratch_bytes);
     float* tmp = carve_head_fwd(hw, B, H, W);
-    SWF_TRY(launch_head(bufs.full[0], bufs.full[1], tmp, out, hp, B, H, W, desc->head_ksize, stream));
+    SWF_TRY(launch_head(bufs.full[0], bufs.full[1], tmp, out, hp, B, H, W, desc->head_ksize, stream, Act(desc->act)));
     return mark();
 }
 

@@ -194,10 +194,34 @@ def _norm(mod: nn.LayerNorm) -> L.Norm:
     return L.Norm(_ptr(mod.weight), _ptr(mod.bias))
 
 
-def _require_elu(act: nn.Module) -> None:
-    if not isinstance(act, nn.ELU) or float(act.alpha) != 1.0:
-        raise NotImplementedError("the HIP kernels implement the reference's configured activation, "
-                                  f"nn.ELU(alpha=1) (A000_CONFIG.py:64); got {act!r}")
+SUPPORTED_ACTIVATIONS = ("nn.ELU(alpha)", "nn.ReLU()", "nn.LeakyReLU(negative_slope)", 'nn.GELU(approximate="none")',
+                         'nn.GELU(approximate="tanh")', "nn.SiLU()")
+
+
+def _activation_of(act: nn.Module) -> Tuple[int, float]:
+    """(kind, param) of swf_activation for `mlp_activation_func` / `activation_func` (the reference's MLP_ACTIVATION_FUNC,
+    A000_CONFIG.py:64), as torch.nn defines each; `inplace` is ignored.  nn.ELU(alpha=1), the reference's default, is kind 0 and the only
+    one the fused fast-tier kernels run; every other one takes the generic family at the requested precision.  Exact types
+    only: a subclass may compute something else.  Anything else, or a non-finite parameter, raises NotImplementedError."""
+    kind = None
+    if type(act) is nn.ELU:
+        alpha = float(act.alpha)
+        kind = (L.ACT_ELU1, 0.0) if alpha == 1.0 else (L.ACT_ELU, alpha)
+    elif type(act) is nn.ReLU:
+        kind = (L.ACT_RELU, 0.0)
+    elif type(act) is nn.LeakyReLU:
+        kind = (L.ACT_LEAKY_RELU, float(act.negative_slope))
+    elif type(act) is nn.GELU and act.approximate in ("none", "tanh"):
+        kind = (L.ACT_GELU if act.approximate == "none" else L.ACT_GELU_TANH, 0.0)
+    elif type(act) is nn.SiLU:
+        kind = (L.ACT_SILU, 0.0)
+    if kind is None or not math.isfinite(kind[1]):
+        raise NotImplementedError(f"the HIP kernels implement {', '.join(SUPPORTED_ACTIVATIONS)} with a finite parameter; got {act!r}")
+    return kind
+
+
+def _act(act: nn.Module) -> L.Activation:
+    return L.Activation(*_activation_of(act))
 
 
 def _schedule_code(s) -> int:
@@ -519,13 +543,14 @@ class AutoPathMLP(_FwdAlias, _BackwardTier, nn.Module):
         swf_mlp_fwd call whichever it is; with dropout one swf_mlp_fwd_drop call per stream (exact fp32; mask stream 0 for x, 1 for y,
         one seed for both)."""
         b, c, h, w = x.shape
-        lib, n, hid, dev = L.lib(), b * h * w, self.hidden_dims, x.device
+        lib, n, hid, dev, act = L.lib(), b * h * w, self.hidden_dims, x.device, _act(self.activation_func)
         if drop is None:
             xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
             prec = _precision_code(self.precision)
             px, py = self._params(s), (self._params("y") if dual else None)
             ws, wsn = _workspace(lib.swf_mlp_workspace_bytes(prec, n, c, hid), dev)
-            L.check(lib.swf_mlp_fwd(prec, _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), n, c, hid, ws, wsn, _stream(dev)))
+            L.check(lib.swf_mlp_fwd_act(C.byref(act), prec, _ref(px), _ref(py), _ptr(xn), _ptr(yn), _ptr(ox), _ptr(oy), n, c, hid, ws, wsn,
+                                        _stream(dev)))
             return _nchw_out(ox, oy)
         outs = []
         for name, t in (("x", x), ("y", y)) if dual else ((s, x),):
@@ -533,8 +558,8 @@ class AutoPathMLP(_FwdAlias, _BackwardTier, nn.Module):
             out = torch.empty_like(tn)
             f1, f2 = self._fcs(name)
             ws, wsn = _workspace(lib.swf_mlp_drop_workspace_bytes(n, c, hid), dev)
-            L.check(lib.swf_mlp_fwd_drop(C.byref(f1), C.byref(f2), _ptr(tn), _ptr(out), n, c, hid, C.byref(drop), _MASK_STREAM[name],
-                                         ws, wsn, _stream(dev)))
+            L.check(lib.swf_mlp_fwd_drop_act(C.byref(act), C.byref(f1), C.byref(f2), _ptr(tn), _ptr(out), n, c, hid, C.byref(drop),
+                                             _MASK_STREAM[name], ws, wsn, _stream(dev)))
             outs.append(_to_nchw(out))
         return tuple(outs) if dual else outs[0]
 
@@ -553,8 +578,9 @@ class AutoPathMLP(_FwdAlias, _BackwardTier, nn.Module):
         size = lib.swf_mlp_bwd_workspace_bytes if drop is None else lib.swf_mlp_drop_workspace_bytes
         ws, wsn = _workspace(size(n, c, hid), dev)
         route = L.BwdRoute()
-        L.check(lib.swf_mlp_bwd_opt(C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c, hid,
-                                    _ref(drop), _MASK_STREAM[s], C.byref(opt), C.byref(route), ws, wsn, _stream(dev)))
+        act = _act(self.activation_func)
+        L.check(lib.swf_mlp_bwd_opt_act(C.byref(act), C.byref(f1), C.byref(f2), _ptr(xn), _ptr(gn), _ptr(gx), C.byref(gf1), C.byref(gf2), n, c,
+                                        hid, _ref(drop), _MASK_STREAM[s], C.byref(opt), C.byref(route), ws, wsn, _stream(dev)))
         self.last_backward_route = route
         return _to_nchw(gx), g1w, g1b, g2w, g2b
 
@@ -569,11 +595,10 @@ class AutoPathMLP(_FwdAlias, _BackwardTier, nn.Module):
         drop = _dropout(self, 0.0, 0.0, self.drop_ratio)
         dual = self.use_dual_path or y is not None
         if _wants_grad(self, x, y):
-            _require_elu(self.activation_func)
+            _activation_of(self.activation_func)
             ox = self._one_grad(x, "x", drop)
             return (ox, self._one_grad(y, "y", drop)) if dual else ox
         _check_4d(x, y)
-        _require_elu(self.activation_func)
         return self._fwd(drop, x, y, dual)
 
 
@@ -626,8 +651,7 @@ class AddAndLayerNormWithOtherModule(_FwdAlias, nn.Module):
         xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
         lib, prec = L.lib(), _precision_code(self.precision)
         if mlp:
-            _require_elu(om.activation_func)
-            desc = L.BlockDesc(L.AttnDesc(om.in_out_dims, 1, 1, 1, 1, 0), om.hidden_dims, 0, prec)
+            desc = L.BlockDesc(L.AttnDesc(om.in_out_dims, 1, 1, 1, 1, 0), om.hidden_dims, 0, prec, 0, _act(om.activation_func))
             entry = lib.swf_mlp_halfblock_fwd
         else:
             desc = L.BlockDesc(om.window_attention_x._desc(), 1, int(bool(om.use_cross_att)), prec)
@@ -708,10 +732,10 @@ class BasicBlock(_FwdAlias, _BackwardTier, nn.Module):
 
     def _desc(self, precision) -> L.BlockDesc:
         return L.BlockDesc(self.auto_path_win_att.window_attention_x._desc(), self.mlp_hidden_dims,
-                           int(bool(self.use_cross_attr)), _precision_code(precision), _schedule_code(self.schedule))
+                           int(bool(self.use_cross_attr)), _precision_code(precision), _schedule_code(self.schedule),
+                           _act(self.mlp_activation_func))
 
     def _stream_params(self, s: str) -> L.BlockStreamParams:
-        _require_elu(self.mlp_activation_func)
         return self.stage_2._fill(self.stage_1._fill(L.BlockStreamParams(), s), s)
 
     # ---- training side (first stage): the block under torch.autograd --------------------------------------------
@@ -789,7 +813,7 @@ class BasicBlock(_FwdAlias, _BackwardTier, nn.Module):
         _check_4d(x, y)
         if _wants_grad(self, x, y):
             # autograd path: forward through the library as usual, backward through swf_basic_block_bwd (kernels_bwd.hip)
-            _require_elu(self.mlp_activation_func)
+            _activation_of(self.mlp_activation_func)
             self.check_input_compatibility_with_option(x=x, y=y)
             streams = ("x", "y") if dual else ("x",)
             params = [t for s in streams for t in self._grad_tensors(s)]
@@ -871,7 +895,7 @@ class SelfAndCrossBlockPair(_FwdAlias, nn.Module):
         b, c, h, w = x.shape
         xn, yn, ox, oy = _nhwc_in_out(x, y, dual)
         desc = blocks[0]._desc(self.precision)
-        desc.schedule = sched
+        desc.schedule, desc.act = sched, _act(self.mlp_activation_func)
         px = (L.BlockStreamParams * 4)(*[blk._stream_params("x") for blk in blocks])
         py = (L.BlockStreamParams * 4)(*[blk._stream_params("y") for blk in blocks]) if dual else None
         lib = L.lib()
@@ -1034,8 +1058,10 @@ class _PatchLayerFunction(torch.autograd.Function):
             lib, enc = L.lib(), int(layer.belongs_to_encoder)
             ws, wsn = _workspace(lib.swf_patch_layer_bwd_workspace_bytes(b, h, w, layer.in_dims, layer.out_dims, mh, mw, enc), dev)
             route = L.BwdRoute()
-            L.check(lib.swf_patch_layer_bwd_opt(C.byref(prm), _ptr(tn), _ptr(gn), _ptr(gin), C.byref(grads), b, h, w, layer.in_dims,
-                                                layer.out_dims, mh, mw, enc, C.byref(ctx.opt), C.byref(route), ws, wsn, _stream(dev)))
+            act = _act(layer.activation_func)
+            L.check(lib.swf_patch_layer_bwd_opt_act(C.byref(act), C.byref(prm), _ptr(tn), _ptr(gn), _ptr(gin), C.byref(grads), b, h, w,
+                                                    layer.in_dims, layer.out_dims, mh, mw, enc, C.byref(ctx.opt), C.byref(route), ws, wsn,
+                                                    _stream(dev)))
             layer.last_backward_route = route
             return None, None, _to_nchw(gin), gw, gb, gg, gbe
 
@@ -1063,7 +1089,7 @@ class PatchMergingAndLinearLayer(_FwdAlias, _BackwardTier, nn.Module):
         self.register_buffer(name="buffer_to_show_device", tensor=torch.zeros(size=(1,)))
 
     def _one(self, t: Tensor, s: str) -> Tensor:
-        _require_elu(self.activation_func)
+        act = _act(self.activation_func)
         b, c, h, w = t.shape
         mh, mw = self.merging_or_unmerging_size
         prm = L.PatchParams(_lin(getattr(self, f"mlp_layer_{s}")), _norm(getattr(self, f"layer_norm_{s}")))
@@ -1074,13 +1100,13 @@ class PatchMergingAndLinearLayer(_FwdAlias, _BackwardTier, nn.Module):
                 raise ValueError(f"map {h}x{w} is not divisible by the merging size {mh}x{mw}")
             out = torch.empty((b, h // mh, w // mw, self.out_dims), dtype=torch.float32, device=t.device)
             ws, wsn = _workspace(lib.swf_patch_workspace_bytes(b, h, w, self.in_dims, self.out_dims, mh, mw, 1, 1, 1), t.device)
-            L.check(lib.swf_patch_merge_fwd(C.byref(prm), _ptr(tn), _ptr(out), b, h, w, self.in_dims, self.out_dims,
-                                            mh, mw, 1, 1, ws, wsn, _stream(t.device)))
+            L.check(lib.swf_patch_merge_fwd_act(C.byref(act), C.byref(prm), _ptr(tn), _ptr(out), b, h, w, self.in_dims, self.out_dims,
+                                                mh, mw, 1, 1, ws, wsn, _stream(t.device)))
         else:
             out = torch.empty((b, h * mh, w * mw, self.out_dims), dtype=torch.float32, device=t.device)
             ws, wsn = _workspace(lib.swf_patch_workspace_bytes(b, h, w, self.in_dims, self.out_dims, mh, mw, 1, 1, 0), t.device)
-            L.check(lib.swf_patch_unmerge_fwd(C.byref(prm), _ptr(tn), None, _ptr(out), b, h, w, h, w, self.in_dims,
-                                              self.out_dims, mh, mw, h * mh, w * mw, ws, wsn, _stream(t.device)))
+            L.check(lib.swf_patch_unmerge_fwd_act(C.byref(act), C.byref(prm), _ptr(tn), None, _ptr(out), b, h, w, h, w, self.in_dims,
+                                                  self.out_dims, mh, mw, h * mh, w * mw, ws, wsn, _stream(t.device)))
         return _to_nchw(out)
 
     def _one_grad(self, t: Tensor, s: str) -> Tensor:
@@ -1117,6 +1143,7 @@ class _HeadFunction(torch.autograd.Function):
         x, y = x.detach().contiguous(), y.detach().contiguous()
         out = torch.empty((b, 1, h, w), dtype=torch.float32, device=x.device)
         lib, hp, ks = L.lib(), model._head_params(), model.final_layer_conv_kernel_size
+        ctx.act = _act(model.final_layer[2])   # the head honours the module that sits in it (a013:134)
         ws, wsn = _workspace(lib.swf_final_head_bwd_workspace_bytes(b, h, w, ks), x.device)
         stats = torch.empty(4, dtype=torch.float32, device=x.device)   # batch mean[2], biased variance[2]
         if ctx.train:
@@ -1148,7 +1175,7 @@ class _HeadFunction(torch.autograd.Function):
                                                        b, h, w, ks, ws, wsn, _stream(x.device)))
             hp.bn_mean, hp.bn_var = stats.data_ptr(), stats.data_ptr() + 8
         ctx.save_for_backward(x, y, stats)
-        L.check(lib.swf_final_head_fwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(out), b, h, w, ks, ws, wsn, _stream(x.device)))
+        L.check(lib.swf_final_head_fwd_act(C.byref(ctx.act), C.byref(hp), _ptr(x), _ptr(y), _ptr(out), b, h, w, ks, ws, wsn, _stream(x.device)))
         return out
 
     @staticmethod
@@ -1171,13 +1198,14 @@ class _HeadFunction(torch.autograd.Function):
                 # the normalisation's own gradient needs two per-channel means over the WHOLE batch: local sums, one all-reduce, then
                 # the backward proper (which recomputes what the first call computed: nothing waits in the workspace for the collective)
                 sums = torch.empty(4, dtype=torch.float32, device=dev)
-                L.check(lib.swf_final_head_bwd_sums(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), b, h, w, ks, ws, wsn, _stream(dev)))
+                L.check(lib.swf_final_head_bwd_sums_act(C.byref(ctx.act), C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), b, h, w, ks,
+                                                        ws, wsn, _stream(dev)))
                 ctx.collective.all_reduce_(sums)
-                L.check(lib.swf_final_head_bwd_synced(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), ctx.count, _ptr(gx), _ptr(gy),
-                                                      C.byref(grads), b, h, w, ks, ws, wsn, _stream(dev)))
+                L.check(lib.swf_final_head_bwd_synced_act(C.byref(ctx.act), C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), sums.data_ptr(), ctx.count,
+                                                          _ptr(gx), _ptr(gy), C.byref(grads), b, h, w, ks, ws, wsn, _stream(dev)))
                 return (None, gx, gy, *bufs)
-            L.check(lib.swf_final_head_bwd(C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), _ptr(gx), _ptr(gy), C.byref(grads), b, h, w, ks,
-                                           int(ctx.train), ws, wsn, _stream(dev)))
+            L.check(lib.swf_final_head_bwd_act(C.byref(ctx.act), C.byref(hp), _ptr(x), _ptr(y), _ptr(gout), _ptr(gx), _ptr(gy), C.byref(grads),
+                                               b, h, w, ks, int(ctx.train), ws, wsn, _stream(dev)))
         return (None, gx, gy, *bufs)
 
 
@@ -1285,6 +1313,7 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
         d.head_ksize = self.final_layer_conv_kernel_size
         d.precision = _precision_code(self.precision)
         d.schedule = _schedule_code(self.schedule)
+        d.act = _act(self.mlp_activation_func)
         return d
 
     def refresh_weights(self) -> None:
@@ -1315,7 +1344,8 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
     def graph_key(self):
         """Everything a captured forward depends on besides the input shape: the weights epoch and fingerprint, the arithmetic mode
         and the addresses of the arena / packed images (None before the first forward)."""
-        return (self.weights_epoch, self._weights_fingerprint(), self.precision, self.schedule,
+        # (the activation straight from the module table: this runs on every step of a graph runner)
+        return (self.weights_epoch, self._weights_fingerprint(), self.precision, self.schedule, _activation_of(self._modules["mlp_activation_func"]),
                 None if self._arena is None else self._arena.data_ptr(), None if self._packed is None else self._packed.data_ptr())
 
     def param_layout(self):
@@ -1333,9 +1363,10 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
         return out
 
     def _get_arena(self, device) -> Tensor:
-        key = (torch.device(device).index, self._weights_fingerprint())
+        # (the activation is no weight, but a replaced mlp_activation_func has to pass _check_one_activation again)
+        key = (torch.device(device).index, self._weights_fingerprint(), _activation_of(self.mlp_activation_func))
         if self._arena is None or self._arena_key != key:
-            _require_elu(self.mlp_activation_func)
+            self._check_one_activation()
             lib, desc = L.lib(), self._model_desc()
             total = lib.swf_model_arena_elems(C.byref(desc))
             sd = self.state_dict()
@@ -1359,6 +1390,23 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
             self._packed = None
             self.weights_epoch += 1
         return self._arena
+
+    def _check_one_activation(self) -> None:
+        """The one-call forward applies `mlp_activation_func` everywhere, the differentiable forward goes module by module and each
+        module honours its own: the two must not disagree, so every sub-module's activation has to map to the model's (kind, param)."""
+        want = _activation_of(self.mlp_activation_func)
+        for name, m in self.named_modules():
+            if isinstance(m, (AutoPathMLP, PatchMergingAndLinearLayer)):
+                own = m.activation_func
+            elif isinstance(m, (BasicBlock, NormalAndShiftWinsBlockPair, SelfAndCrossBlockPair)):
+                own = m.mlp_activation_func
+            elif m is self.final_layer:
+                name, own = "final_layer.2", m[2]
+            else:
+                continue
+            if _activation_of(own) != want:
+                raise NotImplementedError(f"{name} holds {own!r}, the model's mlp_activation_func is {self.mlp_activation_func!r}: the one-call "
+                                          "forward needs one activation for the whole model")
 
     def _get_packed(self, arena: Tensor) -> Optional[Tensor]:
         """Kernel-layout weight images of the fused levels, derived once per arena (swf_model_pack_weights)."""
@@ -1449,7 +1497,7 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
 
     def do_final_layer(self, x: Tensor, y: Tensor) -> Tensor:
         """a013:126-152 on its own: cat -> conv -> BatchNorm2d (batch statistics under train(), running statistics under eval()) ->
-        ELU -> conv, differentiable."""
+        activation (final_layer[2]) -> conv, differentiable."""
         conv1, bn, conv2 = self.final_layer[0], self.final_layer[1], self.final_layer[3]
         return _HeadFunction.apply(self, x, y, conv1.weight, conv1.bias, bn.weight, bn.bias, conv2.weight, conv2.bias)
 
@@ -1476,7 +1524,8 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
         lib, desc = L.lib(), self._model_desc()
         need = lib.swf_model_workspace_bytes(C.byref(desc), b, h, w)
         ws, wsn = _workspace(need, x.device)
-        packed = self._get_packed(arena) if desc.precision == L.PREC_FAST else None
+        # (only the default activation runs the kernels that read packed images: swf_model_packed_bytes is 0 for any other)
+        packed = self._get_packed(arena) if desc.precision == L.PREC_FAST and desc.act.kind == L.ACT_ELU1 else None
         if self.input_compatibility_with_cross_option is None:
             # First forward: the reference checks, in front of every cross-attention block, that its two input streams
             # are not identical everywhere, and otherwise prints and calls exit() (a005:98-118).  The library records
@@ -1495,7 +1544,7 @@ class MyModel(_FwdAlias, _BackwardTier, nn.Module):
             self.input_compatibility_with_cross_option = True
             return out
         if desc.precision == L.PREC_FAST:
-            L.check(lib.swf_model_forward_packed(C.byref(desc), _ptr(arena), packed.data_ptr(), _ptr(x), _ptr(y), _ptr(out),
+            L.check(lib.swf_model_forward_packed(C.byref(desc), _ptr(arena), _raw(packed), _ptr(x), _ptr(y), _ptr(out),
                                                  b, h, w, ws, wsn, _stream(x.device)))
         else:
             L.check(lib.swf_model_forward(C.byref(desc), _ptr(arena), _ptr(x), _ptr(y), _ptr(out), b, h, w, ws, wsn,
